@@ -33,6 +33,19 @@ step of every path executed (the plan's saving depends on the share of left-padd
 Extra objects on the JSON line: "roofline" (dominant kernel family, HIP events on the engine's
 stream inside the timed region) and "cpu_baseline" (the float64 oracle with OpenMP on the host
 cores, bounded sample, rank 0 / N=1 only).
+
+Plain and full runs.  Without --full a run sets up, warms up, times the K steps (the roofline comes from
+events inside them), writes --dump-outputs if asked and prints the line.  Everything else -- the streaming,
+long-run and no-prefix-plan regions, the batch sweep, dropin_minibatch, cpu_baseline, alt_f32x6,
+other_configs, the data-parallel exchange timing and strong_1M -- runs with --full only; their keys are
+null or absent on a plain line.
+
+--dump-outputs DIR (bench_outputs/<name>: git ignores that folder) replays the timed path's last steps --
+the same step function over the same batches, fed the same way -- on a second engine from the seeded state,
+and writes what the last of them computed (probs, loss, the dense parameters and a seeded sample of entity
+rows after the update) as DIR/<name>.npy.  Inputs and starting state are seeded, so two builds run with the
+same arguments can be compared output for output.  The timed engine's own state is not dumped: its gradient
+sums are fp32 atomics, and two runs' states drift apart over the steps (last_step_outputs has the figures).
 """
 import argparse
 import json
@@ -116,7 +129,42 @@ def parse():
                          "and steps, and the same total on rank 0 alone) and report it under \"strong_1M\"; this flag skips it")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher / rank wiring / timing / JSON check without a GPU: gloo backend, the step is a placeholder (CPU tests)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline region: the streaming / long-run / no-prefix-plan regions, the batch sweep, the drop-in minibatch "
+                         "figures, the CPU baselines, the f32x6 line, the other BASELINE configs, the data-parallel exchange timing and strong_1M. "
+                         "Without it a run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, replay the timed path's last min(steps, buckets + 1) steps on a second engine from the seeded state "
+                         "and write what the last of them computed as DIR/<name>.npy (float32 / float64, <= 64 MB in all): the scoring pass's probabilities, "
+                         "the loss, the dense parameters and a fixed sample of entity rows after the update -- the same every run with the same arguments "
+                         "(git ignores bench_outputs/)")
     return ap.parse_args()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as <path>/<name>.npy, float32 (float64 kept), 64 MB at most in all"""
+    arrays = {k: np.ascontiguousarray(v, np.float64 if np.asarray(v).dtype == np.float64 else np.float32) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise ValueError(f"--dump-outputs: {total} bytes > {DUMP_LIMIT_BYTES}")
+    os.makedirs(path, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(path, f"{k}.npy"), v)
+
+
+def entity_sample_rows(idx, F, Ve, de, seed=2024):
+    """the entity rows --dump-outputs reads back: a seeded sample of the rows the batch touched plus a seeded sample of the whole table
+    (sorted, 0-based), at most 32 MB of fp32 rows"""
+    per = max(1, min(32768, (8 << 20) // max(1, 2 * de)))
+    rng = np.random.default_rng(seed)
+    touched = np.unique(idx[..., F - 2].astype(np.int64).ravel() - 1)
+    if touched.size > per:
+        touched = rng.choice(touched, per, replace=False)
+    anywhere = rng.choice(Ve, min(per, Ve), replace=False).astype(np.int64)
+    return np.union1d(touched, anywhere)
 
 
 def free_port():
@@ -221,8 +269,10 @@ def dry_run(a):
         dist.all_reduce(mx, op=dist.ReduceOp.MAX)
         dist.all_reduce(tot, op=dist.ReduceOp.SUM)
         el[0] = mx[0]
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, {"replica": g.numpy()})
     # the strong-scaling experiment beside a weak line (main(): strong_1m): the same total split over ranks and steps, then on rank 0 alone
-    if world > 1 and not a.total_paths and not a.no_strong_1m:
+    if world > 1 and a.full and not a.total_paths and not a.no_strong_1m:
         ks = strong_steps(STRONG_TOTAL, world, a.steps)
         cur_pps[0] = max(64, STRONG_TOTAL // (world * ks))
         dist.barrier()
@@ -612,10 +662,16 @@ def run_c5(a):
     el, n = region(step_res, a.warmup, a.steps)
     eng.profile(False)
     fams = eng.profile_get()
-    for i in range(3):
-        step_str(i)
-    eng.sync()
-    el_s, n_s = region(step_str, 3, a.steps)
+    if a.dump_outputs:   # (the last timed step scored bucket (warmup + steps - 1) mod 5)
+        dump_outputs(a.dump_outputs, {"probs": eng.read_probs(batches[(a.warmup + a.steps - 1) % len(batches)].B)})
+    streaming = None
+    if a.full:
+        for i in range(3):
+            step_str(i)
+        eng.sync()
+        el_s, n_s = region(step_str, 3, a.steps)
+        streaming = {"value": round(n_s / el_s, 1), "unit": "paths/s", "ms_per_step": round(1e3 * el_s / a.steps, 4),
+                     "ratio_to_resident": round((n_s / el_s) / (n / el), 4)}
     roofline = None
     if "lstm_fused_fwd" in fams:
         ms, launches = fams["lstm_fused_fwd"]
@@ -624,7 +680,7 @@ def run_c5(a):
                     "unit": "TFLOP/s", "frac": round(work / (ms * 1e-3) / 1e12 / PEAK_TFLOPS_F32_MFMA, 4), "traffic": None,
                     "avg_launch_ms": round(ms / max(launches, 1), 5), "launches": launches}
     cpu = None
-    if not a.no_cpu_baseline:
+    if a.full and not a.no_cpu_baseline:
         from oracle.oracle import Oracle, make_cfg
         cores = len(os.sched_getaffinity(0))
         os.environ.setdefault("OMP_NUM_THREADS", str(cores))
@@ -645,9 +701,7 @@ def run_c5(a):
                                f"fp32, Ve = {Ve}, C = 46, LSE pool; one scoring forward per bucket batch", "paths_per_step": a.paths_per_step,
                    "buckets_T": Ts, "impl": a.impl, "batch_feed": "resident"},
         "executed_step_fraction": round(sum(exec_of) / float(sum(p * t for p, t in zip(paths_of, Ts))), 4),
-        "streaming": {"value": round(n_s / el_s, 1), "unit": "paths/s", "ms_per_step": round(1e3 * el_s / a.steps, 4),
-                      "ratio_to_resident": round((n_s / el_s) / (n / el), 4)},
-        "roofline": roofline, "cpu_baseline": cpu}))
+        "streaming": streaming, "roofline": roofline, "cpu_baseline": cpu}))
 
 
 def main():
@@ -695,17 +749,22 @@ def main():
     G = 1 if shipped else (3 if gru else 4)   # rows of recurrent weights per hidden unit (gru: r, z and the candidate)
     Vt, Ve, Vr = 6, a.entities, (100 if c4 else 9)
     stream = torch.cuda.current_stream().cuda_stream
-    eng = _ffi.Engine(Vt, Ve, Vr, dt_, de_, dr_, H, L, F=F, num_types=nT, C_=C, reducer=2, device_id=local_rank,
-                      rank=rank, world=world, param_init=0.1, seed=12345, stream=stream,
-                      rnn_type=1 if shipped else (2 if gru else 0), use_relu=1, rnn_init=1 if shipped else 0, compute_dtype=a.compute_dtype)
-    eng.set_option("impl", a.impl)
-    eng.set_option("score_overlap", "0" if a.no_score_overlap else "1")
-    eng.set_option("feed_build", a.feed_build)
-    if a.feed_threads > 0:
-        eng.set_option("feed_threads", str(a.feed_threads))
-    for kv in a.set_option:
-        k_, _, v_ = kv.partition("=")
-        eng.set_option(k_, v_)
+
+    def new_engine():
+        """the engine of the timed steps: seeded parameters, fresh Adam state, this run's options"""
+        e = _ffi.Engine(Vt, Ve, Vr, dt_, de_, dr_, H, L, F=F, num_types=nT, C_=C, reducer=2, device_id=local_rank,
+                        rank=rank, world=world, param_init=0.1, seed=12345, stream=stream,
+                        rnn_type=1 if shipped else (2 if gru else 0), use_relu=1, rnn_init=1 if shipped else 0, compute_dtype=a.compute_dtype)
+        e.set_option("impl", a.impl)
+        e.set_option("score_overlap", "0" if a.no_score_overlap else "1")
+        e.set_option("feed_build", a.feed_build)
+        if a.feed_threads > 0:
+            e.set_option("feed_threads", str(a.feed_threads))
+        for kv in a.set_option:
+            k_, _, v_ = kv.partition("=")
+            e.set_option(k_, v_)
+        return e
+    eng = new_engine()
     opt = _ffi.make_opt(method=1, lr=1e-3, entity_update=a.entity_update)
 
     # bucketed batches (constant P per batch, like the reference's train.txt.<P>.torch files)
@@ -728,7 +787,6 @@ def main():
     if world > 1 or a.force_dp:
         if a.dp_torch_collectives or a.dp_unfused:
             os.environ["KPRN_DP_NATIVE"] = "0"
-        dpx = dp.DataParallel(dp.GpuAdapter(eng, dev, fused_update=not a.dp_unfused))
         # where the scoring pass goes: first (beside the training forward, as in the plain step) when no collective needs hiding, else behind
         # the backward while the all-gather is in flight (the engine's exchange then runs the collective on a stream of its own)
         dp_score_first = a.dp_score_first or (world == 1 and not a.dp_score_under_gather and a.dp_score_split <= 0)
@@ -739,40 +797,50 @@ def main():
         #  work placed under the gather runs alone on 240 CUs in whole rounds of tiles, so the split buys 0.05 ms; opt-in)
         if not dp_score_first and not a.dp_score_under_gather and a.compute_dtype == 0 and a.dp_score_split > 0:
             dp_split = a.dp_score_split
+
+    def new_dp(e):
+        """the data-parallel step's exchange around engine e (collective: every rank calls it)"""
+        d = dp.DataParallel(dp.GpuAdapter(e, dev, fused_update=not a.dp_unfused))
         if 0.0 < dp_split < 1.0:
-            eng.set_option("score_split", str(dp_split))
-        if dpx.native and not dp_score_first:
-            eng.set_option("dp_comm_stream", "1")
+            e.set_option("score_split", str(dp_split))
+        if d.native and not dp_score_first:
+            e.set_option("dp_comm_stream", "1")
         # packing capacity = largest distinct-row count of any batch on any rank (known from the batch index)
-        dpx.set_capacity(max(b.n_uniq for b in batches))
+        d.set_capacity(max(b.n_uniq for b in batches))
+        # A step = one scoring forward + one trainBatch over the same batch.  The scoring pass uses the parameters as they are
+        # BEFORE this step's update ("score the batch, then learn from it"), so it does not depend on the step's gradient
+        # exchange: in data-parallel runs it is enqueued while the entity-row all-gather is in flight (kprn_amd/dp.py), with
+        # a few CUs left free for the collective's copy kernels.
+        if not dp_score_first:   # (a pass queued first shares the chip with the training forward, not with a collective)
+            e.set_option("reserve_cus", str(a.reserve_cus))
+        return d
+    if world > 1 or a.force_dp:
+        dpx = new_dp(eng)
 
-    # A step = one scoring forward + one trainBatch over the same batch.  The scoring pass uses the parameters as they are
-    # BEFORE this step's update ("score the batch, then learn from it"), so it does not depend on the step's gradient
-    # exchange: in data-parallel runs it is enqueued while the entity-row all-gather is in flight (kprn_amd/dp.py), with
-    # a few CUs left free for the collective's copy kernels.
-    if dpx is not None and not dp_score_first:   # (a pass queued first shares the chip with the training forward, not with a collective)
-        eng.set_option("reserve_cus", str(a.reserve_cus))
-
-    def run_batch(b):
-        score = (lambda: eng.forward_async(b, 1)) if not a.train_only else None
-        if a.score_only:
-            eng.forward_async(b, 1)
-        elif dpx is not None:
-            # The scoring pass scores with the pre-update parameters, so it is independent of the exchange and the update waits for it.  It is
-            # queued FIRST (beside the training forward, exactly as in the plain step) when no collective needs hiding (world 1), else behind
-            # the backward while the all-gather is in flight.  profiles/r03 + DESIGN.md section 4 have the measured timelines of both.
-            if score and dp_score_first:
-                score()
-                dpx.train_step(b, opt, 1, overlap=None)
-            elif score and 0.0 < dp_split < 1.0:
-                score()                                                       # first part: beside the training forward
-                dpx.train_step(b, opt, 1, overlap=eng.forward_async_rest)     # the rest: under the all-gather
+    def make_run_batch(eng, dpx):
+        """the timed path's step on engine eng (and its exchange dpx): scoring pass + train step over batch b"""
+        def run_batch(b):
+            score = (lambda: eng.forward_async(b, 1)) if not a.train_only else None
+            if a.score_only:
+                eng.forward_async(b, 1)
+            elif dpx is not None:
+                # The scoring pass scores with the pre-update parameters, so it is independent of the exchange and the update waits for it.  It is
+                # queued FIRST (beside the training forward, exactly as in the plain step) when no collective needs hiding (world 1), else behind
+                # the backward while the all-gather is in flight.  profiles/r03 + DESIGN.md section 4 have the measured timelines of both.
+                if score and dp_score_first:
+                    score()
+                    dpx.train_step(b, opt, 1, overlap=None)
+                elif score and 0.0 < dp_split < 1.0:
+                    score()                                                       # first part: beside the training forward
+                    dpx.train_step(b, opt, 1, overlap=eng.forward_async_rest)     # the rest: under the all-gather
+                else:
+                    dpx.train_step(b, opt, 1, overlap=score)
             else:
-                dpx.train_step(b, opt, 1, overlap=score)
-        else:
-            if score:
-                score()
-            eng.train_step(b, opt, 1, want_loss=False)
+                if score:
+                    score()
+                eng.train_step(b, opt, 1, want_loss=False)
+        return run_batch
+    run_batch = make_run_batch(eng, dpx)
 
     def step_resident(pool):
         def step(i):
@@ -788,7 +856,7 @@ def main():
     NS = AHEAD + 1
     # slots sized once for the largest bucket (BatcherFileList.lua:53-60 preallocates its GPU tensors the same way)
     slots = ([_ffi.Batch.reserve(eng, max(b.B for b in batches), max(paths_of), T, F) for _ in range(NS)]
-             if (a.batch_feed != "resident" or a.stream_total_paths > 0) else [None] * NS)
+             if (a.batch_feed == "streaming" or (a.batch_feed == "both" and a.full) or a.stream_total_paths > 0) else [None] * NS)
     fed_upto = [-1]
     host_t = {"feed": [], "run": []}   # host-side seconds per step spent queueing the feed / the step (KPRN_BENCH_HOST_TIMING=1 prints them)
     def step_streaming(i):
@@ -877,11 +945,61 @@ def main():
     fams = eng.profile_get() if prof else {}
     value = npaths_total / elapsed
 
-    # ---- further regions (not the headline; N = 1 only, no kernel events)
+    def last_step_outputs():
+        """--dump-outputs: the timed path's last min(steps, len(Ps) + 1) steps -- the same step function, the same batches in the same order,
+        fed the same way (resident, or through a ring of streaming slots), so the first bucket comes round twice: a reused batch, Adam past its
+        first step, lazily updated entity rows -- replayed on a second engine from the seeded state (same seed and options, fresh Adam state, a
+        fresh exchange in data-parallel runs), and what the last of them hands its caller: the scoring pass's probabilities and the loss, and the
+        parameters after its update (the dense tensors whole, a fixed sample of the entity table's rows: entity_sample_rows).
+        Why not the timed engine itself: its gradient sums are fp32 atomics whose order varies, and the differences compound over the steps --
+        measured between two runs with the same arguments, 25 timed steps: up to 2e-7 of each array's scale; 205 steps: 1e-5 (probs), thousands
+        of entity-row elements off by more than 1e-5 relative.  A replay of this length from the seeded state repeats to fp32 rounding."""
+        k = min(a.steps, len(Ps) + 1)
+        first = a.warmup + a.steps - k
+        e2 = new_engine()
+        d2 = new_dp(e2) if dpx is not None else None
+        step2 = make_run_batch(e2, d2)
+        made = []
+        if main_streaming:
+            ring = [_ffi.Batch.reserve(e2, max(x.B for x in batches), max(paths_of), T, F) for _ in range(NS)]   # (sized as the timed path's slots)
+            for i in range(first, first + k):
+                ring[i % NS] = b = e2.feed(*host[i % len(host)], slot=ring[i % NS])
+                step2(b)
+            made = ring
+        else:
+            pool = {}
+            for i in range(first, first + k):
+                j = i % len(host)
+                if j not in pool:
+                    pool[j] = e2.batch(*host[j])
+                b = pool[j]
+                step2(b)
+            made = list(pool.values())
+        hi = host[(first + k - 1) % len(host)][0]
+        e2.sync()
+        out = {}
+        if not a.train_only:
+            out["probs"] = e2.read_probs(b.B)
+        if not a.score_only:
+            out["loss"] = np.array([e2.read_loss()], np.float32)
+        out["params_dense"] = np.concatenate([e2.get_param(nm).ravel() for nm in e2.layout() if nm != "entity_emb"])
+        rows = entity_sample_rows(hi, F, Ve, de_)
+        out["entity_rows"] = e2.get_param_rows("entity_emb", rows)
+        out["entity_row_ids"] = rows.astype(np.float64)
+        for x in made:
+            x.free()
+        e2.close()
+        return out
+    if a.dump_outputs:   # (every rank takes part -- the exchange of a data-parallel step is collective -- rank 0 writes)
+        outs = last_step_outputs()
+        if rank == 0:
+            dump_outputs(a.dump_outputs, outs)
+
+    # ---- further regions (not the headline; --full, N = 1 only, no kernel events)
     def region_line(el, n, k):
         return {"value": round(n / el, 1), "unit": "paths/s", "ms_per_step": round(1e3 * el / k, 4), "steps": k}
     extras = {}
-    plain = world == 1 and not a.force_dp and not a.no_extra_regions
+    plain = world == 1 and not a.force_dp and not a.no_extra_regions and a.full
     if plain and a.batch_feed == "both":
         # the same steps with the streaming feed (its own warm-up: the ring of slots fills, their staging is allocated; at least 60 steps,
         # so that the pipeline's start-up transient does not decide the figure)
@@ -974,19 +1092,20 @@ def main():
     # data-parallel runs: the exchange's own time, from a short extra region with events around its parts
     dp_info = None
     if dpx is not None:
-        dpx.timing = True
-        eng.profile_reset()
-        eng.set_option("profile_filter", "dp_")
-        eng.profile(True)
-        k_x = min(a.steps, 12)
-        timed_region(step, a.warmup + a.steps, k_x)
-        eng.profile(False)
-        fx = eng.profile_get()
-        dp_info = {"world": world, "capacity_rows": dpx.capacity, "packed_MB_per_rank": round((4 + dpx.capacity * (1 + de_)) * 4 / 1e6, 2),
-                   "exchange_ms_per_step": dpx.timing_summary(),
-                   "pack_rows_ms": round(fx.get("dp_pack_rows", (0, 1))[0] / max(1, fx.get("dp_pack_rows", (0, 1))[1]), 4),
-                   "merge_rows_ms": round(fx.get("dp_merge_rows", (0, 1))[0] / max(1, fx.get("dp_merge_rows", (0, 1))[1]), 4)}
-        dpx.timing = False
+        dp_info = {"world": world, "capacity_rows": dpx.capacity, "packed_MB_per_rank": round((4 + dpx.capacity * (1 + de_)) * 4 / 1e6, 2)}
+        if a.full:
+            dpx.timing = True
+            eng.profile_reset()
+            eng.set_option("profile_filter", "dp_")
+            eng.profile(True)
+            k_x = min(a.steps, 12)
+            timed_region(step, a.warmup + a.steps, k_x)
+            eng.profile(False)
+            fx = eng.profile_get()
+            dp_info.update({"exchange_ms_per_step": dpx.timing_summary(),
+                            "pack_rows_ms": round(fx.get("dp_pack_rows", (0, 1))[0] / max(1, fx.get("dp_pack_rows", (0, 1))[1]), 4),
+                            "merge_rows_ms": round(fx.get("dp_merge_rows", (0, 1))[0] / max(1, fx.get("dp_merge_rows", (0, 1))[1]), 4)})
+            dpx.timing = False
         tr = torch.ones(1, device=dev)
         if world > 1:
             dist.all_reduce(tr)
@@ -1002,7 +1121,7 @@ def main():
         dp_info["per_rank_ms_per_step"] = [round(float(x.item()), 4) for x in allr]
         dp_info["fallback_reason"] = dpx.fallback_reason   # why the engine's own exchange is not in use (None: it is)
         # ---- the north_star's scaling experiment beside the weak line: 1 M paths strong-scaled, and the same total on rank 0 alone
-        if not a.total_paths and not a.no_strong_1m and a.dims == "A" and a.compute_dtype == 0 and not a.score_only and not a.train_only:
+        if a.full and not a.total_paths and not a.no_strong_1m and a.dims == "A" and a.compute_dtype == 0 and not a.score_only and not a.train_only:
             try:
                 dp_info["strong_1M"] = strong_1m(a, eng, dpx, opt, run_batch, timed_region, barrier, world, rank, local_rank, stream,
                                                  dict(T=T, F=F, Vt=Vt, Ve=Ve, Vr=Vr, nT=nT, dt=dt_, de=de_, dr=dr_, H=H, L=L, C=C), Ps)
@@ -1084,14 +1203,14 @@ def main():
             roofline["other_timed_families"] = {n: dict(family_roofline(n, m, l, lfirst, lk) or {}, region="long_run", steps=lk) for n, (m, l) in sorted(lf.items())}
 
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         cpu = cpu_baseline(a, T, dt_, de_, dr_, H, L, a.cpu_seconds)
 
     # ---- not the headline: the same workload with the forward on the bf16 matrix cores (compute_dtype 2, "f32x6": every fp32
     #      operand split exactly into three bf16 pieces, six partial products, fp32 accumulation; error <= an fp32 FMA chain;
     #      held to the same parity tolerances by tests/test_gpu_parity.py).  A short second run on a second engine.
     alt = None
-    if rank == 0 and world == 1 and a.compute_dtype == 0 and not a.no_alt and not shipped and a.dims == "A" and not a.force_dp \
+    if a.full and rank == 0 and world == 1 and a.compute_dtype == 0 and not a.no_alt and not shipped and a.dims == "A" and not a.force_dp \
             and not a.score_only and not a.train_only and a.impl == "auto":
         eng2 = _ffi.Engine(Vt, Ve, Vr, dt_, de_, dr_, H, L, F=F, num_types=nT, C_=C, reducer=2, device_id=local_rank, rank=rank, world=world,
                            param_init=0.1, seed=12345, stream=stream, compute_dtype=2)
@@ -1129,7 +1248,7 @@ def main():
     # ---- the other BASELINE configurations, compact: each a short run of this script in its own process (its own engine, its own
     #      tables), after everything above has been measured.  Parity-test configs, not the headline.
     other = None
-    if rank == 0 and world == 1 and a.dims == "A" and a.compute_dtype == 0 and not a.no_other_configs and not a.force_dp and not a.score_only \
+    if a.full and rank == 0 and world == 1 and a.dims == "A" and a.compute_dtype == 0 and not a.no_other_configs and not a.force_dp and not a.score_only \
             and not a.train_only and a.impl == "auto" and not a.no_extra_regions:
         other = other_configs()
 

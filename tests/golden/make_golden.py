@@ -3,7 +3,7 @@
 
   python tests/golden/make_golden.py
 
-1. c1_small.npz / c2_small.npz -- inputs, weights and float64 outputs of the CPU oracle (forward,
+1. c1_small.npz / c2_small.npz (+ c2_small_after3.npz) -- inputs, weights and float64 outputs of the CPU oracle (forward,
    gradients, 3 Adam steps) on the plumbing config C1 (T=3, d=16, L=1) and a C2-shaped config
    (T=6, D=H=64, L=2).  The oracle itself is pinned against PyTorch autograd + finite differences
    (tests/test_oracle.py); the reference (Lua/Torch7) cannot run here -- parity unpinned.
@@ -24,7 +24,8 @@ from kprn_amd import synth  # noqa: E402
 from oracle.oracle import Oracle, make_cfg, make_opt  # noqa: E402
 
 
-def oracle_case(name, Ve, dt, de, dr, H, L, T, pairs, P, seed):
+def oracle_case(name, Ve, dt, de, dr, H, L, T, pairs, P, seed, split_after3=False):
+    """split_after3: theta_after3 goes to <name>_after3.npz (no committed fixture file over 1 MiB)"""
     cfg = make_cfg(Vt=6, Ve=Ve, Vr=9, dt=dt, de=de, dr=dr, H=H, L=L)
     o = Oracle(cfg, np.float64)
     theta = o.init_params(seed, 0.1).astype(np.float32).astype(np.float64)
@@ -34,9 +35,13 @@ def oracle_case(name, Ve, dt, de, dr, H, L, T, pairs, P, seed):
     th = theta.copy()
     st = o.new_state()
     losses = [o.train_step(th, st, make_opt(method=1, lr=1e-2), idx, labels)[0] for _ in range(3)]
+    after3 = {"theta_after3": th}
+    if split_after3:
+        np.savez_compressed(os.path.join(HERE, name[:-len(".npz")] + "_after3.npz"), **after3)
+        after3 = {}
     np.savez_compressed(os.path.join(HERE, name), cfg=np.array([6, Ve, 9, dt, de, dr, 3, 1, H, L, 46, 2, 5], np.int32),
                         theta=theta.astype(np.float32), idx=idx, labels=labels, path_scores=ps, pooled=pooled,
-                        probs=probs, loss=np.float64(loss), grad=grad, theta_after3=th, losses3=np.array(losses))
+                        probs=probs, loss=np.float64(loss), grad=grad, losses3=np.array(losses), **after3)
 
 
 def rnn_case(name, Ve, dt, de, dr, H, L, T, pairs, P, seed, use_relu):
@@ -81,7 +86,7 @@ def eval_slices():
 
 if __name__ == "__main__":
     oracle_case("c1_small.npz", 200, 4, 8, 4, 16, 1, 3, 24, 2, 11)
-    oracle_case("c2_small.npz", 400, 16, 32, 16, 64, 2, 6, 16, 3, 21)
+    oracle_case("c2_small.npz", 400, 16, 32, 16, 64, 2, 6, 16, 3, 21, split_after3=True)
     rnn_case("c1_rnn_small.npz", 200, 8, 16, 8, 32, 2, 6, 20, 3, 31, 1)
     if os.path.isdir("/root/reference"):
         eval_slices()
