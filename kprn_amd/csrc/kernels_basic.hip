@@ -1308,9 +1308,9 @@ void onehot_cols(hipStream_t s, const int32_t* idx, int64_t N, int T, int F, int
 // workgroups [0, GH): one gate row each; behind them one (table row, K slice) each (see lstm_bf16.hip k_small_tables_finish: the same kernel on fp32 weights)
 __global__ __launch_bounds__(256) void k_small_tables_finish_f32(const float* __restrict__ Ct, int ns, int GH, int Din, int dt, int de, int dr, int Vt, int Vr,
                                                                  const float* __restrict__ Wt, const float* __restrict__ Wr, const float* __restrict__ Wi,
-                                                                 float* __restrict__ gWi, float* __restrict__ gWt, float* __restrict__ gWr) {
+                                                                 float* __restrict__ gWi, float* __restrict__ gWt, float* __restrict__ gWr, int with_e) {
   __shared__ float g[128];
-  const int tid = threadIdx.x, NZ = ns + de;
+  const int tid = threadIdx.x, NZ = ns + (with_e ? de : 0);
   if ((int)blockIdx.x < GH) {
     const int k = blockIdx.x;
     const float* row = Ct + (int64_t)k * NZ;
@@ -1321,6 +1321,7 @@ __global__ __launch_bounds__(256) void k_small_tables_finish_f32(const float* __
       if (j < dt) {
         for (int y = 0; y < Vt; ++y) v += g[Vr + y] * Wt[y * dt + j];
       } else if (j < dt + de) {
+        if (!with_e) continue;
         v = row[ns + j - dt];
       } else {
         const int jj = j - dt - de;
@@ -1330,25 +1331,33 @@ __global__ __launch_bounds__(256) void k_small_tables_finish_f32(const float* __
     }
     return;
   }
-  // one workgroup per table row, no atomics: two interleaved K sub-sums per column, added in a fixed order (the optimiser tests compare runs BITWISE)
+  // one workgroup per table row, no atomics: 16 interleaved K sub-sums per column (16 columns at a time), added in a fixed order (the optimiser tests
+  // compare runs BITWISE).  (Two sub-sums per column left a lane a chain of GH / 2 load round trips: 36 us at GH = 256, the fused path's whole gain.)
   __shared__ float red[256];
   const int r = (int)blockIdx.x - GH;
   const bool rel = r < Vr;
   const int w = rel ? dr : dt, col0 = rel ? dt + de : 0;
-  const int j = tid & 127, sb = tid >> 7;
-  for (int j0 = 0; j0 < w; j0 += 128) {
+  const int j = tid & 15, sb = tid >> 4;
+  for (int j0 = 0; j0 < w; j0 += 16) {
     const int jj = j0 + j, jc = jj < w ? jj : w - 1;
     float acc = 0.f;
-    for (int k = sb; k < GH; k += 2) acc += Ct[(int64_t)k * NZ + r] * Wi[(int64_t)k * Din + col0 + jc];
+#pragma unroll 4
+    for (int k = sb; k < GH; k += 16) acc += Ct[(int64_t)k * NZ + r] * Wi[(int64_t)k * Din + col0 + jc];
     red[tid] = acc;
     __syncthreads();
-    if (sb == 0 && jj < w) (rel ? gWr + (int64_t)r * dr : gWt + (int64_t)(r - Vr) * dt)[jj] += red[tid] + red[tid + 128];
+    if (sb == 0 && jj < w) {
+      float v = 0.f;
+#pragma unroll
+      for (int q = 0; q < 16; ++q) v += red[q * 16 + j];
+      (rel ? gWr + (int64_t)r * dr : gWt + (int64_t)(r - Vr) * dt)[jj] += v;
+    }
     __syncthreads();
   }
 }
 void small_tables_finish(hipStream_t s, const float* Ct, int ns, int GH, int Din, int dt, int de, int dr, int Vt, int Vr, const float* Wt, const float* Wr,
-                         const float* Wi, float* gWi, float* gWt, float* gWr) {
-  hipLaunchKernelGGL(k_small_tables_finish_f32, dim3((unsigned)(GH + Vr + Vt)), dim3(256), 0, s, Ct, ns, GH, Din, dt, de, dr, Vt, Vr, Wt, Wr, Wi, gWi, gWt, gWr);
+                         const float* Wi, float* gWi, float* gWt, float* gWr, bool ct_has_entity) {
+  hipLaunchKernelGGL(k_small_tables_finish_f32, dim3((unsigned)(GH + Vr + Vt)), dim3(256), 0, s, Ct, ns, GH, Din, dt, de, dr, Vt, Vr, Wt, Wr, Wi, gWi, gWt, gWr,
+                     ct_has_entity ? 1 : 0);
   HIP_TRY(hipGetLastError());
 }
 

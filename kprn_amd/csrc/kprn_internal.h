@@ -318,8 +318,9 @@ void embed_scatter(hipStream_t s, const int32_t* idx, int64_t N, int T, int F, i
 // saved step input are overwritten in place: the backward reads X only as the dW product's operand).
 void onehot_cols(hipStream_t s, const int32_t* idx, int64_t N, int T, int F, int Vr, int Vt, float* X, int64_t ldx, int col0, int ns);
 // Ct [GH][ns + de] = dA^T [S | x_e] -> gWi[:, entity cols] += Ct[:, ns:], gWi[:, type / relation cols] += G Wt / G Wr, gWt += G_t^T Wi_t, gWr += G_r^T Wi_r
+// (ct_has_entity = false: Ct = G [GH][ns], the entity columns of gWi are formed elsewhere -- the fused path)
 void small_tables_finish(hipStream_t s, const float* Ct, int ns, int GH, int Din, int dt, int de, int dr, int Vt, int Vr, const float* Wt, const float* Wr,
-                         const float* Wi, float* gWi, float* gWt, float* gWr);
+                         const float* Wi, float* gWi, float* gWt, float* gWr, bool ct_has_entity = true);
 void sumsq(hipStream_t s, const float* x, int64_t n, float* out);
 void sumsq_rows(hipStream_t s, const float* G, const int32_t* rows, const int32_t* count, int d, float* out);
 // dense optimiser over a contiguous span; scale_src: device float norm2 -> clip factor computed in-kernel
@@ -359,13 +360,17 @@ void prefix_plan(hipStream_t s, const int32_t* idx, int64_t N, int T, int F, int
 // entity-gradient launch can carry in extra workgroups (both run right after the backward kernels and neither fills the chip).
 struct SlabReduce {
   const float* part[2]; float* gWi[2]; float* gWo[2]; float* gbi[2];
-  int nslab, n_elem;   // slabs per layer, floats per slab (2 * G * H + G rows: W_i2g | W_o2g | b)
+  int nslab, n_elem;   // slabs per layer, floats reduced per slab (2 * G * H + G rows: W_i2g | W_o2g | b, then optionally G)
+  int slab;            // floats between two slabs
+  float* gG[2];        // nullable: where that layer's elements past W_i2g | W_o2g | b go (the fused path's small-table identity: G [G * H][16])
   int L, ny;           // layers, slab-range splits
   const float* r1; int kmax, kcap, r1_stride, G, H;  // rank-1 terms of the identical-prefix steps; kmax = 0: none
 };
 __device__ __forceinline__ void slab_reduce_block(const SlabReduce& a, int bx, int by, int l) {
   const int i = bx * 256 + threadIdx.x;
   if (i >= a.n_elem) return;
+  const int GH = a.G * a.H, nW = GH * a.H, nB = 2 * nW + GH;
+  if (i >= nB && !a.gG[l]) return;
   const float* __restrict__ part = a.part[l];
   float acc[4] = {0.f, 0.f, 0.f, 0.f};
   // sixteen slabs in flight per lane (four left the job latency-bound: 19 us for 68 MB, profiles/r03)
@@ -375,15 +380,14 @@ __device__ __forceinline__ void slab_reduce_block(const SlabReduce& a, int bx, i
     for (int u = 0; u < 16; ++u) {
       const int sl = s + (u >> 2) * a.ny * 4 + (u & 3);
       // (unconditional load from a clamped slab, then the select: a load under a condition is a branch with the wait inside it)
-      const float v = part[(int64_t)(sl < a.nslab ? sl : a.nslab - 1) * a.n_elem + i];
+      const float v = part[(int64_t)(sl < a.nslab ? sl : a.nslab - 1) * a.slab + i];
       x[u] = (sl < a.nslab) ? v : 0.f;
     }
 #pragma unroll
     for (int u = 0; u < 16; ++u) acc[u & 3] += x[u];
   }
   float v = (acc[0] + acc[1]) + (acc[2] + acc[3]);
-  const int GH = a.G * a.H, nW = GH * a.H;
-  if (by == 0) {
+  if (by == 0 && i < nB) {
     for (int t = 0; t < a.kmax; ++t) {
       const float* r1 = a.r1 + ((int64_t)l * a.kcap + t) * a.r1_stride;  // dA_{t+1}[GH] | dA_t[GH] | h_t[H] | in_t[H]
       if (i < nW) v += r1[GH + i / a.H] * r1[2 * GH + a.H + i % a.H];               // dW_i2g += dA_t (x) in_t
@@ -393,7 +397,8 @@ __device__ __forceinline__ void slab_reduce_block(const SlabReduce& a, int bx, i
   }
   if (i < nW) unsafeAtomicAdd(a.gWi[l] + i, v);
   else if (i < 2 * nW) unsafeAtomicAdd(a.gWo[l] + (i - nW), v);
-  else unsafeAtomicAdd(a.gbi[l] + (i - 2 * nW), v);
+  else if (i < nB) unsafeAtomicAdd(a.gbi[l] + (i - 2 * nW), v);
+  else unsafeAtomicAdd(a.gG[l] + (i - nB), v);
 }
 // Third job the entity-gradient launch can carry: the type / relation table gradients of the fused path (nn.LookupTable backward for the
 // two tiny tables, FeatureEmbedding.lua:29,41-49) from the bottom layer's fragment-order dx blocks: grad_table[v][:] = sum over the

@@ -54,6 +54,7 @@ struct BwdArgs {
   float* PG;               // [KCAP+1][PFB] this layer: sum over rows of dA at the tile's first executed step | of dc handed below it
   HoArgs ho;               // time-split tile hand-over (lstm_fused_common.h ho_plan)
   int small_lds;           // bottom layer: the type / relation table gradients are formed inside this launch (one-hot MFMAs on dx; option "fused_small_tables")
+  float* gG;               // bottom layer, small-table identity (k_lstm_bwd<.., IDENT>): [256][16] G = dA^T [S_r | S_t], summed from the slabs; zeroed here
   // layer pipeline of small batches (k_lstm_bwd_dual): both layers' workgroups are resident at once, the top layer's publish dx of (tile, step) as soon as it
   // is stored, the bottom layer's wait for it step by step -- the bottom layer runs ONE step behind the top layer instead of a whole launch behind
   unsigned* pipe_flag;     // [n_tiles][MAXT_LDS] epoch (ho.epoch) of the dx of (tile, absolute step)
@@ -62,6 +63,8 @@ struct BwdArgs {
 
 
 constexpr int PART = 2 * 256 * 64 + 256;  // floats per workgroup partial slab
+constexpr int NS_ID = 16;                  // one-hot columns of the small-table identity (relation v < Vr, type at Vr + v)
+constexpr int PART_G = PART + 256 * NS_ID; // slab stride: ... | G [256][NS_ID] (bottom layer on the identity route)
 constexpr int LDD = 4 * DH + 4;  // dA tile row stride
 
 // Cycle probes are compiled in only with -DKPRN_TIMING_PROBES (KPRN_TIMING=1 then prints them): eight 64-bit counters per wave cost
@@ -87,10 +90,36 @@ struct Pre {
 };
 
 // NMT: 16-row m-tiles of a tile -- 4, or 1 for small batches (fused::small_tiles; no identical-prefix plan there)
+// Identity route (below): this thread's share of step t's x tile [S | x_e | 0] from the LDS id planes (raw, 1-based), no type / relation table loads.
+// Thread: 16-byte chunk ch = tid & 15 of rows (tid >> 4) + 16 k.  Chunks 0..3: one-hot columns 4 ch .. 4 ch + 3 (relation v at v, type v at Vr + v, as
+// kk::onehot_cols lays them out); 4..11: the entity row (de = 32); 12..15: zeros (stage C reads 3 column tiles).  Every lane loads an entity chunk
+// (branch-free: no load under a condition), the select keeps it or not.
+__device__ __forceinline__ void gather_load_ident(const BwdArgs& a, const int t, const int32_t* ids, f32x4 (&v)[4]) {
+  const int ch = threadIdx.x & 15, c0 = 4 * ch;
+  const int32_t* p = ids + t * MT + (threadIdx.x >> 4);
+  const float* eb = a.We - a.de + ((ch + 4) & 7) * 4;   // chunk ch - 4 of the row one down (the ids are 1-based)
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const f32x4 e = *(const f32x4*)(eb + (int64_t)p[IDS_PLANE<MT> + k * 16] * a.de);
+    const int rel = p[2 * IDS_PLANE<MT> + k * 16] - 1, typ = a.Vr + p[k * 16] - 1;
+    f32x4 oh;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) oh[i] = (c0 + i == rel || c0 + i == typ) ? 1.f : 0.f;
+    v[k] = (ch < 4) ? oh : ((ch < 12) ? e : f32x4{0.f, 0.f, 0.f, 0.f});
+  }
+}
+
 // bx / G_: this workgroup's index among, and the number of, the workgroups of THIS layer's pass (k_lstm_bwd: the launch's; k_lstm_bwd_dual: half of it)
-template <bool BOTTOM, bool TOP, int NMT>
+// IDENT (bottom layer of two, 64-path tiles, de = 32, one type slot, Vr + Vt <= 16): the small-table identity.  The x tile is
+// [S (NS_ID one-hot columns) | x_e], so stage C forms dW_i2g over 3 column tiles, the first of them G = dA^T S; stage E forms dx for the two
+// entity column tiles only.  To keep the four waves' matrix work equal, wave j forms entity column tile (j & 1) for the m-tiles 2 (j >> 1) and
+// 2 (j >> 1) + 1 over the whole K (the same 64 weight registers as before): a wave walks ITS m-tiles in the order mof(0..3) everywhere, so its
+// own two come first and their indices stay compile-time.
+template <bool BOTTOM, bool TOP, int NMT, bool IDENT = false>
 __device__ __forceinline__ void bwd_body(const BwdArgs& a, const int bx, const int G_) {
+  static_assert(!IDENT || (BOTTOM && !TOP && NMT == 4), "the identity route: bottom layer of two, 64-path tiles");
   constexpr int MTR = 16 * NMT;
+  constexpr int NXT = IDENT ? 3 : 4;   // column tiles of the x tile that stage C multiplies
   extern __shared__ __attribute__((aligned(16))) float lds[];
   unsigned long long tacc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   unsigned long long tlast = (KPRN_PROBES_ON && a.timing) ? __builtin_amdgcn_s_memtime() : 0ull;
@@ -107,12 +136,15 @@ __device__ __forceinline__ void bwd_body(const BwdArgs& a, const int bx, const i
   const int T = a.T, L = a.L, ly = a.layer;
   // (first thing in the kernel: its one round trip is in flight under the weight loads below)
   const HoPlan ho = ho_plan(a.ho, a.tile_k, a.n_tiles, T, 1, bx, G_);
+  // m-tile of this wave's slot i (registers dh[i], dc[i], ... are slot-indexed)
+  auto mof = [&](const int i) -> int { return IDENT ? ((i + 2 * (j >> 1)) & 3) : i; };
+  if (IDENT && bx == 0) for (int c = tid; c < 256 * NS_ID; c += 256) a.gG[c] = 0.f;   // (summed into by the slab reduce behind this launch)
 
   // ---- AGPR residents: this wave's slice of [W_i2g^T | W_o2g^T] (stage E's B operand) and the dW accumulators
-  //      dwi/dwo[q][nt][r] <-> dW row q*64 + 16j + 4ag + r, col 16nt + arow
+  //      dwi/dwo[q][nt][r] <-> dW row q*64 + 16j + 4ag + r, col 16nt + arow  (IDENT: dwi column tile 0 is G, 1 / 2 the entity columns)
   f32x4 wiT[16], woT[16];
   {
-    const float* wi_row = a.WiT + (int64_t)(j * 16 + arow) * (4 * DH) + ag * 4;
+    const float* wi_row = a.WiT + (int64_t)((IDENT ? a.dt + 16 * (j & 1) : j * 16) + arow) * (4 * DH) + ag * 4;
     const float* wo_row = a.WoT + (int64_t)(j * 16 + arow) * (4 * DH) + ag * 4;
 #pragma unroll
     for (int S = 0; S < 16; ++S) { wiT[S] = *(const f32x4*)(wi_row + S * 16); woT[S] = *(const f32x4*)(wo_row + S * 16); }
@@ -127,7 +159,8 @@ __device__ __forceinline__ void bwd_body(const BwdArgs& a, const int bx, const i
 #pragma unroll
     for (int nt = 0; nt < 4; ++nt) {
       dwi[q][nt] = f32x4{0.f, 0.f, 0.f, 0.f}; dwo[q][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
-      asm volatile("" : "+a"(dwi[q][nt])); asm volatile("" : "+a"(dwo[q][nt]));
+      if (nt < NXT) asm volatile("" : "+a"(dwi[q][nt]));
+      asm volatile("" : "+a"(dwo[q][nt]));
     }
   }
 
@@ -202,7 +235,8 @@ __device__ __forceinline__ void bwd_body(const BwdArgs& a, const int bx, const i
     // last consumer has issued (the factors after the VALU block, each B fragment after its 32 MFMAs), so the
     // loads have ~3k cycles of MFMA issue to land in.
     f32x4 P[6], up, bin[4], bhp[4];
-    auto load_P = [&](int mt, int t) {
+    auto load_P = [&](const int slot, int t) {
+      const int mt = mof(slot);
 #pragma unroll
       for (int k = 0; k < 6; ++k) P[k] = *(const f32x4*)frag_ptr(mt, t, ly, j, k);
       if constexpr (!TOP && NMT == 1) {
@@ -221,14 +255,22 @@ __device__ __forceinline__ void bwd_body(const BwdArgs& a, const int bx, const i
         } else up = *(const f32x4*)(dx_tile + (mt * T + t) * 1024);
       } else if (!TOP) up = *(const f32x4*)(dx_tile + (mt * T + t) * 1024);
     };
-    auto load_B = [&](int nt, int mt, int t, bool has_hp) {
+    auto load_B = [&](int nt, const int slot, int t, bool has_hp) {
+      const int mt = mof(slot);
       if (!BOTTOM) bin[nt] = *(const f32x4*)frag_ptr(mt, t, ly - 1, nt, 6);
       if (has_hp) bhp[nt] = *(const f32x4*)frag_ptr(mt, t - 1, ly, nt, 6);
     };
     // bottom layer: the dW_i2g B operands come from the x_t tile in LDS
-    auto load_bin_lds = [&](int nt, int mt) {
+    auto load_bin_lds = [&](int nt, const int slot) {
+      if (nt >= NXT) return;
+      const int mt = mof(slot);
 #pragma unroll
       for (int r = 0; r < 4; ++r) bin[nt][r] = in_t[(mt * 16 + ag * 4 + r) * LDA + nt * 16 + arow];
+    };
+    // bottom layer: this thread's share of step t's x tile (t counted from the batch's step 0)
+    auto gather_load_x = [&](const int t, f32x4 (&v)[MTR * 16 / 256]) {
+      if constexpr (IDENT) gather_load_ident(a, t, ids + ipar * IDS_BUF, v);
+      else gather_load_planes<256, MTR>(a, gsrc, tile, t, ids + ipar * IDS_BUF, v);
     };
     const int tt_hi = late ? Te - 1 - ho.d : Te - 1;   // first step this piece runs
     f32x4 dc[NMT], dh[NMT];
@@ -266,7 +308,7 @@ __device__ __forceinline__ void bwd_body(const BwdArgs& a, const int bx, const i
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's pieces of the tile's ids have landed (requested a tile ago)
         lds_barrier();  // ... everyone's have; the previous tile's x tile is fully consumed
         f32x4 nin[MTR * 16 / 256];
-        gather_load_planes<256, MTR>(a, gsrc, tile, k0 + tt_first, ids + ipar * IDS_BUF, nin);
+        gather_load_x(k0 + tt_first, nin);
         gather_store<256, MTR>(in_t, nin);
       }
       if (next >= 0) request_tile(next, ipar ^ 1);   // (the other id buffer: last read by the tile before, behind the barrier above)
@@ -301,7 +343,7 @@ __device__ __forceinline__ void bwd_body(const BwdArgs& a, const int bx, const i
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
 #pragma unroll
-          for (int r = 0; r < 4; ++r) dA_t[(mt * 16 + ag * 4 + r) * LDD + q * DH + j * 16 + arow] = dA[q][r];
+          for (int r = 0; r < 4; ++r) dA_t[(mof(mt) * 16 + ag * 4 + r) * LDD + q * DH + j * 16 + arow] = dA[q][r];
           dbias[q] += (dA[q][0] + dA[q][1]) + (dA[q][2] + dA[q][3]);
         }
         __builtin_amdgcn_sched_barrier(0);
@@ -316,7 +358,7 @@ __device__ __forceinline__ void bwd_body(const BwdArgs& a, const int bx, const i
           for (int r = 0; r < 4; ++r)
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-              KPRN_MFMA_ACC_A(dwi[q][nt], dA[q][r], bin[nt][r]);
+              if (nt < NXT) KPRN_MFMA_ACC_A(dwi[q][nt], dA[q][r], bin[nt][r]);
               if (REC) KPRN_MFMA_ACC_A(dwo[q][nt], dA[q][r], bhp[nt][r]);
             }
           __builtin_amdgcn_sched_barrier(0);
@@ -338,7 +380,7 @@ __device__ __forceinline__ void bwd_body(const BwdArgs& a, const int bx, const i
       TPROBE(3)  // mid barrier wait
       // bottom layer: x_{t-1} is requested here (latency hides under stage E) and lands after it
       f32x4 nin[MTR * 16 / 256];
-      if (BOTTOM && REC) gather_load_planes<256, MTR>(a, gsrc, tile, k0 + t - 1, ids + ipar * IDS_BUF, nin);
+      if (BOTTOM && REC) gather_load_x(k0 + t - 1, nin);
 
       // ---- E. [dx | dh_prev] = dA * [W_i2g | W_o2g]; this wave: columns 16j..16j+15 of each ----------
       f32x4 ax[4], ah[4];
@@ -346,7 +388,50 @@ __device__ __forceinline__ void bwd_body(const BwdArgs& a, const int bx, const i
 #pragma unroll
         for (int q = NMT; q < 4; ++q) { ax[q] = f32x4{0.f, 0.f, 0.f, 0.f}; ah[q] = f32x4{0.f, 0.f, 0.f, 0.f}; }
       }
-      {
+      if constexpr (IDENT) { ax[2] = f32x4{0.f, 0.f, 0.f, 0.f}; ax[3] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+      if constexpr (IDENT) {
+        // dx: entity column tile (j & 1) of the slots 0, 1; dh: all four slots.  Per k-group S: 8 MFMAs on each own slot's A fragment (dx, dh alternating),
+        // then the other two slots' dh alternating, so that no MFMA chains on the one before it; the next fragment is always in flight.
+        const float* abase = dA_t + arow * LDD + ag * 4;
+        auto afrag = [&](const int slot, const int S) { return *(const f32x4*)(abase + mof(slot) * 16 * LDD + S * 16); };
+        if (REC) {
+          f32x4 p0 = afrag(0, 0), p1, p2, p3;
+#pragma unroll
+          for (int S = 0; S < 16; ++S) {
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+              const f32x4 a4 = (i == 0) ? p0 : p1;
+              if (S == 0) { KPRN_MFMA_Z(ax[i], a4[0], wiT[S][0]); KPRN_MFMA_Z(ah[i], a4[0], woT[S][0]); }
+              else { KPRN_MFMA(ax[i], a4[0], wiT[S][0]); KPRN_MFMA(ah[i], a4[0], woT[S][0]); }
+              KPRN_MFMA(ax[i], a4[1], wiT[S][1]); KPRN_MFMA(ah[i], a4[1], woT[S][1]);
+              if (i == 0) p1 = afrag(1, S);
+              else { p2 = afrag(2, S); p3 = afrag(3, S); }
+              KPRN_MFMA(ax[i], a4[2], wiT[S][2]); KPRN_MFMA(ah[i], a4[2], woT[S][2]);
+              KPRN_MFMA(ax[i], a4[3], wiT[S][3]); KPRN_MFMA(ah[i], a4[3], woT[S][3]);
+            }
+            const f32x4 a2 = p2, a3 = p3;
+            if (S == 0) { KPRN_MFMA_Z(ah[2], a2[0], woT[S][0]); KPRN_MFMA_Z(ah[3], a3[0], woT[S][0]); }
+            else { KPRN_MFMA(ah[2], a2[0], woT[S][0]); KPRN_MFMA(ah[3], a3[0], woT[S][0]); }
+            KPRN_MFMA(ah[2], a2[1], woT[S][1]); KPRN_MFMA(ah[3], a3[1], woT[S][1]);
+            if (S + 1 < 16) p0 = afrag(0, S + 1);
+            KPRN_MFMA(ah[2], a2[2], woT[S][2]); KPRN_MFMA(ah[3], a3[2], woT[S][2]);
+            KPRN_MFMA(ah[2], a2[3], woT[S][3]); KPRN_MFMA(ah[3], a3[3], woT[S][3]);
+          }
+        } else {
+          // t = 0: dx only, the two own slots alternating
+          f32x4 p0 = afrag(0, 0), p1 = afrag(1, 0);
+#pragma unroll
+          for (int S = 0; S < 16; ++S) {
+            const f32x4 a0 = p0, a1 = p1;
+            if (S == 0) { KPRN_MFMA_Z(ax[0], a0[0], wiT[S][0]); KPRN_MFMA_Z(ax[1], a1[0], wiT[S][0]); }
+            else { KPRN_MFMA(ax[0], a0[0], wiT[S][0]); KPRN_MFMA(ax[1], a1[0], wiT[S][0]); }
+            KPRN_MFMA(ax[0], a0[1], wiT[S][1]); KPRN_MFMA(ax[1], a1[1], wiT[S][1]);
+            if (S + 1 < 16) { p0 = afrag(0, S + 1); p1 = afrag(1, S + 1); }
+            KPRN_MFMA(ax[0], a0[2], wiT[S][2]); KPRN_MFMA(ax[1], a1[2], wiT[S][2]);
+            KPRN_MFMA(ax[0], a0[3], wiT[S][3]); KPRN_MFMA(ax[1], a1[3], wiT[S][3]);
+          }
+        }
+      } else {
         const float* abase = dA_t + arow * LDD + ag * 4;
         if (REC) {
           // groups (S, mt): one A fragment feeds 8 MFMAs (4 k-slots x {dx, dh}); the next fragment is requested mid-group
@@ -406,10 +491,11 @@ __device__ __forceinline__ void bwd_body(const BwdArgs& a, const int bx, const i
       if (REC) KPRN_PIN_V4(ah);
       if constexpr (NMT == 1) { if (!REC) ax[0] += ax[1]; }
       if (BOTTOM && REC) gather_store<256, MTR>(in_t, nin);
-      const bool compact = BOTTOM && a.DXe != nullptr && wcls == 1;   // (wave-uniform)
+      const bool compact = !IDENT && BOTTOM && a.DXe != nullptr && wcls == 1;   // (wave-uniform)
 #pragma unroll
       for (int mt = 0; mt < NMT; ++mt) {
         if (REC) dh[mt] = ah[mt];  // already in the layout stage C of step t-1 reads
+        if constexpr (IDENT) continue;   // (dx of the entity slice only: DXe below)
         // dx in fragment order: the layer below (or, bottom layer, the small-table gradient job) reloads it the same way,
         // 1 KiB per instruction; in place -- this thread read this very slot as `up` at the start of the step.
         // Rows past N: exact zeros (dA = 0 there).
@@ -428,7 +514,14 @@ __device__ __forceinline__ void bwd_body(const BwdArgs& a, const int bx, const i
 #pragma unroll
           for (int r = 0; r < 4; ++r) de_row[(int64_t)(mt * 16 + r) * T * a.de] = ax[mt][r];
       }
-      if (BOTTOM && a.small_lds && wcls != 1) {   // (wave-uniform)
+      if constexpr (IDENT) {
+        float* de_row = a.DXe + ((n0 + ag * 4) * T + k0 + t) * (int64_t)a.de + 16 * (j & 1) + arow;
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) de_row[(int64_t)(mof(i) * 16 + r) * T * a.de] = ax[i][r];
+      }
+      if (!IDENT && BOTTOM && a.small_lds && wcls != 1) {   // (wave-uniform)
         // nn.LookupTable backward of the type / relation tables (net/FeatureEmbedding.lua:112-121, 86): tables of at most 16 rows, so the gradient is a one-hot
         // product on the dx registers this wave holds anyway (its 16 columns ARE a type / relation slice): grad[v][col] += sum_rows [id(row) == v] dx[row][col]
         // = D += A B with A = one-hot [16 v x 4 k], B = dx [4 k x 16 col]; MFMA (mt, r) contracts over the rows {16 mt + 4 ag + r}: lane (ag, arow) holds
@@ -501,7 +594,7 @@ __device__ __forceinline__ void bwd_body(const BwdArgs& a, const int bx, const i
       if (v != 0.f) unsafeAtomicAdd(a.PG + c, v);
     }
   }
-  if (BOTTOM && a.small_lds && wcls != 1) {
+  if (!IDENT && BOTTOM && a.small_lds && wcls != 1) {
     const f32x4 sg = sacc[0] + sacc[1];
     const int V = (wcls == 0) ? a.Vt : a.Vr, width = (wcls == 0) ? a.dt : a.dr;
     float* g = ((wcls == 0) ? a.gWt : a.gWr) + (j * 16 + arow - ((wcls == 0) ? 0 : a.dt + a.de));
@@ -517,9 +610,12 @@ __device__ __forceinline__ void bwd_body(const BwdArgs& a, const int bx, const i
   // were measured slower: they execute at the memory side, the per-XCD L2s are not coherent)
   KPRN_MFMA_DRAIN();
 #pragma unroll
-  for (int q = 0; q < 4; ++q) KPRN_PIN_A8(dwi[q], dwo[q]);
+  for (int q = 0; q < 4; ++q) {
+    if constexpr (IDENT) asm volatile("" : "+a"(dwi[q][0]), "+a"(dwi[q][1]), "+a"(dwi[q][2]), "+a"(dwo[q][0]), "+a"(dwo[q][1]), "+a"(dwo[q][2]), "+a"(dwo[q][3]));
+    else KPRN_PIN_A8(dwi[q], dwo[q]);
+  }
   {
-    float* pw = a.part + (int64_t)bx * PART;
+    float* pw = a.part + (int64_t)bx * PART_G;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
 #pragma unroll
@@ -527,7 +623,17 @@ __device__ __forceinline__ void bwd_body(const BwdArgs& a, const int bx, const i
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int64_t grow = (int64_t)q * DH + j * 16 + ag * 4 + r;
-          pw[grow * DH + nt * 16 + arow] = dwi[q][nt][r];
+          if constexpr (IDENT) {
+            if (nt == 0) pw[PART + grow * NS_ID + arow] = dwi[q][0][r];
+            else if (nt < NXT) pw[grow * DH + a.dt + (nt - 1) * 16 + arow] = dwi[q][nt][r];
+            else {
+              // the type / relation columns of the slab: zero (their gradient leaves as G; the slab reduce still adds the prefix steps' rank-1 terms there)
+              pw[grow * DH + (arow < a.dt ? arow : arow + a.de)] = 0.f;
+              pw[grow * DH + (16 + arow < a.dt ? 16 + arow : 16 + arow + a.de)] = 0.f;
+            }
+          } else {
+            pw[grow * DH + nt * 16 + arow] = dwi[q][nt][r];
+          }
           pw[256 * 64 + grow * DH + nt * 16 + arow] = dwo[q][nt][r];
         }
       }
@@ -555,6 +661,8 @@ __device__ __forceinline__ void bwd_body(const BwdArgs& a, const int bx, const i
 
 template <bool BOTTOM, bool TOP, int NMT>
 __global__ __launch_bounds__(256, 1) void k_lstm_bwd(BwdArgs a) { bwd_body<BOTTOM, TOP, NMT>(a, (int)blockIdx.x, (int)gridDim.x); }
+// the bottom layer of two through the small-table identity (bwd_body IDENT)
+__global__ __launch_bounds__(256, 1) void k_lstm_bwd_ident(BwdArgs a) { bwd_body<true, false, 4, true>(a, (int)blockIdx.x, (int)gridDim.x); }
 
 // Two layers, small batches: BOTH layers' BPTT in one launch, workgroups [0, g) the top layer's, [g, 2 g) the bottom layer's, all resident at once (the host
 // launches this only when 2 g <= the CUs: a bottom-layer workgroup that waits must never keep a top-layer one off the chip).  The bottom layer runs one step
@@ -733,14 +841,16 @@ bool transpose_job(kprn_handle* h, kk::TransposeJob* tj) {
 
 bool bwd_supported(const kprn_handle* h, int T) { return fwd_supported(h, T); }
 
-template <bool BOTTOM, bool TOP, int NMT = 4>
+template <bool BOTTOM, bool TOP, int NMT = 4, bool IDENT = false>
 static void launch_bwd(kprn_handle* h, const BwdArgs& a, int grid) {
   size_t lds_bytes = (size_t)MT * LDD * sizeof(float);
   if (BOTTOM) lds_bytes += (size_t)MT * LDA * sizeof(float) + 2 * (MT * MAXT_LDS * 4) * sizeof(int32_t);
   lds_bytes += (size_t)(KCAP + 1) * PFB * sizeof(float);
   static PerDeviceOnce attr_done;  // one per template instantiation (the call is host time in front of every launch otherwise)
-  if (attr_done.need()) HIP_TRY(hipFuncSetAttribute((const void*)k_lstm_bwd<BOTTOM, TOP, NMT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-  hipLaunchKernelGGL((k_lstm_bwd<BOTTOM, TOP, NMT>), dim3(grid), dim3(256), lds_bytes, h->stream, a);
+  const void* fn = IDENT ? (const void*)k_lstm_bwd_ident : (const void*)k_lstm_bwd<BOTTOM, TOP, NMT>;
+  if (attr_done.need()) HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+  if constexpr (IDENT) hipLaunchKernelGGL(k_lstm_bwd_ident, dim3(grid), dim3(256), lds_bytes, h->stream, a);
+  else hipLaunchKernelGGL((k_lstm_bwd<BOTTOM, TOP, NMT>), dim3(grid), dim3(256), lds_bytes, h->stream, a);
   HIP_TRY(hipGetLastError());
 }
 
@@ -761,7 +871,7 @@ void backward(kprn_handle* h, const kprn_batch* b, int cid) {
     HIP_TRY(kprn_dev_malloc((void**)&s->DXe, (size_t)(ct * (cn + 2 * MT) + KCAP) * c.de * sizeof(float)));
     s->cap_Nb = cn; s->cap_Tb = ct;
   }
-  if (!s->part) HIP_TRY(kprn_dev_malloc((void**)&s->part, (size_t)2 * s->num_cu * PART * sizeof(float)));  // one slab set per layer
+  if (!s->part) HIP_TRY(kprn_dev_malloc((void**)&s->part, (size_t)2 * s->num_cu * PART_G * sizeof(float)));  // one slab set per layer
   static const bool want_timing = KPRN_DEV_ENV("KPRN_TIMING") != nullptr;
   if (want_timing && !s->timing) HIP_TRY(kprn_dev_malloc((void**)&s->timing, (size_t)s->num_cu * 12 * sizeof(unsigned long long)));
   if (s->wt_dirty) {  // (normally done already: the transposes ride in the loss-stage launch, transpose_job())
@@ -781,7 +891,7 @@ void backward(kprn_handle* h, const kprn_batch* b, int cid) {
   const int64_t n_tiles = small ? (N + 15) / 16 : n_tiles64;
   const int nmt = small ? 1 : 4;
   const int grid = (int)std::min<int64_t>(n_tiles, (int64_t)s->num_cu);
-  bool have_r1 = false, reduced = false;
+  bool have_r1 = false, reduced = false, ident = false;
   std::unique_ptr<ProfScope> bwd_scope;
   bidx::SlabReduce ra;
   BwdArgs pipe_top;
@@ -799,7 +909,7 @@ void backward(kprn_handle* h, const kprn_batch* b, int cid) {
     a.gWi = gd + h->layer[l].Wi; a.gbi = gd + h->layer[l].bi; a.gWo = gd + h->layer[l].Wo;
     a.gWt = gd + h->off_Wt; a.gWe = h->g_We; a.gWr = gd + h->off_Wr;
     a.n_tiles = n_tiles;
-    a.part = s->part + (size_t)l * s->num_cu * PART; a.timing = s->timing;
+    a.part = s->part + (size_t)l * s->num_cu * PART_G; a.timing = s->timing;
     a.dbg = kprn_dbg_mask();
     a.ho = handover_args(h, grid);
     const bool bottom = (l == 0), top = (l == L - 1);
@@ -812,7 +922,12 @@ void backward(kprn_handle* h, const kprn_batch* b, int cid) {
     a.DXe = (bottom && s->DXe_on) ? s->DXe : nullptr;
     // ... or, round 6, formed inside the bottom layer's launch (one-hot MFMAs on the dx registers; option "fused_small_tables")
     // (64-path tiles only: at small batches the passenger job hides in a launch that is latency-bound anyway, and the 16 extra MFMAs per step do not)
-    const bool small_lds = bottom && small_job && have_index && !(a.dbg & 1) && h->fused_small_tables && !small;
+    // ... or, option "small_tables" (default), through the small-table identity (bwd_body IDENT): no dx for those slices at all, G = dA^T [S_r | S_t] leaves
+    // with the weight-gradient slabs and kk::small_tables_finish forms both tables' gradients and their blocks of dW_i2g from it
+    ident = bottom && !top && !small && small_job && have_index && !(a.dbg & 1) && h->small_tables && c.de == 32 && c.Vt + c.Vr <= NS_ID;
+    if (ident && !s->gG) HIP_TRY(kprn_dev_malloc((void**)&s->gG, (size_t)256 * NS_ID * sizeof(float)));
+    a.gG = ident ? s->gG : nullptr;
+    const bool small_lds = bottom && small_job && have_index && !(a.dbg & 1) && h->fused_small_tables && !small && !ident;
     a.small_lds = small_lds ? 1 : 0;
     {
       // one event pair around the L back-to-back launches of the family (an event pair costs ~4 us of stream time)
@@ -837,6 +952,7 @@ void backward(kprn_handle* h, const kprn_batch* b, int cid) {
       } else
       if (small) { if (bottom) launch_bwd<true, false, 1>(h, a, grid); else launch_bwd<false, true, 1>(h, a, grid); }   // (L == 2)
       else if (bottom && top) launch_bwd<true, true>(h, a, grid);
+      else if (bottom && ident) launch_bwd<true, false, 4, true>(h, a, grid);
       else if (bottom) launch_bwd<true, false>(h, a, grid);
       else if (top) launch_bwd<false, true>(h, a, grid);
       else launch_bwd<false, false>(h, a, grid);
@@ -847,10 +963,11 @@ void backward(kprn_handle* h, const kprn_batch* b, int cid) {
     if (bottom) {
       for (int q = 0; q < 2; ++q) {
         const int ll = q < L ? q : 0;
-        ra.part[q] = s->part + (size_t)ll * s->num_cu * PART;
+        ra.part[q] = s->part + (size_t)ll * s->num_cu * PART_G;
         ra.gWi[q] = gd + h->layer[ll].Wi; ra.gWo[q] = gd + h->layer[ll].Wo; ra.gbi[q] = gd + h->layer[ll].bi;
       }
-      ra.nslab = grid; ra.n_elem = PART; ra.L = L; ra.ny = 16;
+      ra.nslab = grid; ra.n_elem = ident ? PART_G : PART; ra.slab = PART_G; ra.L = L; ra.ny = 16;
+      ra.gG[0] = ident ? s->gG : nullptr; ra.gG[1] = nullptr;
       ra.r1 = s->r1; ra.kmax = have_r1 ? b->h_kmax : 0; ra.kcap = KCAP; ra.r1_stride = R1; ra.G = 4; ra.H = DH;
     }
     if (bottom && have_index && !(a.dbg & 1)) {
@@ -861,7 +978,7 @@ void backward(kprn_handle* h, const kprn_batch* b, int cid) {
       sg.nT = c.num_types; sg.dt = c.dt; sg.de = c.de; sg.dr = c.dr; sg.Vt = c.Vt; sg.Vr = c.Vr; sg.gWt = a.gWt; sg.gWr = a.gWr; sg.nblocks = 4 * s->num_cu;
       { static const int sgb = KPRN_DEV_ENV("KPRN_SG_BLOCKS") ? atoi(KPRN_DEV_ENV("KPRN_SG_BLOCKS")) : 0; if (sgb > 0) sg.nblocks = sgb; }   // (measurement)
       bidx::entity_grad(strm, s->DXe, /*compact entity slice=*/2, b->key_sorted, b->pos_sorted, b->n_index, N, T, DH, c.dt, c.de, c.Ve, a.gWe, &ra,
-                        (small_job && !a.small_lds) ? &sg : nullptr);
+                        (small_job && !a.small_lds && !ident) ? &sg : nullptr);
       reduced = true;
     }
     const bool small_in_kernel = small_job && have_index;   // (handled above)
@@ -915,8 +1032,14 @@ void backward(kprn_handle* h, const kprn_batch* b, int cid) {
   }
   if (!reduced) {
     ProfScope ps(h, "dw_reduce");
-    hipLaunchKernelGGL(k_reduce_partials, dim3((PART + 255) / 256, ra.ny, L), dim3(256), 0, strm, ra);
+    hipLaunchKernelGGL(k_reduce_partials, dim3((ra.n_elem + 255) / 256, ra.ny, L), dim3(256), 0, strm, ra);
     HIP_TRY(hipGetLastError());
+  }
+  if (ident) {
+    // G (summed by the reduce above) -> dW_i2g[:, type | relation cols] += G W_table, gW_table += G^T W_i2g[:, its cols], with this step's weights
+    ProfScope ps(h, "small_tables_finish");
+    kk::small_tables_finish(strm, s->gG, NS_ID, 4 * DH, DH, c.dt, c.de, c.dr, c.Vt, c.Vr, h->dense + h->off_Wt, h->dense + h->off_Wr, h->dense + h->layer[0].Wi,
+                            gd + h->layer[0].Wi, gd + h->off_Wt, gd + h->off_Wr, /*ct_has_entity=*/false);
   }
 }
 
@@ -931,7 +1054,7 @@ void params_changed(kprn_handle* h) {
 void release(kprn_handle* h) {
   State* s = (State*)h->fused_state;
   if (!s) return;
-  for (float* p : {s->save_frag, s->WT, s->DX, s->DXe, s->part, s->part_small, s->pfb, s->pfs, s->pfx, s->PG, s->r1, s->mc_bias, s->mc_hseq[0], s->mc_hseq[1],
+  for (float* p : {s->save_frag, s->WT, s->DX, s->DXe, s->part, s->gG, s->part_small, s->pfb, s->pfs, s->pfx, s->PG, s->r1, s->mc_bias, s->mc_hseq[0], s->mc_hseq[1],
                    s->ho_state[0], s->ho_state[1]}) if (p) hipFree(p);
   for (unsigned* p : {s->ho_flag[0], s->ho_flag[1], s->pipe_flag}) if (p) hipFree(p);
   if (s->mc_wsp) hipFree(s->mc_wsp);

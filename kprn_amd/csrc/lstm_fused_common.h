@@ -371,7 +371,8 @@ struct State {
   float* mc_hseq[2] = {nullptr, nullptr}; int64_t mc_capN[2] = {0, 0}; int mc_capT[2] = {0, 0};  // [stream: main, scoring]
   int64_t pf_batch = -1;    // batch serial the table was computed for (-1: stale)
 
-  float* part = nullptr;    // [L][num_cu][PART]
+  float* part = nullptr;    // [L][num_cu][PART_G]
+  float* gG = nullptr;      // [256][NS_ID] G of the small-table identity (lstm_fused_bwd.hip IDENT)
   // time-split tile hand-over: slots + flags per launch context (0: the engine's main stream, 1: the scoring stream -- the two run side by side),
   // one launch serial for all of them, the fault word in page-locked host memory
   float* ho_state[2] = {nullptr, nullptr}; unsigned* ho_flag[2] = {nullptr, nullptr};
