@@ -82,7 +82,10 @@ typedef struct {
                                     tolerances as 0.
                                 3 = f32x3: as 2 with two fp16 pieces (2 x 11 mantissa bits) of every power-of-two pre-scaled
                                     operand and three partial products: half the matrix instructions of 2; the operands keep 22
-                                    of their 24 mantissa bits.  Same tolerances.  New options, not in the reference.            */
+                                    of their 24 mantissa bits.  Same tolerances.  Operand range: the fp16 high piece overflows,
+                                    and the result is silently NaN, once |W_o2g| or the top layer's |W_i2g| exceeds 88.7 on the g
+                                    rows (177 on i, f, o), the bottom layer's |W_i2g| 1419 (2838), or a table value 4094
+                                    (65504 / (2^8 * 2 log2 e), / (2^4 * ...), / 2^4).  New options, not in the reference.      */
   int32_t reducer;           /* -topK: 0 = Max, 1 = TopK+Mean, 2 = LogSumExp (OneModel.lua:284-293) */
   int32_t K;                 /* -K                                                               */
   int32_t device_id;         /* HIP device ordinal                                               */

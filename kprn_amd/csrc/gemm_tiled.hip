@@ -21,6 +21,7 @@
 
 #include <algorithm>
 
+#include "gate_math.h"
 #include "kprn_internal.h"
 
 namespace {
@@ -53,22 +54,8 @@ struct TArgs {
   const float* bias2; const float* mask; int relu;   // EPI_RNN: h2h bias, MaskZero flags [M], ReLU / Tanh
 };
 
-// Gate functions at fp32 accuracy on v_exp_f32 / v_rcp_f32 (1 ulp each) instead of libm's ~40-instruction expf / tanhf: the cell
-// epilogue of a 128 x 32-unit tile evaluates 80 of them per thread, which with libm cost a quarter of the tile's MFMA time.
-// e^x = 2^t (1 + ln2 (x log2e - t)): the product's rounding residual (and log2e's low word) is folded back in, so the result
-// stays within ~2 ulp for any x; 1 / (1 + e^-x) and tanh x = (1 - e^-2|x|) / (1 + e^-2|x|) then have ABSOLUTE error <= 1.5e-7
-// (the same class as the D = H = 64 persistent kernels' gate math; tests/test_gpu_wide.py gates it against the f64 oracle).
-__device__ __forceinline__ float exp_fast(float x) {
-  const float t = x * 1.4426950408889634f;
-  const float lo = __builtin_fmaf(x, 1.9259629911e-8f, __builtin_fmaf(x, 1.4426950408889634f, -t));
-  const float e = __builtin_amdgcn_exp2f(t);
-  return __builtin_fmaf(e, lo * 0.6931471805599453f, e);
-}
-__device__ __forceinline__ float sigm(float x) { return __builtin_amdgcn_rcpf(1.0f + exp_fast(-x)); }
-__device__ __forceinline__ float tanh_fast(float x) {
-  const float t = exp_fast(-2.0f * __builtin_fabsf(x));
-  return __builtin_copysignf((1.0f - t) * __builtin_amdgcn_rcpf(1.0f + t), x);
-}
+// Gate functions: sigm / tanh_fast of gate_math.h (fp32 accuracy on v_exp_f32 / v_rcp_f32, absolute error <= 1.5e-7 for every
+// finite argument; tests/test_gpu_gate_math.py sweeps them, tests/test_gpu_wide.py gates the cell against the f64 oracle).
 // 16-byte vectors at any 4-byte aligned address: gfx950 runs in unaligned access mode (the compiler itself emits
 // global_load/store_dwordx4 for an align-4 <4 x float>), so rows need no particular pitch -- config.sh's H = 250 takes the same
 // path as H = 256 (8-byte vectors, the previous answer to odd pitches, cost 25 % on the rnn step: twice the load / LDS-store count)

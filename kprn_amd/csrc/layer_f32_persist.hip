@@ -23,6 +23,7 @@
 #include <algorithm>
 #include <type_traits>
 
+#include "gate_math.h"
 #include "kprn_internal.h"
 
 namespace lp32 {
@@ -64,18 +65,7 @@ __device__ __forceinline__ void dma16(const void* gsrc, unsigned lds_dst) {
 }
 __device__ __forceinline__ void bar() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
-// gate functions at fp32 accuracy (gemm_tiled.hip has the error analysis: absolute error of sigma / tanh <= 1.5e-7)
-__device__ __forceinline__ float exp_fast(float x) {
-  const float t = x * 1.4426950408889634f;
-  const float lo = __builtin_fmaf(x, 1.9259629911e-8f, __builtin_fmaf(x, 1.4426950408889634f, -t));
-  const float e = __builtin_amdgcn_exp2f(t);
-  return __builtin_fmaf(e, lo * 0.6931471805599453f, e);
-}
-__device__ __forceinline__ float sigm(float x) { return __builtin_amdgcn_rcpf(1.0f + exp_fast(-x)); }
-__device__ __forceinline__ float tanh_fast(float x) {
-  const float t = exp_fast(-2.0f * __builtin_fabsf(x));
-  return __builtin_copysignf((1.0f - t) * __builtin_amdgcn_rcpf(1.0f + t), x);
-}
+// (gate functions at fp32 accuracy: sigm / tanh_fast of gate_math.h, absolute error <= 1.5e-7 for every finite argument)
 __device__ __forceinline__ void store4(float* __restrict__ p, const f32x4 v, int nv) {
   if (nv >= 4) *(f32x4u*)p = v;
   else {

@@ -15,6 +15,7 @@
 
 #include <algorithm>
 
+#include "gate_math.h"
 #include "kprn_internal.h"
 
 namespace bf16p {
@@ -26,10 +27,8 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int TK = 64, LDB = TK + 8;   // LDS row pitch in elements (144 bytes)
 
-// gate functions on v_exp_f32 / v_rcp_f32 (1 ulp each): at bf16 precision the cell's transcendental functions, not the MFMAs, were
-// most of this kernel's time with libm's expf / tanhf (~40 instructions each against ~17 cycles per 16 KFLOP MFMA)
-__device__ __forceinline__ float sigm(float x) { return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * x)); }
-__device__ __forceinline__ float tanh_fast(float x) { return 2.0f * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-2.8853900817779268f * x)) - 1.0f; }
+// gate functions: sigm_e2 / tanh_e2 of gate_math.h (v_exp_f32 / v_rcp_f32: at bf16 precision the cell's transcendental functions,
+// not the MFMAs, were most of this kernel's time with libm's expf / tanhf, ~40 instructions each against ~17 cycles per 16 KFLOP MFMA)
 __device__ __forceinline__ bf16 tobf(float x) { return (bf16)x; }   // round to nearest even
 
 enum { EPI_STORE = 0, EPI_ACCUM = 1, EPI_LSTM = 2 };
@@ -250,12 +249,12 @@ __global__ __launch_bounds__(Geo<BIG>::NT, BIG ? 1 : 2) void k_gemm16(GArgs a) {
         bf16x4 gi, gg4, gf, go, hb;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const float ig = sigm(acc[i][0][r] + bq[0][r]);
-          const float gg = tanh_fast(acc[i][1][r] + bq[1][r]);
-          const float fg = sigm(acc[i][2][r] + bq[2][r]);
-          const float og = sigm(acc[i][3][r] + bq[3][r]);
+          const float ig = sigm_e2(acc[i][0][r] + bq[0][r]);
+          const float gg = tanh_e2(acc[i][1][r] + bq[1][r]);
+          const float fg = sigm_e2(acc[i][2][r] + bq[2][r]);
+          const float og = sigm_e2(acc[i][3][r] + bq[3][r]);
           cc[r] = fg * cp[r] + ig * gg;
-          hh[r] = og * tanh_fast(cc[r]);
+          hh[r] = og * tanh_e2(cc[r]);
           gi[r] = tobf(ig); gg4[r] = tobf(gg); gf[r] = tobf(fg); go[r] = tobf(og); hb[r] = tobf(hh[r]);
         }
         *(f32x4*)(a.cout + row * a.ldh + u) = cc;

@@ -33,6 +33,7 @@
 #include <algorithm>
 #include <type_traits>
 
+#include "gate_math.h"
 #include "kprn_internal.h"
 
 namespace bf16p {
@@ -118,8 +119,6 @@ template <class V> __device__ __forceinline__ void stb(rsrc_t r, unsigned voff, 
   static_assert(sizeof(V) == 8, "8-byte pieces");
   __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, v), r, (int)voff, (int)soff, 0);
 }
-
-__device__ __forceinline__ float tanh_fast(float x) { return 2.0f * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-2.8853900817779268f * x)) - 1.0f; }
 
 // the saves of this lane's quad of one chunk, per path tile
 template <int NPT> struct SvT { bf16x8 a0[NPT], a1[NPT]; bf16x4 c[NPT], cp[NPT]; };
@@ -249,7 +248,7 @@ __global__ __launch_bounds__(64 * NW, NPT == 1 ? 2 : 1) void k_lstm16_bwd_persis
         if constexpr (Gs < 8 && (Gs >> 2) < NPT) {
           constexpr int pt = Gs >> 2, r = Gs & 3;
           const float ig = (float)s.a0[pt][r], gv = (float)s.a0[pt][4 + r], fg = (float)s.a1[pt][r], og = (float)s.a1[pt][4 + r];
-          const float tc = tanh_fast((float)s.c[pt][r]);
+          const float tc = tanh_e2((float)s.c[pt][r]);
           const float cp = (float)s.cp[pt][r];
           const float dh = dh4[pt][r];
           const float dO = dh * tc;

@@ -35,6 +35,7 @@
 #include <algorithm>
 #include <type_traits>
 
+#include "gate_math.h"
 #include "kprn_internal.h"
 
 namespace bf16p {
@@ -117,9 +118,6 @@ template <class V, int AUX = 0> __device__ __forceinline__ void stb(rsrc_t r, un
   if constexpr (sizeof(V) == 16) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, (int)voff, (int)soff, AUX);
   else { static_assert(sizeof(V) == 8, "8- or 16-byte pieces"); __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, v), r, (int)voff, (int)soff, AUX); }
 }
-
-__device__ __forceinline__ float sigm(float x) { return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * x)); }
-__device__ __forceinline__ float tanh_fast(float x) { return 2.0f * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-2.8853900817779268f * x)) - 1.0f; }
 
 // ---- the cell of one finished chunk, as a software pipeline that rides behind the next chunk's MFMAs ---------------------------
 // A lane owns NPT x 4 elements (path tile, hidden unit) of the chunk.  One element = 25 VALU operations (10 of them exp2 / rcp),

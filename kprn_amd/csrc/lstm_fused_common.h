@@ -64,6 +64,7 @@ __device__ __forceinline__ void lds_atomic_add(float* p, float v) {
   __hip_atomic_fetch_add((lds_float*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 
+// absolute error over every finite float32 (tests/test_gpu_gate_math.py): fast_sigmoid <= 1.2e-7, fast_tanh <= 2.3e-7 (measured 1.108e-7 / 2.216e-7)
 __device__ __forceinline__ float fast_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
 __device__ __forceinline__ float fast_tanh(float x) { return 2.0f * __builtin_amdgcn_rcpf(1.0f + __expf(-2.0f * x)) - 1.0f; }
 
