@@ -45,6 +45,11 @@ int kprn_batch_create(kprn_handle*, const int32_t*, const float*, int32_t, int32
 void kprn_batch_destroy(kprn_handle*, kprn_batch*);
 int kprn_batch_slot_reserve(kprn_handle*, kprn_batch**, int32_t, int64_t, int32_t, int32_t, int32_t);
 int kprn_batch_feed_async(kprn_handle*, kprn_batch**, const int32_t*, const float*, int32_t, int32_t, int32_t, int32_t);
+int kprn_batch_create_ragged(kprn_handle*, const int32_t*, const int32_t*, const float*, int32_t, int64_t, int32_t, int32_t, kprn_batch**);
+int kprn_batch_feed_ragged_async(kprn_handle*, kprn_batch**, const int32_t*, const int32_t*, const float*, int32_t, int64_t, int32_t, int32_t);
+int kprn_host_ragged_plan(const int32_t*, int32_t, int64_t, int32_t*, int32_t*, int32_t*);
+int kprn_batch_num_paths(kprn_handle*, const kprn_batch*, int64_t*);
+int kprn_forward_ragged(kprn_handle*, const int32_t*, const int32_t*, int32_t, int64_t, int32_t, int32_t, int32_t, float*, float*);
 int kprn_batch_feed_rows_async(kprn_handle*, kprn_batch**, const int32_t*, const float*, int64_t, const int64_t*, int32_t, int32_t, int32_t, int32_t);
 int kprn_host_alloc(kprn_handle*, size_t, void**);
 int kprn_host_free(kprn_handle*, void*);

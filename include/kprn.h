@@ -177,6 +177,27 @@ int kprn_batch_slot_reserve(kprn_handle* h, kprn_batch** slot, int32_t max_pairs
 int kprn_host_batch_index(const int32_t* idx, int32_t B, int32_t P, int32_t T, int32_t F, int32_t num_types, int32_t Vt, int32_t Ve, int32_t Vr,
                           int32_t plan, int32_t threads, int32_t* idx_s, int32_t* perm, int32_t* slot_of, int32_t* tile_k, int32_t* pmeta,
                           int32_t* key_sorted, int32_t* pos_sorted, int32_t* uniq, int64_t* summary);
+/* ---- ragged batches (an extension: the reference has one path count per batch, one file per count) ----
+ * A ragged batch is B pairs over a flat id array idx [N,T,F]: pair b owns counts[b] >= 1 consecutive paths, N = sum(counts).  It is accepted
+ * wherever a kprn_batch is (scoring sync / async, kprn_backward_batch, kprn_train_step_batch, the kprn_dp_* calls); the recurrent kernels
+ * are the same (they are flat over the paths), the reducer over a pair's paths and the loss stage are segmented kernels.  The loss is scaled
+ * by the number of PAIRS, path_scores of kprn_forward_batch is [N,C].  A pair of at most 28 paths is reduced in the rectangular kernels'
+ * order (equal counts give the rectangular batch's bits in the forward pass); a batch with a longer pair reduces every pair with one
+ * wave (64 lanes).  At most 4096 paths per pair, N*T within 32-bit positions; a count outside 1..4096 or counts that do not add up to N
+ * are KPRN_E_ARG, and nothing of the slot is changed.                                                                               */
+int kprn_batch_create_ragged(kprn_handle* h, const int32_t* idx, const int32_t* counts, const float* labels /* [B] or NULL */,
+                             int32_t B, int64_t N, int32_t T, int32_t F, kprn_batch** out);
+/* kprn_batch_feed_async for a ragged batch ("feed_build" host or device); counts are read before the call returns.  A slot may hold a
+ * rectangular batch after a ragged one and the reverse (kprn_batch_slot_reserve sizes it for either).                               */
+int kprn_batch_feed_ragged_async(kprn_handle* h, kprn_batch** slot, const int32_t* idx, const int32_t* counts, const float* labels,
+                                 int32_t B, int64_t N, int32_t T, int32_t F);
+/* what the engine derives from the counts, on its own (no handle, no GPU): offsets [B+1]; wg_first [n_wg+1] = the first pair of each
+ * loss-stage workgroup (consecutive pairs, at most 16 pairs and at most 448 paths per workgroup; a longer pair is a workgroup of its own),
+ * room for B+1 entries; summary[8] = {n_wg, longest pair, 1 when the batch is reduced by a wave per pair, the limits: paths per pair,
+ * longest pair one thread reduces, paths per workgroup, pairs per workgroup, 0}.  KPRN_E_ARG as above.                              */
+int kprn_host_ragged_plan(const int32_t* counts, int32_t B, int64_t N, int32_t* offsets, int32_t* wg_first, int32_t* summary);
+/* paths of a batch: B*P, or N of a ragged batch */
+int kprn_batch_num_paths(kprn_handle* h, const kprn_batch* b, int64_t* n);
 /* page-locked host buffers for the feed (the reference preallocates its staging tensors likewise, BatcherFileList.lua:53-60) */
 int kprn_host_alloc(kprn_handle* h, size_t bytes, void** out);
 int kprn_host_free(kprn_handle* h, void* p);
@@ -196,9 +217,13 @@ int kprn_batch_handover_stats(kprn_handle* h, const kprn_batch* b, int64_t* out 
  * probs[B]      = Sigmoid(reduce_p(mapper))[:, classId]       (Select(2,classId))
  * all_probs     = optional [B,C] (before Select)
  * pooled        = optional [B,C] reducer output before Sigmoid
- * path_scores   = optional [B*P,C] mapper output (nn.Linear(H,46), OneModel.lua:275)      */
+ * path_scores   = optional [B*P,C] mapper output (nn.Linear(H,46), OneModel.lua:275); [N,C] for a ragged batch */
 int kprn_forward(kprn_handle* h, const int32_t* idx, int32_t B, int32_t P, int32_t T, int32_t F,
                  int32_t class_id, float* probs, float* all_probs);
+/* the same for a ragged batch in host buffers, one call (one user's candidate items, whatever their path counts): probs [B], all_probs
+ * optional [B,C]                                                                                                                 */
+int kprn_forward_ragged(kprn_handle* h, const int32_t* idx, const int32_t* counts, int32_t B, int64_t N, int32_t T, int32_t F,
+                        int32_t class_id, float* probs, float* all_probs);
 int kprn_forward_batch(kprn_handle* h, const kprn_batch* b, int32_t class_id,
                        float* probs, float* all_probs, float* pooled, float* path_scores);
 /* async variant for throughput loops: results stay on the device until kprn_read_probs  */

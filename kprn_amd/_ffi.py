@@ -71,6 +71,25 @@ def torch_rccl_path():
         return None
 
 
+RAGGED_MAX_SEG = 4096   # paths per pair of a ragged batch (kprn_host_ragged_plan refuses more)
+
+
+def host_ragged_plan(counts, N=None):
+    """kprn_host_ragged_plan (no handle, no GPU): -> dict(offsets [B+1], wg_first [n_wg+1], n_wg, max_count, wave, max_seg, thread_max, wg_paths,
+    wg_pairs); raises KprnError(E_ARG) for a count outside 1..max_seg or counts that do not add up to N"""
+    counts = np.ascontiguousarray(counts, np.int32)
+    B = int(counts.shape[0])
+    N = int(counts.astype(np.int64).sum()) if N is None else int(N)
+    off = np.zeros(B + 1, np.int32)
+    wg = np.zeros(B + 1, np.int32)
+    sm = np.zeros(8, np.int32)
+    rc = lib().kprn_host_ragged_plan(_fp(counts), B, C.c_int64(N), _fp(off), _fp(wg), _fp(sm))
+    if rc != 0:
+        raise KprnError(rc, "kprn_host_ragged_plan: bad counts")
+    return dict(offsets=off, wg_first=wg[:int(sm[0]) + 1].copy(), n_wg=int(sm[0]), max_count=int(sm[1]), wave=int(sm[2]), max_seg=int(sm[3]),
+                thread_max=int(sm[4]), wg_paths=int(sm[5]), wg_pairs=int(sm[6]))
+
+
 def format_score_lines(counter0, probs, labels):
     """bytes of the scoring writer's lines for pairs counter0 .. (kprn_format_score_lines; host-only)"""
     L = lib()
@@ -164,6 +183,7 @@ class Batch:
         if idx.ndim != 4:
             raise KprnError(E_ARG, "idx must be [B,P,T,F]")
         self.B, self.P, self.T, self.F = (int(x) for x in idx.shape)
+        self.counts = None
         lab = None if labels is None else np.ascontiguousarray(labels, dtype=np.float32)
         if lab is not None and lab.shape != (self.B,):
             raise KprnError(E_ARG, "labels must be [B]")
@@ -176,6 +196,7 @@ class Batch:
         self = cls.__new__(cls)
         self._attach(engine)
         self.B = self.P = 0
+        self.counts = None
         self.T, self.F, self.has_labels = T, F, with_labels
         engine._ck(engine.L.kprn_batch_slot_reserve(engine.h, C.byref(self.ptr), int(max_pairs), C.c_int64(int(max_paths)), int(T), int(F), int(bool(with_labels))))
         return self
@@ -188,6 +209,46 @@ class Batch:
         self.engine._ck(self.engine.L.kprn_batch_feed_async(self.engine.h, C.byref(self.ptr), _fp(idx), _fp(lab), self.B, self.P, self.T, self.F))
         return self
 
+    def _check_ragged(self, idx, counts, labels):
+        idx = np.ascontiguousarray(idx, dtype=np.int32)
+        counts = np.ascontiguousarray(counts, dtype=np.int32)
+        if idx.ndim != 3 or counts.ndim != 1 or counts.shape[0] < 1:
+            raise KprnError(E_ARG, "a ragged batch is idx [N,T,F] and counts [B]")
+        lab = None if labels is None else np.ascontiguousarray(labels, dtype=np.float32)
+        if lab is not None and lab.shape != counts.shape:
+            raise KprnError(E_ARG, "labels must be [B]")
+        return idx, counts, lab
+
+    def _set_ragged(self, idx, counts, lab):
+        self.B, self.P = int(counts.shape[0]), 0
+        self.N, self.T, self.F = (int(x) for x in idx.shape)
+        self.counts = counts
+        self.has_labels = lab is not None
+
+    @classmethod
+    def ragged(cls, engine, idx, counts, labels=None, feed=False):
+        """a ragged batch (kprn_batch_create_ragged): pair b owns counts[b] consecutive paths of idx [N,T,F].  feed=True: through the
+        streaming feed, as Batch(..., feed=True)."""
+        self = cls.__new__(cls)
+        self._attach(engine)
+        self.counts = None
+        if feed:
+            return self.refill_ragged(idx, counts, labels)
+        idx, counts, lab = self._check_ragged(idx, counts, labels)
+        engine._ck(engine.L.kprn_batch_create_ragged(engine.h, _fp(idx), _fp(counts), _fp(lab), int(counts.shape[0]), C.c_int64(int(idx.shape[0])),
+                                                     int(idx.shape[1]), int(idx.shape[2]), C.byref(self.ptr)))
+        self._set_ragged(idx, counts, lab)
+        return self
+
+    def refill_ragged(self, idx, counts, labels=None):
+        """streaming feed of a ragged batch into this slot (kprn_batch_feed_ragged_async); the slot may have held a rectangular batch"""
+        idx, counts, lab = self._check_ragged(idx, counts, labels)
+        self._src = (idx, lab)
+        self.engine._ck(self.engine.L.kprn_batch_feed_ragged_async(self.engine.h, C.byref(self.ptr), _fp(idx), _fp(counts), _fp(lab), int(counts.shape[0]),
+                                                                   C.c_int64(int(idx.shape[0])), int(idx.shape[1]), int(idx.shape[2])))
+        self._set_ragged(idx, counts, lab)
+        return self
+
     def refill_rows(self, data, labels, rows):
         """shuffled streaming feed (kprn_batch_feed_rows_async): pair i of the minibatch = row rows[i] of the file's arrays
         data [n,P,T,F] int32 / labels [n] float32, gathered by the engine's worker threads -- no host-side copy here."""
@@ -196,6 +257,7 @@ class Batch:
         rows = np.ascontiguousarray(rows, dtype=np.int64)
         lab = None if labels is None else np.ascontiguousarray(labels, dtype=np.float32)
         self.B, (_, self.P, self.T, self.F) = int(rows.shape[0]), (int(x) for x in data.shape)
+        self.counts = None
         self.has_labels = lab is not None
         self._src = (data, lab, rows)   # alive until the worker threads have read them
         self.engine._ck(self.engine.L.kprn_batch_feed_rows_async(self.engine.h, C.byref(self.ptr), _fp(data), _fp(lab), C.c_int64(int(data.shape[0])), _fp(rows),
@@ -204,7 +266,7 @@ class Batch:
 
     @property
     def n_paths(self):
-        return self.B * self.P
+        return self.N if getattr(self, "counts", None) is not None else self.B * self.P
 
     @property
     def n_uniq(self):
@@ -377,6 +439,29 @@ class Engine:
         if slot is None:
             return Batch(self, idx, labels, feed=True)
         return slot.refill(idx, labels)
+
+    def batch_ragged(self, idx, counts, labels=None):
+        """B pairs with their own path counts in one batch: idx [N,T,F], counts [B] (>= 1, sum N).  Accepted wherever a Batch is."""
+        return Batch.ragged(self, idx, counts, labels)
+
+    def feed_ragged(self, idx, counts, labels=None, slot=None):
+        """the streaming feed for a ragged batch; `slot` may be any Batch (its previous contents may have been rectangular)"""
+        if slot is None:
+            return Batch.ragged(self, idx, counts, labels, feed=True)
+        return slot.refill_ragged(idx, counts, labels)
+
+    def forward_ragged_host(self, idx, counts, class_id=1, want_all=False):
+        """kprn_forward_ragged: host buffers in, the selected class's probabilities [B] (and all classes [B,C]) out, one call"""
+        idx = np.ascontiguousarray(idx, np.int32)
+        counts = np.ascontiguousarray(counts, np.int32)
+        if idx.ndim != 3 or counts.ndim != 1:
+            raise KprnError(E_ARG, "a ragged batch is idx [N,T,F] and counts [B]")
+        B = int(counts.shape[0])
+        probs = np.empty(B, np.float32)
+        allp = np.empty((B, self.cfg.C), np.float32) if want_all else None
+        self._ck(self.L.kprn_forward_ragged(self.h, _fp(idx), _fp(counts), B, C.c_int64(int(idx.shape[0])), int(idx.shape[1]), int(idx.shape[2]),
+                                            int(class_id), _fp(probs), _fp(allp)))
+        return probs, allp
 
     def feed_rows(self, data, labels, rows, slot=None):
         """the feed for a shuffled order: rows of the file's arrays, gathered inside the engine (Batch.refill_rows)"""

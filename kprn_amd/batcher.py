@@ -112,6 +112,7 @@ class BatcherFileList:
         self.endIndex = self.maxBatches
         self.index = (self.rng.permutation(self.numBatchers) + 1) if self.doShuffle else np.arange(1, self.numBatchers + 1)
         self.currentIndex = 1
+        self._merge_pos = 0   # getMergedGroup: position in `index` of the file being drained
 
     def reset(self):  # BatcherFileList.lua:99-116
         self._new_epoch_order()
@@ -134,6 +135,44 @@ class BatcherFileList:
                 n = got[2].shape[0] if rows else got[0].shape[0]
                 return got, n, batcher.getClassId(), (self.index[i - 1] - 1, batcher.curStart - n, batcher.epoch)
         return None
+
+    def getMergedGroup(self, max_paths):
+        """Merged mode, for scoring (an extension: the reference hands out one file's rows at a time).  Walks the list in list x in-file order
+        like getBatch and packs consecutive rows of consecutive files -- whatever their path counts -- into one ragged group of at most
+        max_paths paths (a single row with more paths than that is a group of its own; a file whose T or F differs ends the group).
+        -> (labels [B], idx [N,T,F], counts [B], B, classId) or None at the end of the list.  Order is preserved by construction."""
+        if self.doShuffle:
+            raise ValueError("merged groups follow the list order: not available with shuffle")
+        labs, datas, cnts = [], [], []
+        paths, tf, classId = 0, None, None
+        while self._merge_pos < self.numBatchers:
+            b = self.batchers[self.index[self._merge_pos] - 1]
+            n_rows = b.labels.shape[0]
+            if b.curStart >= n_rows:
+                self._merge_pos += 1
+                continue
+            P = b.numPaths
+            if tf is not None and tuple(b.data.shape[2:]) != tf:
+                break
+            k = min(n_rows - b.curStart, (max_paths - paths) // P)
+            if k <= 0:
+                if labs:
+                    break
+                k = 1
+            s = b.curStart
+            b.curStart = s + k
+            tf = tuple(b.data.shape[2:])
+            classId = b.getClassId() if classId is None else classId
+            labs.append(b.labels[s:s + k])
+            datas.append(b.data[s:s + k].reshape((k * P,) + tf))
+            cnts.append(np.full(k, P, dtype=np.int32))
+            paths += k * P
+            if paths >= max_paths:
+                break
+        if not labs:
+            return None
+        labels = np.concatenate(labs)
+        return labels, np.ascontiguousarray(np.concatenate(datas), dtype=np.int32), np.concatenate(cnts), labels.shape[0], classId
 
     def getBatch(self, with_key=False, rows=False):  # BatcherFileList.lua:169-188
         """-> (labels, data, n, classId[, key]) or None.  rows=True: (labels_all, data_all, rows) of the file instead of the two

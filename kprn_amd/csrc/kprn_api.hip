@@ -214,11 +214,12 @@ static void materialize_step_rows(kprn_handle* h) {
   h->rows_view = h->step_rows; h->count_view = h->step_count; h->view_batch = nullptr;
 }
 
-static void ensure_ws_common(kprn_handle* h, int64_t N, int64_t B) {
-  if (kk::loss_partials((int)B) > h->loss_partial_cap) {
+static void ensure_ws_common(kprn_handle* h, int64_t N, int64_t B, int64_t n_wg = 0) {
+  const int64_t np = std::max<int64_t>(kk::loss_partials((int)B), n_wg);   // (n_wg: the loss-stage workgroups of a ragged batch)
+  if (np > h->loss_partial_cap) {
     HIP_TRY(hipStreamSynchronize(h->stream));
     dfree(h->loss_partial);
-    h->loss_partial_cap = (int64_t)kk::loss_partials((int)B) * 2;
+    h->loss_partial_cap = np * 2;
     h->loss_partial = dalloc<float>(h->loss_partial_cap);
   }
   Workspace& w = h->ws;
@@ -292,7 +293,7 @@ static void forward_generic(kprn_handle* h, const kprn_batch* b, bool save) {
   static const bool no_step = getenv("KPRN_NO_STEP_KERNEL") != nullptr;  // (measurement: GEMM + element-wise kernels per step)
   Workspace& w = h->ws;
   const int H = c.H, L = c.L, T = b->T;
-  const int64_t N = (int64_t)b->B * b->P;
+  const int64_t N = b->N;
   hipStream_t s = h->stream;
   {
     ProfScope ps(h, "embed_gather");
@@ -438,6 +439,11 @@ static void pool_stage(kprn_handle* h, const kprn_batch* b, int cid, bool every_
   const kprn_config& c = h->cfg;
   Workspace& w = h->ws;
   ProfScope ps(h, "pool_sigmoid");
+  if (b->off) {
+    const kk::Segs g{b->B, 0, b->off, b->wg, b->n_wg, b->seg_wave};
+    kk::pool_sigmoid_ragged(h->stream, w.S, g, c.C, c.reducer, c.K, every_class ? w.pooled : nullptr, every_class ? w.probs : nullptr, cid, w.sel, h->sel_host_armed);
+    return;
+  }
   kk::pool_sigmoid(h->stream, w.S, b->B, b->P, c.C, c.reducer, c.K, every_class ? w.pooled : nullptr, every_class ? w.probs : nullptr, cid, w.sel, h->sel_host_armed);
 }
 
@@ -459,9 +465,9 @@ static bool use_fused(kprn_handle* h, const kprn_batch* b, bool save_for_backwar
 
 static void forward_impl(kprn_handle* h, const kprn_batch* b, int class_id, bool save_for_backward, bool do_pool = true, bool every_class = true) {
   check_batch(h, b, class_id);
-  const int64_t N = (int64_t)b->B * b->P;
+  const int64_t N = b->N;
   catch_up(h, b);
-  ensure_ws_common(h, N, b->B);
+  ensure_ws_common(h, N, b->B, b->n_wg);
   if (use_fused(h, b, save_for_backward)) {
     bool dual = false;
     if (save_for_backward && h->score_dual && h->score_rest_batch && h->score_rest_tile0 == 0 && h->ev_score_done) {
@@ -549,7 +555,7 @@ static void backward_layer0_small_tables(kprn_handle* h, const kprn_batch* b, in
   const kprn_config& c = h->cfg;
   Workspace& w = h->ws;
   const int D = h->D, T = b->T;
-  const int64_t N = (int64_t)b->B * b->P, TN = (int64_t)T * N;
+  const int64_t N = b->N, TN = (int64_t)T * N;
   hipStream_t s = h->stream;
   float* gd = h->g_dense;
   const float* Wi = h->dense + h->layer[0].Wi;
@@ -598,7 +604,7 @@ static void backward_generic(kprn_handle* h, const kprn_batch* b, int cid) {
   const bool bf = c.compute_dtype == 1;
   Workspace& w = h->ws;
   const int H = c.H, L = c.L, D = h->D, T = b->T;
-  const int64_t N = (int64_t)b->B * b->P;
+  const int64_t N = b->N;
   hipStream_t s = h->stream;
   float* gd = h->g_dense;
   const int st_ns = small_tables_ns(h, b);   // > 0: layer 0's input gradients through the small-table identity
@@ -827,11 +833,22 @@ static void backward_impl(kprn_handle* h, const kprn_batch* b, int class_id, int
     kk::TransposeJob tj;  // fused path: the backward's W^T copies, stale after an update, are rebuilt by passenger workgroups
     const bool have_tj = fusedp && fused::transpose_job(h, &tj);
     kk::PoolJob pj{h->S2, 0, 0, 0, h->sel2, nullptr};
-    if (h->pool_defer_batch) { pj.B = h->pool_defer_batch->B; pj.P = h->pool_defer_batch->P; pj.cid = h->pool_defer_cid; h->pool_defer_batch = nullptr; }
-    kk::loss_stage(h->stream, h->score_buf, b->labels, /*hT=*/nullptr, b->B, b->P, c.C, c.H, cid, c.reducer, c.K, literal,
-                   invB, /*pooled=*/nullptr, /*probs=*/nullptr, w.sel, w.dS, fusedp ? b->slot_of : nullptr, gd + h->off_outW + (int64_t)cid * c.H, gd + h->off_outb + cid, h->loss_partial,
-                   have_tj ? &tj : nullptr, h->loss_early_armed ? h->loss_mirror : nullptr, pj.B > 0 ? &pj : nullptr);
-    h->loss_pending = kk::loss_partials(b->B);
+    if (h->pool_defer_batch) {
+      const kprn_batch* sb = h->pool_defer_batch;
+      pj.B = sb->B; pj.P = sb->P; pj.off = sb->off; pj.wave = sb->seg_wave; pj.cid = h->pool_defer_cid; h->pool_defer_batch = nullptr;
+    }
+    if (b->off || pj.off) {   // a ragged batch, or a ragged passenger: the segmented loss stage (a rectangular batch launches what it always did)
+      const kk::Segs g{b->B, b->P, b->off, b->wg, b->n_wg, b->seg_wave};
+      h->loss_pending = kk::loss_stage_ragged(h->stream, h->score_buf, b->labels, /*hT=*/nullptr, g, c.C, c.H, cid, c.reducer, c.K, literal, invB, /*pooled=*/nullptr,
+                                              /*probs=*/nullptr, w.sel, w.dS, fusedp ? b->slot_of : nullptr, gd + h->off_outW + (int64_t)cid * c.H,
+                                              gd + h->off_outb + cid, h->loss_partial, have_tj ? &tj : nullptr,
+                                              h->loss_early_armed ? h->loss_mirror : nullptr, pj.B > 0 ? &pj : nullptr);
+    } else {
+      kk::loss_stage(h->stream, h->score_buf, b->labels, /*hT=*/nullptr, b->B, b->P, c.C, c.H, cid, c.reducer, c.K, literal,
+                     invB, /*pooled=*/nullptr, /*probs=*/nullptr, w.sel, w.dS, fusedp ? b->slot_of : nullptr, gd + h->off_outW + (int64_t)cid * c.H, gd + h->off_outb + cid, h->loss_partial,
+                     have_tj ? &tj : nullptr, h->loss_early_armed ? h->loss_mirror : nullptr, pj.B > 0 ? &pj : nullptr);
+      h->loss_pending = kk::loss_partials(b->B);
+    }
     if (h->loss_early_armed) {   // what kprn_train_step_batch waits for instead of the end of the step
       h->loss_early_n = h->loss_pending;
       HIP_TRY(hipEventRecord(h->ev_loss, h->stream));
@@ -1241,8 +1258,9 @@ int kprn_zero_pad_tokens(kprn_handle* h) {
 //   idx | idx_s | perm | slot_of | tile_k | pmeta | key_sorted | pos_sorted | uniq ... count | labels | flag
 // (each rounded to 16 bytes).  The host-built feed prepares a page-locked image of exactly this block and uploads it with a
 // single copy.
-struct BatchLayout { int64_t idx, idx_s, perm, slot_of, tile_k, pmeta, key, pos, uniq, cnt, labels, flag, words; };
-static BatchLayout batch_layout(int64_t B, int64_t N, int T, int F, bool plan, bool labels) {
+struct BatchLayout { int64_t idx, idx_s, perm, slot_of, tile_k, pmeta, off, wg, key, pos, uniq, cnt, labels, flag, words; };
+// ragged: + the offsets [B+1] and the loss-stage workgroup table [<= B+1], in front of the index so that every upload range of the host-built feed holds them
+static BatchLayout batch_layout(int64_t B, int64_t N, int T, int F, bool plan, bool labels, bool ragged = false) {
   auto r4 = [](int64_t v) { return (v + 3) & ~(int64_t)3; };
   const int64_t nsteps = N * T, n_index = nsteps + (plan ? fused::KCAP : 0);
   BatchLayout l;
@@ -1253,6 +1271,8 @@ static BatchLayout batch_layout(int64_t B, int64_t N, int T, int F, bool plan, b
   l.slot_of = o; o += plan ? r4(N) : 0;
   l.tile_k = o; o += plan ? r4((N + 63) / 64 + 1) : 0;
   l.pmeta = o; o += plan ? 24 : 0;
+  l.off = o; o += ragged ? r4(B + 1) : 0;
+  l.wg = o; o += ragged ? r4(B + 1) : 0;
   l.key = o; o += r4(n_index);
   l.pos = o; o += r4(n_index);
   l.uniq = o; o += r4(n_index);
@@ -1266,7 +1286,7 @@ static BatchLayout batch_layout(int64_t B, int64_t N, int T, int F, bool plan, b
 static void batch_free_buffers(kprn_batch* b) {
   dfree(b->block);
   b->block_cap = 0;
-  b->idx = b->idx_s = b->perm = b->slot_of = b->tile_k = b->pmeta = b->key_sorted = b->pos_sorted = b->uniq = b->d_flag = nullptr;
+  b->idx = b->idx_s = b->perm = b->slot_of = b->tile_k = b->pmeta = b->off = b->wg = b->key_sorted = b->pos_sorted = b->uniq = b->d_flag = nullptr;
   b->labels = nullptr;
 }
 
@@ -1282,25 +1302,27 @@ static void batch_release(kprn_batch* b) {
 
 static bool batch_wants_plan(kprn_handle* h, const kprn_batch* b) {
   // (small batches run on tiles of one 16-row m-tile, which have no per-tile prefix classes: lstm_fused_fwd.hip small_tiles)
-  if (fused::small_tiles(h, (int64_t)b->B * b->P, false)) return false;
+  if (fused::small_tiles(h, b->N, false)) return false;
   return h->prefix_plan && use_fused(h, b, true) && b->F <= 16 && !(kprn_dbg_mask() & 64);
 }
 
 // buffers for a [B,P,T,F] batch; a refill that fits the slot's capacities allocates nothing.  quiesce(): called before any
 // buffer of a slot in use is freed.
 static void batch_reserve(kprn_handle* h, kprn_batch* b, int32_t B, int32_t P, int32_t T, int32_t F, bool labels, const std::function<void()>& quiesce,
-                          int64_t min_pairs = 0, int64_t min_paths = 0) {
+                          int64_t min_pairs = 0, int64_t min_paths = 0, int64_t n_ragged = 0) {
+  const bool ragged = n_ragged > 0;   // (P is 0 then)
   b->B = B; b->P = P; b->T = T; b->F = F;
-  const int64_t nsteps = (int64_t)B * P * T, N = (int64_t)B * P;
+  const int64_t N = ragged ? n_ragged : (int64_t)B * P, nsteps = N * T;
+  b->N = N;
   const bool plan = batch_wants_plan(h, b);
   b->kcap = plan ? fused::KCAP : 0;
   b->n_index = nsteps + b->kcap;
   // the allocation only grows (a slot that has held the largest minibatch never allocates again; kprn_batch_slot_reserve sizes
   // it up front, for the larger of the two layouts)
-  const BatchLayout l = batch_layout(B, N, T, F, plan, labels);
+  const BatchLayout l = batch_layout(B, N, T, F, plan, labels, ragged);
   int64_t want = l.words;
-  if (min_pairs > 0 || min_paths > 0)
-    want = std::max(want, batch_layout(std::max<int64_t>(B, min_pairs), std::max<int64_t>(N, min_paths), T, F, true, true).words);
+  if (min_pairs > 0 || min_paths > 0)   // (a reserved slot holds a rectangular or a ragged batch of that size)
+    want = std::max(want, batch_layout(std::max<int64_t>(B, min_pairs), std::max<int64_t>(N, min_paths), T, F, true, true, true).words);
   if (want > b->block_cap) {
     if (b->block) { quiesce(); batch_free_buffers(b); }
     b->block = dalloc<int32_t>(want);
@@ -1310,6 +1332,8 @@ static void batch_reserve(kprn_handle* h, kprn_batch* b, int32_t B, int32_t P, i
   b->idx = k + l.idx;
   b->idx_s = plan ? k + l.idx_s : nullptr; b->perm = plan ? k + l.perm : nullptr; b->slot_of = plan ? k + l.slot_of : nullptr;
   b->tile_k = plan ? k + l.tile_k : nullptr; b->pmeta = plan ? k + l.pmeta : nullptr;
+  b->off = ragged ? k + l.off : nullptr; b->wg = ragged ? k + l.wg : nullptr;
+  if (!ragged) { b->n_wg = 0; b->max_cnt = 0; b->seg_wave = 0; }
   b->key_sorted = k + l.key; b->pos_sorted = k + l.pos; b->uniq = k + l.uniq;
   b->uniq_cap = l.cnt - l.uniq;  // the distinct-row count lives at uniq[uniq_cap]
   b->labels = labels ? (float*)(k + l.labels) : nullptr;
@@ -1333,10 +1357,14 @@ static void scratch_reserve(void** scratch, size_t* bytes, size_t need) {
 // upload + validation + identical-prefix plan + occurrence index on stream s; the host-side summary (validation flag, distinct
 // rows, plan header, per-tile prefix lengths) lands in the slot's pinned block behind them.  Nothing here waits for the device.
 static void batch_enqueue(kprn_handle* h, kprn_batch* b, const int32_t* idx, const float* labels, hipStream_t s, void* scratch, size_t scratch_bytes) {
-  const int32_t B = b->B, P = b->P, T = b->T, F = b->F;
-  const int64_t nsteps = (int64_t)B * P * T, N = (int64_t)B * P;
+  const int32_t B = b->B, T = b->T, F = b->F;
+  const int64_t N = b->N, nsteps = N * T;
   const bool plan = b->kcap > 0;
   HIP_TRY(hipMemcpyAsync(b->idx, idx, (size_t)nsteps * F * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  if (b->off) {   // ragged: offsets + workgroup table as the host derived them (kk::ragged_plan)
+    HIP_TRY(hipMemcpyAsync(b->off, b->hrag.data(), (size_t)(B + 1) * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(b->wg, b->hrag.data() + (B + 1), (size_t)(b->n_wg + 1) * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  }
   if (labels) HIP_TRY(hipMemcpyAsync(b->labels, labels, (size_t)B * sizeof(float), hipMemcpyHostToDevice, s));
   HIP_TRY(hipMemsetAsync(b->d_flag, 0, sizeof(int32_t), s));
   kk::validate_indices(s, b->idx, nsteps, F, h->cfg.num_types, h->cfg.Vt, h->cfg.Ve, h->cfg.Vr, b->d_flag);
@@ -1359,7 +1387,7 @@ static void batch_enqueue(kprn_handle* h, kprn_batch* b, const int32_t* idx, con
 // the device work of batch_enqueue is complete: take the host-side summary over
 static void batch_finish(kprn_handle* h, kprn_batch* b) {
   const int32_t* m = b->h_meta;
-  const int64_t nsteps = (int64_t)b->B * b->P * b->T, N = (int64_t)b->B * b->P;
+  const int64_t nsteps = b->N * b->T, N = b->N;
   b->pending = false;
   b->n_uniq = m[1];
   b->h_kmax = 0;
@@ -1401,6 +1429,9 @@ static void check_batch_args(kprn_handle* h, const int32_t* idx, int32_t B, int3
   KPRN_REQUIRE(F == h->cfg.F, KPRN_E_ARG, "F does not match numFeatureTemplates");
 }
 
+static void ragged_prepare(kprn_handle* h, const int32_t* idx, const int32_t* counts, int32_t B, int64_t N, int32_t T, int32_t F, std::vector<int32_t>* plan,
+                           int32_t* summary);
+
 int kprn_batch_create(kprn_handle* h, const int32_t* idx, const float* labels, int32_t B, int32_t P, int32_t T, int32_t F, kprn_batch** out) {
   API_BEGIN(h)
   KPRN_REQUIRE(out, KPRN_E_ARG, "out is NULL");
@@ -1420,6 +1451,47 @@ int kprn_batch_create(kprn_handle* h, const int32_t* idx, const float* labels, i
     throw;
   }
   *out = b;
+  API_END(h)
+}
+
+int kprn_batch_create_ragged(kprn_handle* h, const int32_t* idx, const int32_t* counts, const float* labels, int32_t B, int64_t N, int32_t T, int32_t F,
+                             kprn_batch** out) {
+  API_BEGIN(h)
+  KPRN_REQUIRE(out, KPRN_E_ARG, "out is NULL");
+  *out = nullptr;
+  std::vector<int32_t> rplan;
+  int32_t rsum[3] = {0, 0, 0};
+  ragged_prepare(h, idx, counts, B, N, T, F, &rplan, rsum);
+  kprn_batch* b = new kprn_batch();
+  try {
+    batch_reserve(h, b, B, 0, T, F, labels != nullptr, [] {}, 0, 0, N);
+    b->hrag.swap(rplan); b->n_wg = rsum[0]; b->max_cnt = rsum[1]; b->seg_wave = rsum[2];
+    b->has_index = true; b->idx_valid = true;
+    scratch_reserve(&h->bidx_scratch, &h->bidx_scratch_bytes, std::max(bidx::scratch_bytes(b->n_index, h->cfg.Ve), bidx::prefix_scratch_bytes(N, fused::KCAP)));
+    batch_enqueue(h, b, idx, labels, h->stream, h->bidx_scratch, h->bidx_scratch_bytes);
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    batch_finish(h, b);
+  } catch (...) {
+    batch_release(b);
+    throw;
+  }
+  *out = b;
+  API_END(h)
+}
+
+int kprn_host_ragged_plan(const int32_t* counts, int32_t B, int64_t N, int32_t* offsets, int32_t* wg_first, int32_t* summary) {
+  int32_t sm[3];
+  if (!summary) return KPRN_E_ARG;
+  if (!kk::ragged_plan(counts, B, N, offsets, wg_first, sm)) return KPRN_E_ARG;
+  summary[0] = sm[0]; summary[1] = sm[1]; summary[2] = sm[2];
+  summary[3] = kk::RAGGED_MAX_SEG; summary[4] = kk::RAGGED_THREAD_MAX; summary[5] = kk::RAGGED_WG_PATHS; summary[6] = kk::RAGGED_WG_PAIRS; summary[7] = 0;
+  return KPRN_OK;
+}
+
+int kprn_batch_num_paths(kprn_handle* h, const kprn_batch* b, int64_t* n) {
+  API_BEGIN(h)
+  KPRN_REQUIRE(b && n, KPRN_E_ARG, "NULL argument");
+  *n = b->N;
   API_END(h)
 }
 
@@ -1444,7 +1516,8 @@ static void ensure_upload_stream(kprn_handle* h) {
 
 static void feed_host(kprn_handle* h, kprn_batch* b, const int32_t* idx, const float* labels, const int64_t* rows, bool inline_now = false) {
   const int32_t B = b->B, P = b->P, T = b->T, F = b->F;
-  const int64_t nsteps = (int64_t)B * P * T, N = (int64_t)B * P, n_index = b->n_index;
+  const int64_t N = b->N, nsteps = N * T, n_index = b->n_index;
+  const bool ragged = b->off != nullptr;
   if (!h->feed_pool && !inline_now) {
     if (h->feed_workers <= 0) {  // defaults from the machine: a GPU host has cores to spare, a small container does not
       const unsigned hc = std::thread::hardware_concurrency();
@@ -1461,7 +1534,7 @@ static void feed_host(kprn_handle* h, kprn_batch* b, const int32_t* idx, const f
     HIP_TRY(hipEventCreateWithFlags(&b->ev_fork2, hipEventDisableTiming));
   }
   const bool plan = b->kcap > 0;
-  const BatchLayout l = batch_layout(B, N, T, F, plan, labels != nullptr);
+  const BatchLayout l = batch_layout(B, N, T, F, plan, labels != nullptr, ragged);
   // a label-less batch is scored only: with no lazy row update pending nothing walks its entity rows -> no occurrence index is
   // built, and with a plan the ids in their original order are not uploaded either (a third of the bytes, none of the sorting)
   const bool want_index = labels != nullptr || h->lazy_pending;
@@ -1474,13 +1547,18 @@ static void feed_host(kprn_handle* h, kprn_batch* b, const int32_t* idx, const f
     b->hs_cap = b->block_cap;
   }
   if ((int64_t)b->hw.size() < 4 * n_index) b->hw.resize((size_t)(4 * std::max(n_index, (b->block_cap / 8))));
-  const hostfeed::Shape g{B, P, T, F, h->cfg.num_types, h->cfg.Vt, h->cfg.Ve, h->cfg.Vr};
+  // (validation, plan and index are flat over the paths: a ragged batch is N "pairs" of one path to them)
+  const hostfeed::Shape g{ragged ? (int)N : B, ragged ? 1 : P, T, F, h->cfg.num_types, h->cfg.Vt, h->cfg.Ve, h->cfg.Vr};
   const int kcap = b->kcap, dev = h->cfg.device_id;
   int32_t* hs = b->hs;
   int32_t* hw = b->hw.data();
   if (labels && rows) { float* hl = (float*)(hs + l.labels); for (int32_t i = 0; i < B; ++i) hl[i] = labels[rows[i]]; }
   else if (labels) memcpy(hs + l.labels, labels, (size_t)B * sizeof(float));
   hs[l.flag] = 0;
+  if (ragged) {
+    memcpy(hs + l.off, b->hrag.data(), (size_t)(B + 1) * sizeof(int32_t));
+    memcpy(hs + l.wg, b->hrag.data() + (B + 1), (size_t)(b->n_wg + 1) * sizeof(int32_t));
+  }
   b->host_built = true;
   auto done = std::make_shared<std::promise<void>>();
   b->job = done->get_future();
@@ -1550,10 +1628,26 @@ static void feed_host(kprn_handle* h, kprn_batch* b, const int32_t* idx, const f
   });
 }
 
+// counts != null: a ragged batch of n_ragged paths (P is ignored); its counts are checked and its plan is derived before the slot is touched
+static void ragged_prepare(kprn_handle* h, const int32_t* idx, const int32_t* counts, int32_t B, int64_t N, int32_t T, int32_t F, std::vector<int32_t>* plan,
+                           int32_t* summary) {
+  KPRN_REQUIRE(idx, KPRN_E_ARG, "idx is NULL");
+  KPRN_REQUIRE(counts, KPRN_E_ARG, "counts is NULL");
+  KPRN_REQUIRE(B > 0 && N >= B && T > 0, KPRN_E_ARG, "B, T must be positive and N >= B");
+  KPRN_REQUIRE(F == h->cfg.F, KPRN_E_ARG, "F does not match numFeatureTemplates");
+  KPRN_REQUIRE(N * T + fused::KCAP <= 0x7fffffffLL, KPRN_E_ARG, "N*T does not fit the 32-bit positions of the occurrence index");
+  plan->resize((size_t)(2 * (int64_t)B + 2));
+  KPRN_REQUIRE(kk::ragged_plan(counts, B, N, plan->data(), plan->data() + (B + 1), summary), KPRN_E_ARG,
+               "counts: every pair needs 1..4096 paths and the counts must add up to N");
+}
+
 static void feed_impl(kprn_handle* h, kprn_batch** slot, const int32_t* idx, const float* labels, const int64_t* rows, int32_t B, int32_t P, int32_t T, int32_t F,
-                      bool inline_now = false) {
+                      bool inline_now = false, const int32_t* counts = nullptr, int64_t n_ragged = 0) {
   KPRN_REQUIRE(slot, KPRN_E_ARG, "slot is NULL");
-  check_batch_args(h, idx, B, P, T, F);
+  std::vector<int32_t> rplan;
+  int32_t rsum[3] = {0, 0, 0};
+  if (counts) { ragged_prepare(h, idx, counts, B, n_ragged, T, F, &rplan, rsum); P = 0; }
+  else check_batch_args(h, idx, B, P, T, F);
   if (!h->feed_build_host && !h->feed_stream) {
     // device-built feed: its kernels are small and latency-bound; they get the CUs the persistent kernels leave idle in their
     // tails.  (Created only when used: HIP multiplexes streams onto a few hardware queues, and a stream that waits on events --
@@ -1590,13 +1684,14 @@ static void feed_impl(kprn_handle* h, kprn_batch** slot, const int32_t* idx, con
       if (h->feed_stream) HIP_TRY(hipStreamSynchronize(h->feed_stream));
       if (h->upload_stream) HIP_TRY(hipStreamSynchronize(h->upload_stream));
     };
-    batch_reserve(h, b, B, P, T, F, labels != nullptr, quiesce);
+    batch_reserve(h, b, B, P, T, F, labels != nullptr, quiesce, 0, 0, counts ? n_ragged : 0);
+    if (counts) { b->hrag.swap(rplan); b->n_wg = rsum[0]; b->max_cnt = rsum[1]; b->seg_wave = rsum[2]; }
     if (!b->ev_ready) HIP_TRY(hipEventCreateWithFlags(&b->ev_ready, hipEventDisableTiming));
     if (h->feed_build_host) {
       feed_host(h, b, idx, labels, rows, inline_now);
     } else {
       b->host_built = false; b->has_index = true; b->idx_valid = true;
-      const int64_t N = (int64_t)B * P;
+      const int64_t N = b->N;
       const size_t need = std::max(bidx::scratch_bytes(b->n_index, h->cfg.Ve), bidx::prefix_scratch_bytes(N, fused::KCAP));
       if (need > h->feed_scratch_bytes) {
         HIP_TRY(hipStreamSynchronize(h->feed_stream));
@@ -1629,6 +1724,14 @@ static void feed_impl(kprn_handle* h, kprn_batch** slot, const int32_t* idx, con
 int kprn_batch_feed_async(kprn_handle* h, kprn_batch** slot, const int32_t* idx, const float* labels, int32_t B, int32_t P, int32_t T, int32_t F) {
   API_BEGIN(h)
   feed_impl(h, slot, idx, labels, nullptr, B, P, T, F);
+  API_END(h)
+}
+
+int kprn_batch_feed_ragged_async(kprn_handle* h, kprn_batch** slot, const int32_t* idx, const int32_t* counts, const float* labels, int32_t B, int64_t N,
+                                 int32_t T, int32_t F) {
+  API_BEGIN(h)
+  KPRN_REQUIRE(counts, KPRN_E_ARG, "counts is NULL");
+  feed_impl(h, slot, idx, labels, nullptr, B, 0, T, F, false, counts, N);
   API_END(h)
 }
 
@@ -1807,7 +1910,7 @@ int kprn_forward_batch_async(kprn_handle* h, const kprn_batch* b, int32_t class_
   if (h->score_overlap && b && use_fused(h, b, false)) {
     // the pass goes to the side stream with its own output buffers; everything it reads is final on the main stream first
     check_batch(h, b, class_id);
-    const int64_t N = (int64_t)b->B * b->P;
+    const int64_t N = b->N;
     catch_up(h, b);
     ensure_ws_common(h, N, b->B);
     if (!h->score_stream) {
@@ -1963,7 +2066,7 @@ int kprn_forward_batch(kprn_handle* h, const kprn_batch* b, int32_t class_id, fl
   if (all_probs) HIP_TRY(hipMemcpyAsync(all_probs, h->ws.probs, (size_t)b->B * C * sizeof(float), hipMemcpyDeviceToHost, s));
   if (pooled) HIP_TRY(hipMemcpyAsync(pooled, h->ws.pooled, (size_t)b->B * C * sizeof(float), hipMemcpyDeviceToHost, s));
   if (path_scores)
-    HIP_TRY(hipMemcpyAsync(path_scores, h->score_buf, (size_t)b->B * b->P * C * sizeof(float), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(path_scores, h->score_buf, (size_t)b->N * C * sizeof(float), hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   if (mirror) memcpy(probs, h->probs_mirror, (size_t)b->B * sizeof(float));
   prof_drain(h);
@@ -1971,7 +2074,8 @@ int kprn_forward_batch(kprn_handle* h, const kprn_batch* b, int32_t class_id, fl
 }
 
 // the host-buffer entry points' minibatch -> an engine-owned slot (0 / 1: training, 2 / 3: scoring), derived on the calling thread
-static int dropin_feed(kprn_handle* h, bool score, const int32_t* idx, const float* labels, int32_t B, int32_t P, int32_t T, int32_t F) {
+static int dropin_feed(kprn_handle* h, bool score, const int32_t* idx, const float* labels, int32_t B, int32_t P, int32_t T, int32_t F,
+                       const int32_t* counts = nullptr, int64_t n_ragged = 0) {
   API_BEGIN(h)
   int& nx = score ? h->dropin_next_score : h->dropin_next_train;
   const int si = (score ? 2 : 0) + nx;
@@ -1979,11 +2083,11 @@ static int dropin_feed(kprn_handle* h, bool score, const int32_t* idx, const flo
   if (!h->feed_build_host) {   // device-built feed selected: the plain create path of that build
     if (h->dropin_slot[si]) { kprn_batch* old = h->dropin_slot[si]; h->dropin_slot[si] = nullptr; kprn_batch_destroy(h, old); }
     kprn_batch* b = nullptr;
-    const int rc = kprn_batch_create(h, idx, labels, B, P, T, F, &b);
+    const int rc = counts ? kprn_batch_create_ragged(h, idx, counts, labels, B, n_ragged, T, F, &b) : kprn_batch_create(h, idx, labels, B, P, T, F, &b);
     if (rc != KPRN_OK) return rc;
     h->dropin_slot[si] = b;
   } else {
-    feed_impl(h, &h->dropin_slot[si], idx, labels, nullptr, B, P, T, F, /*inline_now=*/true);
+    feed_impl(h, &h->dropin_slot[si], idx, labels, nullptr, B, P, T, F, /*inline_now=*/true, counts, n_ragged);
   }
   h->dropin_last = si;
   API_END(h)
@@ -1992,6 +2096,15 @@ static int dropin_feed(kprn_handle* h, bool score, const int32_t* idx, const flo
 int kprn_forward(kprn_handle* h, const int32_t* idx, int32_t B, int32_t P, int32_t T, int32_t F, int32_t class_id, float* probs, float* all_probs) {
   if (!h) return KPRN_E_ARG;
   int rc = dropin_feed(h, /*score=*/true, idx, nullptr, B, P, T, F);   // (engine-owned feed slots: see kprn_train_step)
+  if (rc != KPRN_OK) return rc;
+  return kprn_forward_batch(h, h->dropin_slot[h->dropin_last], class_id, probs, all_probs, nullptr, nullptr);
+}
+
+int kprn_forward_ragged(kprn_handle* h, const int32_t* idx, const int32_t* counts, int32_t B, int64_t N, int32_t T, int32_t F, int32_t class_id, float* probs,
+                        float* all_probs) {
+  if (!h) return KPRN_E_ARG;
+  if (!counts) { h->err = "counts is NULL"; return KPRN_E_ARG; }
+  int rc = dropin_feed(h, /*score=*/true, idx, nullptr, B, 0, T, F, counts, N);
   if (rc != KPRN_OK) return rc;
   return kprn_forward_batch(h, h->dropin_slot[h->dropin_last], class_id, probs, all_probs, nullptr, nullptr);
 }
@@ -2046,7 +2159,7 @@ int kprn_train_step_batch(kprn_handle* h, const kprn_batch* b, int32_t class_id,
   // the loss goes back as soon as the loss stage has run (option "train_step_return" = "loss"); profiling and "drain" wait for the whole step as before
   struct Disarm { kprn_handle* h; ~Disarm() { h->loss_early_armed = false; } } disarm{h};
   if (loss && !h->train_step_drain && !h->prof_on) {
-    const int64_t np = kk::loss_partials(b->B);
+    const int64_t np = std::max<int64_t>(kk::loss_partials(b->B), b->n_wg);   // (n_wg: the loss-stage workgroups of a ragged batch)
     if (np > h->loss_mirror_cap) {
       if (h->loss_mirror) { HIP_TRY(hipStreamSynchronize(h->stream)); HIP_TRY(hipHostFree(h->loss_mirror)); h->loss_mirror = nullptr; h->loss_mirror_cap = 0; }
       HIP_TRY(hipHostMalloc((void**)&h->loss_mirror, (size_t)(2 * np + 64) * sizeof(float)));

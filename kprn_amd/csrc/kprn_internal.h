@@ -68,7 +68,16 @@ namespace fused { constexpr int KCAP = 8; }  // longest identical prefix the fus
 
 struct kprn_batch {
   int32_t B, P, T, F;
-  int32_t* idx = nullptr;     // device [B,P,T,F]
+  int64_t N = 0;              // paths of the batch: B*P, or sum of the counts of a ragged batch
+  // ragged batch (kprn_batch_create_ragged; an extension, the reference has none): pair b owns the paths off[b] .. off[b+1]-1 of the flat
+  // [N,T,F] ids.  off == null: rectangular.  P of a ragged batch is 0 and nothing reads it.
+  int32_t* off = nullptr;     // device [B+1]
+  int32_t* wg = nullptr;      // device [n_wg+1]: first pair of each loss-stage workgroup (kprn_host_ragged_plan)
+  int32_t n_wg = 0;           // loss-stage workgroups = loss partials of a ragged batch
+  int32_t max_cnt = 0;        // longest segment
+  int32_t seg_wave = 0;       // 1: a wave per pair (max_cnt > kk::RAGGED_THREAD_MAX), chosen when the batch is made
+  std::vector<int32_t> hrag;  // host: off [B+1] | wg [n_wg+1], the source of their upload
+  int32_t* idx = nullptr;     // device [B,P,T,F]  ([N,T,F] when ragged)
   float* labels = nullptr;    // device [B] or null
   int32_t* uniq = nullptr;    // device: distinct entity rows of this batch (0-based); count at uniq[uniq_cap]
   int64_t uniq_cap = 0;
@@ -300,7 +309,23 @@ void pool_sigmoid(hipStream_t s, const float* S, int B, int P, int C, int reduce
 struct TransposeJob { const float* W[4]; float* WT[4]; int n; };
 // ... and the pooling stage of a scoring pass that ran in the training forward's launch ("score_dual"): reducer + sigmoid + select of ITS batch, as more
 // workgroups of the loss stage's launch (B = 0: none)
-struct PoolJob { const float* S; int B, P, cid; float* sel; float* sel_host; };
+struct PoolJob { const float* S; int B, P, cid; float* sel; float* sel_host; const int32_t* off = nullptr; int wave = 0; };
+// a batch as the reducer sees it: B pairs of P paths each, or (off != null) pair b = paths off[b] .. off[b+1]-1; wg / n_wg: the loss stage's
+// workgroup table of a ragged batch; wave: a wave per pair instead of a thread per pair
+struct Segs { int B, P; const int32_t* off; const int32_t* wg; int n_wg; int wave; };
+void pool_sigmoid_ragged(hipStream_t s, const float* S, const Segs& g, int C, int reducer, int K, float* pooled, float* probs, int cid, float* sel,
+                         float* sel_host = nullptr);
+// the loss stage when the batch or the passenger pooling job is ragged (either may also be rectangular: off == null); returns the number of partials
+int loss_stage_ragged(hipStream_t s, const float* S, const float* labels, const float* hT, const Segs& g, int C, int H, int cid, int reducer, int K,
+                      int literal, float invB, float* pooled, float* probs, float* sel, float* dS, const int32_t* slot_of, float* gW_row, float* gb_c,
+                      float* partial, const TransposeJob* tj = nullptr, float* partial_host = nullptr, const PoolJob* pj = nullptr);
+// segment limits of a ragged batch (DESIGN.md 'ragged batches')
+constexpr int RAGGED_MAX_SEG = 4096;     // longest pair kprn_host_ragged_plan accepts
+constexpr int RAGGED_THREAD_MAX = 28;    // longest pair a single thread reduces (the reference's largest path count: reduce_col's range)
+constexpr int RAGGED_WG_PAIRS = 16;     // pairs per loss-stage workgroup (= LOSS_PPW of the rectangular loss stage)
+constexpr int RAGGED_WG_PATHS = 448;     // paths per loss-stage workgroup (16 pairs of 28); a longer pair has a workgroup to itself
+// offsets [B+1], workgroup table wg [<= B+1], summary {n_wg, max_cnt, wave}; false: a count < 1 or > RAGGED_MAX_SEG, or sum != N
+bool ragged_plan(const int32_t* counts, int32_t B, int64_t N, int32_t* off, int32_t* wg, int32_t* summary);
 // (partial_host: optional page-locked mirror of the per-workgroup loss partials)
 void loss_stage(hipStream_t s, const float* S, const float* labels, const float* hT, int B, int P, int C, int H, int cid, int reducer, int K,
                 int literal, float invB, float* pooled, float* probs, float* sel, float* dS, const int32_t* slot_of /*nullable: dS[slot_of[n]]*/,

@@ -1608,7 +1608,7 @@ static int64_t wt_off(const kprn_handle* h, int l) {   // offset of layer l's tr
 
 bool supported(const kprn_handle* h, const kprn_batch* b) {
   const kprn_config& c = h->cfg;
-  const int64_t N = (int64_t)b->B * b->P;
+  const int64_t N = b->N;
   return c.compute_dtype == 1 && c.rnn_type == 0 && h->impl == 0 && N >= 256 && c.dt > 0 && c.de > 0 && (c.dt % 8) == 0 && (c.de % 8) == 0 && (c.dr % 8) == 0 && (c.H % 8) == 0;
 }
 
@@ -1786,7 +1786,7 @@ void forward(kprn_handle* h, const kprn_batch* b, bool save) {
   Workspace& w = h->ws;
   hipStream_t strm = h->stream;
   const int H = c.H, L = c.L, T = b->T, D = h->D;
-  const int64_t N = (int64_t)b->B * b->P;
+  const int64_t N = b->N;
   refresh_shadows(h);
   ensure_buffers(h, N, T);
   const bool persist = persist_shape_ok(h, b);
@@ -1853,7 +1853,7 @@ void backward(kprn_handle* h, const kprn_batch* b, int cid) {
   Workspace& w = h->ws;
   hipStream_t strm = h->stream;
   const int H = c.H, L = c.L, T = b->T, D = h->D, G4 = 4 * c.H;
-  const int64_t N = (int64_t)b->B * b->P, TN = (int64_t)T * N;
+  const int64_t N = b->N, TN = (int64_t)T * N;
   float* gd = h->g_dense;
   // the persistent BPTT launch forms dh_T = dS W_out[cid] itself and keeps dh / dc on the chip: no dH plane, no dC plane
   const bool bptt_persist = s->act_frag && L == 1 && persist_bwd_shape_ok(h, s->sv, N, T);

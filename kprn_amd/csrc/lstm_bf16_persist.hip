@@ -511,7 +511,7 @@ void persist_forward(kprn_handle* h, const kprn_batch* b, bool save, void*& st, 
   constexpr int KX = 24, KH = 24;
   const kprn_config& c = h->cfg;
   const int H = c.H, D = h->D, T = b->T;
-  const int64_t N = (int64_t)b->B * b->P;
+  const int64_t N = b->N;
   hipStream_t strm = h->stream;
   PersistState* p = (PersistState*)st;
   if (!p) {

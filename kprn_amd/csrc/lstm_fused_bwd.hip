@@ -858,7 +858,7 @@ static void launch_bwd(kprn_handle* h, const BwdArgs& a, int grid) {
 void backward(kprn_handle* h, const kprn_batch* b, int cid) {
   const kprn_config& c = h->cfg;
   State* s = st(h);
-  const int64_t N = (int64_t)b->B * b->P;
+  const int64_t N = b->N;
   const int T = b->T, L = c.L;
   hipStream_t strm = h->stream;
   if (N > s->cap_Nb || T > s->cap_Tb) {

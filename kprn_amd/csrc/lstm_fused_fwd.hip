@@ -559,7 +559,7 @@ HoArgs handover_args(kprn_handle* h, int grid) {
 // what the hand-over rule does with this batch on the fused kernels' grid (diagnostics, tests, bench.py): evaluated on the host from the device's tile_k
 void handover_stats(kprn_handle* h, const kprn_batch* b, int64_t* out) {
   State* s = st(h);
-  const int64_t N = (int64_t)b->B * b->P;
+  const int64_t N = b->N;
   const bool small = small_tiles(h, N, b->tile_k != nullptr);
   const int64_t n_tiles = small ? (N + 15) / 16 : (N + MT - 1) / MT;
   const int G = (int)std::min<int64_t>(n_tiles, (int64_t)s->num_cu);
@@ -604,7 +604,7 @@ static bool fwd_args(kprn_handle* h, const kprn_batch* b, bool save, int64_t til
                      bool& small) {
   const kprn_config& c = h->cfg;
   State* s = st(h);
-  const int64_t N = (int64_t)b->B * b->P;
+  const int64_t N = b->N;
   a.idx = b->idx_s ? b->idx_s : b->idx; a.N = N; a.T = b->T; a.F = b->F; a.nT = c.num_types;
   a.perm = b->perm; a.tile_k = b->tile_k; a.pmeta = b->pmeta; a.pfb = s->pfb;
   a.Wt = h->dense + h->off_Wt; a.We = h->We; a.Wr = h->dense + h->off_Wr;
@@ -682,7 +682,7 @@ void forward(kprn_handle* h, const kprn_batch* b, bool save, int64_t tile_begin,
   const kprn_config& c = h->cfg;
   if (c.compute_dtype != 0) { forward_mc(h, b, save); return; }  // bf16 / f32x6: the matrix-core forward (lstm_fused_fwd_mc.hip)
   State* s = st(h);
-  const int64_t N = (int64_t)b->B * b->P;
+  const int64_t N = b->N;
   FwdArgs a;
   int grid = 0;
   bool small = false;

@@ -601,7 +601,7 @@ void forward_mc(kprn_handle* h, const kprn_batch* b, bool save) {
   const kprn_config& c = h->cfg;
   State* s = st(h);
   const int ns = (c.compute_dtype == 2) ? 3 : (c.compute_dtype == 3) ? 2 : 1;  // format M of McFmt
-  const int64_t N = (int64_t)b->B * b->P;
+  const int64_t N = b->N;
   const int L = c.L;
   const int64_t n_tiles = (N + MT - 1) / MT;
   prefix_forward(h, b);

@@ -381,7 +381,10 @@ class DataParallel:
 
 
 def shard_pairs(n_pairs, rank, world):
-    """contiguous slice of the pairs of one global minibatch for `rank` (SURVEY 8e partitioning)."""
+    """contiguous slice of the pairs of one global minibatch for `rank` (SURVEY 8e partitioning).  Rectangular minibatches only: a
+    ragged one (counts per pair) has to be cut by the caller, who owns the flat path array."""
+    if not isinstance(n_pairs, (int, np.integer)):
+        raise TypeError("shard_pairs takes a pair count; sharding a ragged batch (counts per pair) is not supported")
     per = (n_pairs + world - 1) // world
     lo = min(n_pairs, rank * per)
     hi = min(n_pairs, lo + per)

@@ -65,13 +65,18 @@ class MyOptimizer:
         """MyOptimizer.lua:177-221: zeroPad; fEval{zeroGrad, forward, BCE, backward, clip/L2}; optim step; zeroPad."""
         assert inputs is not None
         assert targets is not None or isinstance(inputs, _ffi.Batch)
-        b = inputs if isinstance(inputs, _ffi.Batch) else self._device_batch(inputs, targets, key)
+        if isinstance(inputs, tuple):   # (idx [N,T,F], counts [B]): a ragged minibatch (an extension; it stays resident only as long as this step)
+            b = self.engine.batch_ragged(inputs[0], inputs[1], targets)
+        else:
+            b = inputs if isinstance(inputs, _ffi.Batch) else self._device_batch(inputs, targets, key)
         if self.dp is not None:
             # ranks may hold shards of different sizes (last batch of a file): the global pair count is agreed per step (see __init__)
             self.dp.train_step(b, self.opt, classId)
             err = self.engine.read_loss() if want_loss else None
         else:
             err = self.engine.train_step(b, self.opt, classId, want_loss=want_loss)
+        if isinstance(inputs, tuple):
+            b.free()
         if err is not None:
             self.totalError += err
         return err

@@ -12,6 +12,7 @@ def main(argv=None):
     p.add_argument("-input_dir", default=""); p.add_argument("-out_file", default=""); p.add_argument("-predicate_name", default="")
     p.add_argument("-meanModel", type=int, default=0); p.add_argument("-model_path", default=""); p.add_argument("-test_list", default="")
     p.add_argument("-gpu_id", type=int, default=-1); p.add_argument("-top_k", type=int, default=2); p.add_argument("-k", type=int, default=5)
+    p.add_argument("-mergePathCounts", type=int, default=0)   # 1: bucket files are scored in ragged groups (an extension; same output lines)
     args, rest = p.parse_known_args(argv)
     assert args.input_dir != "", "input_dir isnt set. Point to the dir where train/dev/test.list files reside"
     params = model.parse_flags(rest)
@@ -33,7 +34,7 @@ def main(argv=None):
         dist.init_process_group("gloo")   # (a barrier only: no tensor moves between the ranks)
         barrier = dist.barrier
     scoring.test_from_checkpoint(eng, args.input_dir, args.test_list, args.out_file, log=sys.stdout if rank == 0 else None,
-                                 rank=rank, world=world, barrier=barrier)
+                                 rank=rank, world=world, barrier=barrier, merge_path_counts=bool(args.mergePathCounts))
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()

@@ -20,8 +20,27 @@ ENGINE_BATCH_PATHS = 65536   # paths per engine call: the script's minibatch (51
 FEED_AHEAD = 2
 
 
-def score_batches(engine, batcher, class_id=1):
-    """-> (labels [n], probabilities [n]) per group of pairs, in list x in-file order.  With the HIP engine every group is a
+def _next_group(engine, batcher, merge):
+    """-> (labels, pairs, feed(slot) -> slot, batch() -> Batch) of the next group, or None"""
+    if merge:
+        got = batcher.getMergedGroup(ENGINE_BATCH_PATHS)
+        if got is None:
+            return None
+        labs, idx, counts, count, _classId = got
+        return labs, count, (lambda slot: engine.feed_ragged(idx, counts, None, slot=slot)), (lambda: engine.batch_ragged(idx, counts))
+    got = batcher.getBatch()
+    if got is None:
+        return None
+    labs, inputs, count, _classId = got
+    return labs, count, (lambda slot: engine.feed(inputs, None, slot=slot)), (lambda: engine.batch(inputs))
+
+
+def score_batches(engine, batcher, class_id=1, merge=False):
+    """merge=True (an extension, default off): consecutive rows of consecutive bucket files are packed into ragged groups of up to
+    ENGINE_BATCH_PATHS paths (BatcherFileList.getMergedGroup), so that a small bucket does not cost an engine call of its own; the pairs
+    come back in the same order.
+
+    -> (labels [n], probabilities [n]) per group of pairs, in list x in-file order.  With the HIP engine every group is a
     label-less feed slot (upload + identical-prefix plan built by the host threads under the previous group's kernels), scored
     asynchronously; the probabilities of group i come back while group i + 1 runs, so the caller's formatting overlaps too."""
     streaming = hasattr(engine, "feed") and hasattr(engine, "forward_async")
@@ -30,20 +49,20 @@ def score_batches(engine, batcher, class_id=1):
         if streaming:
             for b, _ in saved:       # chip-sized groups per bucket file (the caller's batch sizes are put back when the generator ends)
                 b.batchSize = max(b.batchSize, ENGINE_BATCH_PATHS // max(1, b.numPaths))
-        yield from _score_batches(engine, batcher, class_id, streaming)
+        yield from _score_batches(engine, batcher, class_id, streaming, merge)
     finally:
         for b, size in saved:
             b.batchSize = size
 
 
-def _score_batches(engine, batcher, class_id, streaming):
+def _score_batches(engine, batcher, class_id, streaming, merge=False):
     if not streaming:
         while True:
-            got = batcher.getBatch()
+            got = _next_group(engine, batcher, merge)
             if got is None:
                 return
-            labs, inputs, count, _classId = got
-            yield labs, engine.forward(engine.batch(inputs), class_id)["probs"]  # nn.Select(2,1) is fixed in the script (:82)
+            labs, count, _feed, make = got
+            yield labs, engine.forward(make(), class_id)["probs"]  # nn.Select(2,1) is fixed in the script (:82)
     slots = [None] * (FEED_AHEAD + 2)
     k = 0
     fed = []           # (slot, labels, count): fed, not yet scored
@@ -51,12 +70,12 @@ def _score_batches(engine, batcher, class_id, streaming):
     done = False
     while True:
         while not done and len(fed) < FEED_AHEAD:
-            got = batcher.getBatch()
+            got = _next_group(engine, batcher, merge)
             if got is None:
                 done = True
                 break
-            labs, inputs, count, _classId = got
-            slots[k] = engine.feed(inputs, None, slot=slots[k])
+            labs, count, feed, _make = got
+            slots[k] = feed(slots[k])
             fed.append((slots[k], labs, count))
             k = (k + 1) % len(slots)
         out = None
@@ -81,18 +100,19 @@ def score_lines(engine, batcher, class_id=1):
             counter += 1
 
 
-def write_scores(engine, batcher, f, class_id=1):
+def write_scores(engine, batcher, f, class_id=1, merge=False):
     """the script's output loop (:110-118) into the binary file f; lines formatted by the host cores (kprn_format_score_lines)"""
     from . import _ffi
     counter = 0
-    for labs, preds in score_batches(engine, batcher, class_id):
+    for labs, preds in score_batches(engine, batcher, class_id, merge):
         f.write(_ffi.format_score_lines(counter, preds, labs))
         counter += len(labs)
     return counter
 
 
-def test_from_checkpoint(engine, input_dir, test_list, out_file, minibatch=512, log=None, rank=0, world=1, barrier=None):
-    """engine: built with the same -top_k reducer the script would rebuild (:69-79).
+def test_from_checkpoint(engine, input_dir, test_list, out_file, minibatch=512, log=None, rank=0, world=1, barrier=None, merge_path_counts=False):
+    """engine: built with the same -top_k reducer the script would rebuild (:69-79).  merge_path_counts (an extension, default off): score
+    the bucket files in ragged groups (score_batches merge=True); same lines, same order.
 
     Data-parallel scoring (new; the reference is single-device): pairs are independent units, so the FILES of the test list are
     sharded over the ranks in contiguous ranges (dp.shard_pairs), every rank scores its files with no collective and writes
@@ -104,7 +124,7 @@ def test_from_checkpoint(engine, input_dir, test_list, out_file, minibatch=512, 
         start = time.time()
         n = 0
         with open(out_file, "wb") as f:
-            n = write_scores(engine, batcher, f, 1)
+            n = write_scores(engine, batcher, f, 1, merge_path_counts)
         if log:
             print("total cost time:", time.time() - start, file=log)
         return n
@@ -125,7 +145,7 @@ def test_from_checkpoint(engine, input_dir, test_list, out_file, minibatch=512, 
                 with os.fdopen(fd, "w") as sl:
                     sl.write("\n".join(files[lo:hi]) + "\n")
                 batcher = BatcherFileList(input_dir, minibatch, False, 1000, True, os.path.basename(shard_list), check_ids=False)
-                n = write_scores(engine, batcher, out, 1)
+                n = write_scores(engine, batcher, out, 1, merge_path_counts)
             finally:
                 os.unlink(shard_list)
     if barrier is not None:

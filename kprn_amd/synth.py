@@ -82,3 +82,21 @@ def make_bucketed(n_paths_target, T, F=3, Vt=6, Ve=10000, Vr=9, num_types=1, see
         cnt = int((Ps == P).sum())
         out[int(P)] = make_paths(cnt, int(P), T, F, Vt, Ve, Vr, num_types, seed=seed + 1000 + int(P))
     return out
+
+
+def make_ragged(n_pairs, T, F=3, Vt=6, Ve=10000, Vr=9, num_types=1, seed=SEED, pmax=28, counts=None):
+    """A ragged batch: n_pairs pairs, pair b with counts[b] paths (drawn by draw_num_paths unless given), in pair order.
+    -> (idx int32 [N,T,F], counts int32 [n_pairs], labels f32 [n_pairs]); pairs of one count come from one make_paths call."""
+    rng = np.random.default_rng(seed)
+    counts = draw_num_paths(rng, n_pairs, pmax) if counts is None else np.asarray(counts, dtype=np.int32)
+    assert counts.shape == (n_pairs,) and (counts >= 1).all()
+    off = np.concatenate([[0], np.cumsum(counts, dtype=np.int64)])
+    idx = np.empty((int(off[-1]), T, F), dtype=np.int32)
+    labels = np.empty(n_pairs, dtype=np.float32)
+    for P in np.unique(counts):
+        pairs = np.nonzero(counts == P)[0]
+        gi, gl = make_paths(len(pairs), int(P), T, F, Vt, Ve, Vr, num_types, seed=seed + 1000 + int(P))
+        rows = (off[pairs][:, None] + np.arange(int(P))[None, :]).reshape(-1)
+        idx[rows] = gi.reshape(-1, T, F)
+        labels[pairs] = gl
+    return idx, counts, labels
