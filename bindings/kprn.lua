@@ -70,6 +70,14 @@ int kprn_dp_exchange_finish(kprn_handle*, const kprn_opt*);
 int kprn_forward_batch_async_rest(kprn_handle*);
 int kprn_dp_comm_size(kprn_handle*, int32_t*);
 int kprn_dp_shutdown(kprn_handle*);
+/* ranking stage: score board, group ranking under the evaluation chain's rule, top-K (include/kprn.h "ranking") */
+int kprn_board_reserve(kprn_handle*, int64_t);
+int kprn_board_put(kprn_handle*, int64_t, int32_t);
+int kprn_board_write(kprn_handle*, int64_t, const float*, int64_t);
+int kprn_board_read(kprn_handle*, int64_t, float*, int64_t);
+int kprn_rank_groups(kprn_handle*, const int64_t*, const int64_t*, const int32_t*, int32_t, int32_t, int32_t, int32_t*, int32_t*, float*, int64_t*, int32_t);
+int kprn_recommend_ragged(kprn_handle*, const int32_t*, const int32_t*, int32_t, int64_t, int32_t, int32_t, int32_t, const int32_t*, int32_t, int32_t, int32_t, int32_t*, float*, float*);
+int kprn_host_rank_groups(const float*, int64_t, const int64_t*, const int64_t*, const int32_t*, int32_t, int32_t, int32_t, int32_t*, int32_t*, float*, int64_t*, int32_t);
 ]]
 
 local C = ffi.load('kprn')

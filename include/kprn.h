@@ -237,6 +237,57 @@ int kprn_read_probs(kprn_handle* h, float* probs, int32_t B);
 /* embedding sub-net output x[N,T,D] (FeatureEmbedding.lua:112-121), for bit-exact checks */
 int kprn_embed(kprn_handle* h, const int32_t* idx, int64_t N, int32_t T, int32_t F, float* x);
 
+/* ---- ranking (an extension: the reference ranks in Python, from the text file the scoring writer leaves) ----
+ * The reference's evaluation chain (eval/combine_result.py -> resort.py -> eval_score.py) as an engine stage: scores stay on the device, a kernel
+ * ranks GROUPS of candidates (one user's positive and negatives), and only ranks, top-K lists and a rank histogram come back.
+ * A group is a list of member scores s[0..n-1], 1 <= n <= KPRN_RANK_MAX_GROUP, and optionally the position pos of its positive.
+ *  - mode KPRN_RANK_PRINTED (the chain's rule), for scores in [0, 1]: key = the integer "%.5f" prints, times 1e5 = rint((double)s * 1e5) (the product
+ *    is exact in double and rint rounds half to even, as printf does); mode KPRN_RANK_RAW: key = the fp32 value, any finite value or +-inf.
+ *  - invalid members: NaN in either mode (a board entry nothing wrote), and in mode 0 anything outside [0, 1].  An invalid member sorts below every
+ *    valid one and is counted.
+ *  - order: key descending, then member index ascending (heapq.nlargest keeps the first seen on a tie, eval_score.py:38); a member's place is the
+ *    number of members before it in that order.
+ *  - rank of the group = place of member pos (0-based).  Mode 0: a group in which no member prints above zero has rank KPRN_RANK_ZERO_GROUP (a miss for
+ *    every k, eval_score.py:35-36).  pos = -1: no positive, top-K only, rank KPRN_RANK_NO_POSITIVE.
+ *  - top-K: the first K members in that order, 1 <= K <= KPRN_RANK_MAX_K: index within the group and the RAW fp32 score; -1 / 0.0f where n < K.
+ *  - hist [hist_len + 4] (int64): hist[r] = groups of rank r < hist_len, then [hist_len] = ranked lower, [hist_len + 1] = zero groups,
+ *    [hist_len + 2] = groups without positive, [hist_len + 3] = invalid members seen.  hit@k = sum(hist[:k]) / n_groups, ndcg@k =
+ *    sum(hist[r] * ln 2 / ln(r + 2), r < k) / n_groups with n_groups = every group that has a positive (zero groups included), formed by the caller.
+ * Scores are addressed by global line number on a device-resident BOARD, because a user's candidates are not consecutive in a scored test set (the
+ * pairs are bucketed by path count; the chain reunites them by line number, combine_result.py:24-27).  In a data-parallel run every rank ranks what
+ * it scored; nothing here crosses ranks.                                                                                                        */
+#define KPRN_RANK_PRINTED 0
+#define KPRN_RANK_RAW 1
+#define KPRN_RANK_ZERO_GROUP (-1)
+#define KPRN_RANK_NO_POSITIVE (-2)
+#define KPRN_RANK_MAX_GROUP 4096
+#define KPRN_RANK_MAX_K 64
+/* (re)sizes the board to n entries; keeps nothing; every entry starts as NaN (= invalid until written) */
+int kprn_board_reserve(kprn_handle* h, int64_t n);
+/* the selected-class probabilities of the most recent scoring pass (the B values kprn_read_probs would return) -> board[offset .. offset + B), queued
+ * behind that pass on whichever stream ran it, ordered with events the way kprn_read_probs orders its copy (a forgotten second part of a split pass is
+ * placed first).  Async: no host synchronise.  A later pass does not overwrite the pass's output before the put has read it.  KPRN_E_ARG: no pass to
+ * read from, or B beyond that pass's pairs; KPRN_E_INDEX: the range leaves the board.                                                           */
+int kprn_board_put(kprn_handle* h, int64_t offset, int32_t B);
+/* host scores -> board (scores computed elsewhere) and back; both wait for every put queued so far and return when the copy is done */
+int kprn_board_write(kprn_handle* h, int64_t offset, const float* src, int64_t n);
+int kprn_board_read(kprn_handle* h, int64_t offset, float* dst, int64_t n);
+/* ranks G groups of board entries.  members [M] = board line numbers, group g = members[group_offsets[g] .. group_offsets[g + 1]) (a line may appear
+ * more than once); members NULL: group g is the consecutive run of board entries group_offsets[g] .. group_offsets[g + 1].  pos [G] or NULL (= 0
+ * everywhere).  Any of ranks [G], topk_idx + topk_score [G,K] (both or neither), hist [hist_len + 4] may be NULL.  Waits for every put queued so far;
+ * synchronous: the results are on the host when it returns, hist holds this call's groups only.  A member outside the board is KPRN_E_INDEX; a group
+ * outside 1..4096 members, pos outside -1..n-1, K outside 1..64, hist_len outside 1..4096 or an unknown mode is KPRN_E_ARG; on an error nothing is written. */
+int kprn_rank_groups(kprn_handle* h, const int64_t* members, const int64_t* group_offsets, const int32_t* pos, int32_t G,
+                     int32_t mode, int32_t K, int32_t* ranks, int32_t* topk_idx, float* topk_score, int64_t* hist, int32_t hist_len);
+/* one user's (or G users') candidates in host buffers -> each group's K best in one call: the pass of kprn_forward_ragged, ranked on the device behind
+ * it, one wait.  group_counts [G] = pairs per group, consecutive, summing to B.  topk_idx (index within the group) / topk_score [G,K]; probs [B] may be
+ * NULL.  The board is not involved.                                                                                                             */
+int kprn_recommend_ragged(kprn_handle* h, const int32_t* idx, const int32_t* counts, int32_t B, int64_t N, int32_t T, int32_t F, int32_t class_id,
+                          const int32_t* group_counts, int32_t G, int32_t mode, int32_t K, int32_t* topk_idx, float* topk_score, float* probs);
+/* the same rule on the host cores over a host score array (no handle, no GPU): the arguments of kprn_rank_groups with scores [n_scores] as the board */
+int kprn_host_rank_groups(const float* scores, int64_t n_scores, const int64_t* members, const int64_t* group_offsets, const int32_t* pos, int32_t G,
+                          int32_t mode, int32_t K, int32_t* ranks, int32_t* topk_idx, float* topk_score, int64_t* hist, int32_t hist_len);
+
 /* ---- training ---------------------------------------------------------------------- */
 /* fEval of MyOptimizer.lua:184-195: zeroGradParameters; forward; BCE; backward.
  * inv_batch = 0 -> 1/B; data-parallel callers pass 1/B_global.  loss may be NULL (async). */
@@ -369,6 +420,8 @@ int kprn_profile_get(kprn_handle* h, kprn_prof_entry* out, int32_t cap, int32_t*
  *                     (bit-identical)
  *   "fused_small_tables" "1" (default) | "0": fused D = H = 64 path: type / relation table gradients formed inside the bottom BPTT launch | by a
  *                     passenger job of the entity-gradient launch (equal to fp32 re-association)
+ *   "rank_sort_min"   "512" (default) | 257..4097: kprn_rank_groups ranks groups of this many members and more by a sort in LDS, smaller ones by counting
+ *                     against every member (same results; counting is faster at 257 members, the sort from 512 on: profiles/rank/README.md)
  *   "train_step_return" "loss" (default) | "drain": see kprn_train_step
  *   "inline_upload"   "side" (default): kprn_train_step uploads its minibatch on the upload stream, beside the previous step's backward, whenever the previous
  *                     call waited for its loss (every reader of the slot being refilled is then known to be done); "main": on the engine's stream

@@ -90,6 +90,44 @@ def host_ragged_plan(counts, N=None):
                 thread_max=int(sm[4]), wg_paths=int(sm[5]), wg_pairs=int(sm[6]))
 
 
+RANK_PRINTED, RANK_RAW = 0, 1          # kprn_rank_groups modes: the evaluation chain's printed "%.5f" scores | the raw fp32 values
+RANK_ZERO_GROUP, RANK_NO_POSITIVE = -1, -2
+RANK_MAX_GROUP, RANK_MAX_K = 4096, 64
+
+
+def _rank_args(group_offsets, members, pos, K, hist_len):
+    """the arrays of kprn_rank_groups / kprn_host_rank_groups; K = 0: no top-K (the C call still wants a K in range)"""
+    goff = np.ascontiguousarray(group_offsets, np.int64)
+    if goff.ndim != 1 or goff.shape[0] < 2:
+        raise KprnError(E_ARG, "group_offsets must be [G+1], G >= 1")
+    G = int(goff.shape[0]) - 1
+    mem = None if members is None else np.ascontiguousarray(members, np.int64)
+    if mem is not None and (mem.ndim != 1 or goff[0] < 0 or goff[-1] > mem.shape[0]):
+        raise KprnError(E_ARG, "group_offsets must lie inside members")
+    p = None if pos is None else np.ascontiguousarray(pos, np.int32)
+    if p is not None and p.shape != (G,):
+        raise KprnError(E_ARG, "pos must be [G]")
+    if K < 0:
+        raise KprnError(E_ARG, "K must be in 0..64")
+    out = dict(ranks=np.full(G, -3, np.int32), hist=np.zeros(int(max(hist_len, 0)) + 4, np.int64))
+    if K > 0:
+        out["topk_idx"] = np.full((G, K), -3, np.int32)
+        out["topk_score"] = np.zeros((G, K), np.float32)
+    return goff, G, mem, p, out
+
+
+def host_rank_groups(scores, group_offsets, members=None, pos=None, mode=0, K=0, hist_len=15):
+    """kprn_host_rank_groups (no handle, no GPU): the ranking rule of include/kprn.h over a host score array ->
+    dict(ranks [G], hist [hist_len + 4], and with K > 0 topk_idx / topk_score [G,K])"""
+    sc = np.ascontiguousarray(scores, np.float32)
+    goff, G, mem, p, out = _rank_args(group_offsets, members, pos, K, hist_len)
+    rc = lib().kprn_host_rank_groups(_fp(sc), C.c_int64(int(sc.shape[0])), _fp(mem), _fp(goff), _fp(p), G, int(mode), int(K) if K > 0 else 1,
+                                     _fp(out["ranks"]), _fp(out.get("topk_idx")), _fp(out.get("topk_score")), _fp(out["hist"]), int(hist_len))
+    if rc != 0:
+        raise KprnError(rc, "kprn_host_rank_groups: bad groups / members / pos / K / hist_len / mode")
+    return out
+
+
 def format_score_lines(counter0, probs, labels):
     """bytes of the scoring writer's lines for pairs counter0 .. (kprn_format_score_lines; host-only)"""
     L = lib()
@@ -516,6 +554,47 @@ class Engine:
         a = np.empty(B, np.float32)
         self._ck(self.L.kprn_read_probs(self.h, _fp(a), int(B)))
         return a
+
+    # -- ranking (include/kprn.h "ranking") ------------------------------------------------
+    def board_reserve(self, n):
+        """device-resident scores addressed by global line number; every entry starts as NaN"""
+        self._ck(self.L.kprn_board_reserve(self.h, C.c_int64(int(n))))
+
+    def board_put(self, offset, B):
+        """the most recent scoring pass's probabilities (what read_probs(B) would return) -> board[offset : offset + B], asynchronously"""
+        self._ck(self.L.kprn_board_put(self.h, C.c_int64(int(offset)), int(B)))
+
+    def board_write(self, offset, scores):
+        a = np.ascontiguousarray(scores, np.float32)
+        self._ck(self.L.kprn_board_write(self.h, C.c_int64(int(offset)), _fp(a), C.c_int64(a.size)))
+
+    def board_read(self, offset, n):
+        a = np.empty(int(n), np.float32)
+        self._ck(self.L.kprn_board_read(self.h, C.c_int64(int(offset)), _fp(a), C.c_int64(a.size)))
+        return a
+
+    def rank_groups(self, group_offsets, members=None, pos=None, mode=0, K=0, hist_len=15):
+        """kprn_rank_groups over the board: -> dict(ranks [G], hist [hist_len + 4], and with K > 0 topk_idx / topk_score [G,K])"""
+        goff, G, mem, p, out = _rank_args(group_offsets, members, pos, K, hist_len)
+        self._ck(self.L.kprn_rank_groups(self.h, _fp(mem), _fp(goff), _fp(p), G, int(mode), int(K) if K > 0 else 1, _fp(out["ranks"]),
+                                         _fp(out.get("topk_idx")), _fp(out.get("topk_score")), _fp(out["hist"]), int(hist_len)))
+        return out
+
+    def recommend_ragged(self, idx, counts, group_counts, K, class_id=1, mode=0, want_probs=False):
+        """kprn_recommend_ragged: idx [N,T,F] / counts [B] as forward_ragged_host; group_counts [G] pairs per group (sum B) ->
+        (topk_idx [G,K] index within the group, topk_score [G,K], probs [B] or None)"""
+        idx = np.ascontiguousarray(idx, np.int32)
+        counts = np.ascontiguousarray(counts, np.int32)
+        gc = np.ascontiguousarray(group_counts, np.int32)
+        if idx.ndim != 3 or counts.ndim != 1 or gc.ndim != 1 or K < 1:
+            raise KprnError(E_ARG, "a ragged batch is idx [N,T,F] and counts [B]; group_counts [G]; K >= 1")
+        B, G = int(counts.shape[0]), int(gc.shape[0])
+        ti = np.full((G, K), -3, np.int32)
+        ts = np.zeros((G, K), np.float32)
+        probs = np.empty(B, np.float32) if want_probs else None
+        self._ck(self.L.kprn_recommend_ragged(self.h, _fp(idx), _fp(counts), B, C.c_int64(int(idx.shape[0])), int(idx.shape[1]), int(idx.shape[2]),
+                                              int(class_id), _fp(gc), G, int(mode), int(K), _fp(ti), _fp(ts), _fp(probs)))
+        return ti, ts, probs
 
     def embed(self, idx):
         idx = np.ascontiguousarray(idx, np.int32)

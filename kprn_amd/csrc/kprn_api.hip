@@ -163,6 +163,14 @@ void join_score(kprn_handle* h) {
   h->score_pending = false;
 }
 
+// ranking stage: the main stream waits for the board puts queued on the scoring stream (before it reads the board, and before a pass that runs on the
+// main stream writes the side buffers those puts read: "score_dual")
+static void join_put(kprn_handle* h) {
+  if (!h->put_side) return;
+  HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_put, 0));
+  h->put_side = false;
+}
+
 // bring every entity row up to opt_step (needed before anything reads the whole table)
 static void flush_lazy(kprn_handle* h) {
   join_score(h);
@@ -474,6 +482,7 @@ static void forward_impl(kprn_handle* h, const kprn_batch* b, int class_id, bool
       // a deferred scoring pass ("score_dual") rides in this training forward's launch; its pooling stage follows on this stream, and the event the
       // pass's readers wait for is recorded here
       const kprn_batch* sb = h->score_rest_batch;
+      join_put(h);   // (a board put queued on the scoring stream still reads sel2, which this pass's pooling stage writes from THIS stream)
       dual = fused::forward_dual(h, b, sb, h->S2);
       if (dual) {
         h->score_rest_batch = nullptr;
@@ -1089,6 +1098,10 @@ void kprn_destroy(kprn_handle* h) {
   prof_drain(h);
   for (kprn_batch*& d : h->dropin_slot) if (d) { kprn_batch* old = d; d = nullptr; kprn_batch_destroy(h, old); }
   if (h->score_stream) { hipStreamDestroy(h->score_stream); hipEventDestroy(h->ev_fork); hipEventDestroy(h->ev_score_done); }
+  if (h->ev_put) hipEventDestroy(h->ev_put);
+  dfree(h->board);
+  if (h->rank_buf) { hipFree(h->rank_buf); h->rank_buf = nullptr; }
+  if (h->rank_pin) { hipHostFree(h->rank_pin); h->rank_pin = nullptr; }
   if (h->feed_pool) { hostfeed::free_pool((hostfeed::Pool*)h->feed_pool); h->feed_pool = nullptr; }  // (joins the workers)
   if (h->upload_pool) { hostfeed::free_pool((hostfeed::Pool*)h->upload_pool); h->upload_pool = nullptr; }
   if (h->upload_stream) { hipStreamSynchronize(h->upload_stream); hipStreamDestroy(h->upload_stream); h->upload_stream = nullptr; }
@@ -2109,6 +2122,210 @@ int kprn_forward_ragged(kprn_handle* h, const int32_t* idx, const int32_t* count
   return kprn_forward_batch(h, h->dropin_slot[h->dropin_last], class_id, probs, all_probs, nullptr, nullptr);
 }
 
+// ---- ranking stage: the score board, kprn_rank_groups, kprn_recommend_ragged (kernels: rank_groups.hip) ---------------------------------------
+static void sync_all_streams(kprn_handle* h) {
+  if (h->score_stream) HIP_TRY(hipStreamSynchronize(h->score_stream));
+  if (h->rest_stream) HIP_TRY(hipStreamSynchronize(h->rest_stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+}
+
+int kprn_board_reserve(kprn_handle* h, int64_t n) {
+  API_BEGIN(h)
+  KPRN_REQUIRE(n >= 1 && n < (1ll << 40), KPRN_E_ARG, "board size must be >= 1");
+  sync_all_streams(h);   // (queued puts and a ranking call's reads of the old board)
+  h->put_side = false;
+  dfree(h->board);
+  h->board_n = 0;
+  h->board = dalloc<float>(n);
+  h->board_n = n;
+  for (int64_t o = 0; o < n; o += (1ll << 30))   // every entry NaN: ranking counts an entry nothing wrote as invalid
+    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)(h->board + o), 0x7fc00000, (size_t)std::min<int64_t>(n - o, 1ll << 30), h->stream));
+  API_END(h)
+}
+
+int kprn_board_put(kprn_handle* h, int64_t offset, int32_t B) {
+  API_BEGIN(h)
+  KPRN_REQUIRE(h->board, KPRN_E_ARG, "no board: call kprn_board_reserve first");
+  KPRN_REQUIRE(B > 0 && h->last_B > 0 && B <= h->last_B, KPRN_E_ARG, "no scoring pass to read from, or B beyond its pairs");
+  KPRN_REQUIRE(offset >= 0 && offset <= h->board_n - B, KPRN_E_INDEX, "the range leaves the board");
+  if (h->last_forward_side) {
+    // the order of kprn_read_probs, with the copy staying on the device and nobody waiting on the host
+    if (h->score_rest_batch) launch_score_rest(h);
+    if (h->score_on_main) {   // ("score_dual": the pass ran in a training forward's launch on the main stream)
+      HIP_TRY(hipEventRecord(h->ev_fork, h->stream));
+      HIP_TRY(hipStreamWaitEvent(h->score_stream, h->ev_fork, 0));
+    } else if (h->ev_score_done) HIP_TRY(hipStreamWaitEvent(h->score_stream, h->ev_score_done, 0));
+    HIP_TRY(hipMemcpyAsync(h->board + offset, h->sel2, (size_t)B * sizeof(float), hipMemcpyDeviceToDevice, h->score_stream));
+    // later passes on the scoring stream follow the copy in stream order, one on the rest stream starts behind its first part there; a pass that writes
+    // sel2 from the main stream, and every reader of the board, waits for this event (join_put)
+    if (!h->ev_put) HIP_TRY(hipEventCreateWithFlags(&h->ev_put, hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(h->ev_put, h->score_stream));
+    h->put_side = true;
+  } else {
+    HIP_TRY(hipMemcpyAsync(h->board + offset, h->ws.sel, (size_t)B * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+  }
+  API_END(h)
+}
+
+int kprn_board_write(kprn_handle* h, int64_t offset, const float* src, int64_t n) {
+  API_BEGIN(h)
+  KPRN_REQUIRE(h->board, KPRN_E_ARG, "no board: call kprn_board_reserve first");
+  KPRN_REQUIRE(src && n > 0, KPRN_E_ARG, "bad source / n");
+  KPRN_REQUIRE(offset >= 0 && offset <= h->board_n - n, KPRN_E_INDEX, "the range leaves the board");
+  join_put(h);
+  HIP_TRY(hipMemcpyAsync(h->board + offset, src, (size_t)n * sizeof(float), hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  API_END(h)
+}
+
+int kprn_board_read(kprn_handle* h, int64_t offset, float* dst, int64_t n) {
+  API_BEGIN(h)
+  KPRN_REQUIRE(h->board, KPRN_E_ARG, "no board: call kprn_board_reserve first");
+  KPRN_REQUIRE(dst && n > 0, KPRN_E_ARG, "bad destination / n");
+  KPRN_REQUIRE(offset >= 0 && offset <= h->board_n - n, KPRN_E_INDEX, "the range leaves the board");
+  join_put(h);
+  HIP_TRY(hipMemcpyAsync(dst, h->board + offset, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  API_END(h)
+}
+
+// arguments up, one or two launches, results down, all on the main stream; the caller has validated everything (rk::validate) and synchronises
+// The one-call route (kprn_recommend_ragged) moves nothing with copy operations: the group table is read, and the top-K rows are written, by the kernel itself in
+// page-locked host memory (as kprn_forward_batch's probabilities are), so the call is the pass, the pooling stage, one ranking launch and one wait; the rows are
+// handed out after that wait (rank_pinned_fetch).  Measured with copies: 95 us a user against 68 us for kprn_forward_ragged + the host rule (profiles/rank).
+static void rank_run_pinned(kprn_handle* h, const float* dev_scores, const int64_t* goff, int32_t G, int32_t mode, int32_t K, int max_n) {
+  const size_t o_ti = ((size_t)(G + 1) * 8 + 15) & ~(size_t)15, o_ts = o_ti + (((size_t)G * K * 4 + 15) & ~(size_t)15), total = o_ts + (size_t)G * K * 4;
+  if (total > h->rank_pin_bytes) {
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (h->rank_pin) { HIP_TRY(hipHostFree(h->rank_pin)); h->rank_pin = nullptr; h->rank_pin_bytes = 0; }
+    HIP_TRY(hipHostMalloc(&h->rank_pin, 2 * total + 256));
+    h->rank_pin_bytes = 2 * total + 256;
+  }
+  char* base = (char*)h->rank_pin;
+  memcpy(base, goff, (size_t)(G + 1) * 8);
+  h->rank_pin_off[0] = o_ti; h->rank_pin_off[1] = o_ts;
+  rk::Args a;
+  a.scores = dev_scores; a.members = nullptr; a.goff = (const int64_t*)base; a.pos = nullptr;
+  a.G = G; a.mode = mode; a.K = K; a.hist_len = 1;
+  a.ranks = nullptr; a.tk_idx = (int32_t*)(base + o_ti); a.tk_score = (float*)(base + o_ts); a.hist = nullptr;
+  a.sort_min = h->rank_sort_min;
+  ProfScope ps(h, "rank_groups");
+  rk::launch(h->stream, a, max_n);
+}
+static void rank_pinned_fetch(kprn_handle* h, int32_t G, int32_t K, int32_t* topk_idx, float* topk_score) {
+  memcpy(topk_idx, (char*)h->rank_pin + h->rank_pin_off[0], (size_t)G * K * 4);
+  memcpy(topk_score, (char*)h->rank_pin + h->rank_pin_off[1], (size_t)G * K * 4);
+}
+
+static void rank_run(kprn_handle* h, const float* dev_scores, const int64_t* members, const int64_t* goff, const int32_t* pos, int32_t G, int32_t mode, int32_t K,
+                     int max_n, int32_t* ranks, int32_t* topk_idx, float* topk_score, int64_t* hist, int32_t hist_len) {
+  const int64_t m0 = goff[0], M = members ? goff[G] - m0 : 0;
+  auto up8 = [](size_t b) { return (b + 15) & ~(size_t)15; };
+  const size_t o_goff = 0, o_mem = o_goff + up8((size_t)(G + 1) * 8), o_hist = o_mem + up8((size_t)M * 8), o_pos = o_hist + up8((size_t)(hist_len + 4) * 8),
+               o_ranks = o_pos + up8((size_t)G * 4), o_ti = o_ranks + up8((size_t)G * 4), o_ts = o_ti + up8((size_t)G * K * 4), total = o_ts + up8((size_t)G * K * 4);
+  if (total > h->rank_buf_bytes) {
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (h->rank_buf) { hipFree(h->rank_buf); h->rank_buf = nullptr; h->rank_buf_bytes = 0; }
+    hipError_t e = kprn_dev_malloc(&h->rank_buf, total + total / 4 + 64);
+    if (e != hipSuccess) throw KprnError{KPRN_E_NOMEM, std::string("hipMalloc failed: ") + hipGetErrorString(e)};
+    h->rank_buf_bytes = total + total / 4;
+  }
+  char* base = (char*)h->rank_buf;
+  hipStream_t s = h->stream;
+  std::vector<int64_t> rebased;
+  const int64_t* goff_up = goff;
+  if (members && m0 != 0) {   // (the kernels index the uploaded slice of members from 0)
+    rebased.assign(goff, goff + G + 1);
+    for (auto& v : rebased) v -= m0;
+    goff_up = rebased.data();
+  }
+  HIP_TRY(hipMemcpyAsync(base + o_goff, goff_up, (size_t)(G + 1) * 8, hipMemcpyHostToDevice, s));
+  if (members) HIP_TRY(hipMemcpyAsync(base + o_mem, members + m0, (size_t)M * 8, hipMemcpyHostToDevice, s));
+  if (pos) HIP_TRY(hipMemcpyAsync(base + o_pos, pos, (size_t)G * 4, hipMemcpyHostToDevice, s));
+  if (rebased.size()) HIP_TRY(hipStreamSynchronize(s));   // (the copy's source is a local)
+  if (hist) HIP_TRY(hipMemsetAsync(base + o_hist, 0, (size_t)(hist_len + 4) * 8, s));
+  rk::Args a;
+  a.scores = dev_scores; a.members = members ? (const int64_t*)(base + o_mem) : nullptr; a.goff = (const int64_t*)(base + o_goff);
+  a.pos = pos ? (const int32_t*)(base + o_pos) : nullptr;
+  a.G = G; a.mode = mode; a.K = K; a.hist_len = hist_len;
+  a.ranks = ranks ? (int32_t*)(base + o_ranks) : nullptr;
+  a.tk_idx = topk_idx ? (int32_t*)(base + o_ti) : nullptr; a.tk_score = topk_idx ? (float*)(base + o_ts) : nullptr;
+  a.hist = hist ? (unsigned long long*)(base + o_hist) : nullptr;
+  a.sort_min = h->rank_sort_min;
+  {
+    ProfScope ps(h, "rank_groups");
+    rk::launch(s, a, max_n);
+  }
+  if (ranks) HIP_TRY(hipMemcpyAsync(ranks, base + o_ranks, (size_t)G * 4, hipMemcpyDeviceToHost, s));
+  if (topk_idx) {
+    HIP_TRY(hipMemcpyAsync(topk_idx, base + o_ti, (size_t)G * K * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(topk_score, base + o_ts, (size_t)G * K * 4, hipMemcpyDeviceToHost, s));
+  }
+  if (hist) HIP_TRY(hipMemcpyAsync(hist, base + o_hist, (size_t)(hist_len + 4) * 8, hipMemcpyDeviceToHost, s));
+}
+
+int kprn_rank_groups(kprn_handle* h, const int64_t* members, const int64_t* group_offsets, const int32_t* pos, int32_t G, int32_t mode, int32_t K,
+                     int32_t* ranks, int32_t* topk_idx, float* topk_score, int64_t* hist, int32_t hist_len) {
+  API_BEGIN(h)
+  KPRN_REQUIRE(h->board, KPRN_E_ARG, "no board: call kprn_board_reserve first");
+  KPRN_REQUIRE((topk_idx == nullptr) == (topk_score == nullptr), KPRN_E_ARG, "topk_idx and topk_score go together");
+  int max_n = 0;
+  std::string why;
+  const int rc = rk::validate(h->board_n, members, group_offsets, pos, G, mode, K, hist_len, &max_n, &why);
+  if (rc != KPRN_OK) throw KprnError{rc, why};
+  join_put(h);
+  rank_run(h, h->board, members, group_offsets, pos, G, mode, K, max_n, ranks, topk_idx, topk_score, hist, hist_len);
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  prof_drain(h);
+  API_END(h)
+}
+
+// the refusals of kprn_recommend_ragged that need no device work, before anything is fed
+static int recommend_check(kprn_handle* h, const int32_t* counts, int32_t B, const int32_t* group_counts, int32_t G, int32_t mode, int32_t K,
+                           const int32_t* topk_idx, const float* topk_score, std::vector<int64_t>& goff, int* max_n) {
+  API_BEGIN(h)
+  KPRN_REQUIRE(counts && group_counts && topk_idx && topk_score && G >= 1 && B >= 1, KPRN_E_ARG, "NULL argument, or G / B < 1");
+  goff.assign((size_t)G + 1, 0);
+  for (int32_t g = 0; g < G; ++g) goff[g + 1] = goff[g] + group_counts[g];
+  KPRN_REQUIRE(goff[G] == B, KPRN_E_ARG, "group_counts do not add up to B");
+  std::string why;
+  const int rc = rk::validate(B, nullptr, goff.data(), nullptr, G, mode, K, 1, max_n, &why);
+  if (rc != KPRN_OK) throw KprnError{rc, why};
+  API_END(h)
+}
+
+int kprn_recommend_ragged(kprn_handle* h, const int32_t* idx, const int32_t* counts, int32_t B, int64_t N, int32_t T, int32_t F, int32_t class_id,
+                          const int32_t* group_counts, int32_t G, int32_t mode, int32_t K, int32_t* topk_idx, float* topk_score, float* probs) {
+  if (!h) return KPRN_E_ARG;
+  std::vector<int64_t> goff;
+  int max_n = 0;
+  int rc = recommend_check(h, counts, B, group_counts, G, mode, K, topk_idx, topk_score, goff, &max_n);
+  if (rc != KPRN_OK) return rc;
+  rc = dropin_feed(h, /*score=*/true, idx, nullptr, B, 0, T, F, counts, N);
+  if (rc != KPRN_OK) return rc;
+  API_BEGIN(h)
+  // the pass of kprn_forward_ragged, the ranking kernel behind it on the same stream over the pass's own output, one wait for both; the probabilities come
+  // back through the pool kernel's page-locked mirror as in kprn_forward_batch
+  struct Disarm { kprn_handle* h; ~Disarm() { h->sel_host_armed = nullptr; } } disarm{h};
+  const bool mirror = probs != nullptr && !h->prof_on;
+  if (mirror) {
+    if ((int64_t)B > h->probs_mirror_cap) {
+      if (h->probs_mirror) { HIP_TRY(hipStreamSynchronize(h->stream)); HIP_TRY(hipHostFree(h->probs_mirror)); h->probs_mirror = nullptr; h->probs_mirror_cap = 0; }
+      HIP_TRY(hipHostMalloc((void**)&h->probs_mirror, (size_t)(2 * (int64_t)B + 64) * sizeof(float)));
+      h->probs_mirror_cap = 2 * (int64_t)B + 64;
+    }
+    h->sel_host_armed = h->probs_mirror;
+  }
+  forward_impl(h, h->dropin_slot[h->dropin_last], class_id, false, /*do_pool=*/true, /*every_class=*/false);
+  rank_run_pinned(h, h->ws.sel, goff.data(), G, mode, K, max_n);
+  if (probs && !mirror) HIP_TRY(hipMemcpyAsync(probs, h->ws.sel, (size_t)B * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  rank_pinned_fetch(h, G, K, topk_idx, topk_score);
+  if (mirror) memcpy(probs, h->probs_mirror, (size_t)B * sizeof(float));
+  prof_drain(h);
+  API_END(h)
+}
+
 int kprn_embed(kprn_handle* h, const int32_t* idx, int64_t N, int32_t T, int32_t F, float* x) {
   API_BEGIN(h)
   KPRN_REQUIRE(idx && x && N > 0 && T > 0 && F == h->cfg.F, KPRN_E_ARG, "bad arguments");
@@ -2654,6 +2871,12 @@ int kprn_set_option(kprn_handle* h, const char* key, const char* value) {
     const int v = atoi(value);
     KPRN_REQUIRE(v >= 0 && v <= 2, KPRN_E_ARG, "tile_handover must be 0, 1 or 2");
     h->tile_handover = v;
+  } else if (strcmp(key, "rank_sort_min") == 0) {
+    // ranking stage: groups of this many members and more are ranked by an LDS sort, smaller ones by counting (rank_groups.hip; same results).  257 = every
+    // group the workgroup kernel takes is sorted, 4097 = none is: the two sides of the measurement in profiles/rank/README.md
+    const int v = atoi(value);
+    KPRN_REQUIRE(v >= 257 && v <= 4097, KPRN_E_ARG, "rank_sort_min must be in 257..4097");
+    h->rank_sort_min = v;
   } else if (strcmp(key, "adam_merged") == 0) {
     // lazy-exact Adam: the entity rows' update and the dense arena's update in ONE launch ("1", default) or in two ("0": the A/B reference; bit-identical)
     h->adam_merged = atoi(value) != 0;

@@ -262,6 +262,13 @@ struct kprn_handle {
   float* S2 = nullptr; float* sel2 = nullptr; int64_t cap_N2 = 0, cap_B2 = 0;
   int reserve_cus = 0;          // CUs the SCORING forward leaves free (a collective's copy kernels run beside it; kprn_set_option)
   int32_t last_B = 0;
+  // ranking stage (rank_groups.hip): the score board = device-resident scores addressed by global line number.  kprn_board_put copies a pass's output
+  // on the stream that produced it; a put queued on the scoring stream leaves ev_put behind it (put_side: not yet waited for by the main stream)
+  float* board = nullptr; int64_t board_n = 0;
+  hipEvent_t ev_put = nullptr; bool put_side = false;
+  void* rank_buf = nullptr; size_t rank_buf_bytes = 0;   // device arguments and results of one kprn_rank_groups call
+  int rank_sort_min = 512;   // option "rank_sort_min": counting wins at 257 members, the sort at 512 and above (profiles/rank/README.md, comparison 3)
+  void* rank_pin = nullptr; size_t rank_pin_bytes = 0, rank_pin_off[2] = {0, 0};   // page-locked group table and top-K rows of kprn_recommend_ragged
 
   bool prof_on = false;
 
@@ -371,6 +378,20 @@ void fill_uniform(hipStream_t s, float* x, int64_t n, float a, uint64_t seed, ui
 void fill_i32(hipStream_t s, int32_t* x, int64_t n, int32_t v);
 void clear_rows(hipStream_t s, float* G, const int32_t* rows, const int32_t* count, int64_t max_rows, int d);
 }  // namespace kk
+
+// ---- ranking stage (rank_groups.hip) -------------------------------------------------------------
+namespace rk {
+struct Args {   // device pointers; members / pos / ranks / tk_idx + tk_score / hist may be null
+  const float* scores; const int64_t* members; const int64_t* goff; const int32_t* pos;
+  int G, mode, K, hist_len;
+  int32_t* ranks; int32_t* tk_idx; float* tk_score; unsigned long long* hist;
+  int sort_min;   // groups of this many members and more are sorted in LDS, smaller ones counted
+};
+// the refusals of kprn_rank_groups / kprn_host_rank_groups on host arrays: KPRN_OK, or the status with its text in *why; *max_n = the longest group
+int validate(int64_t n_scores, const int64_t* members, const int64_t* goff, const int32_t* pos, int32_t G, int32_t mode, int32_t K, int32_t hist_len,
+             int* max_n, std::string* why);
+void launch(hipStream_t s, const Args& a, int max_n);   // hist must be zero; every group is ranked by exactly one of the two kernels
+}  // namespace rk
 
 // ---- batch occurrence index (batch_index.hip) -------------------------------------------------
 namespace bidx {

@@ -41,6 +41,9 @@ def flag_parser():
     a("-seed", type=int, default=12345); a("-entityUpdate", type=int, default=0)
     a("-checkpointFormat", default="native", choices=["native", "t7", "both"],
       help="the native checkpoint is always written at <model>-latest; t7 / both ALSO write <model>-latest.t7, the parameters in a Torch7 {embeddingLayer, predictor_net} container (the reference writes its container at <model>-latest itself)")
+    # evaluation during training (the slot OneModel.lua:389 left commented out): every -evaluationFrequency epochs the pairs of -testList are scored
+    # and the groups of -rank_samples ranked on the device (scoring.rank_test_set); without -rank_samples nothing is evaluated
+    a("-rank_samples", default=""); a("-rank_entity", default=""); a("-rank_users", default=""); a("-testList", default="test.list")
     return p
 
 

@@ -13,6 +13,9 @@ def main(argv=None):
     p.add_argument("-meanModel", type=int, default=0); p.add_argument("-model_path", default=""); p.add_argument("-test_list", default="")
     p.add_argument("-gpu_id", type=int, default=-1); p.add_argument("-top_k", type=int, default=2); p.add_argument("-k", type=int, default=5)
     p.add_argument("-mergePathCounts", type=int, default=0)   # 1: bucket files are scored in ragged groups (an extension; same output lines)
+    # ranking on the device (an extension): the evaluation chain's hit@k / ndcg@k (eval/combine_result.py, resort.py, eval_score.py) in the same run
+    p.add_argument("-rank_samples", default=""); p.add_argument("-rank_entity", default=""); p.add_argument("-rank_users", default="")
+    p.add_argument("-rank_out", default="")
     args, rest = p.parse_known_args(argv)
     assert args.input_dir != "", "input_dir isnt set. Point to the dir where train/dev/test.list files reside"
     params = model.parse_flags(rest)
@@ -33,6 +36,12 @@ def main(argv=None):
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         dist.init_process_group("gloo")   # (a barrier only: no tensor moves between the ranks)
         barrier = dist.barrier
+    if args.rank_samples:
+        assert args.rank_entity != "", "-rank_samples needs -rank_entity (the positional test.list.entity file)"
+        assert world == 1, "-rank_samples ranks what one rank scored: run it on a single rank"
+        scoring.test_and_rank(eng, args.input_dir, args.test_list, args.out_file, args.rank_samples, args.rank_entity, args.rank_users or None,
+                              args.rank_out or None, log=sys.stdout, merge_path_counts=bool(args.mergePathCounts))
+        return 0
     scoring.test_from_checkpoint(eng, args.input_dir, args.test_list, args.out_file, log=sys.stdout if rank == 0 else None,
                                  rank=rank, world=world, barrier=barrier, merge_path_counts=bool(args.mergePathCounts))
     if world > 1:

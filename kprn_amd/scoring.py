@@ -92,6 +92,51 @@ def _score_batches(engine, batcher, class_id, streaming, merge=False):
             return
 
 
+def rank_test_set(engine, batcher, members, group_offsets, mode=0, K=0, merge=False, class_id=1, pos=None, hist_len=15, on_scores=None):
+    """Scores the batcher's test set and ranks groups of its pairs on the device: the streaming loop of score_batches with Engine.board_put in
+    place of read_probs -- the probabilities never leave the device and no engine call waits for the host -- and ONE Engine.rank_groups at the end.
+    members / group_offsets address pairs by global line number (= the counter of the scoring writer's lines; evalrank.group_index builds them).
+    on_scores(counter, labels, count): called per group of pairs once its put is queued (the caller that also wants the lines reads the board).
+    -> (dict of Engine.rank_groups, number of pairs scored)"""
+    import numpy as np
+    group_offsets = np.ascontiguousarray(group_offsets, np.int64)
+    members = None if members is None else np.ascontiguousarray(members, np.int64)
+    saved = [(b, b.batchSize) for b in getattr(batcher, "batchers", [])]
+    total = sum(int(b.labels.shape[0]) for b, _ in saved)
+    need = int(members.max()) + 1 if members is not None and members.size else int(group_offsets[-1])
+    engine.board_reserve(max(total, need, 1))
+    counter = 0
+    try:
+        for b, _ in saved:
+            b.batchSize = max(b.batchSize, ENGINE_BATCH_PATHS // max(1, b.numPaths))
+        slots = [None] * (FEED_AHEAD + 2)
+        k = 0
+        fed = []
+        done = False
+        while True:
+            while not done and len(fed) < FEED_AHEAD:
+                got = _next_group(engine, batcher, merge)
+                if got is None:
+                    done = True
+                    break
+                labs, count, feed, _make = got
+                slots[k] = feed(slots[k])
+                fed.append((slots[k], labs, count))
+                k = (k + 1) % len(slots)
+            if not fed:
+                break
+            slot, labs, count = fed.pop(0)
+            engine.forward_async(slot, class_id)
+            engine.board_put(counter, count)
+            if on_scores is not None:
+                on_scores(counter, labs, count)
+            counter += count
+    finally:
+        for b, size in saved:
+            b.batchSize = size
+    return engine.rank_groups(group_offsets, members, pos=pos, mode=mode, K=K, hist_len=hist_len), counter
+
+
 def score_lines(engine, batcher, class_id=1):
     counter = 0
     for labs, preds in score_batches(engine, batcher, class_id):
@@ -164,3 +209,45 @@ def test_from_checkpoint(engine, input_dir, test_list, out_file, minibatch=512, 
         if log:
             print("total cost time:", time.time() - start, file=log)
     return n
+
+
+def test_and_rank(engine, input_dir, test_list, out_file, samples_file, entity_file, users_file=None, rank_out=None, minibatch=512, log=None,
+                  merge_path_counts=False):
+    """test_from_checkpoint (single rank) + the evaluation chain's metrics in one pass: every pair is scored once, its probability goes to the
+    engine's board, the groups of `samples_file` (eval_score.py's test samples) are ranked on the device, and `out_file` gets the scoring writer's
+    lines from the same board -- byte-identical to test_from_checkpoint's.  rank_out: the two lines of eval_score.py:158-159.
+    -> (pairs scored, hits, ndcgs, groups ranked)"""
+    import numpy as np
+    from . import _ffi, evalrank
+    with open(entity_file) as f:
+        entity_lines = f.readlines()
+    with open(samples_file) as f:
+        samples = evalrank.read_samples(f)
+    users = None
+    if users_file:
+        with open(users_file) as f:
+            users = f.readlines()
+    members, group_offsets, n_used = evalrank.group_index(entity_lines, samples, users)
+    batcher = BatcherFileList(input_dir, minibatch, False, 1000, True, test_list, check_ids=False)
+    start = time.time()
+    labels = []
+    ks = range(1, 16)
+    if n_used == 0:
+        res, n = None, 0
+        with open(out_file, "wb") as f:
+            n = write_scores(engine, batcher, f, 1, merge_path_counts)
+        hits, ndcgs = {k: 0.0 for k in ks}, {k: 0.0 for k in ks}
+    else:
+        res, n = rank_test_set(engine, batcher, members, group_offsets, merge=merge_path_counts, on_scores=lambda c, labs, cnt: labels.append(np.array(labs[:cnt], np.float32)))
+        with open(out_file, "wb") as f:
+            if n:
+                f.write(_ffi.format_score_lines(0, engine.board_read(0, n), np.concatenate(labels)))
+        hits, ndcgs, n_used = evalrank.metrics_from_hist(res["hist"], 15, ks)
+    if log:
+        print("total cost time:", time.time() - start, file=log)
+        print("hit score:", ["%.5f" % hits[k] for k in ks], file=log)      # eval_score.py:153-154
+        print("ndcg score:", ["%.5f" % ndcgs[k] for k in ks], file=log)
+    if rank_out:
+        with open(rank_out, "w") as f:
+            f.writelines(evalrank.format_metric_lines(hits, ndcgs, ks))
+    return n, hits, ndcgs, n_used

@@ -12,6 +12,34 @@ from .batcher import BatcherFileList
 from .optimizer import MyOptimizer, OptimizerCallback
 
 
+def make_evaluator(eng, params, log=None):
+    """the epoch hook behind -evaluationFrequency: scores -testList, ranks the groups of -rank_samples on the device, prints hit@k / ndcg@k"""
+    from . import evalrank, scoring
+    assert params.rank_entity, "-rank_samples needs -rank_entity (the positional test.list.entity file)"
+    with open(params.rank_entity) as f:
+        entity_lines = f.readlines()
+    with open(params.rank_samples) as f:
+        samples = evalrank.read_samples(f)
+    users = None
+    if params.rank_users:
+        with open(params.rank_users) as f:
+            users = f.readlines()
+    members, group_offsets, n_used = evalrank.group_index(entity_lines, samples, users)
+    testBatcher = BatcherFileList(params.dataDir, params.testTimeMinibatch, False, 1000, params.gpuid != -1, params.testList, check_ids=False)
+
+    def evaluator(i):
+        if n_used == 0:
+            print("evaluation: no test sample has all its pairs in " + params.rank_entity, file=log or sys.stdout)
+            return None
+        testBatcher.reset()
+        res, _n = scoring.rank_test_set(eng, testBatcher, members, group_offsets)
+        hits, ndcgs, n = evalrank.metrics_from_hist(res["hist"], 15)
+        print("evaluation at epoch %d over %d samples: " % (i, n) +
+              "  ".join("hit@%d %.5f ndcg@%d %.5f" % (k, hits[k], k, ndcgs[k]) for k in (1, 5, 10, 15)), file=log or sys.stdout)
+        return hits, ndcgs, n
+    return evaluator
+
+
 def main(argv=None):
     params = model.parse_flags(argv)
     if params.createExptDir == 1 and params.exptDir:
@@ -35,6 +63,8 @@ def main(argv=None):
             callbacks.append(OptimizerCallback(params.saveFrequency, saver, "saving"))
         else:
             print("WARNING! - createExptDir is NOT set!")
+    if params.rank_samples:
+        callbacks.append(OptimizerCallback(params.evaluationFrequency, make_evaluator(eng, params), "evaluation"))   # (OneModel.lua:389)
     opt = model.opt_from_flags(params)
     optimizer = MyOptimizer(eng, {"numEpochs": params.numEpochs, "epochHooks": callbacks, "minibatchsize": params.minibatch},
                             opt, startIteration=params.startIteration, gradientStepCounter=params.gradientStepCounter)
