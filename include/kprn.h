@@ -420,6 +420,10 @@ int kprn_profile_get(kprn_handle* h, kprn_prof_entry* out, int32_t cap, int32_t*
  *                     (bit-identical)
  *   "fused_small_tables" "1" (default) | "0": fused D = H = 64 path: type / relation table gradients formed inside the bottom BPTT launch | by a
  *                     passenger job of the entity-gradient launch (equal to fp32 re-association)
+ *   "small_tables_fwd" "1" (default) | "0": fused D = H = 64 forward (fp32, two layers, one type slot, dt = dr = 16, de = 32, Vt + Vr <= 16): layer 0's input
+ *                     half multiplies [one-hot(relation, type) | entity row] by [Q ; W_i2g[:, entity cols]^T] with Q = table W_i2g[:, its cols]^T formed in the
+ *                     launch's prologue (K = 48 instead of 64) | the full x row (equal to fp32 re-association of 32 of the 64 terms).  Independent of
+ *                     "small_tables", which leaves the forward bit-identical
  *   "rank_sort_min"   "512" (default) | 257..4097: kprn_rank_groups ranks groups of this many members and more by a sort in LDS, smaller ones by counting
  *                     against every member (same results; counting is faster at 257 members, the sort from 512 on: profiles/rank/README.md)
  *   "train_step_return" "loss" (default) | "drain": see kprn_train_step

@@ -2909,6 +2909,11 @@ int kprn_set_option(kprn_handle* h, const char* key, const char* value) {
     // generic fp32 pipelines: layer 0's type / relation gradients from G = dA^T [S_r | S_t] ("1", default) or from the full dx product + the
     // table-gradient launch ("0": the A/B reference)
     h->small_tables = atoi(value) != 0;
+  } else if (strcmp(key, "small_tables_fwd") == 0) {
+    // fused D = H = 64 forward (fp32, two layers, one type slot, dt = dr = 16, de = 32, Vt + Vr <= 16): layer 0's input half through the small-table identity,
+    // K = 48 instead of 64 ("1", default) or over the full x row ("0": the A/B reference).  A key of its own: "small_tables" must leave the forward bit-identical.
+    join_score(h);   // (a pass already queued keeps the route it was queued under)
+    h->small_tables_fwd = atoi(value) != 0;
   } else if (strcmp(key, "bf16_t_pad") == 0) {
     bf16p::set_t_pad(atoi(value));   // small-table route: pad (elements) of the row pitch of dA^T / Z^T ("0": rows 2^18-aligned at the bench's size)
   } else if (strcmp(key, "bf16_gemm_regstage") == 0) {

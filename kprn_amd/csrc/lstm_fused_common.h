@@ -32,6 +32,7 @@ struct FwdArgs {
   int T, F, nT;
   const float *Wt, *We, *Wr;
   int dt, de, dr;
+  int Vt, Vr;        // rows of the type / relation tables (the forward's identity route: one-hot column of relation v = v, of type v = Vr + v)
   const float* Wi[2];
   const float* bi[2];
   const float* Wo[2];
@@ -195,6 +196,49 @@ __device__ __forceinline__ void gather_store(float* xbuf, const f32x4 (&v)[MTR *
   }
 }
 
+// ---- the forward's identity route (lstm_fused_fwd.hip fwd_body IDENT) ----------------------------
+// The x tile is [S | x_e]: 16 one-hot columns (relation v at column v, type v at Vr + v, as kk::onehot_cols and the backward's gather_load_ident lay
+// them out), then the entity row (de = 32): 12 16-byte chunks per row, of which only the 8 entity ones are loads (columns 48..63 of the LDS tile are
+// neither written nor read).  64-row tiles: a thread serves entity chunk (tid & 7) of rows (tid >> 3) and (tid >> 3) + 32, and one-hot chunk (tid & 3)
+// of row tid >> 2.  16-row tiles: threads 0..127 one entity chunk, threads 128..191 one one-hot chunk, the last 64 threads a one-hot chunk of rows 16..31
+// of the LDS tile, which nothing reads (no load and no LDS write under a condition: DESIGN.md 3.4c).  The one-hot chunk is formed at the store: two id
+// registers wait through the slot instead of four floats.
+constexpr int IDENT_DE = 32, IDENT_NS = 16;
+template <int MTR> struct IdentGather { f32x4 e[MTR == 64 ? 2 : 1]; int rel, typ; };
+template <int NTHREADS, int MTR, class Args>
+__device__ __forceinline__ void gather_load_ident_fwd(const Args& a, int t, const int32_t* ids, IdentGather<MTR>& g) {
+  static_assert(NTHREADS == 256 && (MTR == 64 || MTR == 16), "3 pieces per thread of a 64-row tile, at most one of a 16-row tile");
+  const int tid = threadIdx.x;
+  const float* eb = a.We - IDENT_DE + (tid & 7) * 4;   // the row one down: the ids are raw (1-based)
+  const int32_t* p = ids + t * MTR;
+  if constexpr (MTR == 64) {
+#pragma unroll
+    for (int k = 0; k < 2; ++k) g.e[k] = *(const f32x4*)(eb + (int64_t)p[IDS_PLANE<MTR> + (tid >> 3) + 32 * k] * IDENT_DE);
+    g.rel = p[2 * IDS_PLANE<MTR> + (tid >> 2)] - 1;
+    g.typ = a.Vr + p[tid >> 2] - 1;
+  } else {
+    g.e[0] = *(const f32x4*)(eb + (int64_t)p[IDS_PLANE<MTR> + ((tid >> 3) & 15)] * IDENT_DE);
+    g.rel = p[2 * IDS_PLANE<MTR> + ((tid >> 2) & 15)] - 1;
+    g.typ = a.Vr + p[(tid >> 2) & 15] - 1;
+  }
+}
+template <int NTHREADS, int MTR>
+__device__ __forceinline__ void gather_store_ident_fwd(float* xbuf, const IdentGather<MTR>& g) {
+  const int tid = threadIdx.x, c0 = 4 * (tid & 3);
+  f32x4 oh;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) oh[i] = (c0 + i == g.rel || c0 + i == g.typ) ? 1.f : 0.f;
+  if constexpr (MTR == 64) {
+    *(f32x4*)(xbuf + (tid >> 2) * LDA + c0) = oh;
+#pragma unroll
+    for (int k = 0; k < 2; ++k) *(f32x4*)(xbuf + ((tid >> 3) + 32 * k) * LDA + IDENT_NS + (tid & 7) * 4) = g.e[k];
+  } else {
+    const bool ent = tid < 128;
+    const int off = ent ? (tid >> 3) * LDA + IDENT_NS + (tid & 7) * 4 : ((tid >> 2) - 32) * LDA + c0;
+    *(f32x4*)(xbuf + off) = ent ? g.e[0] : oh;
+  }
+}
+
 // Training saves, per (16-row m-tile, t, layer, wave): NPL planes of 1 KiB in MFMA C-fragment order (lane-major
 // float4: lane (ag, arow), register r <-> row 4 ag + r, hidden col 16 wave + arow).  The forward stores the
 // factors the backward multiplies by, not the raw gates, so the cell backward is 7 VALU ops per element:
@@ -235,6 +279,10 @@ __device__ __forceinline__ gchar* uniform_global(const void* p) {
 // write needs 2 wait states before an MFMA may read it, which hipcc inserts for its own MFMAs only
 #define KPRN_MFMA_VV(ACC, A_, B_) asm volatile("s_nop 1\n\tv_mfma_f32_16x16x4_f32 %0, %1, %2, %0" : "+v"(ACC) : "v"(A_), "v"(B_))
 #define KPRN_MFMA_VVZ(ACC, A_, B_) asm volatile("s_nop 1\n\tv_mfma_f32_16x16x4_f32 %0, %1, %2, 0" : "=&v"(ACC) : "v"(A_), "v"(B_))
+// A operand possibly a VALU result of the instruction right before (hipcc copies vector elements between asm statements), B operand a pinned ("a") register;
+// _Z: first MFMA of a chain, srcC = 0
+#define KPRN_MFMA_VA_Z(ACC, A_, B_) asm volatile("s_nop 1\n\tv_mfma_f32_16x16x4_f32 %0, %1, %2, 0" : "=&v"(ACC) : "v"(A_), "a"(B_))
+#define KPRN_MFMA_VA(ACC, A_, B_) asm volatile("s_nop 1\n\tv_mfma_f32_16x16x4_f32 %0, %1, %2, %0" : "+v"(ACC) : "v"(A_), "a"(B_))
 #define KPRN_MFMA_DRAIN() asm volatile("s_nop 15\n\ts_nop 15" ::: "memory")
 // A drain orders nothing for hipcc's scheduler by itself: an operand-less asm statement has no data dependency on the values it
 // protects, and a VALU read of an MFMA result may be scheduled above it (seen on the matrix-core forward: the first two
