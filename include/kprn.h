@@ -288,6 +288,36 @@ int kprn_recommend_ragged(kprn_handle* h, const int32_t* idx, const int32_t* cou
 int kprn_host_rank_groups(const float* scores, int64_t n_scores, const int64_t* members, const int64_t* group_offsets, const int32_t* pos, int32_t G,
                           int32_t mode, int32_t K, int32_t* ranks, int32_t* topk_idx, float* topk_score, int64_t* hist, int32_t hist_len);
 
+/* ---- explaining a recommendation (an extension: the paper's pooling layer read backwards) ----
+ * Which paths put a pair where it is: the M strongest paths behind the pair's pooled score in the selected class, each with the share it takes of that
+ * score, w_q = d pooled / d s_q (the factor the loss stage multiplies dy by).  For a pair whose cnt paths have the fp32 scores s_0 .. s_{cnt-1}:
+ *  - order: score descending, then path index ascending among equal scores (plain fp32 > / ==, so -0 and +0 tie; the reducers' own tie rule); a NaN
+ *    score sorts after every number, lower index first.
+ *  - weight: LogSumExp: expf(s_q - m) / sum_p expf(s_p - m), m = the maximum; Max: 1 for the first place, 0 elsewhere; TopK + Mean: 1 / kk for the
+ *    first kk = min(K, cnt) places, 0 elsewhere.
+ *  - per explained pair, 1 <= M <= KPRN_EXPLAIN_MAX_M: path_idx [M] (index within the pair, 0-based; -1 where cnt < M), path_score [M] (the raw fp32
+ *    score; 0.0f in empty places), path_weight [M] (0.0f in empty places), pooled (the reducer's output) and prob = sigmoid(pooled): the bits a scoring
+ *    pass over the batch returns for that pair.
+ * The mapper output stays on the device; only the M rows per pair come back.                                                                */
+#define KPRN_EXPLAIN_MAX_M 32
+/* runs the scoring pass of kprn_forward_batch on the batch (rectangular or ragged), then explains n_pairs pairs (0-based, repeats allowed; pairs NULL =
+ * every pair in order, n_pairs = the batch's pair count) behind it on the same stream; one wait.  path_idx / path_score / path_weight [n_pairs,M];
+ * pooled, probs [n_pairs] or NULL.  M outside 1..32 is KPRN_E_ARG, a pair outside 0..B-1 KPRN_E_INDEX; a refused call writes nothing.     */
+int kprn_explain_batch(kprn_handle* h, const kprn_batch* b, int32_t class_id, const int32_t* pairs /* [n_pairs] or NULL */, int32_t n_pairs, int32_t M,
+                       int32_t* path_idx, float* path_score, float* path_weight, float* pooled /* or NULL */, float* probs /* or NULL */);
+/* kprn_recommend_ragged, and each group's K winners explained: the explanation launch reads its pair list from the rows the ranking kernel wrote, so
+ * nothing returns to the host between ranking and explanation; one wait in all.  path_idx / path_score / path_weight [G,K,M]; the places n <= s < K
+ * of a group of n < K members are -1 / 0 rows.                                                                                              */
+int kprn_recommend_explain_ragged(kprn_handle* h, const int32_t* idx, const int32_t* counts, int32_t B, int64_t N, int32_t T, int32_t F, int32_t class_id,
+                                  const int32_t* group_counts, int32_t G, int32_t mode, int32_t K, int32_t M, int32_t* topk_idx, float* topk_score,
+                                  int32_t* path_idx, float* path_score, float* path_weight, float* probs /* [B] or NULL */);
+/* the same rule on the host cores over a host score matrix path_scores [N,C] (no handle, no GPU): pair b owns the rows offsets[b] .. offsets[b+1]-1
+ * (1..4096 each), class_id is 1-based, reducer / K_reducer as kprn_config's reducer / K; the other arguments as kprn_explain_batch's.  A pair of more
+ * than 28 paths sums its exponentials in the order the wave kernel does.                                                                     */
+int kprn_host_explain(const float* path_scores, const int32_t* offsets /* [B+1] */, int32_t B, int32_t C, int32_t class_id, int32_t reducer,
+                      int32_t K_reducer, const int32_t* pairs, int32_t n_pairs, int32_t M, int32_t* path_idx, float* path_score, float* path_weight,
+                      float* pooled, float* probs);
+
 /* ---- training ---------------------------------------------------------------------- */
 /* fEval of MyOptimizer.lua:184-195: zeroGradParameters; forward; BCE; backward.
  * inv_batch = 0 -> 1/B; data-parallel callers pass 1/B_global.  loss may be NULL (async). */

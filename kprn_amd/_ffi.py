@@ -128,6 +128,44 @@ def host_rank_groups(scores, group_offsets, members=None, pos=None, mode=0, K=0,
     return out
 
 
+EXPLAIN_MAX_M = 32   # strongest paths per explained pair (KPRN_EXPLAIN_MAX_M)
+
+
+def _explain_out(shape, M, out, scalars=True):
+    """the result arrays of the explanation calls: path_idx / path_score / path_weight [*shape, M] (+ pooled / probs [*shape]); `out` supplies any of them"""
+    M = max(int(M), 1)   # (the range is the library's to refuse)
+    spec = [("path_idx", np.int32, tuple(shape) + (M,)), ("path_score", np.float32, tuple(shape) + (M,)), ("path_weight", np.float32, tuple(shape) + (M,))]
+    if scalars:
+        spec += [("pooled", np.float32, tuple(shape)), ("probs", np.float32, tuple(shape))]
+    res = {}
+    for name, dt, shp in spec:
+        a = (out or {}).get(name)
+        if a is None:
+            a = np.full(shp, -3 if dt is np.int32 else 0, dt)
+        if a.dtype != dt or a.shape != shp or not a.flags.c_contiguous:
+            raise KprnError(E_ARG, "%s must be a C-contiguous %s array of shape %s" % (name, np.dtype(dt).name, shp))
+        res[name] = a
+    return res
+
+
+def host_explain(path_scores, offsets, class_id, reducer, K_reducer, M, pairs=None, out=None):
+    """kprn_host_explain (no handle, no GPU): the explanation rule of include/kprn.h over a host score matrix path_scores [N,C]; pair b owns the rows
+    offsets[b] .. offsets[b+1]-1; pairs None = every pair -> dict(path_idx / path_score / path_weight [n,M], pooled / probs [n])"""
+    sc = np.ascontiguousarray(path_scores, np.float32)
+    off = np.ascontiguousarray(offsets, np.int32)
+    if sc.ndim != 2 or off.ndim != 1 or off.shape[0] < 2 or int(off[-1]) > sc.shape[0]:
+        raise KprnError(E_ARG, "path_scores must be [N,C] and offsets [B+1] inside it")
+    B = int(off.shape[0]) - 1
+    pr = None if pairs is None else np.ascontiguousarray(pairs, np.int32).reshape(-1)
+    n = B if pr is None else int(pr.shape[0])
+    res = _explain_out((n,), M, out)
+    rc = lib().kprn_host_explain(_fp(sc), _fp(off), B, int(sc.shape[1]), int(class_id), int(reducer), int(K_reducer), _fp(pr), n, int(M),
+                                 _fp(res["path_idx"]), _fp(res["path_score"]), _fp(res["path_weight"]), _fp(res["pooled"]), _fp(res["probs"]))
+    if rc != 0:
+        raise KprnError(rc, "kprn_host_explain: bad offsets / class_id / reducer / pairs / M")
+    return res
+
+
 def format_score_lines(counter0, probs, labels):
     """bytes of the scoring writer's lines for pairs counter0 .. (kprn_format_score_lines; host-only)"""
     L = lib()
@@ -595,6 +633,38 @@ class Engine:
         self._ck(self.L.kprn_recommend_ragged(self.h, _fp(idx), _fp(counts), B, C.c_int64(int(idx.shape[0])), int(idx.shape[1]), int(idx.shape[2]),
                                               int(class_id), _fp(gc), G, int(mode), int(K), _fp(ti), _fp(ts), _fp(probs)))
         return ti, ts, probs
+
+    # -- explanation (include/kprn.h "explaining a recommendation") ---------------------------
+    def explain_batch(self, batch, M, class_id=1, pairs=None, out=None):
+        """kprn_explain_batch: the scoring pass over `batch`, then the M strongest paths of `pairs` (0-based, repeats allowed; None = every pair) ->
+        dict(path_idx / path_score / path_weight [n,M], pooled / probs [n]); `out` may supply any of the arrays"""
+        if not isinstance(batch, Batch):
+            batch = Batch(self, batch)
+        pr = None if pairs is None else np.ascontiguousarray(pairs, np.int32).reshape(-1)
+        n = batch.B if pr is None else int(pr.shape[0])
+        res = _explain_out((n,), M, out)
+        self._ck(self.L.kprn_explain_batch(self.h, batch.ptr, int(class_id), _fp(pr), n, int(M), _fp(res["path_idx"]), _fp(res["path_score"]),
+                                           _fp(res["path_weight"]), _fp(res["pooled"]), _fp(res["probs"])))
+        return res
+
+    def recommend_explain_ragged(self, idx, counts, group_counts, K, M, class_id=1, mode=0, want_probs=False, out=None):
+        """kprn_recommend_explain_ragged: recommend_ragged, and each group's K winners explained in the same call ->
+        dict(topk_idx / topk_score [G,K], path_idx / path_score / path_weight [G,K,M], probs [B] or None)"""
+        idx = np.ascontiguousarray(idx, np.int32)
+        counts = np.ascontiguousarray(counts, np.int32)
+        gc = np.ascontiguousarray(group_counts, np.int32)
+        if idx.ndim != 3 or counts.ndim != 1 or gc.ndim != 1 or K < 1:
+            raise KprnError(E_ARG, "a ragged batch is idx [N,T,F] and counts [B]; group_counts [G]; K >= 1")
+        B, G = int(counts.shape[0]), int(gc.shape[0])
+        res = _explain_out((G, int(K)), M, out, scalars=False)
+        res["topk_idx"] = np.full((G, K), -3, np.int32)
+        res["topk_score"] = np.zeros((G, K), np.float32)
+        res["probs"] = np.empty(B, np.float32) if want_probs else None
+        self._ck(self.L.kprn_recommend_explain_ragged(self.h, _fp(idx), _fp(counts), B, C.c_int64(int(idx.shape[0])), int(idx.shape[1]),
+                                                      int(idx.shape[2]), int(class_id), _fp(gc), G, int(mode), int(K), int(M), _fp(res["topk_idx"]),
+                                                      _fp(res["topk_score"]), _fp(res["path_idx"]), _fp(res["path_score"]), _fp(res["path_weight"]),
+                                                      _fp(res["probs"])))
+        return res
 
     def embed(self, idx):
         idx = np.ascontiguousarray(idx, np.int32)

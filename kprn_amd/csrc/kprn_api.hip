@@ -1102,6 +1102,8 @@ void kprn_destroy(kprn_handle* h) {
   dfree(h->board);
   if (h->rank_buf) { hipFree(h->rank_buf); h->rank_buf = nullptr; }
   if (h->rank_pin) { hipHostFree(h->rank_pin); h->rank_pin = nullptr; }
+  if (h->explain_buf) { hipFree(h->explain_buf); h->explain_buf = nullptr; }
+  if (h->explain_pin) { hipHostFree(h->explain_pin); h->explain_pin = nullptr; }
   if (h->feed_pool) { hostfeed::free_pool((hostfeed::Pool*)h->feed_pool); h->feed_pool = nullptr; }  // (joins the workers)
   if (h->upload_pool) { hostfeed::free_pool((hostfeed::Pool*)h->upload_pool); h->upload_pool = nullptr; }
   if (h->upload_stream) { hipStreamSynchronize(h->upload_stream); hipStreamDestroy(h->upload_stream); h->upload_stream = nullptr; }
@@ -2321,6 +2323,115 @@ int kprn_recommend_ragged(kprn_handle* h, const int32_t* idx, const int32_t* cou
   if (probs && !mirror) HIP_TRY(hipMemcpyAsync(probs, h->ws.sel, (size_t)B * sizeof(float), hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
   rank_pinned_fetch(h, G, K, topk_idx, topk_score);
+  if (mirror) memcpy(probs, h->probs_mirror, (size_t)B * sizeof(float));
+  prof_drain(h);
+  API_END(h)
+}
+
+// ---- explanation stage: kprn_explain_batch, kprn_recommend_explain_ragged (kernels: explain_paths.hip) ---------------------------------------
+static ex::Args explain_args(kprn_handle* h, const kprn_batch* b, int class_id, int M) {
+  const kprn_config& c = h->cfg;
+  ex::Args a;
+  a.S = h->score_buf; a.off = b->off; a.B = b->B; a.P = b->P; a.seg_wave = b->off ? b->seg_wave : 0;
+  a.C = c.C; a.cid = class_id - 1; a.reducer = c.reducer; a.K = c.K; a.M = M;
+  a.pairs = nullptr; a.goff = nullptr; a.per_group = 1; a.n = 0;
+  a.idx = nullptr; a.score = nullptr; a.weight = nullptr; a.pooled = nullptr; a.prob = nullptr;
+  return a;
+}
+
+int kprn_explain_batch(kprn_handle* h, const kprn_batch* b, int32_t class_id, const int32_t* pairs, int32_t n_pairs, int32_t M, int32_t* path_idx,
+                       float* path_score, float* path_weight, float* pooled, float* probs) {
+  API_BEGIN(h)
+  KPRN_REQUIRE(b != nullptr, KPRN_E_ARG, "batch is NULL");
+  KPRN_REQUIRE(path_idx && path_score && path_weight, KPRN_E_ARG, "path_idx, path_score and path_weight are required");
+  std::string why;
+  const int rc = ex::validate(b->B, pairs, n_pairs, M, &why);
+  if (rc != KPRN_OK) throw KprnError{rc, why};
+  forward_impl(h, b, class_id, false, /*do_pool=*/true, /*every_class=*/false);   // (refuses a bad class_id / an id out of range before anything is queued)
+  const int64_t n = n_pairs;
+  auto up = [](size_t x) { return (x + 15) & ~(size_t)15; };
+  const size_t rows = up((size_t)n * M * 4), o_pairs = 0, o_idx = up((size_t)n * 4), o_score = o_idx + rows, o_weight = o_score + rows,
+               o_pooled = o_weight + rows, o_prob = o_pooled + up((size_t)n * 4), total = o_prob + up((size_t)n * 4);
+  if (total > h->explain_buf_bytes) {
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (h->explain_buf) { hipFree(h->explain_buf); h->explain_buf = nullptr; h->explain_buf_bytes = 0; }
+    hipError_t e = kprn_dev_malloc(&h->explain_buf, total + total / 4 + 64);
+    if (e != hipSuccess) throw KprnError{KPRN_E_NOMEM, std::string("hipMalloc failed: ") + hipGetErrorString(e)};
+    h->explain_buf_bytes = total + total / 4;
+  }
+  char* base = (char*)h->explain_buf;
+  hipStream_t s = h->stream;
+  if (pairs) HIP_TRY(hipMemcpyAsync(base + o_pairs, pairs, (size_t)n * 4, hipMemcpyHostToDevice, s));
+  ex::Args a = explain_args(h, b, class_id, M);
+  a.pairs = pairs ? (const int32_t*)(base + o_pairs) : nullptr;
+  a.n = n;
+  a.idx = (int32_t*)(base + o_idx); a.score = (float*)(base + o_score); a.weight = (float*)(base + o_weight);
+  a.pooled = pooled ? (float*)(base + o_pooled) : nullptr; a.prob = probs ? (float*)(base + o_prob) : nullptr;
+  {
+    ProfScope ps(h, "explain_paths");
+    ex::launch(s, a, b->off ? b->max_cnt : b->P);
+  }
+  HIP_TRY(hipMemcpyAsync(path_idx, a.idx, (size_t)n * M * 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(path_score, a.score, (size_t)n * M * 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(path_weight, a.weight, (size_t)n * M * 4, hipMemcpyDeviceToHost, s));
+  if (pooled) HIP_TRY(hipMemcpyAsync(pooled, a.pooled, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+  if (probs) HIP_TRY(hipMemcpyAsync(probs, a.prob, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  prof_drain(h);
+  API_END(h)
+}
+
+int kprn_recommend_explain_ragged(kprn_handle* h, const int32_t* idx, const int32_t* counts, int32_t B, int64_t N, int32_t T, int32_t F, int32_t class_id,
+                                  const int32_t* group_counts, int32_t G, int32_t mode, int32_t K, int32_t M, int32_t* topk_idx, float* topk_score,
+                                  int32_t* path_idx, float* path_score, float* path_weight, float* probs) {
+  if (!h) return KPRN_E_ARG;
+  if (!path_idx || !path_score || !path_weight) { h->err = "path_idx, path_score and path_weight are required"; return KPRN_E_ARG; }
+  if (M < 1 || M > KPRN_EXPLAIN_MAX_M) { h->err = "M must be in 1..32"; return KPRN_E_ARG; }
+  std::vector<int64_t> goff;
+  int max_n = 0;
+  int rc = recommend_check(h, counts, B, group_counts, G, mode, K, topk_idx, topk_score, goff, &max_n);
+  if (rc != KPRN_OK) return rc;
+  rc = dropin_feed(h, /*score=*/true, idx, nullptr, B, 0, T, F, counts, N);
+  if (rc != KPRN_OK) return rc;
+  API_BEGIN(h)
+  // kprn_recommend_ragged, and one more launch behind the ranking kernel: its pair list is the top-K rows that kernel wrote (page-locked memory the device
+  // reads in place), its own rows land in page-locked memory too: still one wait, no copy operation
+  struct Disarm { kprn_handle* h; ~Disarm() { h->sel_host_armed = nullptr; } } disarm{h};
+  const bool mirror = probs != nullptr && !h->prof_on;
+  if (mirror) {
+    if ((int64_t)B > h->probs_mirror_cap) {
+      if (h->probs_mirror) { HIP_TRY(hipStreamSynchronize(h->stream)); HIP_TRY(hipHostFree(h->probs_mirror)); h->probs_mirror = nullptr; h->probs_mirror_cap = 0; }
+      HIP_TRY(hipHostMalloc((void**)&h->probs_mirror, (size_t)(2 * (int64_t)B + 64) * sizeof(float)));
+      h->probs_mirror_cap = 2 * (int64_t)B + 64;
+    }
+    h->sel_host_armed = h->probs_mirror;
+  }
+  const int64_t n = (int64_t)G * K;
+  const size_t rows = ((size_t)n * M * 4 + 15) & ~(size_t)15;
+  if (3 * rows > h->explain_pin_bytes) {
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (h->explain_pin) { HIP_TRY(hipHostFree(h->explain_pin)); h->explain_pin = nullptr; h->explain_pin_bytes = 0; }
+    HIP_TRY(hipHostMalloc(&h->explain_pin, 6 * rows + 256));
+    h->explain_pin_bytes = 6 * rows + 256;
+  }
+  const kprn_batch* b = h->dropin_slot[h->dropin_last];
+  forward_impl(h, b, class_id, false, /*do_pool=*/true, /*every_class=*/false);
+  rank_run_pinned(h, h->ws.sel, goff.data(), G, mode, K, max_n);
+  ex::Args a = explain_args(h, b, class_id, M);
+  char* pin = (char*)h->explain_pin;
+  a.pairs = (const int32_t*)((char*)h->rank_pin + h->rank_pin_off[0]); a.goff = (const int64_t*)h->rank_pin; a.per_group = K;
+  a.n = n;
+  a.idx = (int32_t*)pin; a.score = (float*)(pin + rows); a.weight = (float*)(pin + 2 * rows);
+  {
+    ProfScope ps(h, "explain_paths");
+    ex::launch(h->stream, a, b->max_cnt);
+  }
+  if (probs && !mirror) HIP_TRY(hipMemcpyAsync(probs, h->ws.sel, (size_t)B * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  rank_pinned_fetch(h, G, K, topk_idx, topk_score);
+  memcpy(path_idx, pin, (size_t)n * M * 4);
+  memcpy(path_score, pin + rows, (size_t)n * M * 4);
+  memcpy(path_weight, pin + 2 * rows, (size_t)n * M * 4);
   if (mirror) memcpy(probs, h->probs_mirror, (size_t)B * sizeof(float));
   prof_drain(h);
   API_END(h)

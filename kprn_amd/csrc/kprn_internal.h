@@ -270,6 +270,8 @@ struct kprn_handle {
   void* rank_buf = nullptr; size_t rank_buf_bytes = 0;   // device arguments and results of one kprn_rank_groups call
   int rank_sort_min = 512;   // option "rank_sort_min": counting wins at 257 members, the sort at 512 and above (profiles/rank/README.md, comparison 3)
   void* rank_pin = nullptr; size_t rank_pin_bytes = 0, rank_pin_off[2] = {0, 0};   // page-locked group table and top-K rows of kprn_recommend_ragged
+  void* explain_buf = nullptr; size_t explain_buf_bytes = 0;   // device pair list and results of one kprn_explain_batch call
+  void* explain_pin = nullptr; size_t explain_pin_bytes = 0;   // page-locked explanation rows of kprn_recommend_explain_ragged
 
   bool prof_on = false;
 
@@ -393,6 +395,24 @@ int validate(int64_t n_scores, const int64_t* members, const int64_t* goff, cons
              int* max_n, std::string* why);
 void launch(hipStream_t s, const Args& a, int max_n);   // hist must be zero; every group is ranked by exactly one of the two kernels
 }  // namespace rk
+
+// ---- explanation stage (explain_paths.hip) -------------------------------------------------------
+namespace ex {
+struct Args {   // device pointers
+  const float* S;            // mapper output [N][C] in the caller's path order
+  const int32_t* off; int B, P;   // the batch's pairs: off [B+1], or null = P paths each
+  int seg_wave;              // the batch pools a pair of more than RAGGED_THREAD_MAX paths by a wave (kprn_batch::seg_wave): pooled's order
+  int C, cid, reducer, K, M;
+  const int32_t* pairs;      // [n] pair per item; null = item i is pair i
+  const int64_t* goff; int per_group;   // non-null: pairs holds a ranking's top-K rows [G][per_group] (index within the group, -1 = empty place)
+  int64_t n;
+  int32_t* idx; float* score; float* weight;   // [n][M]
+  float* pooled; float* prob;                  // [n] or null
+};
+// the refusals on a host pair list: KPRN_OK, or the status with its text in *why
+int validate(int32_t B, const int32_t* pairs, int64_t n, int32_t M, std::string* why);
+void launch(hipStream_t s, const Args& a, int max_cnt);   // max_cnt: the batch's longest pair: <= RAGGED_THREAD_MAX = a thread per item, else a wave
+}  // namespace ex
 
 // ---- batch occurrence index (batch_index.hip) -------------------------------------------------
 namespace bidx {

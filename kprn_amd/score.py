@@ -16,6 +16,9 @@ def main(argv=None):
     # ranking on the device (an extension): the evaluation chain's hit@k / ndcg@k (eval/combine_result.py, resort.py, eval_score.py) in the same run
     p.add_argument("-rank_samples", default=""); p.add_argument("-rank_entity", default=""); p.add_argument("-rank_users", default="")
     p.add_argument("-rank_out", default="")
+    # explaining every scored line by its strongest paths (an extension): -explain_out FILE gets the -explain_paths M strongest paths per line and their
+    # weights (scoring.explain_test_set); -out_file is written as without the flags
+    p.add_argument("-explain_out", default=""); p.add_argument("-explain_paths", type=int, default=3)
     args, rest = p.parse_known_args(argv)
     assert args.input_dir != "", "input_dir isnt set. Point to the dir where train/dev/test.list files reside"
     params = model.parse_flags(rest)
@@ -36,6 +39,18 @@ def main(argv=None):
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         dist.init_process_group("gloo")   # (a barrier only: no tensor moves between the ranks)
         barrier = dist.barrier
+    if args.explain_out:
+        if args.rank_samples:
+            sys.exit("-explain_out cannot be combined with -rank_samples: run the ranking and the explanation as two commands")
+        if world > 1:
+            sys.exit("-explain_out explains what one rank scored: run it on a single rank")
+        if not 1 <= args.explain_paths <= 32:
+            sys.exit("-explain_paths must be in 1..32")
+        from .batcher import BatcherFileList
+        fl = BatcherFileList(args.input_dir, 512, False, 1000, True, args.test_list, check_ids=False)
+        with open(args.out_file, "wb") as res, open(args.explain_out, "w") as ex:
+            scoring.explain_test_set(eng, fl, ex, args.explain_paths, merge=bool(args.mergePathCounts), res_file=res)
+        return 0
     if args.rank_samples:
         assert args.rank_entity != "", "-rank_samples needs -rank_entity (the positional test.list.entity file)"
         assert world == 1, "-rank_samples ranks what one rank scored: run it on a single rank"

@@ -155,6 +155,63 @@ def write_scores(engine, batcher, f, class_id=1, merge=False):
     return counter
 
 
+def format_path(path, pad_entity):
+    """a path [T,F] of 1-based ids -> its non-pad steps in step order, a step as `type ids,entity id,relation id` (the .int files' step feature), steps
+    joined with ' '.  A pad step is one whose entity is the entity table's pad row (id = entityVocabSize: the row zeroPadTokens clears, the id
+    pathformat.format_entity_pair skips)."""
+    return " ".join(",".join(str(int(v)) for v in step) for step in path if int(step[-2]) != pad_entity)
+
+
+def explain_test_set(engine, batcher, f, M, class_id=1, merge=False, res_file=None):
+    """Scores the batcher's test set like write_scores and writes, into the text file f, the M strongest paths behind every scored line
+    (Engine.explain_batch: one synchronous call per group of pairs; not a throughput mode).  One line per (scored line, filled place), tab separated:
+    the global 0-based line counter of the score writer, the place (0-based), the path's index within its pair, its weight "%.5f", its score "%.6g",
+    the path (format_path).  A pair with fewer than M paths has that many lines.  res_file (binary): also gets the score writer's lines, from the
+    same pass -- the bytes write_scores writes.  -> pairs scored"""
+    import numpy as np
+    from . import _ffi
+    pad_entity = int(engine.cfg.Ve)
+    saved = [(b, b.batchSize) for b in getattr(batcher, "batchers", [])]
+    counter = 0
+    try:
+        for b, _ in saved:       # the groups score_batches forms, so that both runs hand the engine the same batches
+            b.batchSize = max(b.batchSize, ENGINE_BATCH_PATHS // max(1, b.numPaths))
+        while True:
+            if merge:
+                got = batcher.getMergedGroup(ENGINE_BATCH_PATHS)
+                if got is None:
+                    break
+                labs, idx, counts, count, _classId = got
+                batch = engine.batch_ragged(idx, counts)
+                off = np.concatenate([[0], np.cumsum(counts, dtype=np.int64)])
+            else:
+                got = batcher.getBatch()
+                if got is None:
+                    break
+                labs, inputs, count, _classId = got
+                batch = engine.batch(inputs)
+                idx = np.asarray(inputs).reshape((-1,) + tuple(inputs.shape[2:]))
+                off = np.arange(count + 1, dtype=np.int64) * int(inputs.shape[1])
+            res = engine.explain_batch(batch, M, class_id)
+            batch.free()
+            if res_file is not None:
+                res_file.write(_ffi.format_score_lines(counter, res["probs"], labs))
+            pi, ps, pw = res["path_idx"], res["path_score"], res["path_weight"]
+            lines = []
+            for b in range(count):
+                for r in range(pi.shape[1]):
+                    q = int(pi[b, r])
+                    if q < 0:
+                        break
+                    lines.append("%d\t%d\t%d\t%.5f\t%.6g\t%s\n" % (counter + b, r, q, pw[b, r], ps[b, r], format_path(idx[off[b] + q], pad_entity)))
+            f.write("".join(lines))
+            counter += count
+    finally:
+        for b, size in saved:
+            b.batchSize = size
+    return counter
+
+
 def test_from_checkpoint(engine, input_dir, test_list, out_file, minibatch=512, log=None, rank=0, world=1, barrier=None, merge_path_counts=False):
     """engine: built with the same -top_k reducer the script would rebuild (:69-79).  merge_path_counts (an extension, default off): score
     the bucket files in ragged groups (score_batches merge=True); same lines, same order.
