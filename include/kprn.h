@@ -459,6 +459,17 @@ int kprn_profile_get(kprn_handle* h, kprn_prof_entry* out, int32_t cap, int32_t*
  *   "train_step_return" "loss" (default) | "drain": see kprn_train_step
  *   "inline_upload"   "side" (default): kprn_train_step uploads its minibatch on the upload stream, beside the previous step's backward, whenever the previous
  *                     call waited for its loss (every reader of the slot being refilled is then known to be done); "main": on the engine's stream
+ *   "deterministic"   "0" (default) | "1": bit-reproducible training.  With "1" every float the engine hands back -- losses, kprn_get_grad / kprn_get_flat_grads,
+ *                     parameters, both optimiser state slots -- is a function of the inputs only, never of timing: the same sequence of calls with the same
+ *                     inputs gives the same bits across repeats, handles, processes and whatever else runs on the device, for a fixed build, device model (CU
+ *                     count) and fixed values of all other options (no promise across grid or tile sizes, option values or builds).  Covered: the fused fp32
+ *                     path (FastLSTM, D = H = 64, one or two layers, compute_dtype 0, 2 and 3; one type slot, slices in 16-column blocks, type / relation
+ *                     tables of at most 16 rows), every tile size, batch form, entry point, optimiser and value of the other options: its float atomics are
+ *                     replaced by plain-stored partial sums added in a fixed order.  Not covered, and REFUSED: kprn_backward_batch,
+ *                     kprn_train_step_batch and kprn_train_step return KPRN_E_UNSUPPORTED -- before anything is launched or written, the message names the
+ *                     pipeline -- when the call would run on the generic pipeline ("impl" "generic", any other shape), on rnn / gru, on the bf16 pipeline
+ *                     (compute_dtype 1) or on a KPRN_DBG scatter route.  Scoring, ranking, explanation and parameter access are never refused; data-parallel
+ *                     handles are accepted (the exchange sums in rank order).  "0" again makes the same handle train as before; with "0" nothing changes.
  *   (also: "small_tiles", "score_split", "loss_accumulate", "feed_build" / "feed_threads" / "feed_workers", "dp_comm_stream",
  *    "dp_fused_update", "dp_dense_in_pack" -- described at the calls they modify)                                                 */
 int kprn_set_option(kprn_handle* h, const char* key, const char* value);

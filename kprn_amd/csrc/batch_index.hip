@@ -181,11 +181,14 @@ void build(hipStream_t s, const int32_t* idx, int64_t N, int T, int F, int Ve, c
 //   FRAG = 0: dx time-major row-major [T][N][D] (generic pipeline).
 namespace bidx {
 namespace {
-template <int FRAG>
-__global__ __launch_bounds__(256) void k_entity_grad(const float* __restrict__ DX, const int32_t* __restrict__ key_sorted,
-                                                     const int32_t* __restrict__ pos_sorted, int64_t nsteps, int64_t N, int T, int D, int dt, int de,
-                                                     int sentinel, float* __restrict__ gWe, int n_ent_blocks, int n_red_blocks, SlabReduce red,
-                                                     SmallGrad sg, int dbg) {
+// DET (deterministic mode; a kernel of its own, k_egrad_det): the partial sum of a run that straddles segments leaves with a plain store --
+// slot 0 of its segment's scratch row pair when the run came in from the segment before, slot 1 when this segment opens it -- and k_det_tail, a launch behind
+// this one, lets the opening segment add the parts in segment order.  The small-table passenger job stores its blocks likewise.
+template <int FRAG, bool DET>
+__device__ __forceinline__ void entity_grad_body(const float* __restrict__ DX, const int32_t* __restrict__ key_sorted,
+                                                 const int32_t* __restrict__ pos_sorted, int64_t nsteps, int64_t N, int T, int D, int dt, int de,
+                                                 int sentinel, float* __restrict__ gWe, int n_ent_blocks, int n_red_blocks, const SlabReduce red,
+                                                 const SmallGrad sg, const int dbg, float* const det_seg, float* const det_sg) {
   // Which workgroup does what (workgroup-uniform).  The passenger jobs (weight-gradient slab reduce, small-table gradients) stream
   // coalesced data and start at once; a gather-reduce workgroup first walks key -> position -> row (three dependent round trips) with
   // little in flight.  order 1 dispatches the passengers FIRST so that their traffic fills the time the gathers spend waiting
@@ -202,7 +205,11 @@ __global__ __launch_bounds__(256) void k_entity_grad(const float* __restrict__ D
   } else if (bid >= n_ent_blocks) rb = bid - n_ent_blocks;
   if (rb >= 0) {
     if (dbg & 2) return;
-    if (rb >= n_red_blocks) { if (!(dbg & 8)) small_grad_block(sg, rb - n_red_blocks); return; }
+    if (rb >= n_red_blocks) {
+      if constexpr (DET) small_grad_block<true>(sg, rb - n_red_blocks, det_sg);
+      else if (!(dbg & 8)) small_grad_block(sg, rb - n_red_blocks);
+      return;
+    }
     if (dbg & 4) return;
     const int nbx = (red.n_elem + 255) / 256;
     slab_reduce_block(red, rb % nbx, (rb / nbx) % red.ny, rb / (nbx * red.ny));
@@ -273,7 +280,9 @@ __global__ __launch_bounds__(256) void k_entity_grad(const float* __restrict__ D
           const bool whole = opened_here && !(i == cnt - 1 && continues);  // every occurrence of row k was in this segment
           if (act && k != sentinel) {
             float* dst = gWe + (int64_t)k * de + ecol;
-            if (whole) *dst = acc; else if (!(dbg & 1)) unsafeAtomicAdd(dst, acc);
+            if (whole) *dst = acc;
+            else if constexpr (DET) det_seg[(seg * 2 + (opened_here ? 1 : 0)) * de + ecol] = acc;
+            else if (!(dbg & 1)) unsafeAtomicAdd(dst, acc);
           }
           acc = 0.f;
           opened_here = true;
@@ -282,10 +291,94 @@ __global__ __launch_bounds__(256) void k_entity_grad(const float* __restrict__ D
     }
   }
 }
+template <int FRAG>
+__global__ __launch_bounds__(256) void k_entity_grad(const float* __restrict__ DX, const int32_t* __restrict__ key_sorted,
+                                                     const int32_t* __restrict__ pos_sorted, int64_t nsteps, int64_t N, int T, int D, int dt, int de,
+                                                     int sentinel, float* __restrict__ gWe, int n_ent_blocks, int n_red_blocks, SlabReduce red,
+                                                     SmallGrad sg, int dbg) {
+  entity_grad_body<FRAG, false>(DX, key_sorted, pos_sorted, nsteps, N, T, D, dt, de, sentinel, gWe, n_ent_blocks, n_red_blocks, red, sg, dbg, nullptr, nullptr);
+}
+__global__ __launch_bounds__(256) void k_egrad_det(const float* __restrict__ DX, const int32_t* __restrict__ key_sorted, const int32_t* __restrict__ pos_sorted,
+                                                   int64_t nsteps, int64_t N, int T, int D, int dt, int de, int sentinel, float* __restrict__ gWe,
+                                                   int n_ent_blocks, int n_red_blocks, SlabReduce red, SmallGrad sg, DetEntity det) {
+  entity_grad_body<2, true>(DX, key_sorted, pos_sorted, nsteps, N, T, D, dt, de, sentinel, gWe, n_ent_blocks, n_red_blocks, red, sg, 0, det.seg_part, det.sg_part);
+}
+
+// The launch behind k_egrad_det.  Workgroups [0, n_ent_blocks): a wave per segment, lane = column.  The segment that OPENS a run which goes on in the next
+// segment owns that row: row += (((own part + part of segment s + 1) + part of s + 2) + ...), one running fp32 sum in segment order over every segment the
+// run reaches (DEPTH parts requested at a time, added in order).  Every other wave leaves after three key reads.  Workgroups behind them: one per 16-column
+// block of the type / relation slices -- table[v][c] += ((block 0 + block 1) + ...) over the small-table job's workgroups of that column block, in workgroup order.
+__global__ __launch_bounds__(256) void k_det_tail(const int32_t* __restrict__ key_sorted, int64_t nsteps, int de, int sentinel, float* __restrict__ gWe,
+                                                  int n_ent_blocks, DetEntity det, SmallGrad sg, int n_sg_groups) {
+  constexpr int DEPTH = 16;
+  if ((int)blockIdx.x >= n_ent_blocks) {
+    const int ncb_t = sg.dt >> 4, ncb = ncb_t + (sg.dr >> 4);
+    const int cb = (int)blockIdx.x - n_ent_blocks;
+    const bool is_type = cb < ncb_t;
+    const int v = threadIdx.x >> 4, c = threadIdx.x & 15;
+    float acc = 0.f;
+    for (int g0 = 0; g0 < n_sg_groups; g0 += DEPTH) {
+      float x[DEPTH];
+#pragma unroll
+      for (int u = 0; u < DEPTH; ++u) {
+        const int g = g0 + u < n_sg_groups ? g0 + u : n_sg_groups - 1;
+        x[u] = det.sg_part[((int64_t)g * ncb + cb) * 256 + threadIdx.x];
+      }
+#pragma unroll
+      for (int u = 0; u < DEPTH; ++u) if (g0 + u < n_sg_groups) acc += x[u];
+    }
+    if (v < (is_type ? sg.Vt : sg.Vr)) {
+      if (is_type) sg.gWt[(int64_t)v * sg.dt + cb * 16 + c] += acc;
+      else sg.gWr[(int64_t)v * sg.dr + (cb - ncb_t) * 16 + c] += acc;
+    }
+    return;
+  }
+  const int lane = threadIdx.x & 63;
+  const int64_t seg = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int64_t base = seg * 64;
+  if (base + 64 >= nsteps) return;   // (the last segment, or past it: nothing goes on behind it)
+  const int k = key_sorted[base + 63];
+  if (k == sentinel || key_sorted[base + 64] != k) return;                        // the last run ends here
+  if (key_sorted[base] == k && base > 0 && key_sorted[base - 1] == k) return;     // ... or was opened further up: that segment owns it
+  const int64_t n_seg = (nsteps + 63) / 64;
+  for (int c0 = 0; c0 < de; c0 += 64) {
+    const int ecol = c0 + lane < de ? c0 + lane : de - 1;
+    float acc = det.seg_part[(seg * 2 + 1) * de + ecol];
+    bool more = true;
+    for (int64_t s0 = seg + 1; more; s0 += DEPTH) {
+      float x[DEPTH];
+      int ks[DEPTH];
+#pragma unroll
+      for (int u = 0; u < DEPTH; ++u) {   // (unconditional loads from clamped addresses, masked below: DEPTH round trips in flight)
+        const int64_t sc = s0 + u < n_seg ? s0 + u : n_seg - 1;
+        ks[u] = key_sorted[sc * 64];
+        x[u] = det.seg_part[(sc * 2) * de + ecol];
+      }
+#pragma unroll
+      for (int u = 0; u < DEPTH; ++u) {
+        more = more && s0 + u < n_seg && ks[u] == k;   // (sorted keys: the run reaches segment s iff the segment starts with k)
+        if (more) acc += x[u];
+      }
+    }
+    if (c0 + lane < de) gWe[(int64_t)k * de + ecol] += acc;
+  }
+}
 }  // namespace
 
+void entity_grad_tail(hipStream_t s, const int32_t* key_sorted, int64_t n_index, int de, int Ve, float* gWe, const DetEntity& det, const SmallGrad* sg) {
+  const int64_t segs = (n_index + 63) / 64;
+  const int n_ent = (int)((segs + 3) / 4);
+  SmallGrad g;
+  memset(&g, 0, sizeof(g));
+  int ncb = 0, groups = 0;
+  if (sg) { g = *sg; ncb = (g.dt >> 4) + (g.dr >> 4); groups = g.nblocks / ncb; }
+  if (n_ent + ncb <= 0) return;
+  hipLaunchKernelGGL(k_det_tail, dim3((unsigned)(n_ent + ncb)), dim3(256), 0, s, key_sorted, n_index, de, Ve, gWe, n_ent, det, g, groups);
+  HIP_TRY(hipGetLastError());
+}
+
 void entity_grad(hipStream_t s, const float* DX, int frag_order, const int32_t* key_sorted, const int32_t* pos_sorted, int64_t n_index, int64_t N,
-                 int T, int D, int dt, int de, int Ve, float* gWe, const SlabReduce* red, const SmallGrad* sg) {
+                 int T, int D, int dt, int de, int Ve, float* gWe, const SlabReduce* red, const SmallGrad* sg, const DetEntity* det) {
   if (n_index <= 0 && !red && !sg) return;
   const int64_t segs = (n_index + 63) / 64;
   const int n_ent = (int)((segs + 3) / 4);
@@ -298,6 +391,10 @@ void entity_grad(hipStream_t s, const float* DX, int frag_order, const int32_t* 
   if (sg) { g = *sg; n_sg = g.nblocks; }
   static const int dbg = KPRN_DEV_ENV("KPRN_EGRAD_DBG") ? atoi(KPRN_DEV_ENV("KPRN_EGRAD_DBG")) : 0;   // (measurement: 1 no atomics, 2 no passenger work; 16 x workgroup order)
   const dim3 grid((unsigned)(n_ent + n_red + n_sg));
+  if (det) {
+    KPRN_REQUIRE(frag_order == 2, KPRN_E_UNSUPPORTED, "deterministic entity gradient: the compact entity slice only");
+    hipLaunchKernelGGL(k_egrad_det, grid, dim3(256), 0, s, DX, key_sorted, pos_sorted, n_index, N, T, D, dt, de, Ve, gWe, n_ent, n_red, r, g, *det);
+  } else
   if (frag_order == 1) hipLaunchKernelGGL(k_entity_grad<1>, grid, dim3(256), 0, s, DX, key_sorted, pos_sorted, n_index, N, T, D, dt, de, Ve, gWe, n_ent, n_red, r, g, dbg);
   else if (frag_order == 2) hipLaunchKernelGGL(k_entity_grad<2>, grid, dim3(256), 0, s, DX, key_sorted, pos_sorted, n_index, N, T, D, dt, de, Ve, gWe, n_ent, n_red, r, g, dbg);
   else hipLaunchKernelGGL(k_entity_grad<0>, grid, dim3(256), 0, s, DX, key_sorted, pos_sorted, n_index, N, T, D, dt, de, Ve, gWe, n_ent, n_red, r, g, dbg);

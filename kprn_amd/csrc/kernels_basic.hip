@@ -775,6 +775,28 @@ __global__ void k_sumsq_rows(const float* __restrict__ G, const int32_t* __restr
   if ((threadIdx.x & 63) == 0) unsafeAtomicAdd(out, acc);
 }
 
+// deterministic mode: workgroups [0, nb) take x, [nb, 2 nb) the listed rows of G (rows == null: they write 0); a thread sums its strided
+// elements in ascending order, the wave adds its lanes by the butterfly of wave_sum, the workgroup's four waves are added as (0 + 1) + (2 + 3); the partial
+// leaves with a plain store and k_sum_partials adds the 2 nb partials in index order
+__global__ __launch_bounds__(256) void k_sumsq_det(const float* __restrict__ x, int64_t n, const float* __restrict__ G, const int32_t* __restrict__ rows,
+                                                   const int32_t* __restrict__ count, int d, int nb, float* __restrict__ partial) {
+  __shared__ float red[4];
+  float acc = 0.f;
+  if ((int)blockIdx.x < nb) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)nb * 256) acc += x[i] * x[i];
+  } else if (rows) {
+    const int64_t total = (int64_t)(*count) * d;
+    for (int64_t i = (int64_t)((int)blockIdx.x - nb) * 256 + threadIdx.x; i < total; i += (int64_t)nb * 256) {
+      const float v = G[(int64_t)rows[i / d] * d + (i % d)];
+      acc += v * v;
+    }
+  }
+  acc = wave_sum(acc);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
 // ---- optimisers (optim.adam / optim.adagrad, OneModel.lua:347-361; MyOptimizer.lua:196-218) ----
 #pragma clang fp contract(off)
 __device__ __forceinline__ float clip_factor(const float* norm2, float clip) {
@@ -1608,6 +1630,13 @@ void sumsq(hipStream_t s, const float* x, int64_t n, float* out) {
 
 void sumsq_rows(hipStream_t s, const float* G, const int32_t* rows, const int32_t* count, int d, float* out) {
   hipLaunchKernelGGL(k_sumsq_rows, dim3(1024), dim3(TPB), 0, s, G, rows, count, d, out);
+  CHECK_LAUNCH();
+}
+
+void sumsq_det(hipStream_t s, const float* x, int64_t n, const float* G, const int32_t* rows, const int32_t* count, int d, float* partial, float* out) {
+  const int nb = SUMSQ_DET_BLOCKS / 2;
+  hipLaunchKernelGGL(k_sumsq_det, dim3(2 * nb), dim3(256), 0, s, x, n, G, rows, count, d, nb, partial);
+  hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, s, partial, 2 * nb, out, 0);
   CHECK_LAUNCH();
 }
 

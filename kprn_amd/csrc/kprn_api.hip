@@ -822,8 +822,26 @@ static void form_loss(kprn_handle* h) {
   h->loss_pending = 0;
 }
 
+// Option "deterministic": a training call goes on only where every float sum of the step has a fixed order -- the fused fp32 path (D = H = 64, FastLSTM, compute_dtype
+// 0 / 2 / 3) on its index routes.  Everything else is refused HERE, before anything is launched or any state is written.
+static void det_check(const kprn_handle* h, int T) {
+  if (!h->deterministic) return;
+  const kprn_config& c = h->cfg;
+  const char* why = nullptr;
+  if (h->impl != 0) why = "the generic pipeline (impl = generic: split-K atomics in its weight-gradient products)";
+  else if (c.rnn_type != 0) why = "the rnn / gru pipeline";
+  else if (c.compute_dtype == 1) why = "the bf16 pipeline (compute_dtype 1)";
+  else if (!fused::fwd_supported(h, T) || !fused::bwd_supported(h, T) || c.dt == 0 || c.de == 0)
+    why = "the generic pipeline (this shape is not the fused D = H = 64 path's: wide persistent layers / split-K products)";
+  else if (!(c.num_types == 1 && (c.dt % 16) == 0 && (c.de % 16) == 0 && (c.dr % 16) == 0 && c.Vt <= 16 && c.Vr <= 16))
+    why = "the fused path's general embedding scatter (more than one type slot, slices not in 16-column blocks, or a type / relation table of more than 16 rows)";
+  else if (kprn_dbg_mask() & (1 | 8 | 16)) why = "a KPRN_DBG route of the fused path (scatter kernels with atomics)";
+  if (why) throw KprnError{KPRN_E_UNSUPPORTED, std::string("deterministic = 1: training would run on ") + why + ", which has no deterministic form; set deterministic = 0"};
+}
+
 static void backward_impl(kprn_handle* h, const kprn_batch* b, int class_id, int literal, float inv_batch) {
   check_batch(h, b, class_id);
+  det_check(h, b->T);
   KPRN_REQUIRE(b->labels != nullptr && b->has_index, KPRN_E_ARG, "batch has no labels (targets are required, MyOptimizer.lua:179)");
   const kprn_config& c = h->cfg;
   zero_grads(h);
@@ -893,9 +911,14 @@ static void apply_update_impl(kprn_handle* h, const kprn_opt* o) {
   const float* norm2 = nullptr;
   if (reg && o->use_grad_clip) {
     ProfScope ps(h, "grad_norm");
-    HIP_TRY(hipMemsetAsync(h->d_norm2, 0, sizeof(float), s));
-    kk::sumsq(s, h->g_dense, h->n_dense, h->d_norm2);
-    if (h->step_rows_ub > 0) kk::sumsq_rows(s, h->g_We, rows, rcount, c.de, h->d_norm2);
+    if (h->deterministic) {   // one plain-stored partial per workgroup, added in index order (kk::sumsq_det)
+      if (!h->det_norm_part) h->det_norm_part = dalloc<float>(kk::SUMSQ_DET_BLOCKS);
+      kk::sumsq_det(s, h->g_dense, h->n_dense, h->g_We, h->step_rows_ub > 0 ? rows : nullptr, rcount, c.de, h->det_norm_part, h->d_norm2);
+    } else {
+      HIP_TRY(hipMemsetAsync(h->d_norm2, 0, sizeof(float), s));
+      kk::sumsq(s, h->g_dense, h->n_dense, h->d_norm2);
+      if (h->step_rows_ub > 0) kk::sumsq_rows(s, h->g_We, rows, rcount, c.de, h->d_norm2);
+    }
     norm2 = h->d_norm2;
   }
   const float l2 = reg ? o->l2 : 0.f;
@@ -1125,7 +1148,7 @@ void kprn_destroy(kprn_handle* h) {
   Workspace& w = h->ws;
   for (float** p : {&w.X, &w.Hs, &w.Cs, &w.ACT, &w.dA, &w.dIn, &w.dH, &w.dC, &w.S, &w.dS, &w.pooled, &w.probs, &w.sel, &w.dy, &w.mask}) dfree(*p);
   for (float** p : {&h->dense, &h->g_dense, &h->s1_dense, &h->s2_dense, &h->We, &h->g_We, &h->s1_We, &h->s2_We, &h->d_loss, &h->d_norm2,
-                    &h->step_tab})
+                    &h->step_tab, &h->det_norm_part})
     dfree(*p);
   for (int32_t** p : {&h->We_last, &h->d_flag, &h->step_rows, &h->step_count, &h->pack_buf, &h->dp_mark}) dfree(*p);
   if (h->step_tab_host) hipHostFree(h->step_tab_host);
@@ -2482,6 +2505,7 @@ int kprn_train_step_batch(kprn_handle* h, const kprn_batch* b, int32_t class_id,
   API_BEGIN(h)
   KPRN_REQUIRE(opt, KPRN_E_ARG, "opt is NULL");
   check_batch(h, b, class_id);
+  det_check(h, b->T);
   catch_up(h, b);
   if (!h->pad_clean) { zero_pad_tokens(h); fused::params_changed(h); bf16p::params_changed(h, false); }  // MyOptimizer.lua:181 (a no-op when the last step left them zero)
   // the loss goes back as soon as the loss stage has run (option "train_step_return" = "loss"); profiling and "drain" wait for the whole step as before
@@ -2516,6 +2540,7 @@ int kprn_train_step(kprn_handle* h, const int32_t* idx, int32_t B, int32_t P, in
                     const kprn_opt* opt, float* loss) {
   if (!h) return KPRN_E_ARG;
   if (!labels) { h->err = "assert(targets) (MyOptimizer.lua:179)"; return KPRN_E_ARG; }
+  try { det_check(h, T); } catch (const KprnError& e) { h->err = e.msg; return e.code; }   // (before the feed: a refused call uploads nothing)
   // The minibatch goes through one of two engine-owned feed slots (grow-only capacity, page-locked staging: steady state allocates nothing and
   // frees nothing; alternating, so that the rows the lazy optimiser still names belong to the OTHER slot) instead of a batch created and
   // destroyed per call (two device allocations, a device-side index build with its synchronisations and three stream drains per step:
@@ -3098,6 +3123,12 @@ int kprn_set_option(kprn_handle* h, const char* key, const char* value) {
     // data-parallel exchange: the dense gradient arena travels behind the packed entity rows (one all-gather, no all-reduce); the merge sums
     // the ranks' copies in rank order
     h->dp_dense_in_pack = atoi(value) != 0;
+  } else if (strcmp(key, "deterministic") == 0) {
+    // "1": every float a training step hands back (loss, gradients, parameters, optimiser state) is a function of the inputs only -- the fused fp32 path's
+    // atomic joins are replaced by plain-stored partials summed in a fixed order; a training call that would take any other pipeline returns
+    // KPRN_E_UNSUPPORTED.  "0" (default): the kernels launched before this option existed.  Read at every training call.
+    KPRN_REQUIRE(strcmp(value, "0") == 0 || strcmp(value, "1") == 0, KPRN_E_ARG, "deterministic must be 0 or 1");
+    h->deterministic = value[0] == '1';
   } else if (strcmp(key, "reserve_cus") == 0) {
     // the fused SCORING forward is a persistent one-workgroup-per-CU kernel that fills the register file of every CU it runs
     // on; leaving a few CUs free lets the copy kernels of a concurrently running collective (RCCL) make progress beside it

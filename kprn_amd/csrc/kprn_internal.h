@@ -273,6 +273,11 @@ struct kprn_handle {
   void* explain_buf = nullptr; size_t explain_buf_bytes = 0;   // device pair list and results of one kprn_explain_batch call
   void* explain_pin = nullptr; size_t explain_pin_bytes = 0;   // page-locked explanation rows of kprn_recommend_explain_ragged
 
+  // option "deterministic": every float sum of a training step whose addends come from different waves or workgroups of one launch is formed in an order that
+  // depends on the batch and the launch geometry only; pipelines that cannot do that refuse to train
+  bool deterministic = false;
+  float* det_norm_part = nullptr;   // [kk::SUMSQ_DET_BLOCKS] per-workgroup partials of the gradient norm
+
   bool prof_on = false;
 
   std::string prof_filter;  // profile only the kernel families whose name starts with this ("": all)
@@ -358,6 +363,10 @@ void small_tables_finish(hipStream_t s, const float* Ct, int ns, int GH, int Din
                          const float* Wi, float* gWi, float* gWt, float* gWr, bool ct_has_entity = true);
 void sumsq(hipStream_t s, const float* x, int64_t n, float* out);
 void sumsq_rows(hipStream_t s, const float* G, const int32_t* rows, const int32_t* count, int d, float* out);
+// deterministic mode: *out = |x|^2 + |listed rows of G|^2 (rows == null: the first term only) from one plain-stored partial per workgroup (a grid that depends on
+// nothing but n), summed in index order by kk::sum_partials' kernel -- no atomics
+constexpr int SUMSQ_DET_BLOCKS = 512;   // 256 for x, 256 for the rows
+void sumsq_det(hipStream_t s, const float* x, int64_t n, const float* G, const int32_t* rows, const int32_t* count, int d, float* partial, float* out);
 // dense optimiser over a contiguous span; scale_src: device float norm2 -> clip factor computed in-kernel
 // consume: zero the gradient as it is used; [z0,z0+zn0), [z1,z1+zn1): pad rows re-zeroed after the update; tab_slot: device step table entry
 void adam_dense(hipStream_t s, float* x, float* g, float* m, float* v, int64_t n, float step, float b1, float b2, float eps,
@@ -476,7 +485,9 @@ struct SmallGrad {
   int64_t N, n_mtiles; int T, F, nT, dt, de, dr, Vt, Vr;
   float* gWt; float* gWr; int nblocks;   // workgroups of this job
 };
-__device__ __forceinline__ void small_grad_block(const SmallGrad& a, int bx) {
+// DET (deterministic mode): the workgroup's [16][16] block leaves with plain stores (det_part[bx][v][c]); bidx::entity_grad_tail adds the blocks in workgroup order
+template <bool DET = false>
+__device__ __forceinline__ void small_grad_block(const SmallGrad& a, int bx, float* det_part = nullptr) {
   typedef float f32x4_ __attribute__((ext_vector_type(4)));
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int arow = lane & 15, ag = lane >> 4;
@@ -539,6 +550,7 @@ __device__ __forceinline__ void small_grad_block(const SmallGrad& a, int bx) {
   {
     const int v = threadIdx.x >> 4, c = threadIdx.x & 15;   // 256 threads = 16 table rows x 16 columns
     const float s = (sg_red[0][v][c] + sg_red[1][v][c]) + (sg_red[2][v][c] + sg_red[3][v][c]);
+    if constexpr (DET) { det_part[(int64_t)bx * 256 + threadIdx.x] = s; return; }
     if (v < V && s != 0.f) {
       if (is_type) unsafeAtomicAdd(a.gWt + (int64_t)v * a.dt + cb * 16 + c, s);
       else unsafeAtomicAdd(a.gWr + (int64_t)v * a.dr + (cb - ncb_t) * 16 + c, s);
@@ -548,8 +560,15 @@ __device__ __forceinline__ void small_grad_block(const SmallGrad& a, int bx) {
 // entity-table gradient = gather-reduce of dx over the occurrence index.  frag_order 1: the fused backward's fragment-order dx;
 // 2: its compact entity slice [(n T + t)][de]; 0: time-major row-major [T][N][D] (generic pipeline).
 // red / sg (nullable): the slab reduce / the small-table gradients carried by the same launch
+// det (deterministic mode, frag_order 2 only): the partial sums of runs that straddle segments and the small-table job's blocks go to det's scratch with plain
+// stores, and entity_grad_tail -- a launch behind this one -- adds them in a fixed order
+struct DetEntity {
+  float* seg_part;   // [segments][2][de]: the part of a run that came in from the segment before | the part of the run this segment opens and hands on
+  float* sg_part;    // [sg.nblocks][16][16]
+};
 void entity_grad(hipStream_t s, const float* DX, int frag_order, const int32_t* key_sorted, const int32_t* pos_sorted, int64_t n_index, int64_t N,
-                 int T, int D, int dt, int de, int Ve, float* gWe, const SlabReduce* red = nullptr, const SmallGrad* sg = nullptr);
+                 int T, int D, int dt, int de, int Ve, float* gWe, const SlabReduce* red = nullptr, const SmallGrad* sg = nullptr, const DetEntity* det = nullptr);
+void entity_grad_tail(hipStream_t s, const int32_t* key_sorted, int64_t n_index, int de, int Ve, float* gWe, const DetEntity& det, const SmallGrad* sg);
 size_t merge_scratch_bytes(int64_t n, int Ve);
 void merge_rows(hipStream_t s, const void* all, int world, int cap, int de, int Ve, float* G, int32_t* union_rows, int32_t* union_count,
                 int32_t* mark /*persistent [Ve], zero on entry and exit*/, void* scratch, size_t scratch_sz, int64_t tail_words = 0);

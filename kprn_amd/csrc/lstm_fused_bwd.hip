@@ -1,4 +1,6 @@
 // Fused BPTT kernels of the KPRN path scorer for gfx950 (forward: lstm_fused_fwd.hip; design: DESIGN.md).
+#include <string.h>
+
 #include <memory>
 
 #include "lstm_fused_common.h"
@@ -66,6 +68,11 @@ constexpr int PART = 2 * 256 * 64 + 256;  // floats per workgroup partial slab
 constexpr int NS_ID = 16;                  // one-hot columns of the small-table identity (relation v < Vr, type at Vr + v)
 constexpr int PART_G = PART + 256 * NS_ID; // slab stride: ... | G [256][NS_ID] (bottom layer on the identity route)
 constexpr int LDD = 4 * DH + 4;  // dA tile row stride
+// Deterministic mode (option "deterministic"): what a workgroup of the default kernels adds atomically at its end -- the head's gradient, its share
+// of the prefix table PG, the type / relation table gradients formed in the launch -- leaves in a slab of its own instead, with plain stores; k_det_join, one
+// launch behind the BPTT launches, adds the slabs in workgroup order.  Floats per workgroup: gW_out[cid][64] | gb_out[cid] | pad, PG [KCAP + 1][PFB],
+// gWt [Vt][dt] | gWr [Vr][dr] in table layout (<= 16 rows of <= 32 columns each: 16 (dt + dr) <= 16 * 48)
+constexpr int DET_PG = 80, DET_SMALL = DET_PG + (KCAP + 1) * PFB, DET_STRIDE = DET_SMALL + 1024;
 
 // Cycle probes are compiled in only with -DKPRN_TIMING_PROBES (KPRN_TIMING=1 then prints them): eight 64-bit counters per wave cost
 // 16 scalar registers for the whole launch, and with them the bottom-layer kernel spilled.
@@ -115,8 +122,9 @@ __device__ __forceinline__ void gather_load_ident(const BwdArgs& a, const int t,
 // entity column tiles only.  To keep the four waves' matrix work equal, wave j forms entity column tile (j & 1) for the m-tiles 2 (j >> 1) and
 // 2 (j >> 1) + 1 over the whole K (the same 64 weight registers as before): a wave walks ITS m-tiles in the order mof(0..3) everywhere, so its
 // own two come first and their indices stay compile-time.
-template <bool BOTTOM, bool TOP, int NMT, bool IDENT = false>
-__device__ __forceinline__ void bwd_body(const BwdArgs& a, const int bx, const int G_) {
+// DET: deterministic mode (kernels of their own, k_lstm_bwd_det / k_lstm_bwd_dual_det): only the flush at the end differs -- det_part is this pass's slab array
+template <bool BOTTOM, bool TOP, int NMT, bool IDENT = false, bool DET = false>
+__device__ __forceinline__ void bwd_body(const BwdArgs& a, const int bx, const int G_, float* const det_part = nullptr) {
   static_assert(!IDENT || (BOTTOM && !TOP && NMT == 4), "the identity route: bottom layer of two, 64-path tiles");
   constexpr int MTR = 16 * NMT;
   constexpr int NXT = IDENT ? 3 : 4;   // column tiles of the x tile that stage C multiplies
@@ -587,21 +595,24 @@ __device__ __forceinline__ void bwd_body(const BwdArgs& a, const int bx, const i
       if (ag == 0) pg[k0 * PFB + 4 * DH + j * 16 + arow] += cs;  // one owner lane per entry
     }
   }
+  float* const det_slab = DET ? det_part + (int64_t)bx * DET_STRIDE : nullptr;
   if (a.tile_k) {
     lds_barrier();
     for (int c = PFB + tid; c < (KCAP + 1) * PFB; c += 256) {
       const float v = pg[c];
-      if (v != 0.f) unsafeAtomicAdd(a.PG + c, v);
+      if constexpr (DET) det_slab[DET_PG + c] = v;
+      else if (v != 0.f) unsafeAtomicAdd(a.PG + c, v);
     }
   }
   if (!IDENT && BOTTOM && a.small_lds && wcls != 1) {
     const f32x4 sg = sacc[0] + sacc[1];
     const int V = (wcls == 0) ? a.Vt : a.Vr, width = (wcls == 0) ? a.dt : a.dr;
-    float* g = ((wcls == 0) ? a.gWt : a.gWr) + (j * 16 + arow - ((wcls == 0) ? 0 : a.dt + a.de));
+    float* g = (DET ? det_slab + DET_SMALL + ((wcls == 0) ? 0 : a.Vt * a.dt) : ((wcls == 0) ? a.gWt : a.gWr)) + (j * 16 + arow - ((wcls == 0) ? 0 : a.dt + a.de));
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int v = 4 * ag + i;
-      if (v < V && sg[i] != 0.f) unsafeAtomicAdd(g + (int64_t)v * width, sg[i]);
+      if constexpr (DET) { if (v < V) g[(int64_t)v * width] = sg[i]; }
+      else if (v < V && sg[i] != 0.f) unsafeAtomicAdd(g + (int64_t)v * width, sg[i]);
     }
   }
 
@@ -647,11 +658,13 @@ __device__ __forceinline__ void bwd_body(const BwdArgs& a, const int bx, const i
     float v = gwo;
     v += __shfl_xor(v, 16, 64);
     v += __shfl_xor(v, 32, 64);
-    if (ag == 0) unsafeAtomicAdd(a.gWout_row + j * 16 + arow, v);
+    if constexpr (DET) { if (ag == 0) det_slab[j * 16 + arow] = v; }
+    else if (ag == 0) unsafeAtomicAdd(a.gWout_row + j * 16 + arow, v);
     float bsum = gbo;
     bsum += __shfl_xor(bsum, 16, 64);
     bsum += __shfl_xor(bsum, 32, 64);
-    if (j == 0 && lane == 0) unsafeAtomicAdd(a.gbout_c, bsum);
+    if constexpr (DET) { if (j == 0 && lane == 0) det_slab[DH] = bsum; }
+    else if (j == 0 && lane == 0) unsafeAtomicAdd(a.gbout_c, bsum);
   }
   TPROBE(6)  // flush
   if (KPRN_PROBES_ON && a.timing && tid == 0) {
@@ -671,6 +684,37 @@ template <int NMT>
 __global__ __launch_bounds__(256, 1) void k_lstm_bwd_dual(BwdArgs top, BwdArgs bottom, int g) {
   if ((int)blockIdx.x < g) bwd_body<false, true, NMT>(top, (int)blockIdx.x, g);
   else bwd_body<true, false, NMT>(bottom, (int)blockIdx.x - g, g);
+}
+
+// ---- deterministic mode: the same bodies with the plain-store flush, and the join behind them ----
+template <bool BOTTOM, bool TOP, int NMT, bool IDENT>
+__global__ __launch_bounds__(256, 1) void k_lstm_bwd_det(BwdArgs a, float* det_part) {
+  bwd_body<BOTTOM, TOP, NMT, IDENT, true>(a, (int)blockIdx.x, (int)gridDim.x, det_part);
+}
+template <int NMT>
+__global__ __launch_bounds__(256, 1) void k_lstm_bwd_dual_det(BwdArgs top, BwdArgs bottom, int g, float* det_top, float* det_bottom) {
+  if ((int)blockIdx.x < g) bwd_body<false, true, NMT, false, true>(top, (int)blockIdx.x, g, det_top);
+  else bwd_body<true, false, NMT, false, true>(bottom, (int)blockIdx.x - g, g, det_bottom);
+}
+// dst[i] += ((slab 0 + slab 1) + slab 2) + ... : one running fp32 sum over the nslab workgroup slabs in workgroup order, one owner thread per element
+// (DEPTH slabs requested at a time).  Up to six spans: each layer's PG, the head's row and bias, the two small tables.
+struct DetJoin { int nseg, nslab; float* dst[6]; const float* src[6]; int n[6]; int blk0[7]; };
+__global__ __launch_bounds__(256) void k_det_join(DetJoin a) {
+  constexpr int DEPTH = 16;
+  int sgm = 0;
+  while (sgm + 1 < a.nseg && (int)blockIdx.x >= a.blk0[sgm + 1]) ++sgm;
+  const int i = ((int)blockIdx.x - a.blk0[sgm]) * 256 + threadIdx.x;
+  if (i >= a.n[sgm]) return;
+  const float* __restrict__ src = a.src[sgm] + i;
+  float acc = 0.f;
+  for (int w0 = 0; w0 < a.nslab; w0 += DEPTH) {
+    float x[DEPTH];
+#pragma unroll
+    for (int u = 0; u < DEPTH; ++u) x[u] = src[(int64_t)(w0 + u < a.nslab ? w0 + u : a.nslab - 1) * DET_STRIDE];
+#pragma unroll
+    for (int u = 0; u < DEPTH; ++u) if (w0 + u < a.nslab) acc += x[u];
+  }
+  a.dst[sgm][i] += acc;
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -842,10 +886,21 @@ bool transpose_job(kprn_handle* h, kk::TransposeJob* tj) {
 bool bwd_supported(const kprn_handle* h, int T) { return fwd_supported(h, T); }
 
 template <bool BOTTOM, bool TOP, int NMT = 4, bool IDENT = false>
-static void launch_bwd(kprn_handle* h, const BwdArgs& a, int grid) {
+static void launch_bwd(kprn_handle* h, const BwdArgs& a, int grid, float* det_part = nullptr) {
   size_t lds_bytes = (size_t)MT * LDD * sizeof(float);
   if (BOTTOM) lds_bytes += (size_t)MT * LDA * sizeof(float) + 2 * (MT * MAXT_LDS * 4) * sizeof(int32_t);
   lds_bytes += (size_t)(KCAP + 1) * PFB * sizeof(float);
+  if (det_part) {   // deterministic mode: the same body with the plain-store flush
+    if constexpr (BOTTOM || TOP) {
+      static PerDeviceOnce det_attr_done;
+      if (det_attr_done.need())
+        HIP_TRY(hipFuncSetAttribute((const void*)k_lstm_bwd_det<BOTTOM, TOP, NMT, IDENT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+      hipLaunchKernelGGL((k_lstm_bwd_det<BOTTOM, TOP, NMT, IDENT>), dim3(grid), dim3(256), lds_bytes, h->stream, a, det_part);
+      HIP_TRY(hipGetLastError());
+      return;
+    }
+    throw KprnError{KPRN_E_UNSUPPORTED, "deterministic: the fused path has no middle layer"};
+  }
   static PerDeviceOnce attr_done;  // one per template instantiation (the call is host time in front of every launch otherwise)
   const void* fn = IDENT ? (const void*)k_lstm_bwd_ident : (const void*)k_lstm_bwd<BOTTOM, TOP, NMT>;
   if (attr_done.need()) HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
@@ -872,6 +927,8 @@ void backward(kprn_handle* h, const kprn_batch* b, int cid) {
     s->cap_Nb = cn; s->cap_Tb = ct;
   }
   if (!s->part) HIP_TRY(kprn_dev_malloc((void**)&s->part, (size_t)2 * s->num_cu * PART_G * sizeof(float)));  // one slab set per layer
+  const bool det = h->deterministic;
+  if (det && !s->det_part) HIP_TRY(kprn_dev_malloc((void**)&s->det_part, (size_t)2 * s->num_cu * DET_STRIDE * sizeof(float)));
   static const bool want_timing = KPRN_DEV_ENV("KPRN_TIMING") != nullptr;
   if (want_timing && !s->timing) HIP_TRY(kprn_dev_malloc((void**)&s->timing, (size_t)s->num_cu * 12 * sizeof(unsigned long long)));
   if (s->wt_dirty) {  // (normally done already: the transposes ride in the loss-stage launch, transpose_job())
@@ -911,6 +968,7 @@ void backward(kprn_handle* h, const kprn_batch* b, int cid) {
     a.n_tiles = n_tiles;
     a.part = s->part + (size_t)l * s->num_cu * PART_G; a.timing = s->timing;
     a.dbg = kprn_dbg_mask();
+    float* const det_l = det ? s->det_part + (size_t)l * s->num_cu * DET_STRIDE : nullptr;
     a.ho = handover_args(h, grid);
     const bool bottom = (l == 0), top = (l == L - 1);
     // type / relation gradients: a passenger job of the entity-gradient launch when the shapes allow (one type slot, slices in
@@ -945,18 +1003,46 @@ void backward(kprn_handle* h, const kprn_batch* b, int cid) {
       } else if (pipe && bottom) {
         a.pipe = 2; a.pipe_flag = s->pipe_flag; a.ho = pipe_top.ho;   // (one epoch for the pair)
         size_t lds_bytes = (size_t)MT * LDD * sizeof(float) + (size_t)MT * LDA * sizeof(float) + 2 * (MT * MAXT_LDS * 4) * sizeof(int32_t) + (size_t)(KCAP + 1) * PFB * sizeof(float);
-        static PerDeviceOnce once;
-        if (once.need()) HIP_TRY(hipFuncSetAttribute((const void*)k_lstm_bwd_dual<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-        hipLaunchKernelGGL((k_lstm_bwd_dual<1>), dim3(2 * grid), dim3(256), lds_bytes, h->stream, pipe_top, a, grid);
+        if (det) {
+          static PerDeviceOnce det_once;
+          if (det_once.need()) HIP_TRY(hipFuncSetAttribute((const void*)k_lstm_bwd_dual_det<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+          hipLaunchKernelGGL((k_lstm_bwd_dual_det<1>), dim3(2 * grid), dim3(256), lds_bytes, h->stream, pipe_top, a, grid,
+                             s->det_part + (size_t)(L - 1) * s->num_cu * DET_STRIDE, det_l);
+        } else {
+          static PerDeviceOnce once;
+          if (once.need()) HIP_TRY(hipFuncSetAttribute((const void*)k_lstm_bwd_dual<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+          hipLaunchKernelGGL((k_lstm_bwd_dual<1>), dim3(2 * grid), dim3(256), lds_bytes, h->stream, pipe_top, a, grid);
+        }
         HIP_TRY(hipGetLastError());
       } else
-      if (small) { if (bottom) launch_bwd<true, false, 1>(h, a, grid); else launch_bwd<false, true, 1>(h, a, grid); }   // (L == 2)
-      else if (bottom && top) launch_bwd<true, true>(h, a, grid);
-      else if (bottom && ident) launch_bwd<true, false, 4, true>(h, a, grid);
-      else if (bottom) launch_bwd<true, false>(h, a, grid);
-      else if (top) launch_bwd<false, true>(h, a, grid);
-      else launch_bwd<false, false>(h, a, grid);
+      if (small) { if (bottom) launch_bwd<true, false, 1>(h, a, grid, det_l); else launch_bwd<false, true, 1>(h, a, grid, det_l); }   // (L == 2)
+      else if (bottom && top) launch_bwd<true, true>(h, a, grid, det_l);
+      else if (bottom && ident) launch_bwd<true, false, 4, true>(h, a, grid, det_l);
+      else if (bottom) launch_bwd<true, false>(h, a, grid, det_l);
+      else if (top) launch_bwd<false, true>(h, a, grid, det_l);
+      else launch_bwd<false, false>(h, a, grid, det_l);
       if (bottom || s->timing) bwd_scope.reset();
+      if (bottom && det) {
+        // every layer's BPTT has run: the slabs of the head's gradient, of PG (read by the prefix backward below) and of the small tables, in workgroup order
+        ProfScope ps(h, "det_join");
+        DetJoin dj;
+        memset(&dj, 0, sizeof(dj));
+        dj.nslab = grid;
+        int nb = 0;
+        auto span = [&](float* dst, const float* src, int n) {
+          if (n <= 0) return;
+          dj.dst[dj.nseg] = dst; dj.src[dj.nseg] = src; dj.n[dj.nseg] = n; dj.blk0[dj.nseg] = nb;
+          nb += (n + 255) / 256; ++dj.nseg; dj.blk0[dj.nseg] = nb;
+        };
+        const float* dtop = s->det_part + (size_t)(L - 1) * s->num_cu * DET_STRIDE;
+        span(a.gWout_row, dtop, DH);
+        span(a.gbout_c, dtop + DH, 1);
+        if (b->tile_k) for (int ll = 0; ll < L; ++ll)
+          span(s->PG + (size_t)ll * (KCAP + 1) * PFB + PFB, s->det_part + (size_t)ll * s->num_cu * DET_STRIDE + DET_PG + PFB, KCAP * PFB);
+        if (a.small_lds) { span(a.gWt, det_l + DET_SMALL, c.Vt * c.dt); span(a.gWr, det_l + DET_SMALL + c.Vt * c.dt, c.Vr * c.dr); }
+        hipLaunchKernelGGL(k_det_join, dim3(nb), dim3(256), 0, strm, dj);
+        HIP_TRY(hipGetLastError());
+      }
       if (bottom && h->after_bptt_hook) h->after_bptt_hook(h);   // (a deferred part of the scoring pass: beside the tail below, kprn_internal.h score_rest_in_backward)
     }
     if (bottom) have_r1 = prefix_backward(h, b, n_tiles64);  // the skipped steps of every layer; leaves their dx sums in DX's virtual tile
@@ -966,7 +1052,7 @@ void backward(kprn_handle* h, const kprn_batch* b, int cid) {
         ra.part[q] = s->part + (size_t)ll * s->num_cu * PART_G;
         ra.gWi[q] = gd + h->layer[ll].Wi; ra.gWo[q] = gd + h->layer[ll].Wo; ra.gbi[q] = gd + h->layer[ll].bi;
       }
-      ra.nslab = grid; ra.n_elem = ident ? PART_G : PART; ra.slab = PART_G; ra.L = L; ra.ny = 16;
+      ra.nslab = grid; ra.n_elem = ident ? PART_G : PART; ra.slab = PART_G; ra.L = L; ra.ny = det ? 1 : 16;   // (one range: a single owner per element, slabs in the fixed order of slab_reduce_block)
       ra.gG[0] = ident ? s->gG : nullptr; ra.gG[1] = nullptr;
       ra.r1 = s->r1; ra.kmax = have_r1 ? b->h_kmax : 0; ra.kcap = KCAP; ra.r1_stride = R1; ra.G = 4; ra.H = DH;
     }
@@ -977,8 +1063,21 @@ void backward(kprn_handle* h, const kprn_batch* b, int cid) {
       sg.DX = s->DX; sg.idx = b->idx_s ? b->idx_s : b->idx; sg.tile_k = b->tile_k; sg.N = N; sg.n_mtiles = n_tiles * nmt; sg.T = T; sg.F = b->F;
       sg.nT = c.num_types; sg.dt = c.dt; sg.de = c.de; sg.dr = c.dr; sg.Vt = c.Vt; sg.Vr = c.Vr; sg.gWt = a.gWt; sg.gWr = a.gWr; sg.nblocks = 4 * s->num_cu;
       { static const int sgb = KPRN_DEV_ENV("KPRN_SG_BLOCKS") ? atoi(KPRN_DEV_ENV("KPRN_SG_BLOCKS")) : 0; if (sgb > 0) sg.nblocks = sgb; }   // (measurement)
+      const bool sg_on = small_job && !a.small_lds && !ident;
+      if (det) {
+        const int ncb = (c.dt + c.dr) >> 4;
+        sg.nblocks = ncb * (int)std::min<int64_t>(64, std::max<int64_t>(1, (sg.n_mtiles * T + 15) / 16));   // (whole groups of column blocks: a function of the batch shape only)
+        const int64_t need_seg = (b->n_index + 63) / 64 * 2 * c.de, need_sg = (int64_t)sg.nblocks * 256;
+        if (need_seg > s->det_seg_cap || need_sg > s->det_sg_cap) {
+          HIP_TRY(hipStreamSynchronize(strm));
+          if (need_seg > s->det_seg_cap) { if (s->det_seg) hipFree(s->det_seg); HIP_TRY(kprn_dev_malloc((void**)&s->det_seg, (size_t)need_seg * sizeof(float))); s->det_seg_cap = need_seg; }
+          if (need_sg > s->det_sg_cap) { if (s->det_sg) hipFree(s->det_sg); HIP_TRY(kprn_dev_malloc((void**)&s->det_sg, (size_t)need_sg * sizeof(float))); s->det_sg_cap = need_sg; }
+        }
+      }
+      const bidx::DetEntity de_{s->det_seg, s->det_sg};
       bidx::entity_grad(strm, s->DXe, /*compact entity slice=*/2, b->key_sorted, b->pos_sorted, b->n_index, N, T, DH, c.dt, c.de, c.Ve, a.gWe, &ra,
-                        (small_job && !a.small_lds && !ident) ? &sg : nullptr);
+                        sg_on ? &sg : nullptr, det ? &de_ : nullptr);
+      if (det) bidx::entity_grad_tail(strm, b->key_sorted, b->n_index, c.de, c.Ve, a.gWe, de_, sg_on ? &sg : nullptr);   // (the owners' pass: behind the launch that stored the parts)
       reduced = true;
     }
     const bool small_in_kernel = small_job && have_index;   // (handled above)
@@ -1054,6 +1153,7 @@ void params_changed(kprn_handle* h) {
 void release(kprn_handle* h) {
   State* s = (State*)h->fused_state;
   if (!s) return;
+  for (float* p : {s->det_part, s->det_seg, s->det_sg}) if (p) hipFree(p);
   for (float* p : {s->save_frag, s->WT, s->DX, s->DXe, s->part, s->gG, s->part_small, s->pfb, s->pfs, s->pfx, s->PG, s->r1, s->mc_bias, s->mc_hseq[0], s->mc_hseq[1],
                    s->ho_state[0], s->ho_state[1]}) if (p) hipFree(p);
   for (unsigned* p : {s->ho_flag[0], s->ho_flag[1], s->pipe_flag}) if (p) hipFree(p);

@@ -430,6 +430,10 @@ struct State {
   int part_small_n = 0;
   unsigned long long* timing = nullptr;  // [num_cu][8] when KPRN_TIMING=1
   int64_t cap_Nb = 0; int cap_Tb = 0;
+  // deterministic mode (lstm_fused_bwd.hip DET_STRIDE, batch_index.hip DetEntity): grow-only scratch of the plain-store partial sums
+  float* det_part = nullptr;                          // [2 layers][num_cu][DET_STRIDE]
+  float* det_seg = nullptr; int64_t det_seg_cap = 0;  // [segments][2][de]
+  float* det_sg = nullptr; int64_t det_sg_cap = 0;    // [small-table job workgroups][256]
 };
 
 static inline State* st(kprn_handle* h) {

@@ -39,6 +39,8 @@ def flag_parser():
     a("-numLayers", type=int, default=1); a("-useDropout", type=int, default=0); a("-dropout", type=float, default=0.0)
     # engine-side additions (not in the reference)
     a("-seed", type=int, default=12345); a("-entityUpdate", type=int, default=0)
+    a("-deterministic", type=int, default=0, choices=[0, 1],
+      help="1: bit-reproducible training (the engine's option \"deterministic\": fixed-order gradient sums on the fused fp32 path; a model that would train on any other pipeline is refused with KPRN_E_UNSUPPORTED)")
     a("-checkpointFormat", default="native", choices=["native", "t7", "both"],
       help="the native checkpoint is always written at <model>-latest; t7 / both ALSO write <model>-latest.t7, the parameters in a Torch7 {embeddingLayer, predictor_net} container (the reference writes its container at <model>-latest itself)")
     # evaluation during training (the slot OneModel.lua:389 left commented out): every -evaluationFrequency epochs the pairs of -testList are scored
@@ -117,6 +119,8 @@ def build_engine(params, rank=0, world=1, device_id=None, stream=None):
                       C_=LABEL_DIMENSION, reducer=getattr(params, "reducer", reducer_of_train_flag(params.topK)), K=params.K, rnn_type=RNN_TYPES[params.rnnType],
                       use_relu=params.useReLU, rnn_init=params.rnnInitialization,
                       device_id=device_id, rank=rank, world=world, param_init=params.paramInit, seed=params.seed, stream=stream)
+    if getattr(params, "deterministic", 0):
+        eng.set_option("deterministic", "1")   # (a training call on a pipeline without fixed-order sums then raises KprnError(E_UNSUPPORTED))
     if params.initModel:
         load_checkpoint(eng, params.initModel)  # OneModel.lua:277-282
     return eng
