@@ -346,6 +346,22 @@ int kprn_read_loss(kprn_handle* h, float* loss);
 int kprn_read_loss_sum(kprn_handle* h, float* sum, int32_t* steps, int32_t reset);
 int kprn_sync(kprn_handle* h);
 
+/* ---- dropout on the rnn cell's input (-useDropout / -dropout, OneModel.lua:246-265) ----
+ * kprn_set_option(h, "dropout", "p") with 0 < p < 1 makes every TRAINING forward of an rnn_type 1, compute_dtype 0 handle (a forward that saves for the
+ * backward: kprn_backward_batch, kprn_train_step, kprn_train_step_batch) apply nn.Dropout(p) to every layer's step input -- x_t for layer 1, h^{l-1}_t
+ * above, never the recurrent input: y = x * m / (1 - p), m ~ Bernoulli(1 - p), independent per (layer, step, path, element).  Scoring passes never drop
+ * (the module in evaluation mode).  MaskZero's flag of a step is taken from the UNDROPPED row.  The generator is the engine's own (torch's stream is not
+ * the target) and is fully specified, so that a mask can be rebuilt anywhere:
+ *   Philox4x32-10, key = (seed & 0xffffffff, seed >> 32), counter = (e / 4, n, t + 65536 * l, draw); word e % 4 of the call is element e's word r
+ *   (l = layer, 0-based; t = step; n = the path's index in the batch, rectangular or ragged; e = element of the layer's Din-wide input row);
+ *   kept iff r >= thr, thr = min(2^32 - 1, floor(p * 2^32)) in double, p the rate rounded to fp32; kept: x * (float)(1.0 / (1.0 - (double)p)); dropped: +0.0f;
+ *   draw = training forwards this handle has run since the seed was last set (32 bits); the backward of a step regenerates the masks of its forward.
+ * Nothing stores a mask.  T <= 65535 and N < 2^32 per batch, or the training call returns KPRN_E_ARG.
+ * kprn_host_dropout_keep is the rule on the host cores (no handle, no GPU): keep [T][N][Din], 1 = kept; KPRN_E_ARG for layer / T outside 0 / 1..65535,
+ * N outside 1..2^32 - 1, Din < 1 or p outside [0, 1).                                                                                          */
+int kprn_host_dropout_keep(uint64_t seed, unsigned int draw /* uint32 */, int32_t layer, int32_t T, int64_t N, int32_t Din, float p,
+                           unsigned char* keep /* uint8 [T][N][Din] */);
+
 /* The scoring writer's lines (eval/test_from_checkpoint.lua:110-118: counter \t string.format("%.5f", score) \t label, one per
  * pair, the label as Lua 5.1 prints a number = "%.14g"), n of them from counter0 on, formatted by the host cores into out.
  * Host-only (no handle, no GPU).  *written = bytes written; KPRN_E_ARG with *written = -(bytes needed) when cap is too small. */
@@ -470,6 +486,12 @@ int kprn_profile_get(kprn_handle* h, kprn_prof_entry* out, int32_t cap, int32_t*
  *                     pipeline -- when the call would run on the generic pipeline ("impl" "generic", any other shape), on rnn / gru, on the bf16 pipeline
  *                     (compute_dtype 1) or on a KPRN_DBG scatter route.  Scoring, ranking, explanation and parameter access are never refused; data-parallel
  *                     handles are accepted (the exchange sums in rank order).  "0" again makes the same handle train as before; with "0" nothing changes.
+ *   "dropout"         "0" (default) | a decimal rate in (0, 1): nn.Dropout on the step input of every rnn layer in training forwards (see kprn_host_dropout_keep).
+ *                     Not a number or outside [0, 1): KPRN_E_ARG.  A rate > 0 on a handle with rnn_type != 1 (the reference's lstm / gru ignore the flag) or
+ *                     compute_dtype != 0 is refused with KPRN_E_UNSUPPORTED when it is set.  With a rate > 0 layer 0's backward leaves the small-table identity
+ *                     ("small_tables") for the dx product + table-gradient route.  "0" restores the launches of a handle that never had the option
+ *   "dropout_seed"    decimal or 0x hex uint64 (default: kprn_config.seed + rank, so data-parallel replicas draw different masks): the generator's seed;
+ *                     setting it restarts the draw count at 0
  *   (also: "small_tiles", "score_split", "loss_accumulate", "feed_build" / "feed_threads" / "feed_workers", "dp_comm_stream",
  *    "dp_fused_update", "dp_dense_in_pack" -- described at the calls they modify)                                                 */
 int kprn_set_option(kprn_handle* h, const char* key, const char* value);

@@ -166,6 +166,17 @@ def host_explain(path_scores, offsets, class_id, reducer, K_reducer, M, pairs=No
     return res
 
 
+def host_dropout_keep(seed, draw, layer, T, N, Din, p):
+    """kprn_host_dropout_keep (no handle, no GPU): the keep flags [T, N, Din] (uint8, 1 = kept) of the engine's dropout generator for one layer of one
+    training forward (include/kprn.h: Philox4x32-10 addressed by seed, draw, layer, step, path, element)"""
+    keep = np.zeros((max(int(T), 0), max(int(N), 0), max(int(Din), 0)), np.uint8)
+    rc = lib().kprn_host_dropout_keep(C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), C.c_uint32(int(draw) & 0xFFFFFFFF), int(layer), int(T), C.c_int64(int(N)), int(Din),
+                                      C.c_float(float(p)), _fp(keep) if keep.size else None)
+    if rc != 0:
+        raise KprnError(rc, "kprn_host_dropout_keep: bad layer / T / N / Din / p")
+    return keep
+
+
 def format_score_lines(counter0, probs, labels):
     """bytes of the scoring writer's lines for pairs counter0 .. (kprn_format_score_lines; host-only)"""
     L = lib()

@@ -3,7 +3,9 @@
 // One handle = the reference's training_net (MapReduce(predictor_net, reducer) + Sigmoid,
 // release/songPathRnn/model/OneModel.lua:204-294) plus MyOptimizer's state
 // (model/optimizer/MyOptimizer.lua:13-72), resident in HBM.
+#include <ctype.h>
 #include <dlfcn.h>
+#include <errno.h>
 #include <math.h>
 #include <stdio.h>
 #include <string.h>
@@ -293,6 +295,21 @@ static void catch_up(kprn_handle* h, const kprn_batch* b) {
   h->caught_serial = b->serial; h->caught_step = h->opt_step;
 }
 
+// Option "dropout": what a launch needs to regenerate layer l's masks of the training forward in flight (philox_dev.h), and the addressing limits of
+// the counter (step and layer share a 32-bit word, the path has one of its own), checked before a training call launches or writes anything
+static philox::DropArgs drop_args(const kprn_handle* h, int l) {
+  philox::DropArgs a;
+  a.k0 = (uint32_t)(h->dropout_seed & 0xffffffffu); a.k1 = (uint32_t)(h->dropout_seed >> 32);
+  a.draw = h->drop_draw_cur; a.layer16 = 65536u * (uint32_t)l;
+  a.thr = philox::threshold((double)h->dropout_p); a.scale = philox::keep_scale(h->dropout_p);
+  return a;
+}
+static void drop_check(const kprn_handle* h, const kprn_batch* b) {
+  if (!(h->dropout_p > 0.f) || h->cfg.rnn_type != 1) return;
+  KPRN_REQUIRE(b->T <= 65535 && h->cfg.L <= 65535 && b->N < ((int64_t)1 << 32), KPRN_E_ARG,
+               "dropout: the mask generator addresses at most 65535 steps, 65535 layers and 2^32 - 1 paths per batch");
+}
+
 // ---------------------------------------------------------------------------------------
 // generic (unfused) forward: gather -> per layer {input GEMM, per step recurrent GEMM + gates} -> head
 static void forward_generic(kprn_handle* h, const kprn_batch* b, bool save) {
@@ -303,7 +320,23 @@ static void forward_generic(kprn_handle* h, const kprn_batch* b, bool save) {
   const int H = c.H, L = c.L, T = b->T;
   const int64_t N = b->N;
   hipStream_t s = h->stream;
-  {
+  // option "dropout" (rnn, fp32): a TRAINING forward drops every layer's step input; a scoring pass never does
+  const bool drop = save && h->dropout_p > 0.f && c.rnn_type == 1;
+  if (drop) drop_check(h, b);   // (throws before the flag below says that a dropped forward is behind the backward)
+  h->drop_live = drop;
+  if (drop) {
+    h->drop_draw_cur = h->drop_draw++;
+    const int64_t need = (int64_t)(L - 1) * T * N * H;
+    if (need > w.cap_HsD) {
+      HIP_TRY(hipStreamSynchronize(s));
+      dfree(w.HsD);
+      w.HsD = dalloc<float>(need);
+      w.cap_HsD = need;
+    }
+    ProfScope ps(h, "embed_gather_drop");
+    // the dropped rows go to X; MaskZero's flags come from the undropped values in the same pass
+    kk::embed_gather_drop(s, b->idx, N, T, b->F, c.num_types, h->dense + h->off_Wt, h->We, h->dense + h->off_Wr, c.dt, c.de, c.dr, w.X, w.mask, drop_args(h, 0));
+  } else {
     ProfScope ps(h, "embed_gather");
     // (rnnType rnn: MaskZero's mask of the bottom layer's input rows comes out of the same pass)
     kk::embed_gather(s, b->idx, N, T, b->F, c.num_types, h->dense + h->off_Wt, h->We, h->dense + h->off_Wr, c.dt, c.de, c.dr, w.X, true,
@@ -357,6 +390,14 @@ static void forward_generic(kprn_handle* h, const kprn_batch* b, bool save) {
       float* pre = w.ACT + (int64_t)l * T * N * H;
       float* hs = w.Hs + (int64_t)l * T * N * H;
       float* mask = w.mask + (int64_t)l * T * N;
+      const float* in0 = in;   // the undropped rows: what MaskZero looks at
+      if (drop && l > 0) {
+        // the layer reads a dropped COPY of the plane below: the undropped one stays for the layer below's BPTT and for the mask above
+        ProfScope ps(h, "drop_rows_fwd");
+        float* din = w.HsD + (int64_t)(l - 1) * T * N * H;
+        kk::drop_rows(s, in, din, N, T, Din, drop_args(h, l));
+        in = din;
+      }
       const bool stepk = !bf && !no_step && gemm::step_supported(in, Din, Din, hs, H, H, h->dense + h->layer[l].Wi, h->dense + h->layer[l].Wo, N);
       if (!stepk) {
         ProfScope ps(h, "gemm_i2g_fwd");
@@ -364,7 +405,7 @@ static void forward_generic(kprn_handle* h, const kprn_batch* b, bool save) {
       }
       if (l > 0) {
         ProfScope ps(h, "rnn_mask");
-        kk::row_nonzero(s, in, (int64_t)T * N, Din, mask);  // layer l > 1: the mask follows the ACTUAL input rows (h^{l-1}_t), as MaskZero does
+        kk::row_nonzero(s, in0, (int64_t)T * N, Din, mask);  // layer l > 1: the mask follows the ACTUAL input rows (h^{l-1}_t), as MaskZero does
       }
       if (stepk && h->persist_layers && lp32::supported(1, N, Din, H, h->persist_layers == 2)) {
         // all T steps of the layer in ONE persistent launch: h never leaves the CU, weights stream L2 -> LDS by DMA (layer_f32_persist.hip)
@@ -556,7 +597,8 @@ static void zero_grads(kprn_handle* h) {
 static int small_tables_ns(const kprn_handle* h, const kprn_batch* b) {
   const kprn_config& c = h->cfg;
   const int ns = (c.Vr + c.Vt + 3) & ~3;
-  const bool ok = h->small_tables && c.num_types == 1 && c.rnn_type != 2 && ns <= c.dt && ns <= 128 && c.de > 0 && c.dr > 0 && b->key_sorted != nullptr && !b->tile_k &&
+  // (a dropped x_t is no sum of table rows, and the route overwrites type columns of the saved input, which the dropped dW product reads: DESIGN.md 3.12)
+  const bool ok = !h->drop_live && h->small_tables && c.num_types == 1 && c.rnn_type != 2 && ns <= c.dt && ns <= 128 && c.de > 0 && c.dr > 0 && b->key_sorted != nullptr && !b->tile_k &&
                   b->F >= 3;
   return ok ? ns : 0;
 }
@@ -704,7 +746,8 @@ static void backward_generic(kprn_handle* h, const kprn_batch* b, int cid) {
     const int relu = c.use_relu == 1 ? 1 : 0;
     for (int l = L - 1; l >= 0; --l) {
       const int Din = h->layer[l].Din;
-      const float* in = (l == 0) ? w.X : w.Hs + (int64_t)(l - 1) * T * N * H;
+      // (dropout: the input the layer saw is the dropped one -- X holds it for layer 0, HsD for the layers above)
+      const float* in = (l == 0) ? w.X : (h->drop_live ? w.HsD : w.Hs) + (int64_t)(l - 1) * T * N * H;
       const float* pre = w.ACT + (int64_t)l * T * N * H;
       const float* hs = w.Hs + (int64_t)l * T * N * H;
       const float* mask = w.mask + (int64_t)l * T * N;
@@ -749,6 +792,12 @@ static void backward_generic(kprn_handle* h, const kprn_batch* b, int cid) {
       {
         ProfScope ps(h, "gemm_i2g_bwd_dx");
         gemm::run(s, w.dA, H, 1, Wi, Din, 1, w.dIn, Din, (int64_t)T * N, Din, H, false, nullptr, 1, bf);
+      }
+      if (h->drop_live) {
+        // the product is the gradient wrt the DROPPED input: times the regenerated m s it is the gradient from above of layer l - 1, or what the table
+        // gradients of layer 0 are formed from
+        ProfScope ps(h, "drop_rows_bwd");
+        kk::drop_rows(s, w.dIn, w.dIn, N, T, Din, drop_args(h, l));
       }
     }
   } else
@@ -842,6 +891,7 @@ static void det_check(const kprn_handle* h, int T) {
 static void backward_impl(kprn_handle* h, const kprn_batch* b, int class_id, int literal, float inv_batch) {
   check_batch(h, b, class_id);
   det_check(h, b->T);
+  drop_check(h, b);
   KPRN_REQUIRE(b->labels != nullptr && b->has_index, KPRN_E_ARG, "batch has no labels (targets are required, MyOptimizer.lua:179)");
   const kprn_config& c = h->cfg;
   zero_grads(h);
@@ -1063,6 +1113,7 @@ int kprn_create(const kprn_config* cfg, kprn_handle** out) {
     else if (c.stream) { h->stream = (hipStream_t)c.stream; h->own_stream = false; h->stream_known = true; }
     else { HIP_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking)); h->own_stream = true; h->stream_known = false; }
     build_layout(h);
+    h->dropout_seed = c.seed + (uint64_t)c.rank;   // (data-parallel replicas do not share masks)
     h->dense = dalloc<float>(h->n_dense); h->g_dense = dalloc<float>(h->n_dense);
     h->s1_dense = dalloc<float>(h->n_dense); h->s2_dense = dalloc<float>(h->n_dense);
     h->We = dalloc<float>(h->n_ent); h->g_We = dalloc<float>(h->n_ent);
@@ -1133,7 +1184,7 @@ void kprn_destroy(kprn_handle* h) {
   if (h->feed_stream) { hipStreamSynchronize(h->feed_stream); hipStreamDestroy(h->feed_stream); hipEventDestroy(h->ev_feed_fork); }
   if (h->feed_scratch) { hipFree(h->feed_scratch); h->feed_scratch = nullptr; }
   dp_release(h);
-  dfree(h->S2); dfree(h->sel2); dfree(h->st_ctmp); dfree(h->lp_wot);
+  dfree(h->S2); dfree(h->sel2); dfree(h->st_ctmp); dfree(h->lp_wot); dfree(h->ws.HsD);
   fused::release(h);
   bf16p::release(h);
   if (h->bidx_scratch) { hipFree(h->bidx_scratch); h->bidx_scratch = nullptr; }
@@ -2506,6 +2557,7 @@ int kprn_train_step_batch(kprn_handle* h, const kprn_batch* b, int32_t class_id,
   KPRN_REQUIRE(opt, KPRN_E_ARG, "opt is NULL");
   check_batch(h, b, class_id);
   det_check(h, b->T);
+  drop_check(h, b);
   catch_up(h, b);
   if (!h->pad_clean) { zero_pad_tokens(h); fused::params_changed(h); bf16p::params_changed(h, false); }  // MyOptimizer.lua:181 (a no-op when the last step left them zero)
   // the loss goes back as soon as the loss stage has run (option "train_step_return" = "loss"); profiling and "drain" wait for the whole step as before
@@ -3129,6 +3181,30 @@ int kprn_set_option(kprn_handle* h, const char* key, const char* value) {
     // KPRN_E_UNSUPPORTED.  "0" (default): the kernels launched before this option existed.  Read at every training call.
     KPRN_REQUIRE(strcmp(value, "0") == 0 || strcmp(value, "1") == 0, KPRN_E_ARG, "deterministic must be 0 or 1");
     h->deterministic = value[0] == '1';
+  } else if (strcmp(key, "dropout") == 0) {
+    // rate p of nn.Dropout on every rnn layer's step input in training forwards (OneModel.lua:246-265); "0" (default): the kernels launched
+    // before this option existed.  Refused HERE where the reference ignores the flag (lstm, gru) or the pipeline has no dropped form (bf16 products).
+    char* end = nullptr;
+    // (strtod alone would take leading white space and hex floats: digits, '.', an exponent and its sign only, a digit or '.' first)
+    const bool decimal = (isdigit((unsigned char)value[0]) || value[0] == '.') && value[strspn(value, "0123456789.eE+-")] == 0;
+    const double p = decimal ? strtod(value, &end) : 0.0;
+    KPRN_REQUIRE(decimal && end != value && *end == 0 && p >= 0.0 && p < 1.0 && (double)(float)p < 1.0, KPRN_E_ARG, "dropout must be a decimal rate in [0, 1)");
+    if (p > 0.0) {
+      KPRN_REQUIRE(h->cfg.rnn_type == 1, KPRN_E_UNSUPPORTED,
+                   "dropout > 0: built for rnn_type 1 (rnn) only -- the reference's lstm / gru modules ignore -useDropout (OneModel.lua:237-239), so there is nothing to reproduce");
+      KPRN_REQUIRE(h->cfg.compute_dtype == 0, KPRN_E_UNSUPPORTED, "dropout > 0: built for compute_dtype 0 (fp32) only; the bf16-product pipeline has no dropped form");
+    }
+    h->dropout_p = (float)p;
+  } else if (strcmp(key, "dropout_seed") == 0) {
+    // seed of the mask generator (decimal or 0x hex uint64; default cfg.seed + cfg.rank); setting it restarts the draw count
+    char* end = nullptr;
+    errno = 0;
+    // (a digit first: no white space, no sign; base 10 unless "0x" leads, so a leading 0 is not octal)
+    const bool hex = value[0] == '0' && (value[1] == 'x' || value[1] == 'X');
+    const unsigned long long v = isdigit((unsigned char)value[0]) ? strtoull(value, &end, hex ? 16 : 10) : 0;
+    KPRN_REQUIRE(end != nullptr && end != value && !(hex && end == value + 2) && *end == 0 && errno == 0, KPRN_E_ARG, "dropout_seed must be a decimal or 0x hex unsigned 64-bit number");
+    h->dropout_seed = (uint64_t)v;
+    h->drop_draw = 0;
   } else if (strcmp(key, "reserve_cus") == 0) {
     // the fused SCORING forward is a persistent one-workgroup-per-CU kernel that fills the register file of every CU it runs
     // on; leaving a few CUs free lets the copy kernels of a concurrently running collective (RCCL) make progress beside it

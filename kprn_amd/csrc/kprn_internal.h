@@ -10,6 +10,7 @@
 #include <map>
 
 #include "../../include/kprn.h"
+#include "philox_dev.h"
 
 #define KPRN_MAX_LAYERS 8
 
@@ -60,6 +61,8 @@ struct Workspace {
   float* sel = nullptr;    // [B] probs[:, classId]
   float* dy = nullptr;     // [B]
   float* mask = nullptr;   // [L][T][N]  rnn: MaskZero flags of the step inputs
+  float* HsD = nullptr;    // [L-1][T][N][H] rnn with dropout: the dropped copies of Hs[0 .. L-2] the layers above read (allocated at the first such training forward)
+  int64_t cap_HsD = 0;     // floats
 };
 
 struct ProfEntry { double total_ms = 0; int64_t launches = 0; };
@@ -276,6 +279,12 @@ struct kprn_handle {
   // option "deterministic": every float sum of a training step whose addends come from different waves or workgroups of one launch is formed in an order that
   // depends on the batch and the launch geometry only; pipelines that cannot do that refuse to train
   bool deterministic = false;
+  // option "dropout" (rnn cell, fp32): nn.Dropout on every layer's step input in TRAINING forwards.  Masks are regenerated, never stored:
+  // drop_draw counts the training forwards since the seed was set; the backward of a step uses the draw of its forward (drop_draw_cur)
+  float dropout_p = 0.f;
+  uint64_t dropout_seed = 0;   // default cfg.seed + cfg.rank (kprn_create)
+  uint32_t drop_draw = 0, drop_draw_cur = 0;
+  bool drop_live = false;      // the state saved by the last generic training forward was dropped (what backward_generic must undo)
   float* det_norm_part = nullptr;   // [kk::SUMSQ_DET_BLOCKS] per-workgroup partials of the gradient norm
 
   bool prof_on = false;
@@ -308,6 +317,10 @@ void lstm_gates_fwd(hipStream_t s, float* act /*[N][4H] in: pre-act, out: gates*
 void lstm_gates_bwd(hipStream_t s, const float* act, const float* c, const float* c_prev, const float* dH_up /*nullable*/,
                     float* dH, float* dC, float* dA, int64_t N, int H);
 void row_nonzero(hipStream_t s, const float* in, int64_t N, int D, float* mask);
+// dropout.hip: embed_gather (time-major) writing the DROPPED rows, mask from the undropped values; out = in (.) m s over [T][N][W] rows (out may be in)
+void embed_gather_drop(hipStream_t s, const int32_t* idx, int64_t N, int T, int F, int nT, const float* Wt, const float* We, const float* Wr, int dt, int de,
+                       int dr, float* X, float* mask, const philox::DropArgs& a);
+void drop_rows(hipStream_t s, const float* in, float* out, int64_t N, int T, int W, const philox::DropArgs& a);
 void rnn_cell_fwd(hipStream_t s, float* pre, const float* bh, const float* mask, float* h, int64_t N, int H, int relu);
 void rnn_cell_bwd(hipStream_t s, const float* pre, const float* hcur, const float* mask, const float* dH_up, const float* dH, float* dA, int64_t N,
                   int H, int relu);

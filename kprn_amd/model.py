@@ -3,7 +3,7 @@
 `parse_flags` accepts the torch.CmdLine flags of OneModel.lua:27-87 with the same names and
 defaults; `build_engine` turns them into a kprn Engine the way OneModel.lua:204-309 builds
 predictor_net / reducer / training_net.  Options the engine does not implement fail loudly with
-the library's KPRN_E_UNSUPPORTED (dropout) instead of silently doing something else.
+the library's KPRN_E_UNSUPPORTED (dropout on lstm / gru, where the reference ignores the flag) instead of silently doing something else.
 """
 import argparse
 
@@ -39,6 +39,8 @@ def flag_parser():
     a("-numLayers", type=int, default=1); a("-useDropout", type=int, default=0); a("-dropout", type=float, default=0.0)
     # engine-side additions (not in the reference)
     a("-seed", type=int, default=12345); a("-entityUpdate", type=int, default=0)
+    a("-dropoutSeed", type=lambda v: int(v, 0), default=None,
+      help="seed of the dropout mask generator (decimal or 0x hex, 64 bits; default: -seed); a data-parallel rank r seeds with this + r, so replicas do not share masks; the engine's option \"dropout_seed\"")
     a("-deterministic", type=int, default=0, choices=[0, 1],
       help="1: bit-reproducible training (the engine's option \"deterministic\": fixed-order gradient sums on the fused fp32 path; a model that would train on any other pipeline is refused with KPRN_E_UNSUPPORTED)")
     a("-checkpointFormat", default="native", choices=["native", "t7", "both"],
@@ -54,6 +56,11 @@ def parse_flags(argv=None):
 
 
 RNN_TYPES = {"lstm": 0, "rnn": 1, "gru": 2}
+
+
+def dropout_rate(params):
+    """the engine's option "dropout" for these flags: -dropout where -useDropout is on (OneModel.lua:246 builds nn.Dropout(params.dropout) only then), else 0"""
+    return float(params.dropout) if params.useDropout != 0 and params.dropout > 0 else 0.0
 
 
 def reducer_of_train_flag(topK):
@@ -107,10 +114,12 @@ def build_engine(params, rank=0, world=1, device_id=None, stream=None):
     inc_types, inc_ent = params.includeEntityTypes == 1, params.includeEntity == 1
     if params.numEntityTypes > params.numFeatureTemplates:
         raise _ffi.KprnError(_ffi.E_ARG, "assert(numEntityTypes <= numFeatureTemplates) (OneModel.lua:107)")
-    if params.useDropout != 0:
-        raise _ffi.KprnError(_ffi.E_UNSUPPORTED, "dropout is off in every shipped config (config.sh:48) and is not built")
     if params.rnnType not in RNN_TYPES:
         raise _ffi.KprnError(_ffi.E_ARG, f"rnnType must be lstm, rnn or gru, got {params.rnnType}")
+    rate = dropout_rate(params)
+    if rate == 0 and params.useDropout != 0 and params.rnnType != "rnn":
+        # -useDropout 1 at rate 0 sets no option, and the refusal of the flag on lstm / gru stays what it was
+        raise _ffi.KprnError(_ffi.E_UNSUPPORTED, "-useDropout is built for -rnnType rnn only (the reference's lstm / gru modules ignore it)")
     if device_id is None:
         device_id = max(0, params.gpuid)
     eng = _ffi.Engine(params.entityTypeVocabSize, params.entityVocabSize, params.relationVocabSize,
@@ -119,10 +128,19 @@ def build_engine(params, rank=0, world=1, device_id=None, stream=None):
                       C_=LABEL_DIMENSION, reducer=getattr(params, "reducer", reducer_of_train_flag(params.topK)), K=params.K, rnn_type=RNN_TYPES[params.rnnType],
                       use_relu=params.useReLU, rnn_init=params.rnnInitialization,
                       device_id=device_id, rank=rank, world=world, param_init=params.paramInit, seed=params.seed, stream=stream)
-    if getattr(params, "deterministic", 0):
-        eng.set_option("deterministic", "1")   # (a training call on a pipeline without fixed-order sums then raises KprnError(E_UNSUPPORTED))
-    if params.initModel:
-        load_checkpoint(eng, params.initModel)  # OneModel.lua:277-282
+    try:
+        if rate > 0:
+            eng.set_option("dropout", repr(rate))   # (lstm / gru, where the reference ignores the flag: KprnError(E_UNSUPPORTED) from the library)
+        if getattr(params, "dropoutSeed", None) is not None:
+            # like the default seed (-seed + rank), the given one is offset by the rank: data-parallel replicas do not share masks
+            eng.set_option("dropout_seed", str((int(params.dropoutSeed) + rank) & 0xFFFFFFFFFFFFFFFF))
+        if getattr(params, "deterministic", 0):
+            eng.set_option("deterministic", "1")   # (a training call on a pipeline without fixed-order sums then raises KprnError(E_UNSUPPORTED))
+        if params.initModel:
+            load_checkpoint(eng, params.initModel)  # OneModel.lua:277-282
+    except Exception:
+        eng.close()   # (a refused option or an unreadable checkpoint: the handle and its device memory go now, not when the object is collected)
+        raise
     return eng
 
 

@@ -1,0 +1,129 @@
+"""The yardstick of the dropout tests: the engine's documented mask generator and the rnn graph with the masks applied, restated without any of the engine's code.
+
+1. A numpy Philox4x32-10 (Salmon et al., SC'11: multipliers 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 / 0xBB67AE85) and keep_mask, the addressing and
+   decision rule of include/kprn.h: key = (seed & 0xffffffff, seed >> 32), counter = (e / 4, n, t + 65536 l, draw), word e % 4; kept iff word >= thr,
+   thr = min(2^32 - 1, floor(p 2^32)) in double with p rounded to fp32 first; scale = (float)(1 / (1 - (double)p)).
+2. forward_backward: a torch-CPU float64 autograd restatement of the rnn graph (OneModel.lua:240-266 with -useDropout 1): gathers, per layer
+   rowmask (.) act((x (.) m s) Wi^T + bi + h Wh^T + bh) with rowmask from the UNDROPPED input row (MaskZero wraps the module, dropout included), last step,
+   nn.Linear head, LogSumExp over a pair's paths, sigmoid, BCE mean.  With all-ones masks and scale 1 it must equal oracle.forward_backward
+   (tests/test_dropout_host.py checks that)."""
+import numpy as np
+
+M0, M1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57)
+W0, W1 = 0x9E3779B9, 0xBB67AE85
+_LO = np.uint64(0xFFFFFFFF)
+_S32 = np.uint64(32)
+
+
+def philox4x32_10(c0, c1, c2, c3, k0, k1):
+    """counter words c0..c3 (broadcastable arrays or ints, < 2^32), key (k0, k1) ints -> four uint32 arrays"""
+    c0, c1, c2, c3 = (np.asarray(c, np.uint64) & _LO for c in np.broadcast_arrays(c0, c1, c2, c3))
+    k0, k1 = int(k0) & 0xFFFFFFFF, int(k1) & 0xFFFFFFFF
+    for _ in range(10):
+        p0, p1 = M0 * c0, M1 * c2   # (32 x 32 -> 64 bits: exact in uint64)
+        c0, c1, c2, c3 = (p1 >> _S32) ^ c1 ^ np.uint64(k0), p1 & _LO, (p0 >> _S32) ^ c3 ^ np.uint64(k1), p0 & _LO
+        k0, k1 = (k0 + W0) & 0xFFFFFFFF, (k1 + W1) & 0xFFFFFFFF
+    return tuple(c.astype(np.uint32) for c in (c0, c1, c2, c3))
+
+
+def threshold(p):
+    p = float(np.float32(p))
+    return min(2 ** 32 - 1, int(np.floor(p * 4294967296.0)))
+
+
+def scale(p):
+    return float(np.float32(1.0 / (1.0 - float(np.float32(p)))))
+
+
+def keep_mask(seed, draw, layer, T, N, Din, p):
+    """bool [T, N, Din]: element e of path n's step-t input row of layer `layer` (0-based) is kept in training forward number `draw`"""
+    Q = (Din + 3) // 4
+    q = np.arange(Q, dtype=np.uint64)[None, None, :]
+    n = np.arange(N, dtype=np.uint64)[None, :, None]
+    t = np.arange(T, dtype=np.uint64)[:, None, None] + np.uint64(65536 * layer)
+    words = philox4x32_10(q, n, t, np.uint64(draw), int(seed) & 0xFFFFFFFF, (int(seed) >> 32) & 0xFFFFFFFF)
+    r = np.stack(words, axis=-1).reshape(T, N, 4 * Q)[:, :, :Din]
+    return r.astype(np.uint64) >= np.uint64(threshold(p))
+
+
+def forward_backward(lay, cfg, theta, idx, labels, masks, s, class_id=1):
+    """lay: Oracle.layout(); cfg: the oracle's Cfg (rnn_type 1, F = 3, one type slot, reducer LogSumExp); theta float64 flat; idx [B, P, T, 3] 1-based;
+    masks: per layer a bool / 0-1 array [T, N, Din] (N = B P, path n = b P + p); s: the kept elements' factor -> loss, flat gradient (float64), probs [B]"""
+    import torch
+    assert cfg.rnn_type == 1 and cfg.F == 3 and cfg.numTypes == 1 and cfg.reducer == 2
+    th = torch.tensor(np.asarray(theta, np.float64), dtype=torch.float64, requires_grad=True)
+
+    def par(name):
+        off, shp = lay[name]
+        return th[off:off + int(np.prod(shp))].reshape(shp)
+
+    idx = np.asarray(idx)
+    B, P, T, _ = idx.shape
+    N = B * P
+    ids = torch.tensor(idx.reshape(N, T, 3).astype(np.int64)) - 1
+    x = torch.cat([par("type_emb")[ids[:, :, 0]], par("entity_emb")[ids[:, :, 1]], par("relation_emb")[ids[:, :, 2]]], dim=2)   # [N, T, D]
+    inp = x.permute(1, 0, 2)   # [T, N, D]
+    for l in range(cfg.L):
+        Wi, bi = par(f"rnn{l + 1}.i2h.weight"), par(f"rnn{l + 1}.i2h.bias")
+        Wh, bh = par(f"rnn{l + 1}.h2h.weight"), par(f"rnn{l + 1}.h2h.bias")
+        rowmask = (inp.detach() != 0).any(dim=2, keepdim=True).to(torch.float64)   # MaskZero: from the undropped row
+        m = torch.tensor(np.asarray(masks[l], np.float64)) * s
+        dropped = inp * m
+        h = torch.zeros(N, cfg.H, dtype=torch.float64)
+        hs = []
+        for t in range(T):
+            a = dropped[t] @ Wi.T + bi + h @ Wh.T + bh
+            h = rowmask[t] * (torch.relu(a) if cfg.use_relu == 1 else torch.tanh(a))
+            hs.append(h)
+        inp = torch.stack(hs)
+    S = inp[T - 1] @ par("out.weight").T + par("out.bias")   # [N, C]
+    pooled = torch.logsumexp(S.reshape(B, P, -1), dim=1)
+    prob = torch.sigmoid(pooled[:, class_id - 1])
+    y = torch.tensor(np.asarray(labels, np.float64))
+    loss = -(y * torch.log(prob) + (1 - y) * torch.log(1 - prob)).mean()
+    loss.backward()
+    return float(loss.detach()), th.grad.numpy().copy(), prob.detach().numpy().copy()
+
+
+def ones_masks(cfg, T, N):
+    D = cfg.dt + cfg.de + cfg.dr
+    return [np.ones((T, N, D if l == 0 else cfg.H)) for l in range(cfg.L)]
+
+
+class Case:
+    """the small shape of the dropout tests: parameters from Oracle.init_params rounded to fp32, inputs from synth.make_paths(seed=8) unless given"""
+
+    def __init__(self, relu, L, dims=(8, 24, 16, 48), pairs=37, P=3, T=6, Vt=6, Ve=300, Vr=9, idx=None, labels=None):
+        from kprn_amd import synth
+        from oracle.oracle import Oracle, make_cfg
+        dt, de, dr, H = dims
+        self.dims, self.relu, self.L, self.Vt, self.Ve, self.Vr = dims, relu, L, Vt, Ve, Vr
+        self.cfg = make_cfg(Vt=Vt, Ve=Ve, Vr=Vr, dt=dt, de=de, dr=dr, H=H, L=L, rnn_type=1, use_relu=relu)
+        self.oracle = Oracle(self.cfg, np.float64)
+        self.lay = self.oracle.layout()
+        self.theta = self.oracle.init_params(3, 0.35).astype(np.float32).astype(np.float64)
+        if idx is None:
+            idx, labels = synth.make_paths(pairs, P, T, Vt=Vt, Ve=Ve, Vr=Vr, seed=8)
+        self.idx, self.labels = idx, labels
+        self.B, self.P, self.T = idx.shape[:3]
+        self.N = self.B * self.P
+
+    def masks(self, seed, draw, p):
+        D = sum(self.dims[:3])
+        return [keep_mask(seed, draw, l, self.T, self.N, D if l == 0 else self.dims[3], p) for l in range(self.L)]
+
+    def reference(self, seed, draw, p):
+        """loss, flat gradient, probs of training forward `draw` at rate p (p = 0: no dropout)"""
+        if p == 0:
+            return forward_backward(self.lay, self.cfg, self.theta, self.idx, self.labels, ones_masks(self.cfg, self.T, self.N), 1.0)
+        return forward_backward(self.lay, self.cfg, self.theta, self.idx, self.labels, self.masks(seed, draw, p), scale(p))
+
+    def tensors(self, *flats):
+        for nm, (off, shp) in self.lay.items():
+            n = int(np.prod(shp))
+            yield (nm,) + tuple(np.asarray(f, np.float64)[off:off + n] for f in flats)
+
+
+def rel_inf(a, b):
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    return float(np.max(np.abs(a - b))) / max(1e-30, float(np.max(np.abs(b))))
