@@ -475,7 +475,7 @@ int kprn_profile_get(kprn_handle* h, kprn_prof_entry* out, int32_t cap, int32_t*
  *   "train_step_return" "loss" (default) | "drain": see kprn_train_step
  *   "inline_upload"   "side" (default): kprn_train_step uploads its minibatch on the upload stream, beside the previous step's backward, whenever the previous
  *                     call waited for its loss (every reader of the slot being refilled is then known to be done); "main": on the engine's stream
- *   "deterministic"   "0" (default) | "1": bit-reproducible training.  With "1" every float the engine hands back -- losses, kprn_get_grad / kprn_get_flat_grads,
+ *   "deterministic"   "0" (default) | "1" | "2": bit-reproducible training ("2": below).  With "1" every float the engine hands back -- losses, kprn_get_grad / kprn_get_flat_grads,
  *                     parameters, both optimiser state slots -- is a function of the inputs only, never of timing: the same sequence of calls with the same
  *                     inputs gives the same bits across repeats, handles, processes and whatever else runs on the device, for a fixed build, device model (CU
  *                     count) and fixed values of all other options (no promise across grid or tile sizes, option values or builds).  Covered: the fused fp32
@@ -486,6 +486,13 @@ int kprn_profile_get(kprn_handle* h, kprn_prof_entry* out, int32_t cap, int32_t*
  *                     pipeline -- when the call would run on the generic pipeline ("impl" "generic", any other shape), on rnn / gru, on the bf16 pipeline
  *                     (compute_dtype 1) or on a KPRN_DBG scatter route.  Scoring, ranking, explanation and parameter access are never refused; data-parallel
  *                     handles are accepted (the exchange sums in rank order).  "0" again makes the same handle train as before; with "0" nothing changes.
+ *                     "2": everything "1" covers runs exactly as under "1" (same kernels, same bits), and the generic fp32 pipeline trains under the same
+ *                     contract: rnn_type 0 (FastLSTM) and 1 (rnn, "dropout" included), compute_dtype 0, any D, H, L, "impl" "generic", every "persist_layers" /
+ *                     "small_tables" value, optimiser, batch form and entry point -- its split-K products, column sums, head, entity and table gradients store
+ *                     one slab of partials per workgroup or split, and a launch behind adds the slabs in index order.  Still KPRN_E_UNSUPPORTED under "2":
+ *                     rnn_type 2 (gru), compute_dtype 1 and any compute_dtype != 0 that would land on the generic pipeline, a generic-pipeline batch without
+ *                     the occurrence index or with an identical-prefix plan, and, where layer 0 takes the scatter route, a type / relation table of more than
+ *                     128 rows or a slice wider than 128 columns.  Any other value: KPRN_E_ARG.
  *   "dropout"         "0" (default) | a decimal rate in (0, 1): nn.Dropout on the step input of every rnn layer in training forwards (see kprn_host_dropout_keep).
  *                     Not a number or outside [0, 1): KPRN_E_ARG.  A rate > 0 on a handle with rnn_type != 1 (the reference's lstm / gru ignore the flag) or
  *                     compute_dtype != 0 is refused with KPRN_E_UNSUPPORTED when it is set.  With a rate > 0 layer 0's backward leaves the small-table identity

@@ -303,6 +303,12 @@ __global__ __launch_bounds__(256) void k_egrad_det(const float* __restrict__ DX,
                                                    int n_ent_blocks, int n_red_blocks, SlabReduce red, SmallGrad sg, DetEntity det) {
   entity_grad_body<2, true>(DX, key_sorted, pos_sorted, nsteps, N, T, D, dt, de, sentinel, gWe, n_ent_blocks, n_red_blocks, red, sg, 0, det.seg_part, det.sg_part);
 }
+// ... and for the generic pipeline's row-major dx (option "deterministic" = "2"; no passenger jobs there)
+__global__ __launch_bounds__(256) void k_egrad_det_rowmajor(const float* __restrict__ DX, const int32_t* __restrict__ key_sorted, const int32_t* __restrict__ pos_sorted,
+                                                            int64_t nsteps, int64_t N, int T, int D, int dt, int de, int sentinel, float* __restrict__ gWe,
+                                                            int n_ent_blocks, int n_red_blocks, SlabReduce red, SmallGrad sg, DetEntity det) {
+  entity_grad_body<0, true>(DX, key_sorted, pos_sorted, nsteps, N, T, D, dt, de, sentinel, gWe, n_ent_blocks, n_red_blocks, red, sg, 0, det.seg_part, det.sg_part);
+}
 
 // The launch behind k_egrad_det.  Workgroups [0, n_ent_blocks): a wave per segment, lane = column.  The segment that OPENS a run which goes on in the next
 // segment owns that row: row += (((own part + part of segment s + 1) + part of s + 2) + ...), one running fp32 sum in segment order over every segment the
@@ -392,7 +398,11 @@ void entity_grad(hipStream_t s, const float* DX, int frag_order, const int32_t* 
   static const int dbg = KPRN_DEV_ENV("KPRN_EGRAD_DBG") ? atoi(KPRN_DEV_ENV("KPRN_EGRAD_DBG")) : 0;   // (measurement: 1 no atomics, 2 no passenger work; 16 x workgroup order)
   const dim3 grid((unsigned)(n_ent + n_red + n_sg));
   if (det) {
-    KPRN_REQUIRE(frag_order == 2, KPRN_E_UNSUPPORTED, "deterministic entity gradient: the compact entity slice only");
+    KPRN_REQUIRE(frag_order == 2 || (frag_order == 0 && !red && !sg), KPRN_E_UNSUPPORTED,
+                 "deterministic entity gradient: the compact entity slice, or row-major dx without passenger jobs");
+    if (frag_order == 0)
+      hipLaunchKernelGGL(k_egrad_det_rowmajor, grid, dim3(256), 0, s, DX, key_sorted, pos_sorted, n_index, N, T, D, dt, de, Ve, gWe, n_ent, n_red, r, g, *det);
+    else
     hipLaunchKernelGGL(k_egrad_det, grid, dim3(256), 0, s, DX, key_sorted, pos_sorted, n_index, N, T, D, dt, de, Ve, gWe, n_ent, n_red, r, g, *det);
   } else
   if (frag_order == 1) hipLaunchKernelGGL(k_entity_grad<1>, grid, dim3(256), 0, s, DX, key_sorted, pos_sorted, n_index, N, T, D, dt, de, Ve, gWe, n_ent, n_red, r, g, dbg);

@@ -32,7 +32,9 @@ constexpr int TM = 128, TN = 128, TK = 32;
 constexpr int LDK = TK + 4;   // row stride of a [rows][k] tile (floats): 16-byte aligned, spreads the b128 fragment reads
 constexpr int TILE_F = TM * LDK;  // floats per operand tile (the larger of the two layouts)
 
-enum { EPI_STORE = 0, EPI_ACCUM = 1, EPI_LSTM = 2, EPI_RNN = 3 };
+// EPI_SLAB (option "deterministic" = "2"): a split-K partial leaves with plain stores in slab split_idx of a scratch [nsplit][M][ldc] that
+// C points to; kk::slab_join adds the slabs in split order.  An instantiation of its own: EPI_ACCUM and EPI_STORE keep their instruction streams.
+enum { EPI_STORE = 0, EPI_ACCUM = 1, EPI_LSTM = 2, EPI_RNN = 3, EPI_SLAB = 4 };
 
 struct TArgs {
   // C[M,N] (+)= A(M,K) B(K,N).  Layout 0: the operand is row-major over its m (n) index with k contiguous, ld = row stride;
@@ -173,7 +175,7 @@ __device__ __forceinline__ void frag_read(const float* __restrict__ T, int row_b
 template <int LA, int LB, int EPI, int NTW>
 __global__ __launch_bounds__(256, 2) void k_gemm_tiled(TArgs a) {
   constexpr int TNn = 32 * NTW;
-  constexpr bool TR = (EPI != EPI_ACCUM);   // result blocks transposed in the lanes (see the epilogue)
+  constexpr bool TR = (EPI != EPI_ACCUM && EPI != EPI_SLAB);   // result blocks transposed in the lanes (see the epilogue)
   extern __shared__ __attribute__((aligned(16))) float lds[];
   auto As = [&](int i) -> float* { return lds + i * (2 * TILE_F); };              // buffer i: A tile | B tile
   auto Bs = [&](int i) -> float* { return lds + i * (2 * TILE_F) + TILE_F; };
@@ -297,6 +299,22 @@ __global__ __launch_bounds__(256, 2) void k_gemm_tiled(TArgs a) {
           else *dst += acc[i][jn][r];
         }
       }
+  } else if constexpr (EPI == EPI_SLAB) {
+    // the += epilogue's layout (plain C/D, lane = column: a wave's store covers 64-byte row segments), every element of the tile stored, zeros included
+    float* const slab = a.C + split_idx * a.M * a.ldc;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int jn = 0; jn < NTW; ++jn) {
+        const int col = n0 + wn * (16 * NTW) + jn * 16 + arow;
+        if (col >= a.N) continue;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int64_t row = m0 + wm * 64 + i * 16 + ag * 4 + r;
+          if (row >= a.M) continue;
+          slab[row * a.ldc + col] = acc[i][jn][r];
+        }
+      }
   } else if constexpr (EPI == EPI_STORE) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -411,7 +429,7 @@ namespace gemm {
 
 // the tiled kernel takes a call when both operands are in one of its two layouts with 16-byte granularity; returns false otherwise
 bool run_tiled(hipStream_t s, const float* A, int64_t sAm, int64_t sAk, const float* B, int64_t sBk, int64_t sBn, float* C, int64_t ldc, int64_t M, int N,
-               int64_t K, bool accumulate, const float* bias, int split_k) {
+               int64_t K, bool accumulate, const float* bias, int split_k, DetScratch* det) {
   if (M < 256 || N < 64 || K < 16) return false;   // (tried from 192 rows, for the shipped rnn's dW products with M = H = 250: 0.55 -> 1.54 ms, two row tiles leave the split-K launch three quarters empty -- profiles/r05/bench_k_*)
   int LA, LB;
   int64_t lda, ldb;
@@ -440,12 +458,22 @@ bool run_tiled(hipStream_t s, const float* A, int64_t sAm, int64_t sAk, const fl
     const int64_t tiles = a.mtiles * (nt128 + nt64);
     const int64_t want = (3 * 256 + tiles - 1) / tiles;
     if (split_k > want) split_k = (int)std::max<int64_t>(1, want);
+    if (det) split_k = (int)std::max<int64_t>(1, std::min<int64_t>(split_k, DET_SLAB_FLOATS / (M * N)));   // (a function of the shape only)
   }
   int64_t kchunk = (K + split_k - 1) / split_k;
   kchunk = ((kchunk + TK - 1) / TK) * TK;
   split_k = (int)((K + kchunk - 1) / kchunk);
   a.kchunk = kchunk; a.use_atomic = split_k > 1 ? 1 : 0;
   KPRN_REQUIRE(!(split_k > 1 && !accumulate), KPRN_E_ARG, "gemm: split-K needs accumulate mode");
+  if (det && split_k > 1) {
+    // deterministic mode: the same tiles and K ranges, the partials into slabs [split_k][M][N]; whatever a split adds today it adds to its own slab
+    float* const slabs = kk::det_reserve(det, s, (int64_t)split_k * M * N);
+    a.C = slabs; a.ldc = N; a.use_atomic = 0;
+    if (nt128 > 0) { a.ntiles = nt128; a.n_begin = 0; launch_layouts<EPI_SLAB, 4>(s, a, LA, LB, split_k); }
+    if (nt64 > 0) { a.ntiles = nt64; a.n_begin = n_full * TN; launch_layouts<EPI_SLAB, 2>(s, a, LA, LB, split_k); }
+    kk::slab_join(s, slabs, split_k, M * N, M, N, C, ldc);
+    return true;
+  }
   if (nt128 > 0) {
     a.ntiles = nt128; a.n_begin = 0;
     if (accumulate) launch_layouts<EPI_ACCUM, 4>(s, a, LA, LB, split_k); else launch_layouts<EPI_STORE, 4>(s, a, LA, LB, split_k);

@@ -168,7 +168,10 @@ __global__ void k_add_bias(float* __restrict__ Y, const float* __restrict__ b, i
 }
 
 // out[c] += sum_r A[r][c]; block = 256 threads handles 256 rows x 64-col strip with LDS-free partials
-__global__ void k_colsum(const float* __restrict__ A, int64_t rows, int cols, int64_t ld, float* __restrict__ out, int rows_per_block, float* __restrict__ out2) {
+// DET (option "deterministic" = "2"; a kernel of its own, k_colsum_det): the workgroup's sums leave with plain stores in row blockIdx.x of
+// out = slab [gridDim.x][cols]; kk::slab_join adds the rows in workgroup order
+template <bool DET>
+__device__ __forceinline__ void colsum_body(const float* __restrict__ A, int64_t rows, int cols, int64_t ld, float* __restrict__ out, int rows_per_block, float* __restrict__ out2) {
   int c = blockIdx.y * 64 + (threadIdx.x & 63);
   int sub = threadIdx.x >> 6;  // 4 row-subgroups
   int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
@@ -191,9 +194,16 @@ __global__ void k_colsum(const float* __restrict__ A, int64_t rows, int cols, in
   __syncthreads();
   if (sub == 0 && c < cols) {
     float v = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
+    if constexpr (DET) { out[(int64_t)blockIdx.x * cols + c] = v; return; }
     unsafeAtomicAdd(out + c, v);
     if (out2) unsafeAtomicAdd(out2 + c, v);   // (a second vector that sees the same gradient: the rnn cell's h2h.bias next to i2h.bias)
   }
+}
+__global__ void k_colsum(const float* __restrict__ A, int64_t rows, int cols, int64_t ld, float* __restrict__ out, int rows_per_block, float* __restrict__ out2) {
+  colsum_body<false>(A, rows, cols, ld, out, rows_per_block, out2);
+}
+__global__ void k_colsum_det(const float* __restrict__ A, int64_t rows, int cols, int64_t ld, float* __restrict__ slab, int rows_per_block) {
+  colsum_body<true>(A, rows, cols, ld, slab, rows_per_block, nullptr);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -648,6 +658,9 @@ __global__ void k_sum_partials(const float* __restrict__ partial, int n, float* 
 }
 
 // nn.Linear(H,46) backward restricted to the selected column (OneModel.lua:275; Select at MyOptimizer.lua:126)
+// DET (option "deterministic" = "2"; instantiations of their own, here and in k_head_bwd_w): the workgroup's H sums and its bias sum leave with plain stores in
+// row blockIdx.x of gWout = slab [gridDim.x][H + 1] (gbout unused); kk::slab_join adds the rows in workgroup order
+template <bool DET = false>
 __global__ void k_head_bwd(const float* __restrict__ dS, const float* __restrict__ hT, const float* __restrict__ Wout, int64_t N, int H,
                            int cid, float* __restrict__ dH, float* __restrict__ gWout, float* __restrict__ gbout, int rows_per_block) {
   int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
@@ -660,12 +673,14 @@ __global__ void k_head_bwd(const float* __restrict__ dS, const float* __restrict
       acc += d * hT[n * H + j];
       if (dH) dH[n * H + j] = d * w;
     }
-    unsafeAtomicAdd(gWout + (int64_t)cid * H + j, acc);
+    if constexpr (DET) gWout[(int64_t)blockIdx.x * (H + 1) + j] = acc;
+    else unsafeAtomicAdd(gWout + (int64_t)cid * H + j, acc);
   }
   if (threadIdx.x == 0) {
     float acc = 0.f;
     for (int64_t n = r0; n < r1; ++n) acc += dS[n];
-    unsafeAtomicAdd(gbout + cid, acc);
+    if constexpr (DET) gWout[(int64_t)blockIdx.x * (H + 1) + H] = acc;
+    else unsafeAtomicAdd(gbout + cid, acc);
   }
 }
 
@@ -673,7 +688,7 @@ __global__ void k_head_bwd(const float* __restrict__ dS, const float* __restrict
 // columns lane + 64 g; the waves' sums meet in LDS and leave as H atomics per workgroup.  (k_head_bwd above: 64 rows per workgroup = 1 024 atomics
 // on each of the H addresses of the selected row at 65 536 paths -- same-address atomics serialise in L2 -- and one load in flight per thread:
 // 0.08-0.09 ms for 100 MB on configs[3] / the shipped shape.)  Loads are unconditional (idle lanes re-read column H - 1 and drop the sum).
-template <int NG, bool HAS_DH>
+template <int NG, bool HAS_DH, bool DET = false>
 __global__ __launch_bounds__(256) void k_head_bwd_w(const float* __restrict__ dS, const float* __restrict__ hT, const float* __restrict__ Wout, int64_t N, int H,
                                                     int cid, float* __restrict__ dH, float* __restrict__ gWout, float* __restrict__ gbout, int rows_per_block) {
   __shared__ float red[4][NG * 64 + 1];
@@ -704,6 +719,12 @@ __global__ __launch_bounds__(256) void k_head_bwd_w(const float* __restrict__ dS
   for (int g = 0; g < NG; ++g) red[wave][g * 64 + lane] = acc[g];
   if (lane == 0) red[wave][NG * 64] = bsum;
   __syncthreads();
+  if constexpr (DET) {
+    float* const slab = gWout + (int64_t)blockIdx.x * (H + 1);
+    for (int j = threadIdx.x; j < H; j += 256) slab[j] = red[0][j] + red[1][j] + red[2][j] + red[3][j];
+    if (threadIdx.x == 0) slab[H] = red[0][NG * 64] + red[1][NG * 64] + red[2][NG * 64] + red[3][NG * 64];
+    return;
+  }
   for (int j = threadIdx.x; j < H; j += 256) unsafeAtomicAdd(gWout + (int64_t)cid * H + j, red[0][j] + red[1][j] + red[2][j] + red[3][j]);
   if (threadIdx.x == 0) unsafeAtomicAdd(gbout + cid, red[0][NG * 64] + red[1][NG * 64] + red[2][NG * 64] + red[3][NG * 64]);
 }
@@ -1151,17 +1172,61 @@ void add_into(hipStream_t s, float* dst, const float* src, int64_t n) {
   hipLaunchKernelGGL(k_add_into, dim3(nblocks(n)), dim3(TPB), 0, s, dst, src, n);
 }
 
+// ---- option "deterministic" = "2" (DESIGN.md 3.11): the join behind every slab producer of the generic backward ----
+// dst[r][c] += ((slab 0 + slab 1) + slab 2) + ... : one running fp32 sum over the slabs in slab order, one owner thread per element (DEPTH slabs requested at a
+// time, from clamped addresses, added in order)
+__global__ __launch_bounds__(256) void k_slab_join(const float* __restrict__ slabs, int nslab, int64_t stride, int64_t n, int cols, float* __restrict__ dst,
+                                                   int64_t ldc, float* __restrict__ dst2) {
+  constexpr int DEPTH = 16;
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const float* __restrict__ src = slabs + i;
+  float acc = 0.f;
+  for (int w0 = 0; w0 < nslab; w0 += DEPTH) {
+    float x[DEPTH];
+#pragma unroll
+    for (int u = 0; u < DEPTH; ++u) x[u] = src[(int64_t)(w0 + u < nslab ? w0 + u : nslab - 1) * stride];
+#pragma unroll
+    for (int u = 0; u < DEPTH; ++u) if (w0 + u < nslab) acc += x[u];
+  }
+  const int64_t r = i / cols, o = r * ldc + (i - r * cols);
+  dst[o] += acc;
+  if (dst2) dst2[o] += acc;
+}
+void slab_join(hipStream_t s, const float* slabs, int nslab, int64_t stride, int64_t rows, int cols, float* dst, int64_t ldc, float* dst2) {
+  const int64_t n = rows * cols;
+  if (n <= 0 || nslab <= 0) return;
+  hipLaunchKernelGGL(k_slab_join, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, slabs, nslab, stride, n, cols, dst, ldc, dst2);
+  CHECK_LAUNCH();
+}
+float* det_reserve(DetScratch* det, hipStream_t s, int64_t n) {
+  if (n > det->cap) {   // (grow-only: what is queued may still read the old block)
+    HIP_TRY(hipStreamSynchronize(s));
+    if (det->p) { hipFree(det->p); det->p = nullptr; det->cap = 0; }
+    HIP_TRY(kprn_dev_malloc((void**)&det->p, (size_t)(n + 16) * sizeof(float)));
+    det->cap = n;
+  }
+  return det->p;
+}
+
 void add_bias_rows(hipStream_t s, float* Y, const float* b, int64_t rows, int cols) {
   if (rows <= 0) return;
   hipLaunchKernelGGL(k_add_bias, dim3(nblocks(rows * cols)), dim3(TPB), 0, s, Y, b, rows * cols, cols);
   CHECK_LAUNCH();
 }
 
-void col_sum_add(hipStream_t s, const float* A, int64_t rows, int cols, float* out, int64_t ld, float* out2) {
+void col_sum_add(hipStream_t s, const float* A, int64_t rows, int cols, float* out, int64_t ld, float* out2, DetScratch* det) {
   if (rows <= 0) return;
   if (ld <= 0) ld = cols;
   const int rpb = 512;
   dim3 grid((unsigned)((rows + rpb - 1) / rpb), (unsigned)((cols + 63) / 64));
+  if (det) {   // one pass still feeds both vectors: the join adds the same sum to out and out2
+    float* const slab = det_reserve(det, s, (int64_t)grid.x * cols);
+    hipLaunchKernelGGL(k_colsum_det, grid, dim3(256), 0, s, A, rows, cols, ld, slab, rpb);
+    CHECK_LAUNCH();
+    slab_join(s, slab, (int)grid.x, cols, 1, cols, out, cols, out2);
+    return;
+  }
   hipLaunchKernelGGL(k_colsum, grid, dim3(256), 0, s, A, rows, cols, ld, out, rpb, out2);
   CHECK_LAUNCH();
 }
@@ -1249,8 +1314,32 @@ void sum_partials(hipStream_t s, const float* partial, int n, float* out, int ac
 
 
 
-void head_bwd(hipStream_t s, const float* dS, const float* hT, const float* Wout, int64_t N, int H, int cid, float* dH, float* gWout, float* gbout) {
+void head_bwd(hipStream_t s, const float* dS, const float* hT, const float* Wout, int64_t N, int H, int cid, float* dH, float* gWout, float* gbout, DetScratch* det) {
   if (N <= 0) return;
+  if (det) {   // the same two kernels' det forms (same grids, same sums inside a workgroup), slab [workgroup][H + 1], then the join: the row, then the bias
+    const bool wide = H <= 512 && N >= 4096;
+    const int rpb = wide ? 256 : 64;
+    const dim3 grid((unsigned)((N + rpb - 1) / rpb));
+    float* const slab = det_reserve(det, s, (int64_t)grid.x * (H + 1));
+    float* const nogb = nullptr;
+    if (wide) {
+      const int ng = (H + 63) / 64;
+#define KPRN_HBD(NG)                                                                                                                        \
+    do {                                                                                                                                   \
+      if (dH) hipLaunchKernelGGL((k_head_bwd_w<NG, true, true>), grid, dim3(256), 0, s, dS, hT, Wout, N, H, cid, dH, slab, nogb, rpb);      \
+      else hipLaunchKernelGGL((k_head_bwd_w<NG, false, true>), grid, dim3(256), 0, s, dS, hT, Wout, N, H, cid, dH, slab, nogb, rpb);        \
+    } while (0)
+      if (ng <= 1) KPRN_HBD(1); else if (ng == 2) KPRN_HBD(2); else if (ng == 3) KPRN_HBD(3); else if (ng == 4) KPRN_HBD(4);
+      else if (ng <= 6) KPRN_HBD(6); else KPRN_HBD(8);
+#undef KPRN_HBD
+    } else {
+      hipLaunchKernelGGL(k_head_bwd<true>, grid, dim3(H >= 256 ? 256 : (H > 64 ? 128 : 64)), 0, s, dS, hT, Wout, N, H, cid, dH, slab, nogb, rpb);
+    }
+    CHECK_LAUNCH();
+    slab_join(s, slab, (int)grid.x, H + 1, 1, H, gWout + (int64_t)cid * H, H);
+    slab_join(s, slab + H, (int)grid.x, H + 1, 1, 1, gbout + cid, 1);
+    return;
+  }
   if (H <= 512 && N >= 4096) {   // the wave-per-row form (below that the 64-row workgroups of the plain kernel fill more of the chip)
     const int rpb = 256;
     const dim3 grid((unsigned)((N + rpb - 1) / rpb));
@@ -1267,7 +1356,7 @@ void head_bwd(hipStream_t s, const float* dS, const float* hT, const float* Wout
     return;
   }
   const int rpb = 64;
-  hipLaunchKernelGGL(k_head_bwd, dim3((unsigned)((N + rpb - 1) / rpb)), dim3(H >= 256 ? 256 : (H > 64 ? 128 : 64)), 0, s, dS, hT, Wout, N, H, cid,
+  hipLaunchKernelGGL(k_head_bwd<false>, dim3((unsigned)((N + rpb - 1) / rpb)), dim3(H >= 256 ? 256 : (H > 64 ? 128 : 64)), 0, s, dS, hT, Wout, N, H, cid,
                      dH, gWout, gbout, rpb);
   CHECK_LAUNCH();
 }
@@ -1391,7 +1480,9 @@ __global__ __launch_bounds__(256) void k_table_grad_lds(const int32_t* __restric
 // wave w owns the 16-column blocks w and w + 4 and keeps one accumulator tile per (row tile, column block).  Lane (k, n) loads its B
 // element dX[pos + k][16 cb + n] and the id of position pos + k (its A element for row tile rt is [id == 16 rt + n]); a row tile none of
 // the four ids falls into is skipped (wave-uniform).  No LDS atomics (0.35 of 0.55 ms on configs[3]), no 16 compare-selects per element.
-template <int RT>
+// DET (option "deterministic" = "2"; instantiations of their own): the workgroup's [V][dcols] block leaves with plain stores, zeros included, in block
+// blockIdx.x of gW = slab [gridDim.x][V][dcols]; kk::slab_join adds the blocks in workgroup order
+template <int RT, bool DET = false>
 __global__ __launch_bounds__(256) void k_table_grad_mfma(const int32_t* __restrict__ idx, int64_t N, int T, int F, int idcol, int slots,
                                                           const float* __restrict__ dX, int D, int col0, int dcols, int V, float* __restrict__ gW,
                                                           int pos_per_block) {
@@ -1455,20 +1546,37 @@ __global__ __launch_bounds__(256) void k_table_grad_mfma(const int32_t* __restri
     for (int i = 0; i < 4; ++i) {
       const int v = 16 * r + 4 * kk + i;
       if (v < V) {
-        if (has_a && acc[r][0][i] != 0.f) unsafeAtomicAdd(gW + (int64_t)v * dcols + c_a, acc[r][0][i]);
-        if (has_b && acc[r][1][i] != 0.f) unsafeAtomicAdd(gW + (int64_t)v * dcols + c_b, acc[r][1][i]);
+        if constexpr (DET) {
+          float* const blk = gW + (int64_t)blockIdx.x * V * dcols;
+          if (has_a) blk[(int64_t)v * dcols + c_a] = acc[r][0][i];
+          if (has_b) blk[(int64_t)v * dcols + c_b] = acc[r][1][i];
+        } else {
+          if (has_a && acc[r][0][i] != 0.f) unsafeAtomicAdd(gW + (int64_t)v * dcols + c_a, acc[r][0][i]);
+          if (has_b && acc[r][1][i] != 0.f) unsafeAtomicAdd(gW + (int64_t)v * dcols + c_b, acc[r][1][i]);
+        }
       }
     }
 }
 
 static bool table_grad_mfma(hipStream_t s, const int32_t* idx, int64_t N, int T, int F, int idcol, int slots, const float* dX, int D, int col0, int dcols,
-                            int V, float* gW) {
+                            int V, float* gW, DetScratch* det = nullptr) {
   if (dcols <= 0 || dcols > 128 || V <= 0 || V > 128) return false;
   static const int ppb_env = KPRN_DEV_ENV("KPRN_TABLE_GRAD_PPB") ? atoi(KPRN_DEV_ENV("KPRN_TABLE_GRAD_PPB")) : 0;   // (measurement)
   const int ppb = ppb_env > 0 ? ppb_env : 512;   // (round 4, after the loads went unconditional: 512 beats 256 on configs[3] 0.175 : 0.198 ms, shipped 0.147 : 0.198, D = 192
                                                  //  0.106 : 0.113 -- half the workgroups = half the epilogue atomics on the same table rows; 1 024 loses parallelism: 0.253)
   const int64_t total = N * T;
   const dim3 grid((unsigned)((total + ppb - 1) / ppb));
+  if (det) {
+    float* const slab = det_reserve(det, s, (int64_t)grid.x * V * dcols);
+#define KPRN_TGD(RT_) hipLaunchKernelGGL((k_table_grad_mfma<RT_, true>), grid, dim3(256), 0, s, idx, N, T, F, idcol, slots, dX, D, col0, dcols, V, slab, ppb)
+    if (V <= 16) KPRN_TGD(1);
+    else if (V <= 32) KPRN_TGD(2);
+    else if (V <= 64) KPRN_TGD(4);
+    else KPRN_TGD(8);
+#undef KPRN_TGD
+    slab_join(s, slab, (int)grid.x, (int64_t)V * dcols, 1, V * dcols, gW, (int64_t)V * dcols);
+    return true;
+  }
 #define KPRN_TG(RT_) hipLaunchKernelGGL(k_table_grad_mfma<RT_>, grid, dim3(256), 0, s, idx, N, T, F, idcol, slots, dX, D, col0, dcols, V, gW, ppb)
   if (V <= 16) KPRN_TG(1);
   else if (V <= 32) KPRN_TG(2);
@@ -1578,8 +1686,10 @@ void small_tables_finish(hipStream_t s, const float* Ct, int ns, int GH, int Din
   HIP_TRY(hipGetLastError());
 }
 
+bool embed_scatter_det_ok(int dt, int dr, int Vt, int Vr) { return (dt == 0 || (dt <= 128 && Vt >= 1 && Vt <= 128)) && (dr == 0 || (dr <= 128 && Vr >= 1 && Vr <= 128)); }
+
 void embed_scatter(hipStream_t s, const int32_t* idx, int64_t N, int T, int F, int nT, const float* dX, int dt, int de, int dr, int Vt, int Vr,
-                   float* gWt, float* gWe, float* gWr, bool skip_entity) {
+                   float* gWt, float* gWe, float* gWr, bool skip_entity, DetScratch* det) {
   if (N <= 0) return;
   // tables that fit LDS (every type / relation table of the named configs): one wave per position, LDS accumulators (k_table_grad_lds);
   // KPRN_TABLE_GRAD=old keeps the 16-register one-hot kernel for tiny tables and the element-indexed scatter for the rest
@@ -1589,6 +1699,14 @@ void embed_scatter(hipStream_t s, const int32_t* idx, int64_t N, int T, int F, i
   // KPRN_TABLE_GRAD: mfma (default) = the one-hot product on the matrix cores for tables up to 128 x 128; lds = LDS accumulators above 16 rows
   // (0.54 ms on configs[3], 0.35 of it ds_add_f32) + the 16-register one-hot kernel below; old = that kernel + the element-indexed scatter
   static const bool lds_path = KPRN_DEV_ENV("KPRN_TABLE_GRAD") && strcmp(KPRN_DEV_ENV("KPRN_TABLE_GRAD"), "lds") == 0;
+  if (det) {   // deterministic mode: the one-hot products' det forms and nothing else (kprn_api.hip det_check refuses the other shapes before anything is launched)
+    KPRN_REQUIRE(!old_path && !lds_path && skip_entity && embed_scatter_det_ok(dt, dr, Vt, Vr), KPRN_E_UNSUPPORTED,
+                 "deterministic: the embedding scatter has a deterministic form for type / relation tables of at most 128 rows x 128 columns behind the occurrence index only");
+    if (dt > 0) table_grad_mfma(s, idx, N, T, F, F - nT - 2, nT, dX, D_, 0, dt, Vt, gWt, det);
+    if (dr > 0) table_grad_mfma(s, idx, N, T, F, F - 1, 1, dX, D_, dt + de, dr, Vr, gWr, det);
+    CHECK_LAUNCH();
+    return;
+  }
   if (!old_path && !lds_path) {
     if (dt > 0) type_small = table_grad_mfma(s, idx, N, T, F, F - nT - 2, nT, dX, D_, 0, dt, Vt, gWt);
     if (dr > 0) rel_small = table_grad_mfma(s, idx, N, T, F, F - 1, 1, dX, D_, dt + de, dr, Vr, gWr);

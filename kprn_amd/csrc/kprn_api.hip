@@ -602,6 +602,26 @@ static int small_tables_ns(const kprn_handle* h, const kprn_batch* b) {
                   b->F >= 3;
   return ok ? ns : 0;
 }
+// the generic pipeline's entity gradient from row-major dx over the occurrence index; option "deterministic" = "2": the partial sums of runs that straddle
+// 64-position segments leave with plain stores and the launch behind adds them in segment order, as "1" does for the fused path's compact slice
+static void entity_grad_rowmajor(kprn_handle* h, const kprn_batch* b, const float* dx, int D, int dt) {
+  const kprn_config& c = h->cfg;
+  if (h->deterministic != 2) {
+    bidx::entity_grad(h->stream, dx, /*frag_order=*/0, b->key_sorted, b->pos_sorted, b->n_index, b->N, b->T, D, dt, c.de, c.Ve, h->g_We);
+    return;
+  }
+  const int64_t need = (b->n_index + 63) / 64 * 2 * c.de;
+  if (need > h->det_seg_cap) {
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    dfree(h->det_seg);
+    h->det_seg = dalloc<float>(need);
+    h->det_seg_cap = need;
+  }
+  const bidx::DetEntity de_{h->det_seg, nullptr};
+  bidx::entity_grad(h->stream, dx, /*frag_order=*/0, b->key_sorted, b->pos_sorted, b->n_index, b->N, b->T, D, dt, c.de, c.Ve, h->g_We, nullptr, nullptr, &de_);
+  bidx::entity_grad_tail(h->stream, b->key_sorted, b->n_index, c.de, c.Ve, h->g_We, de_, nullptr);
+}
+
 static void backward_layer0_small_tables(kprn_handle* h, const kprn_batch* b, int ns, int GH, int split, bool bf) {
   const kprn_config& c = h->cfg;
   Workspace& w = h->ws;
@@ -621,7 +641,7 @@ static void backward_layer0_small_tables(kprn_handle* h, const kprn_batch* b, in
     ProfScope ps(h, "gemm_bwd_dw_merged");   // Ct [GH][ns + de] = dA^T [S | x_e]
     kk::onehot_cols(s, b->idx, N, T, b->F, c.Vr, c.Vt, w.X, D, c.dt - ns, ns);
     HIP_TRY(hipMemsetAsync(h->st_ctmp, 0, (size_t)GH * NZ * sizeof(float), s));
-    gemm::run(s, w.dA, 1, GH, w.X + (c.dt - ns), D, 1, h->st_ctmp, NZ, GH, NZ, TN, true, nullptr, split, bf);
+    gemm::run(s, w.dA, 1, GH, w.X + (c.dt - ns), D, 1, h->st_ctmp, NZ, GH, NZ, TN, true, nullptr, split, bf, false, h->deterministic == 2 ? &h->det_slab : nullptr);
   }
   {
     ProfScope ps(h, "gemm_i2g_bwd_dx_e");    // dx_e [T N][de] = dA W_i2g[:, entity columns], compact
@@ -634,7 +654,7 @@ static void backward_layer0_small_tables(kprn_handle* h, const kprn_batch* b, in
   }
   {
     ProfScope ps(h, "entity_grad");
-    bidx::entity_grad(s, w.dIn, /*frag_order=*/0, b->key_sorted, b->pos_sorted, b->n_index, N, T, c.de, 0, c.de, c.Ve, h->g_We);
+    entity_grad_rowmajor(h, b, w.dIn, c.de, 0);
   }
 }
 
@@ -659,10 +679,13 @@ static void backward_generic(kprn_handle* h, const kprn_batch* b, int cid) {
   hipStream_t s = h->stream;
   float* gd = h->g_dense;
   const int st_ns = small_tables_ns(h, b);   // > 0: layer 0's input gradients through the small-table identity
+  // option "deterministic" = "2" (FastLSTM and rnn cells; det_check has refused the rest): every join of partial sums below takes its slab form -- the producer
+  // plain-stores one slab per workgroup or K split into det's scratch, kk::slab_join behind it adds the slabs in index order
+  DetScratch* const det = (h->deterministic == 2 && c.rnn_type != 2) ? &h->det_slab : nullptr;
   {
     ProfScope ps(h, "head_bwd");
     const float* hT = w.Hs + ((int64_t)(L - 1) * T + (T - 1)) * N * H;
-    kk::head_bwd(s, w.dS, hT, h->dense + h->off_outW, N, H, cid, w.dH, gd + h->off_outW, gd + h->off_outb);
+    kk::head_bwd(s, w.dS, hT, h->dense + h->off_outW, N, H, cid, w.dH, gd + h->off_outW, gd + h->off_outb, det);
   }
   HIP_TRY(hipMemsetAsync(w.dC, 0, (size_t)N * H * sizeof(float), s));
   const int split = (int)std::min<int64_t>(1024, std::max<int64_t>(1, (T * N) / 2048));
@@ -758,8 +781,9 @@ static void backward_generic(kprn_handle* h, const kprn_batch* b, int cid) {
       if (bptt1) {
         // the cell backward of all T steps + the recurrent gradient in ONE persistent launch (layer_f32_persist.hip k_bptt): dh never leaves the CU
         ProfScope ps(h, "rnn_layer_bwd");
-        lp32::bptt_layer(s, 1, nullptr, nullptr, hs, mask, has_up ? w.dIn : w.dH, has_up, Wo, lp_wot_buffer(h, H, H), w.dA, N, T, H, relu, nullptr, gd + h->layer[l].bi,
-                         gd + h->layer[l].bo);
+        // (det: no bias sums inside the launch -- its workgroups join them with atomics; the column sum over dA below takes them)
+        lp32::bptt_layer(s, 1, nullptr, nullptr, hs, mask, has_up ? w.dIn : w.dH, has_up, Wo, lp_wot_buffer(h, H, H), w.dA, N, T, H, relu, nullptr,
+                         det ? nullptr : gd + h->layer[l].bi, det ? nullptr : gd + h->layer[l].bo);
       } else if (has_up) HIP_TRY(hipMemsetAsync(w.dH, 0, (size_t)N * H * sizeof(float), s));
       for (int t = T - 1; t >= 0 && !bptt1; --t) {
         float* dA_t = w.dA + (int64_t)t * N * H;
@@ -775,11 +799,11 @@ static void backward_generic(kprn_handle* h, const kprn_batch* b, int cid) {
       }
       if (T > 1) {
         ProfScope ps(h, "gemm_o2g_bwd_dw");
-        gemm::run(s, w.dA + (int64_t)N * H, 1, H, hs, H, 1, gd + h->layer[l].Wo, H, H, H, (int64_t)(T - 1) * N, true, nullptr, split, bf);
+        gemm::run(s, w.dA + (int64_t)N * H, 1, H, hs, H, 1, gd + h->layer[l].Wo, H, H, H, (int64_t)(T - 1) * N, true, nullptr, split, bf, false, det);
       }
-      if (!(bptt1 && lp32::bptt_sums_bias(1, H))) {   // (the persistent BPTT launch forms the sums itself)
+      if (det || !(bptt1 && lp32::bptt_sums_bias(1, H))) {   // (the persistent BPTT launch forms the sums itself)
         ProfScope ps(h, "bias_colsum");  // i2h.bias and h2h.bias see the same gradient (both are added to every pre-activation)
-        kk::col_sum_add(s, w.dA, (int64_t)T * N, H, gd + h->layer[l].bi, 0, gd + h->layer[l].bo);   // (one pass over dA for both)
+        kk::col_sum_add(s, w.dA, (int64_t)T * N, H, gd + h->layer[l].bi, 0, gd + h->layer[l].bo, det);   // (one pass over dA for both)
       }
       if (l == 0 && st_ns > 0) {
         backward_layer0_small_tables(h, b, st_ns, H, split, bf);
@@ -787,7 +811,7 @@ static void backward_generic(kprn_handle* h, const kprn_batch* b, int cid) {
       }
       {
         ProfScope ps(h, "gemm_i2g_bwd_dw");
-        gemm::run(s, w.dA, 1, H, in, Din, 1, gd + h->layer[l].Wi, Din, H, Din, (int64_t)T * N, true, nullptr, split, bf);
+        gemm::run(s, w.dA, 1, H, in, Din, 1, gd + h->layer[l].Wi, Din, H, Din, (int64_t)T * N, true, nullptr, split, bf, false, det);
       }
       {
         ProfScope ps(h, "gemm_i2g_bwd_dx");
@@ -814,7 +838,8 @@ static void backward_generic(kprn_handle* h, const kprn_batch* b, int cid) {
     if (bptt0) {
       // the cell backward of all T steps + the recurrent gradient in ONE persistent launch (layer_f32_persist.hip k_bptt): dh / dc never leave the CU
       ProfScope ps(h, "lstm_layer_bwd");
-      lp32::bptt_layer(s, 0, act, cs, nullptr, nullptr, has_up ? w.dIn : w.dH, has_up, Wo, lp_wot_buffer(h, H, 4 * H), w.dA, N, T, H, 0, nullptr, gd + h->layer[l].bi);
+      lp32::bptt_layer(s, 0, act, cs, nullptr, nullptr, has_up ? w.dIn : w.dH, has_up, Wo, lp_wot_buffer(h, H, 4 * H), w.dA, N, T, H, 0, nullptr,
+                       det ? nullptr : gd + h->layer[l].bi);   // (det: the column sum over dA below takes the bias)
     } else if (has_up) {
       HIP_TRY(hipMemsetAsync(w.dH, 0, (size_t)N * H * sizeof(float), s));
       HIP_TRY(hipMemsetAsync(w.dC, 0, (size_t)N * H * sizeof(float), s));
@@ -834,11 +859,11 @@ static void backward_generic(kprn_handle* h, const kprn_batch* b, int cid) {
     if (T > 1) {
       ProfScope ps(h, "gemm_o2g_bwd_dw");
       // gWo[4H,H] += dA[1..T-1]^T * h[0..T-2]
-      gemm::run(s, w.dA + (int64_t)N * 4 * H, 1, 4 * H, hs, H, 1, gd + h->layer[l].Wo, H, 4 * H, H, (int64_t)(T - 1) * N, true, nullptr, split, bf);
+      gemm::run(s, w.dA + (int64_t)N * 4 * H, 1, 4 * H, hs, H, 1, gd + h->layer[l].Wo, H, 4 * H, H, (int64_t)(T - 1) * N, true, nullptr, split, bf, false, det);
     }
-    if (!(bptt0 && lp32::bptt_sums_bias(0, H))) {   // (the persistent BPTT launch forms the sums itself)
+    if (det || !(bptt0 && lp32::bptt_sums_bias(0, H))) {   // (the persistent BPTT launch forms the sums itself)
       ProfScope ps(h, "bias_colsum");
-      kk::col_sum_add(s, w.dA, (int64_t)T * N, 4 * H, gd + h->layer[l].bi);
+      kk::col_sum_add(s, w.dA, (int64_t)T * N, 4 * H, gd + h->layer[l].bi, 0, nullptr, det);
     }
     if (l == 0 && st_ns > 0) {
       backward_layer0_small_tables(h, b, st_ns, 4 * H, split, bf);
@@ -846,7 +871,7 @@ static void backward_generic(kprn_handle* h, const kprn_batch* b, int cid) {
     }
     {
       ProfScope ps(h, "gemm_i2g_bwd_dw");
-      gemm::run(s, w.dA, 1, 4 * H, in, Din, 1, gd + h->layer[l].Wi, Din, 4 * H, Din, (int64_t)T * N, true, nullptr, split, bf);
+      gemm::run(s, w.dA, 1, 4 * H, in, Din, 1, gd + h->layer[l].Wi, Din, 4 * H, Din, (int64_t)T * N, true, nullptr, split, bf, false, det);
     }
     {
       ProfScope ps(h, "gemm_i2g_bwd_dx");
@@ -856,11 +881,11 @@ static void backward_generic(kprn_handle* h, const kprn_batch* b, int cid) {
   {
     ProfScope ps(h, "embed_scatter");
     const bool have_index = b->key_sorted != nullptr && !b->tile_k;  // (an index built for a prefix plan lives in the reordered path space)
-    kk::embed_scatter(s, b->idx, N, T, b->F, c.num_types, w.dIn, c.dt, c.de, c.dr, c.Vt, c.Vr, gd + h->off_Wt, h->g_We, gd + h->off_Wr, have_index);
+    kk::embed_scatter(s, b->idx, N, T, b->F, c.num_types, w.dIn, c.dt, c.de, c.dr, c.Vt, c.Vr, gd + h->off_Wt, h->g_We, gd + h->off_Wr, have_index, det);
   }
   if (b->key_sorted != nullptr && !b->tile_k) {
     ProfScope ps(h, "entity_grad");
-    bidx::entity_grad(s, w.dIn, /*frag_order=*/0, b->key_sorted, b->pos_sorted, b->n_index, N, T, D, c.dt, c.de, c.Ve, h->g_We);
+    entity_grad_rowmajor(h, b, w.dIn, D, c.dt);
   }
 }
 
@@ -871,26 +896,54 @@ static void form_loss(kprn_handle* h) {
   h->loss_pending = 0;
 }
 
-// Option "deterministic": a training call goes on only where every float sum of the step has a fixed order -- the fused fp32 path (D = H = 64, FastLSTM, compute_dtype
-// 0 / 2 / 3) on its index routes.  Everything else is refused HERE, before anything is launched or any state is written.
-static void det_check(const kprn_handle* h, int T) {
+// Option "deterministic": a training call goes on only where every float sum of the step has a fixed order.  "1": the fused fp32 path (D = H = 64,
+// FastLSTM, compute_dtype 0 / 2 / 3) on its index routes.  "2": that path exactly as under "1", and the generic fp32 pipeline (FastLSTM and rnn cells, compute_dtype
+// 0) with the slab forms of its joins.  Everything else is refused HERE, before anything is launched or any state is written.  b == null (kprn_train_step, before its
+// feed): the handle's part of the check; the batch's part follows in kprn_train_step_batch.
+static const char* det_fused_why(const kprn_handle* h) {
+  const kprn_config& c = h->cfg;
+  if (!(c.num_types == 1 && (c.dt % 16) == 0 && (c.de % 16) == 0 && (c.dr % 16) == 0 && c.Vt <= 16 && c.Vr <= 16))
+    return "the fused path's general embedding scatter (more than one type slot, slices not in 16-column blocks, or a type / relation table of more than 16 rows)";
+  if (kprn_dbg_mask() & (1 | 8 | 16)) return "a KPRN_DBG route of the fused path (scatter kernels with atomics)";
+  return nullptr;
+}
+static void det_check(const kprn_handle* h, int T, const kprn_batch* b = nullptr) {
   if (!h->deterministic) return;
   const kprn_config& c = h->cfg;
   const char* why = nullptr;
-  if (h->impl != 0) why = "the generic pipeline (impl = generic: split-K atomics in its weight-gradient products)";
-  else if (c.rnn_type != 0) why = "the rnn / gru pipeline";
-  else if (c.compute_dtype == 1) why = "the bf16 pipeline (compute_dtype 1)";
-  else if (!fused::fwd_supported(h, T) || !fused::bwd_supported(h, T) || c.dt == 0 || c.de == 0)
-    why = "the generic pipeline (this shape is not the fused D = H = 64 path's: wide persistent layers / split-K products)";
-  else if (!(c.num_types == 1 && (c.dt % 16) == 0 && (c.de % 16) == 0 && (c.dr % 16) == 0 && c.Vt <= 16 && c.Vr <= 16))
-    why = "the fused path's general embedding scatter (more than one type slot, slices not in 16-column blocks, or a type / relation table of more than 16 rows)";
-  else if (kprn_dbg_mask() & (1 | 8 | 16)) why = "a KPRN_DBG route of the fused path (scatter kernels with atomics)";
-  if (why) throw KprnError{KPRN_E_UNSUPPORTED, std::string("deterministic = 1: training would run on ") + why + ", which has no deterministic form; set deterministic = 0"};
+  if (h->deterministic == 1) {
+    if (h->impl != 0) why = "the generic pipeline (impl = generic: split-K atomics in its weight-gradient products)";
+    else if (c.rnn_type != 0) why = "the rnn / gru pipeline";
+    else if (c.compute_dtype == 1) why = "the bf16 pipeline (compute_dtype 1)";
+    else if (!fused::fwd_supported(h, T) || !fused::bwd_supported(h, T) || c.dt == 0 || c.de == 0)
+      why = "the generic pipeline (this shape is not the fused D = H = 64 path's: wide persistent layers / split-K products)";
+    else why = det_fused_why(h);
+    if (why) throw KprnError{KPRN_E_UNSUPPORTED, std::string("deterministic = 1: training would run on ") + why + ", which has no deterministic form; set deterministic = 0"};
+    return;
+  }
+  // "2".  The fused path trains where use_fused(.., true) says so: the same refusals as under "1" there
+  const bool fusedp = h->impl == 0 && c.rnn_type == 0 && c.compute_dtype != 1 && c.dt != 0 && c.de != 0 && fused::fwd_supported(h, T) && fused::bwd_supported(h, T);
+  if (fusedp) why = det_fused_why(h);
+  else if (c.rnn_type == 2) why = "the gru pipeline";
+  else if (c.compute_dtype == 1) why = "the bf16 pipeline or the generic pipeline's bf16 products (compute_dtype 1)";
+  else if (c.compute_dtype != 0) why = "the generic pipeline with a compute_dtype other than 0";
+  else {
+    // the generic fp32 pipeline.  Layer 0's table gradients: the small-table identity (no sums across workgroups but the split-K product's), or the scatter route,
+    // whose one-hot products take tables of at most 128 rows x 128 columns (kernels_basic.hip table_grad_mfma; the kernels behind it have no deterministic form)
+    const int ns = (c.Vr + c.Vt + 3) & ~3;
+    const bool will_drop = h->dropout_p > 0.f && c.rnn_type == 1;
+    const bool ident = !will_drop && h->small_tables && c.num_types == 1 && ns <= c.dt && ns <= 128 && c.de > 0 && c.dr > 0 && (!b || b->F >= 3);
+    if (!ident && !kk::embed_scatter_det_ok(c.dt, c.dr, c.Vt, c.Vr))
+      why = "the generic pipeline's general embedding scatter (a type / relation table of more than 128 rows or a slice of more than 128 columns)";
+    else if (b && c.de > 0 && (b->key_sorted == nullptr || b->tile_k))
+      why = "the generic pipeline's entity scatter (a batch without the occurrence index, or with an identical-prefix plan)";
+  }
+  if (why) throw KprnError{KPRN_E_UNSUPPORTED, std::string("deterministic = 2: training would run on ") + why + ", which has no deterministic form; set deterministic = 0"};
 }
 
 static void backward_impl(kprn_handle* h, const kprn_batch* b, int class_id, int literal, float inv_batch) {
   check_batch(h, b, class_id);
-  det_check(h, b->T);
+  det_check(h, b->T, b);
   drop_check(h, b);
   KPRN_REQUIRE(b->labels != nullptr && b->has_index, KPRN_E_ARG, "batch has no labels (targets are required, MyOptimizer.lua:179)");
   const kprn_config& c = h->cfg;
@@ -1199,7 +1252,7 @@ void kprn_destroy(kprn_handle* h) {
   Workspace& w = h->ws;
   for (float** p : {&w.X, &w.Hs, &w.Cs, &w.ACT, &w.dA, &w.dIn, &w.dH, &w.dC, &w.S, &w.dS, &w.pooled, &w.probs, &w.sel, &w.dy, &w.mask}) dfree(*p);
   for (float** p : {&h->dense, &h->g_dense, &h->s1_dense, &h->s2_dense, &h->We, &h->g_We, &h->s1_We, &h->s2_We, &h->d_loss, &h->d_norm2,
-                    &h->step_tab, &h->det_norm_part})
+                    &h->step_tab, &h->det_norm_part, &h->det_slab.p, &h->det_seg})
     dfree(*p);
   for (int32_t** p : {&h->We_last, &h->d_flag, &h->step_rows, &h->step_count, &h->pack_buf, &h->dp_mark}) dfree(*p);
   if (h->step_tab_host) hipHostFree(h->step_tab_host);
@@ -2556,7 +2609,7 @@ int kprn_train_step_batch(kprn_handle* h, const kprn_batch* b, int32_t class_id,
   API_BEGIN(h)
   KPRN_REQUIRE(opt, KPRN_E_ARG, "opt is NULL");
   check_batch(h, b, class_id);
-  det_check(h, b->T);
+  det_check(h, b->T, b);
   drop_check(h, b);
   catch_up(h, b);
   if (!h->pad_clean) { zero_pad_tokens(h); fused::params_changed(h); bf16p::params_changed(h, false); }  // MyOptimizer.lua:181 (a no-op when the last step left them zero)
@@ -3179,8 +3232,10 @@ int kprn_set_option(kprn_handle* h, const char* key, const char* value) {
     // "1": every float a training step hands back (loss, gradients, parameters, optimiser state) is a function of the inputs only -- the fused fp32 path's
     // atomic joins are replaced by plain-stored partials summed in a fixed order; a training call that would take any other pipeline returns
     // KPRN_E_UNSUPPORTED.  "0" (default): the kernels launched before this option existed.  Read at every training call.
-    KPRN_REQUIRE(strcmp(value, "0") == 0 || strcmp(value, "1") == 0, KPRN_E_ARG, "deterministic must be 0 or 1");
-    h->deterministic = value[0] == '1';
+    // "2": the same, and the generic fp32 pipeline (FastLSTM and rnn cells, compute_dtype 0) trains too, its atomic joins -- split-K products, column sums, head,
+    // entity and table gradients -- replaced by slabs joined in index order; wherever "1" trains, "2" launches exactly what "1" launches.
+    KPRN_REQUIRE(strcmp(value, "0") == 0 || strcmp(value, "1") == 0 || strcmp(value, "2") == 0, KPRN_E_ARG, "deterministic must be 0, 1 or 2");
+    h->deterministic = value[0] - '0';
   } else if (strcmp(key, "dropout") == 0) {
     // rate p of nn.Dropout on every rnn layer's step input in training forwards (OneModel.lua:246-265); "0" (default): the kernels launched
     // before this option existed.  Refused HERE where the reference ignores the flag (lstm, gru) or the pipeline has no dropped form (bf16 products).

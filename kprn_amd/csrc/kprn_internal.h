@@ -67,6 +67,11 @@ struct Workspace {
 
 struct ProfEntry { double total_ms = 0; int64_t launches = 0; };
 
+// Option "deterministic" = "2" (DESIGN.md 3.11): grow-only scratch, owned by the handle, that a producer kernel of the generic backward fills with one slab of
+// partial sums per workgroup or K split (plain stores) and kk::slab_join, the launch behind it, adds up in slab order.  A null DetScratch* argument anywhere
+// below means the default kernels with their fp32 atomics.
+struct DetScratch { float* p = nullptr; int64_t cap = 0; };
+
 namespace fused { constexpr int KCAP = 8; }  // longest identical prefix the fused kernels skip (lstm_fused_common.h)
 
 struct kprn_batch {
@@ -278,7 +283,10 @@ struct kprn_handle {
 
   // option "deterministic": every float sum of a training step whose addends come from different waves or workgroups of one launch is formed in an order that
   // depends on the batch and the launch geometry only; pipelines that cannot do that refuse to train
-  bool deterministic = false;
+  // "2" (generic fp32 pipelines too): 1 and 2 launch the same kernels wherever 1 trains; 2 adds the slab forms of the generic backward's joins
+  int deterministic = 0;
+  DetScratch det_slab;         // "2": where the generic backward's producers plain-store their partials (one buffer: producer and join are stream-ordered)
+  float* det_seg = nullptr; int64_t det_seg_cap = 0;   // "2": bidx::DetEntity::seg_part of the row-major entity gradient [segments][2][de]
   // option "dropout" (rnn cell, fp32): nn.Dropout on every layer's step input in TRAINING forwards.  Masks are regenerated, never stored:
   // drop_draw counts the training forwards since the seed was set; the backward of a step uses the draw of its forward (drop_draw_cur)
   float dropout_p = 0.f;
@@ -326,7 +334,14 @@ void rnn_cell_bwd(hipStream_t s, const float* pre, const float* hcur, const floa
                   int H, int relu);
 void add_bias_rows(hipStream_t s, float* Y, const float* b, int64_t rows, int cols);
 void add_into(hipStream_t s, float* dst, const float* src, int64_t n);   // dst[i] += src[i]
-void col_sum_add(hipStream_t s, const float* A, int64_t rows, int cols, float* out, int64_t ld = 0, float* out2 = nullptr);  // ld: row stride of A (0 = cols); out2: also += there
+// det (here and below): the workgroups' partials leave as slabs in det's scratch and slab_join adds them in workgroup order (no atomics)
+void col_sum_add(hipStream_t s, const float* A, int64_t rows, int cols, float* out, int64_t ld = 0, float* out2 = nullptr,   // ld: row stride of A (0 = cols); out2: also += there
+                 DetScratch* det = nullptr);
+// n floats of det's scratch (grown if need be: the stream is drained first)
+float* det_reserve(DetScratch* det, hipStream_t s, int64_t n);
+// dst[r * ldc + c] += ((slab 0 + slab 1) + slab 2) + ... over nslab slabs of [rows][cols] floats, `stride` floats apart: one running fp32 sum per element in slab
+// order, one owner thread per element (sixteen slabs requested at a time); dst2 (nullable): the same sum is added there too
+void slab_join(hipStream_t s, const float* slabs, int nslab, int64_t stride, int64_t rows, int cols, float* dst, int64_t ldc, float* dst2 = nullptr);
 void gru_gates_fwd(hipStream_t s, float* a, const float* hp, int64_t N, int H);
 void gru_out_fwd(hipStream_t s, float* a, const float* hp, float* h, int64_t N, int H);
 void gru_bwd1(hipStream_t s, const float* a, const float* hp, const float* dH, const float* dH_up, float* dA, float* dHdir, int64_t N, int H);
@@ -361,9 +376,12 @@ void loss_stage(hipStream_t s, const float* S, const float* labels, const float*
 void sum_partials(hipStream_t s, const float* partial, int n, float* out, int accumulate);
 int loss_partials(int B);  // number of per-workgroup loss partials the loss stage writes for B pairs
 void zero_pad3(hipStream_t s, float* a, int na, float* b, int nb, float* c, int nc);
-void head_bwd(hipStream_t s, const float* dS, const float* hT, const float* Wout, int64_t N, int H, int cid, float* dH, float* gWout, float* gbout);
+void head_bwd(hipStream_t s, const float* dS, const float* hT, const float* Wout, int64_t N, int H, int cid, float* dH, float* gWout, float* gbout,
+              DetScratch* det = nullptr);
+// det: the one-hot product route only (embed_scatter_det_ok) with skip_entity; anything else throws KPRN_E_UNSUPPORTED
 void embed_scatter(hipStream_t s, const int32_t* idx, int64_t N, int T, int F, int nT, const float* dX /*[T][N][D]*/, int dt, int de, int dr,
-                   int Vt, int Vr, float* gWt, float* gWe, float* gWr, bool skip_entity = false);
+                   int Vt, int Vr, float* gWt, float* gWe, float* gWr, bool skip_entity = false, DetScratch* det = nullptr);
+bool embed_scatter_det_ok(int dt, int dr, int Vt, int Vr);   // both small tables go to k_table_grad_mfma (at most 128 rows, slices of at most 128 columns)
 // Small tables (generic fp32 pipelines; lstm_bf16.hip has the bf16 twin and the derivation): with x = [Wt[type] | We[entity] | Wr[relation]] the
 // type / relation blocks of dW_i2g and both table gradients follow from G = dA^T [S_r | S_t] (one-hot selectors):
 //   dW_i2g[:, relation cols] = G_r Wr,  dWr = G_r^T W_i2g[:, relation cols]   (likewise for the type table)
@@ -573,7 +591,7 @@ __device__ __forceinline__ void small_grad_block(const SmallGrad& a, int bx, flo
 // entity-table gradient = gather-reduce of dx over the occurrence index.  frag_order 1: the fused backward's fragment-order dx;
 // 2: its compact entity slice [(n T + t)][de]; 0: time-major row-major [T][N][D] (generic pipeline).
 // red / sg (nullable): the slab reduce / the small-table gradients carried by the same launch
-// det (deterministic mode, frag_order 2 only): the partial sums of runs that straddle segments and the small-table job's blocks go to det's scratch with plain
+// det (deterministic mode, frag_order 2 and, without passenger jobs, 0): the partial sums of runs that straddle segments and the small-table job's blocks go to det's scratch with plain
 // stores, and entity_grad_tail -- a launch behind this one -- adds them in a fixed order
 struct DetEntity {
   float* seg_part;   // [segments][2][de]: the part of a run that came in from the segment before | the part of the run this segment opens and hands on
@@ -681,11 +699,16 @@ namespace gemm {
 // element (m,k) of A at A[m*sAm + k*sAk]; (k,n) of B at B[k*sBk + n*sBn]; C row-major ldc.
 // accumulate: C += (atomic when split_k > 1); else C = A*B (+ bias[n]).
 void run(hipStream_t s, const float* A, int64_t sAm, int64_t sAk, const float* B, int64_t sBk, int64_t sBn, float* C, int64_t ldc,
-         int64_t M, int N, int64_t K, bool accumulate, const float* bias, int split_k, bool bf16 = false, bool untiled = false);
+         int64_t M, int N, int64_t K, bool accumulate, const float* bias, int split_k, bool bf16 = false, bool untiled = false, DetScratch* det = nullptr);
+// det (fp32, accumulate): split s plain-stores its partial product into slab s of a scratch [nsplit][M][N] and kk::slab_join adds the slabs to C in split order.
+// The split count is capped so that one product's slabs stay within DET_SLAB_FLOATS (a function of M and N only).
+constexpr int64_t DET_SLAB_FLOATS = (int64_t)1 << 24;   // 64 MiB
+void run_untiled_slab(hipStream_t s, const float* A, int64_t sAm, int64_t sAk, const float* B, int64_t sBk, int64_t sBn, float* C, int64_t ldc, int64_t M, int N,
+                      int64_t K, int64_t kchunk, int split_k, DetScratch* det);   // gemm_f32_slab.hip
 // (untiled: keep the product off gemm_tiled.hip -- the GRU's split-K dW products, M = 2H / 3H = 500 / 750 rows: 1.53 against 2.06 ms, profiles/r06/bench_r_gru_*)
 // gemm_tiled.hip: 128 x 128 x 32 LDS-tiled kernel (16-byte loads, XCD-aware tile order); false: shape / layout not covered
 bool run_tiled(hipStream_t s, const float* A, int64_t sAm, int64_t sAk, const float* B, int64_t sBk, int64_t sBn, float* C, int64_t ldc, int64_t M, int N,
-               int64_t K, bool accumulate, const float* bias, int split_k);
+               int64_t K, bool accumulate, const float* bias, int split_k, DetScratch* det = nullptr);
 // one recurrent step of one layer with the cell in the GEMM's epilogue: gates = [x_t | h_{t-1}] [W_i | W_o]^T + b
 bool step_supported(const float* X, int64_t ldx, int Din, const float* Hprev, int64_t ldh, int H, const float* Wi, const float* Wo, int64_t N);
 void lstm_step(hipStream_t s, const float* X, int64_t ldx, int Din, const float* Wi, const float* bi, const float* Hprev, const float* Wo,

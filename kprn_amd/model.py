@@ -41,8 +41,9 @@ def flag_parser():
     a("-seed", type=int, default=12345); a("-entityUpdate", type=int, default=0)
     a("-dropoutSeed", type=lambda v: int(v, 0), default=None,
       help="seed of the dropout mask generator (decimal or 0x hex, 64 bits; default: -seed); a data-parallel rank r seeds with this + r, so replicas do not share masks; the engine's option \"dropout_seed\"")
-    a("-deterministic", type=int, default=0, choices=[0, 1],
-      help="1: bit-reproducible training (the engine's option \"deterministic\": fixed-order gradient sums on the fused fp32 path; a model that would train on any other pipeline is refused with KPRN_E_UNSUPPORTED)")
+    a("-deterministic", type=int, default=0, choices=[0, 1, 2],
+      help="1: bit-reproducible training (the engine's option \"deterministic\": fixed-order gradient sums on the fused fp32 path; a model that would train on any other pipeline is refused with KPRN_E_UNSUPPORTED); "
+           "2: the same, and the generic fp32 pipeline (lstm and rnn cells of any width, -useDropout included) trains with fixed-order sums too")
     a("-checkpointFormat", default="native", choices=["native", "t7", "both"],
       help="the native checkpoint is always written at <model>-latest; t7 / both ALSO write <model>-latest.t7, the parameters in a Torch7 {embeddingLayer, predictor_net} container (the reference writes its container at <model>-latest itself)")
     # evaluation during training (the slot OneModel.lua:389 left commented out): every -evaluationFrequency epochs the pairs of -testList are scored
@@ -135,7 +136,7 @@ def build_engine(params, rank=0, world=1, device_id=None, stream=None):
             # like the default seed (-seed + rank), the given one is offset by the rank: data-parallel replicas do not share masks
             eng.set_option("dropout_seed", str((int(params.dropoutSeed) + rank) & 0xFFFFFFFFFFFFFFFF))
         if getattr(params, "deterministic", 0):
-            eng.set_option("deterministic", "1")   # (a training call on a pipeline without fixed-order sums then raises KprnError(E_UNSUPPORTED))
+            eng.set_option("deterministic", str(int(params.deterministic)))   # (a training call on a pipeline without fixed-order sums then raises KprnError(E_UNSUPPORTED))
         if params.initModel:
             load_checkpoint(eng, params.initModel)  # OneModel.lua:277-282
     except Exception:
