@@ -431,7 +431,8 @@ int kprn_profile_get(kprn_handle* h, kprn_prof_entry* out, int32_t cap, int32_t*
  *                     same step, which does not depend on it.  Whatever would change what the pass reads (an optimiser step, a row
  *                     catch-up, kprn_set_*) waits for it; kprn_read_probs / kprn_sync wait for it on the host.  "0" (default): in
  *                     order on the handle's stream.
- *   "reserve_cus"     CUs the persistent scoring kernel leaves free (a collective's copy kernels run beside it), 0..128
+ *   "reserve_cus"     CUs the persistent scoring kernel leaves free (a collective's copy kernels run beside it), 0..1024; the pass always keeps
+ *                     at least one workgroup
  *   "profile_filter"  kernel-family name prefix: only those families get HIP events while profiling is on ("" = all); an event
  *                     pair costs ~4 us of stream time
  *   round 5 (each is the A/B switch of one design choice; the defaults are the fast paths, the tests run both sides in one process):
@@ -470,6 +471,10 @@ int kprn_profile_get(kprn_handle* h, kprn_prof_entry* out, int32_t cap, int32_t*
  *                     half multiplies [one-hot(relation, type) | entity row] by [Q ; W_i2g[:, entity cols]^T] with Q = table W_i2g[:, its cols]^T formed in the
  *                     launch's prologue (K = 48 instead of 64) | the full x row (equal to fp32 re-association of 32 of the 64 terms).  Independent of
  *                     "small_tables", which leaves the forward bit-identical
+ *   "head_select"     "1" (default) | "0": fused D = H = 64 fp32 forward: the nn.Linear(H, C) head forms column classId alone (what nn.Select(2, classId) keeps)
+ *                     in the training forward and in every scoring pass whose caller reads the selected class only; a call that asks for all_probs,
+ *                     pooled or path_scores takes the every-class head | the every-class head always.  The selected column is bit-identical either way;
+ *                     the other columns of a pass that took the selected head are not written
  *   "rank_sort_min"   "512" (default) | 257..4097: kprn_rank_groups ranks groups of this many members and more by a sort in LDS, smaller ones by counting
  *                     against every member (same results; counting is faster at 257 members, the sort from 512 on: profiles/rank/README.md)
  *   "train_step_return" "loss" (default) | "drain": see kprn_train_step

@@ -19,14 +19,14 @@
 
 namespace fused {
 bool fwd_supported(const kprn_handle* h, int T);
-void forward(kprn_handle* h, const kprn_batch* b, bool save, int64_t tile_begin = 0, int64_t tile_end = -1, bool ignore_reserve = false);
+void forward(kprn_handle* h, const kprn_batch* b, bool save, int64_t tile_begin = 0, int64_t tile_end = -1, bool ignore_reserve = false, int sel = -1);
 bool small_tiles(const kprn_handle* h, int64_t N, bool has_plan);
 bool bwd_supported(const kprn_handle* h, int T);
 void backward(kprn_handle* h, const kprn_batch* b, int cid);
 void params_changed(kprn_handle* h);
 bool transpose_job(kprn_handle* h, kk::TransposeJob* tj);
 void prefix_forward(kprn_handle* h, const kprn_batch* b);
-bool forward_dual(kprn_handle* h, const kprn_batch* bt, const kprn_batch* bs, float* S_score);
+bool forward_dual(kprn_handle* h, const kprn_batch* bt, const kprn_batch* bs, float* S_score, int sel_train, int sel_score);
 bool catch_up_with_prefix(kprn_handle* h, const kprn_batch* b, float* W, float* g, float* m, float* v, int32_t* last, int32_t t_now, const float* step_tab,
                           float b1, float b2, float eps);
 void mc_prepare(kprn_handle* h);
@@ -512,9 +512,14 @@ static bool use_fused(kprn_handle* h, const kprn_batch* b, bool save_for_backwar
   return !save_for_backward || fused::bwd_supported(h, b->T);
 }
 
-static void forward_impl(kprn_handle* h, const kprn_batch* b, int class_id, bool save_for_backward, bool do_pool = true, bool every_class = true) {
+// all_scores: the caller reads S itself, every column of it (path_scores).  The fused fp32 forward's head forms column classId alone unless a reader of the pass
+// needs other columns (option "head_select"): the training forward never does (the loss stage and the BPTT launches read S[:, cid] and W_out[cid]), a scoring
+// pass does when its pooling stage runs for every class or the caller copies S.
+static void forward_impl(kprn_handle* h, const kprn_batch* b, int class_id, bool save_for_backward, bool do_pool = true, bool every_class = true,
+                         bool all_scores = false) {
   check_batch(h, b, class_id);
   const int64_t N = b->N;
+  const int sel = (save_for_backward || !(every_class || all_scores)) ? class_id - 1 : -1;
   catch_up(h, b);
   ensure_ws_common(h, N, b->B, b->n_wg);
   if (use_fused(h, b, save_for_backward)) {
@@ -524,7 +529,7 @@ static void forward_impl(kprn_handle* h, const kprn_batch* b, int class_id, bool
       // pass's readers wait for is recorded here
       const kprn_batch* sb = h->score_rest_batch;
       join_put(h);   // (a board put queued on the scoring stream still reads sel2, which this pass's pooling stage writes from THIS stream)
-      dual = fused::forward_dual(h, b, sb, h->S2);
+      dual = fused::forward_dual(h, b, sb, h->S2, sel, h->score_rest_cid - 1);   // (the pass's pooling stage reads its own class's column)
       if (dual) {
         h->score_rest_batch = nullptr;
         h->pool_defer_batch = sb; h->pool_defer_cid = h->score_rest_cid - 1;   // (its pooling stage: more workgroups of the loss stage's launch, backward_impl)
@@ -534,7 +539,7 @@ static void forward_impl(kprn_handle* h, const kprn_batch* b, int class_id, bool
         h->score_on_main = true;
       }
     }
-    if (!dual) fused::forward(h, b, save_for_backward);
+    if (!dual) fused::forward(h, b, save_for_backward, 0, -1, false, sel);
   } else if (!b->idx_valid) {
     throw KprnError{KPRN_E_ARG, "this label-less batch was fed for the fused kernels (plan only); feed it again after changing impl"};
   } else if (bf16p::supported(h, b)) {
@@ -2099,7 +2104,7 @@ int kprn_forward_batch_async(kprn_handle* h, const kprn_batch* b, int32_t class_
     const int64_t t_split = (h->score_split > 0.f && h->cfg.compute_dtype == 0 && n_tiles >= 64 && !fused::small_tiles(h, N, b->tile_k != nullptr))
                                 ? std::max<int64_t>(1, std::min<int64_t>(n_tiles - 1, (int64_t)((1.0 - h->score_split) * n_tiles + 0.5))) : n_tiles;
     try {
-      fused::forward(h, b, false, 0, t_split < n_tiles ? t_split : -1, t_split < n_tiles);
+      fused::forward(h, b, false, 0, t_split < n_tiles ? t_split : -1, t_split < n_tiles, class_id - 1);   // (kprn_read_probs / kprn_board_put: the selected class)
       if (t_split == n_tiles) pool_stage(h, b, class_id - 1, false);
     } catch (...) { h->stream = main_stream; w.S = S0; w.sel = sel0; throw; }
     h->stream = main_stream; w.S = S0; w.sel = sel0;
@@ -2142,7 +2147,7 @@ static void launch_score_rest(kprn_handle* h) {
   float* S0 = w.S; float* sel0 = w.sel;
   h->stream = rs; w.S = h->S2; w.sel = h->sel2;
   try {
-    fused::forward(h, b, false, h->score_rest_tile0, -1);
+    fused::forward(h, b, false, h->score_rest_tile0, -1, false, h->score_rest_cid - 1);
     pool_stage(h, b, h->score_rest_cid - 1, false);
   } catch (...) {
     // the pass cannot finish: nobody may wait for it on a stale event, or hand out its half-filled S2 / sel2 as a finished pass
@@ -2201,7 +2206,7 @@ int kprn_forward_batch(kprn_handle* h, const kprn_batch* b, int32_t class_id, fl
     }
     h->sel_host_armed = h->probs_mirror;
   }
-  forward_impl(h, b, class_id, false, /*do_pool=*/true, /*every_class=*/all_probs != nullptr || pooled != nullptr);
+  forward_impl(h, b, class_id, false, /*do_pool=*/true, /*every_class=*/all_probs != nullptr || pooled != nullptr, /*all_scores=*/path_scores != nullptr);
   const int C = h->cfg.C;
   hipStream_t s = h->stream;
   if (probs && !mirror) HIP_TRY(hipMemcpyAsync(probs, h->ws.sel, (size_t)b->B * sizeof(float), hipMemcpyDeviceToHost, s));
@@ -3155,6 +3160,11 @@ int kprn_set_option(kprn_handle* h, const char* key, const char* value) {
     // K = 48 instead of 64 ("1", default) or over the full x row ("0": the A/B reference).  A key of its own: "small_tables" must leave the forward bit-identical.
     join_score(h);   // (a pass already queued keeps the route it was queued under)
     h->small_tables_fwd = atoi(value) != 0;
+  } else if (strcmp(key, "head_select") == 0) {
+    // fused D = H = 64 fp32 forward: the head forms the selected class's column alone wherever no reader of the pass needs another ("1", default), or all C
+    // columns always ("0": the A/B reference).  The selected column is bit-identical either way.
+    join_score(h);   // (a pass already queued keeps the head it was queued under)
+    h->head_select = atoi(value) != 0;
   } else if (strcmp(key, "bf16_t_pad") == 0) {
     bf16p::set_t_pad(atoi(value));   // small-table route: pad (elements) of the row pitch of dA^T / Z^T ("0": rows 2^18-aligned at the bench's size)
   } else if (strcmp(key, "bf16_gemm_regstage") == 0) {
@@ -3264,7 +3274,7 @@ int kprn_set_option(kprn_handle* h, const char* key, const char* value) {
     // the fused SCORING forward is a persistent one-workgroup-per-CU kernel that fills the register file of every CU it runs
     // on; leaving a few CUs free lets the copy kernels of a concurrently running collective (RCCL) make progress beside it
     const int v = atoi(value);
-    KPRN_REQUIRE(v >= 0 && v <= 128, KPRN_E_ARG, "reserve_cus must be in 0..128");
+    KPRN_REQUIRE(v >= 0 && v <= 1024, KPRN_E_ARG, "reserve_cus must be in 0..1024");   // (the pass keeps at least one workgroup: lstm_fused_fwd.hip fwd_args)
     h->reserve_cus = v;
   } else {
     throw KprnError{KPRN_E_ARG, std::string("unknown option: ") + key};

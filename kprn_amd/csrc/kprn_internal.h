@@ -239,6 +239,7 @@ struct kprn_handle {
   int bf16_bptt_dxe = 8;          // option "bf16_bptt_dxe": the persistent BPTT launch also forms dx for the entity slice (weight ring depth 8 | 16; 0: a separate product)
   int persist_layers = 1;     // option "persist_layers": generic fp32 LSTM / rnn layers as one persistent launch per layer where the shape allows (layer_f32_persist.hip)
   bool small_tables_fwd = true;   // option "small_tables_fwd": the fused D = H = 64 forward multiplies [S | x_e] by [Q ; W_i2g[:, e cols]^T] in layer 0 (lstm_fused_fwd.hip fwd_body IDENT)
+  bool head_select = true;        // option "head_select": the fused fp32 forward's head forms column classId alone when no reader of the pass needs another (lstm_fused_fwd.hip head_tile_sel)
   bool small_tables = true;       // option "small_tables": generic fp32 pipelines (LSTM / rnn cells) form the layer-0 type / relation gradients from G (kprn_api.hip backward_generic)
   float* lp_wot = nullptr; int64_t lp_wot_cap = 0;     // layer_f32_persist.hip: W_o2g^T of the layer whose BPTT launch is queued
   float* st_ctmp = nullptr; int64_t st_ctmp_cap = 0;   //   ... its [GH][ns + de] product result

@@ -39,6 +39,7 @@ struct FwdArgs {
   const float* Wout;
   const float* bout;
   int C;
+  int sel = -1;      // the head forms this class column only (0-based; fused fp32 forward, option "head_select"); -1: every class
   float* S;          // [N][C]
   const int32_t* perm;    // identical-prefix plan (nullable): tile slot n holds original path perm[n] (S is written in the original order)
   const int32_t* tile_k;  // [n_tiles] leading steps of the tile that are replaced by the prefix state (nullable: 0)
@@ -75,6 +76,13 @@ constexpr int MAXT_LDS = 16;  // steps whose ids are staged in LDS per tile
 // k copies of the batch's reference step starts at step k from the state the prefix kernel computed once.
 constexpr int R1 = 2 * 4 * DH + 2 * DH;  // floats per (layer, prefix step) of the rank-1 term buffer
 constexpr int PFB = 4 * DH + DH; // floats per (class, layer) of the prefix table: recurrent half of the first step [256] | c[64]
+constexpr int HSEL = DH + 4;     // floats of the selected-class head's operands behind the prefix table: W_out[sel][0..64) | b_out[sel] | pad to 16 bytes
+// the fused fp32 forward's dynamic LDS: x + h double buffers | two id tiles | prefix table | selected head row
+template <int L>
+constexpr size_t fwd_lds_bytes() {
+  return (size_t)(2 + 2 * L) * MT * LDA * sizeof(float) + 2 * MT * MAXT_LDS * 4 * sizeof(int32_t) + (size_t)(KCAP + 1) * L * PFB * sizeof(float) + HSEL * sizeof(float);
+}
+static_assert(fwd_lds_bytes<2>() <= 160 * 1024, "one workgroup per CU: 160 KiB of LDS");
 
 // all the tile's ids -> LDS: ids[(row*T + t)*4 + {0: first type, 1: entity, 2: relation}] (0-based).
 // Rows past N repeat row N-1 (their results are never stored).  Removes the dependent id -> row load
@@ -454,7 +462,7 @@ bool small_tiles(const kprn_handle* h, int64_t N, bool has_plan);
 void handover_stats(kprn_handle* h, const kprn_batch* b, int64_t* out /*[4]: pairs, steps moved, longest workgroup in half steps without / with*/);
 HoArgs handover_args(kprn_handle* h, int grid);   // this launch's hand-over context (epoch 0: off)
 void prefix_forward(kprn_handle* h, const kprn_batch* b);
-bool forward_dual(kprn_handle* h, const kprn_batch* bt, const kprn_batch* bs, float* S_score);
+bool forward_dual(kprn_handle* h, const kprn_batch* bt, const kprn_batch* bs, float* S_score, int sel_train, int sel_score);
 bool catch_up_with_prefix(kprn_handle* h, const kprn_batch* b, float* W, float* g, float* m, float* v, int32_t* last, int32_t t_now, const float* step_tab,
                           float b1, float b2, float eps);
 void forward_mc(kprn_handle* h, const kprn_batch* b, bool save);

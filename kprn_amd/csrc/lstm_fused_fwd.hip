@@ -233,6 +233,42 @@ __device__ __forceinline__ void head_tile(const FwdArgs& a, const float* hbuf, i
   }
 }
 
+// The head with ONE class selected (FwdArgs::sel; option "head_select"): every caller of the step and of the scoring passes reads column classId alone (the
+// reference's nn.Select(2, classId)), so only S[.][sel] is formed -- 16 MFMAs per 16-row m-tile where the full head issues 16 per column tile, wave j takes
+// m-tile j (a 16-row tile: wave 0), and the operands W_out[sel] | b_out[sel] come from LDS, staged once per launch (hsel), not from the L2 at every tile.
+// The column keeps its bits: an MFMA output element is a function of its A row and its B column only, the B fragment carries W_out[sel] in ALL 16 columns
+// (lane (arow, ag), register jj <-> W_out[sel][16 S + 4 ag + jj] whatever arow), and the chain per row is head_tile's: bias, then S = 0..3, jj = 0..3.  All 16
+// output columns being the wanted one, lane (arow < 4, ag) holds row 4 ag + arow in register arow: ONE store instruction, one position per lane.
+template <int NMT>
+__device__ __forceinline__ void head_tile_sel(const FwdArgs& a, const float* hbuf, const float* hsel, int64_t tile, int j, int lane) {
+  if (NMT == 1 && j != 0) return;   // (wave-uniform)
+  const int mt = (NMT == 1) ? 0 : j;
+  const int arow = lane & 15, ag = lane >> 4, r = arow & 3;
+  const int64_t n = tile * (16 * NMT) + mt * 16 + ag * 4 + r;
+  const int64_t nc = n < a.N ? n : a.N - 1;
+  const int pr = a.perm ? a.perm[nc] : (int)nc;   // (uniform branch; the load itself is unconditional, and needed last)
+  const float b = hsel[DH];
+  f32x4 w4[4], a4[4];
+#pragma unroll
+  for (int S = 0; S < 4; ++S) {
+    w4[S] = *(const f32x4*)(hsel + S * 16 + ag * 4);
+    a4[S] = *(const f32x4*)(hbuf + (mt * 16 + arow) * LDA + S * 16 + ag * 4);
+  }
+  f32x4 acc = f32x4{b, b, b, b};
+#pragma unroll
+  for (int S = 0; S < 4; ++S)
+#pragma unroll
+    for (int jj = 0; jj < 4; ++jj) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a4[S][jj], w4[S][jj], acc, 0, 0, 0);
+  const float v = (r == 0) ? acc[0] : ((r == 1) ? acc[1] : ((r == 2) ? acc[2] : acc[3]));
+  if (arow < 4 && n < a.N) a.S[(int64_t)pr * a.C + a.sel] = v;
+}
+
+template <int NMT>
+__device__ __forceinline__ void head(const FwdArgs& a, const float* hbuf, const float* hsel, int64_t tile, int j, int lane) {
+  if (a.sel >= 0) head_tile_sel<NMT>(a, hbuf, hsel, tile, j, lane);   // (launch-uniform)
+  else head_tile<NMT>(a, hbuf, tile, j, lane);
+}
+
 // NMT: 16-row m-tiles of a tile -- 4 (64-path tiles), or 1 for small batches (fused::small_tiles: four times as many workgroups, each a quarter
 // of the latency; the unit pipeline below is the same, a slot is then the chain of L units (layer l, m-tile 0))
 // bx / G_: this workgroup's index among, and the number of, the workgroups that walk THIS pass's tiles (k_lstm_fwd: the launch's; k_lstm_fwd_dual: a part of it)
@@ -253,6 +289,8 @@ __device__ __forceinline__ void fwd_body(const FwdArgs& a, const int bx, const i
   auto idbuf = [&](int i) -> int32_t* { return (int32_t*)(lds + (2 + 2 * L) * (MT * LDA)) + i * (MT * MAXT_LDS * 4); };
   // prefix table [KCAP+1][L][PFB]: per class k the recurrent half of a tile's first executed step (W_o2g h_prefix(k)) and c_prefix(k)
   const float* pft = (const float*)idbuf(2);
+  // selected-class head (head_tile_sel): W_out[sel] | b_out[sel], staged once per launch
+  float* hsel = (float*)pft + (KCAP + 1) * L * PFB;
 
   const int lane = threadIdx.x & 63;
   const int j = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // hidden tile owned by this wave
@@ -352,6 +390,8 @@ __device__ __forceinline__ void fwd_body(const FwdArgs& a, const int bx, const i
     const int n_cls = __builtin_amdgcn_readfirstlane(a.pmeta[0]) + 1;
     for (int c = L * PFB + threadIdx.x; c < n_cls * L * PFB; c += NT) ((float*)pft)[c] = a.pfb[c];
   }
+  if (a.sel >= 0 && threadIdx.x <= DH)   // (launch-uniform; 65 threads: the weight row, then the bias)
+    hsel[threadIdx.x] = threadIdx.x < DH ? a.Wout[(int64_t)a.sel * DH + threadIdx.x] : a.bout[a.sel];
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's id pieces have landed
   lds_barrier();
   FPROBE(11)  // ... first ids + prefix table
@@ -494,7 +534,7 @@ __device__ __forceinline__ void fwd_body(const FwdArgs& a, const int bx, const i
           if (cross) { FPROBE(8) }   // (measurement build) first slot: prefix lookup + the pending cell of the tile before
           lds_barrier();
           if (cross) { FPROBE(9) }   // ... barrier
-          if (cross && has_prev) head_tile<NMT>(a, hbuf(L - 1, q_par), p_tile, j, lane);
+          if (cross && has_prev) head<NMT>(a, hbuf(L - 1, q_par), hsel, p_tile, j, lane);
           if (cross) { FPROBE(10) }  // ... the head of the tile before
           apre = *(const f32x4*)(in_base);
           if (IDENT && l == 0) half_unit<SAVE, false, true, true, false, 3>(in_base, wi[l], bias4[l], acc, apre, nxt, pacc, c[pl][pm], pout, sv);
@@ -582,7 +622,7 @@ __device__ __forceinline__ void fwd_body(const FwdArgs& a, const int bx, const i
     cell_all<SAVE>(accs[LAST], c[L - 1][NMT - 1], hbuf(L - 1, par) + (NMT - 1) * 16 * LDA + o_off, sv);
     save_unit(SAVE ? tile_region(p_tile) : nullptr, p_t, L - 1, NMT - 1);
     lds_barrier();
-    head_tile<NMT>(a, hbuf(L - 1, par), p_tile, j, lane);
+    head<NMT>(a, hbuf(L - 1, par), hsel, p_tile, j, lane);
   }
   FPROBE(5)  // drain
   if (KPRN_PROBES_ON && a.timing && threadIdx.x == 0) {
@@ -675,7 +715,7 @@ static bool fwd_ident(const kprn_handle* h) {
 
 template <int L, bool SAVE, bool IDENT = false, int NMT = 4>
 static void launch_fwd(kprn_handle* h, const FwdArgs& a, int grid) {
-  const size_t lds_bytes = (size_t)(2 + 2 * L) * MT * LDA * sizeof(float) + 2 * MT * MAXT_LDS * 4 * sizeof(int32_t) + (size_t)(KCAP + 1) * L * PFB * sizeof(float);
+  const size_t lds_bytes = fwd_lds_bytes<L>();
   static PerDeviceOnce attr_done;  // one per template instantiation
   if (attr_done.need()) {
     HIP_TRY(hipFuncSetAttribute((const void*)k_lstm_fwd<L, SAVE, IDENT, NMT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
@@ -688,8 +728,9 @@ static void launch_fwd(kprn_handle* h, const FwdArgs& a, int grid) {
 // in two around a data-parallel step's collective (kprn_set_option "score_split").  The kernel sees a shorter batch: the per-tile arrays are
 // handed over shifted, scores still land at their path's own row of S.
 // the arguments of one pass (S: where its scores go); false: nothing to launch (an empty tile range)
-static bool fwd_args(kprn_handle* h, const kprn_batch* b, bool save, int64_t tile_begin, int64_t tile_end, bool ignore_reserve, float* S, FwdArgs& a, int& grid,
-                     bool& small) {
+// sel: the one class column (0-based) this pass's readers need, -1: every class; option "head_select" = 0 keeps the every-class head whatever they need
+static bool fwd_args(kprn_handle* h, const kprn_batch* b, bool save, int64_t tile_begin, int64_t tile_end, bool ignore_reserve, float* S, int sel, FwdArgs& a,
+                     int& grid, bool& small) {
   const kprn_config& c = h->cfg;
   State* s = st(h);
   const int64_t N = b->N;
@@ -703,6 +744,7 @@ static bool fwd_args(kprn_handle* h, const kprn_batch* b, bool save, int64_t til
   }
   a.Wout = h->dense + h->off_outW; a.bout = h->dense + h->off_outb; a.C = c.C;
   a.S = S;
+  a.sel = (h->head_select && sel >= 0 && sel < c.C) ? sel : -1;
   small = small_tiles(h, N, b->tile_k != nullptr);   // (c.L == 2: the only small-tile instantiation)
   a.n_tiles = small ? (N + 15) / 16 : (N + MT - 1) / MT;
   if (!small && !save && (tile_begin > 0 || tile_end >= 0)) {
@@ -747,10 +789,14 @@ static void launch_dual(kprn_handle* h, const FwdArgs& a0, const FwdArgs& a1, in
 static void ident_mark(kprn_handle* h) {
   if (h->prof_on) { ProfScope mark(h, "small_tables_fwd"); }
 }
+// ... likewise a pass whose head formed the selected class only (head_tile_sel): one mark per pass
+static void head_select_mark(kprn_handle* h, const FwdArgs& a) {
+  if (h->prof_on && a.sel >= 0) { ProfScope mark(h, "head_select"); }
+}
 
 // The training forward of `bt` and a whole scoring pass over `bs` (scores to S_score) as one launch (k_lstm_fwd_dual); false: not applicable -- the caller
-// launches them the usual way.  Both passes read ONE identical-prefix table: the two batches must be the same one, or neither may have a plan.
-bool forward_dual(kprn_handle* h, const kprn_batch* bt, const kprn_batch* bs, float* S_score) {
+// launches them the usual way.  sel_train / sel_score: each pass's own class column (fwd_args; the two may differ).  Both passes read ONE identical-prefix table: the two batches must be the same one, or neither may have a plan.
+bool forward_dual(kprn_handle* h, const kprn_batch* bt, const kprn_batch* bs, float* S_score, int sel_train, int sel_score) {
   const kprn_config& c = h->cfg;
   State* s = st(h);
   if (c.compute_dtype != 0 || c.L != 2 || !fwd_supported(h, bt->T) || !fwd_supported(h, bs->T) || s->timing) return false;
@@ -762,18 +808,20 @@ bool forward_dual(kprn_handle* h, const kprn_batch* bt, const kprn_batch* bs, fl
   bool small0 = false, small1 = false;
   prefix_forward(h, bt);
   if (h->score_rest_batch != bs) return false;   // (a rewrite of the prefix table joins the scoring stream first: the deferred pass has then run the usual way)
-  if (!fwd_args(h, bt, true, 0, -1, false, h->ws.S, a0, g0, small0) || !fwd_args(h, bs, false, 0, -1, true, S_score, a1, g1, small1) || small0 != small1) return false;
+  if (!fwd_args(h, bt, true, 0, -1, false, h->ws.S, sel_train, a0, g0, small0) || !fwd_args(h, bs, false, 0, -1, true, S_score, sel_score, a1, g1, small1) || small0 != small1) return false;
   a0.timing = a1.timing = nullptr;
-  const size_t lds_bytes = (size_t)(2 + 2 * 2) * MT * LDA * sizeof(float) + 2 * MT * MAXT_LDS * 4 * sizeof(int32_t) + (size_t)(KCAP + 1) * 2 * PFB * sizeof(float);
+  const size_t lds_bytes = fwd_lds_bytes<2>();
   const bool ident = fwd_ident(h);
   if (ident) ident_mark(h);
+  head_select_mark(h, a0);
+  head_select_mark(h, a1);
   ProfScope ps(h, "lstm_fused_fwd_dual");
   if (small0) { if (ident) launch_dual<true, 1>(h, a0, a1, g0, g1, lds_bytes); else launch_dual<false, 1>(h, a0, a1, g0, g1, lds_bytes); }
   else { if (ident) launch_dual<true, 4>(h, a0, a1, g0, g1, lds_bytes); else launch_dual<false, 4>(h, a0, a1, g0, g1, lds_bytes); }
   return true;
 }
 
-void forward(kprn_handle* h, const kprn_batch* b, bool save, int64_t tile_begin, int64_t tile_end, bool ignore_reserve) {
+void forward(kprn_handle* h, const kprn_batch* b, bool save, int64_t tile_begin, int64_t tile_end, bool ignore_reserve, int sel) {
   const kprn_config& c = h->cfg;
   if (c.compute_dtype != 0) { forward_mc(h, b, save); return; }  // bf16 / f32x6: the matrix-core forward (lstm_fused_fwd_mc.hip)
   State* s = st(h);
@@ -782,9 +830,10 @@ void forward(kprn_handle* h, const kprn_batch* b, bool save, int64_t tile_begin,
   int grid = 0;
   bool small = false;
   prefix_forward(h, b);  // (cached while neither the parameters nor the batch change)
-  if (!fwd_args(h, b, save, tile_begin, tile_end, ignore_reserve, h->ws.S, a, grid, small)) return;
+  if (!fwd_args(h, b, save, tile_begin, tile_end, ignore_reserve, h->ws.S, sel, a, grid, small)) return;
   const bool ident = fwd_ident(h);
   if (ident) ident_mark(h);
+  head_select_mark(h, a);
   ProfScope ps(h, save ? "lstm_fused_fwd_train" : "lstm_fused_fwd");
   if (c.L == 1) { if (save) launch_fwd<1, true>(h, a, grid); else launch_fwd<1, false>(h, a, grid); }
   else if (ident) {
