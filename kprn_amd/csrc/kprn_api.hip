@@ -17,23 +17,6 @@
 
 #include "kprn_internal.h"
 
-namespace fused {
-bool fwd_supported(const kprn_handle* h, int T);
-void forward(kprn_handle* h, const kprn_batch* b, bool save, int64_t tile_begin = 0, int64_t tile_end = -1, bool ignore_reserve = false, int sel = -1);
-bool small_tiles(const kprn_handle* h, int64_t N, bool has_plan);
-bool bwd_supported(const kprn_handle* h, int T);
-void backward(kprn_handle* h, const kprn_batch* b, int cid);
-void params_changed(kprn_handle* h);
-bool transpose_job(kprn_handle* h, kk::TransposeJob* tj);
-void prefix_forward(kprn_handle* h, const kprn_batch* b);
-bool forward_dual(kprn_handle* h, const kprn_batch* bt, const kprn_batch* bs, float* S_score, int sel_train, int sel_score);
-bool catch_up_with_prefix(kprn_handle* h, const kprn_batch* b, float* W, float* g, float* m, float* v, int32_t* last, int32_t t_now, const float* step_tab,
-                          float b1, float b2, float eps);
-void mc_prepare(kprn_handle* h);
-void release(kprn_handle* h);
-void handover_stats(kprn_handle* h, const kprn_batch* b, int64_t* out);
-}  // namespace fused
-
 static thread_local std::string g_create_error;
 
 // ---------------------------------------------------------------------------------------
@@ -76,18 +59,6 @@ void prof_drain(kprn_handle* h) {
 }
 
 // ---------------------------------------------------------------------------------------
-template <typename T>
-static T* dalloc(int64_t n) {
-  void* p = nullptr;
-  if (n <= 0) n = 1;
-  // 64 bytes of slack: the tiled GEMMs fetch 16-byte vectors that may straddle the end of a matrix's last row (gemm_tiled.hip)
-  hipError_t e = kprn_dev_malloc(&p, (size_t)n * sizeof(T) + 64);
-  if (e != hipSuccess) throw KprnError{KPRN_E_NOMEM, std::string("hipMalloc failed: ") + hipGetErrorString(e)};
-  return (T*)p;
-}
-template <typename T>
-static void dfree(T*& p) { if (p) { hipFree(p); p = nullptr; } }
-
 static void build_layout(kprn_handle* h) {
   const kprn_config& c = h->cfg;
   h->D = c.dt + c.de + c.dr;
@@ -211,12 +182,7 @@ static void materialize_step_rows(kprn_handle* h) {
   if (!h->view_batch) { h->rows_view = h->step_rows; h->count_view = h->step_count; return; }
   const kprn_batch* b = h->view_batch;
   int64_t need = std::max<int64_t>(b->n_uniq, 1);
-  if (need > h->step_rows_cap) {
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    dfree(h->step_rows);
-    h->step_rows_cap = need * 2;
-    h->step_rows = dalloc<int32_t>(h->step_rows_cap);
-  }
+  dev_grow2(h->stream, h->step_rows, h->step_rows_cap, need);
   if (b->n_uniq > 0)
     HIP_TRY(hipMemcpyAsync(h->step_rows, b->uniq, (size_t)b->n_uniq * sizeof(int32_t), hipMemcpyDeviceToDevice, h->stream));
   HIP_TRY(hipMemcpyAsync(h->step_count, b->uniq + b->uniq_cap, sizeof(int32_t), hipMemcpyDeviceToDevice, h->stream));
@@ -226,12 +192,7 @@ static void materialize_step_rows(kprn_handle* h) {
 
 static void ensure_ws_common(kprn_handle* h, int64_t N, int64_t B, int64_t n_wg = 0) {
   const int64_t np = std::max<int64_t>(kk::loss_partials((int)B), n_wg);   // (n_wg: the loss-stage workgroups of a ragged batch)
-  if (np > h->loss_partial_cap) {
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    dfree(h->loss_partial);
-    h->loss_partial_cap = np * 2;
-    h->loss_partial = dalloc<float>(h->loss_partial_cap);
-  }
+  dev_grow2(h->stream, h->loss_partial, h->loss_partial_cap, np);
   Workspace& w = h->ws;
   const kprn_config& c = h->cfg;
   if (N > w.cap_Nc) {
@@ -253,7 +214,7 @@ static void ensure_ws_common(kprn_handle* h, int64_t N, int64_t B, int64_t n_wg 
   h->score_buf = w.S;
 }
 
-static void ensure_ws_generic(kprn_handle* h, int64_t N, int T) {
+void ensure_ws_generic(kprn_handle* h, int64_t N, int T) {
   Workspace& w = h->ws;
   const kprn_config& c = h->cfg;
   const int H = c.H, L = c.L, D = h->D;
@@ -295,194 +256,6 @@ static void catch_up(kprn_handle* h, const kprn_batch* b) {
   h->caught_serial = b->serial; h->caught_step = h->opt_step;
 }
 
-// Option "dropout": what a launch needs to regenerate layer l's masks of the training forward in flight (philox_dev.h), and the addressing limits of
-// the counter (step and layer share a 32-bit word, the path has one of its own), checked before a training call launches or writes anything
-static philox::DropArgs drop_args(const kprn_handle* h, int l) {
-  philox::DropArgs a;
-  a.k0 = (uint32_t)(h->dropout_seed & 0xffffffffu); a.k1 = (uint32_t)(h->dropout_seed >> 32);
-  a.draw = h->drop_draw_cur; a.layer16 = 65536u * (uint32_t)l;
-  a.thr = philox::threshold((double)h->dropout_p); a.scale = philox::keep_scale(h->dropout_p);
-  return a;
-}
-static void drop_check(const kprn_handle* h, const kprn_batch* b) {
-  if (!(h->dropout_p > 0.f) || h->cfg.rnn_type != 1) return;
-  KPRN_REQUIRE(b->T <= 65535 && h->cfg.L <= 65535 && b->N < ((int64_t)1 << 32), KPRN_E_ARG,
-               "dropout: the mask generator addresses at most 65535 steps, 65535 layers and 2^32 - 1 paths per batch");
-}
-
-// ---------------------------------------------------------------------------------------
-// generic (unfused) forward: gather -> per layer {input GEMM, per step recurrent GEMM + gates} -> head
-static void forward_generic(kprn_handle* h, const kprn_batch* b, bool save) {
-  const kprn_config& c = h->cfg;
-  const bool bf = c.compute_dtype == 1;  // bf16 MFMA products, fp32 accumulation (gemm_f32.hip)
-  static const bool no_step = getenv("KPRN_NO_STEP_KERNEL") != nullptr;  // (measurement: GEMM + element-wise kernels per step)
-  Workspace& w = h->ws;
-  const int H = c.H, L = c.L, T = b->T;
-  const int64_t N = b->N;
-  hipStream_t s = h->stream;
-  // option "dropout" (rnn, fp32): a TRAINING forward drops every layer's step input; a scoring pass never does
-  const bool drop = save && h->dropout_p > 0.f && c.rnn_type == 1;
-  if (drop) drop_check(h, b);   // (throws before the flag below says that a dropped forward is behind the backward)
-  h->drop_live = drop;
-  if (drop) {
-    h->drop_draw_cur = h->drop_draw++;
-    const int64_t need = (int64_t)(L - 1) * T * N * H;
-    if (need > w.cap_HsD) {
-      HIP_TRY(hipStreamSynchronize(s));
-      dfree(w.HsD);
-      w.HsD = dalloc<float>(need);
-      w.cap_HsD = need;
-    }
-    ProfScope ps(h, "embed_gather_drop");
-    // the dropped rows go to X; MaskZero's flags come from the undropped values in the same pass
-    kk::embed_gather_drop(s, b->idx, N, T, b->F, c.num_types, h->dense + h->off_Wt, h->We, h->dense + h->off_Wr, c.dt, c.de, c.dr, w.X, w.mask, drop_args(h, 0));
-  } else {
-    ProfScope ps(h, "embed_gather");
-    // (rnnType rnn: MaskZero's mask of the bottom layer's input rows comes out of the same pass)
-    kk::embed_gather(s, b->idx, N, T, b->F, c.num_types, h->dense + h->off_Wt, h->We, h->dense + h->off_Wr, c.dt, c.de, c.dr, w.X, true,
-                     c.rnn_type == 1 ? w.mask : nullptr);
-  }
-  if (c.rnn_type == 2) {
-    // nn.Sequencer(nn.GRU(D, H)) x L (OneModel.lua:237-238,268-273); step record a[n][4H] = [r | z | n | r*h']
-    for (int l = 0; l < L; ++l) {
-      const int Din = h->layer[l].Din;
-      const float* in = (l == 0) ? w.X : w.Hs + (int64_t)(l - 1) * T * N * H;
-      float* act = w.ACT + (int64_t)l * T * N * 4 * H;
-      float* hs = w.Hs + (int64_t)l * T * N * H;
-      const float* Wo = h->dense + h->layer[l].Wo;
-      const float* Uc = h->dense + h->layer[l].Uc;
-      if (!bf && h->persist_layers && lp32::supported(2, N, Din, H, h->persist_layers == 2)) {
-        // all T steps of the layer -- both dependent products of a step -- in ONE persistent launch (layer_f32_persist.hip, CELL 2)
-        ProfScope ps(h, "gru_layer_fwd");
-        lp32::forward_layer(s, 2, in, N, T, Din, H, h->dense + h->layer[l].Wi, Wo, h->dense + h->layer[l].bi, nullptr, hs, nullptr, act, nullptr, 0, save,
-                            /*write_all_h=*/l < L - 1, h->dense + h->layer[l].Wc, Uc, h->dense + h->layer[l].bc);
-        continue;
-      }
-      {
-        ProfScope ps(h, "gemm_i2g_fwd");
-        gemm::run(s, in, Din, 1, h->dense + h->layer[l].Wi, 1, Din, act, 4 * H, (int64_t)T * N, 2 * H, Din, false, h->dense + h->layer[l].bi, 1, bf);
-        gemm::run(s, in, Din, 1, h->dense + h->layer[l].Wc, 1, Din, act + 2 * H, 4 * H, (int64_t)T * N, H, Din, false, h->dense + h->layer[l].bc, 1, bf);
-      }
-      for (int t = 0; t < T; ++t) {
-        float* a_t = act + (int64_t)t * N * 4 * H;
-        const float* hp = t > 0 ? hs + (int64_t)(t - 1) * N * H : nullptr;
-        if (t > 0) {
-          ProfScope ps(h, "gemm_o2g_fwd");
-          gemm::run(s, hp, H, 1, Wo, 1, H, a_t, 4 * H, N, 2 * H, H, true, nullptr, 1, bf);
-        }
-        {
-          ProfScope ps(h, "gru_cell_fwd");
-          kk::gru_gates_fwd(s, a_t, hp, N, H);
-        }
-        if (t > 0) {
-          ProfScope ps(h, "gemm_o2g_fwd");
-          gemm::run(s, a_t + 3 * H, 4 * H, 1, Uc, 1, H, a_t + 2 * H, 4 * H, N, H, H, true, nullptr, 1, bf);
-        }
-        ProfScope ps(h, "gru_cell_fwd");
-        kk::gru_out_fwd(s, a_t, hp, hs + (int64_t)t * N * H, N, H);
-      }
-    }
-  } else if (c.rnn_type == 1) {
-    // nn.Sequencer(nn.Recurrence(nn.MaskZero(act(i2h x_t + h2h h_{t-1}), 1))) x L (OneModel.lua:240-266,268-273)
-    for (int l = 0; l < L; ++l) {
-      const int Din = h->layer[l].Din;
-      const float* in = (l == 0) ? w.X : w.Hs + (int64_t)(l - 1) * T * N * H;
-      float* pre = w.ACT + (int64_t)l * T * N * H;
-      float* hs = w.Hs + (int64_t)l * T * N * H;
-      float* mask = w.mask + (int64_t)l * T * N;
-      const float* in0 = in;   // the undropped rows: what MaskZero looks at
-      if (drop && l > 0) {
-        // the layer reads a dropped COPY of the plane below: the undropped one stays for the layer below's BPTT and for the mask above
-        ProfScope ps(h, "drop_rows_fwd");
-        float* din = w.HsD + (int64_t)(l - 1) * T * N * H;
-        kk::drop_rows(s, in, din, N, T, Din, drop_args(h, l));
-        in = din;
-      }
-      const bool stepk = !bf && !no_step && gemm::step_supported(in, Din, Din, hs, H, H, h->dense + h->layer[l].Wi, h->dense + h->layer[l].Wo, N);
-      if (!stepk) {
-        ProfScope ps(h, "gemm_i2g_fwd");
-        gemm::run(s, in, Din, 1, h->dense + h->layer[l].Wi, 1, Din, pre, H, (int64_t)T * N, H, Din, false, h->dense + h->layer[l].bi, 1, bf);
-      }
-      if (l > 0) {
-        ProfScope ps(h, "rnn_mask");
-        kk::row_nonzero(s, in0, (int64_t)T * N, Din, mask);  // layer l > 1: the mask follows the ACTUAL input rows (h^{l-1}_t), as MaskZero does
-      }
-      if (stepk && h->persist_layers && lp32::supported(1, N, Din, H, h->persist_layers == 2)) {
-        // all T steps of the layer in ONE persistent launch: h never leaves the CU, weights stream L2 -> LDS by DMA (layer_f32_persist.hip)
-        ProfScope ps(h, "rnn_layer_fwd");
-        lp32::forward_layer(s, 1, in, N, T, Din, H, h->dense + h->layer[l].Wi, h->dense + h->layer[l].Wo, h->dense + h->layer[l].bi, h->dense + h->layer[l].bo, hs,
-                            nullptr, pre, mask, c.use_relu == 1 ? 1 : 0, save, /*write_all_h=*/l < L - 1);   // (a scoring pass needs the top layer's last step only; the training forward writes every step: forward_layer)
-        continue;
-      }
-      if (stepk) {
-        // i2h, h2h, both biases, the activation and MaskZero in one launch per step (gemm_tiled.hip)
-        ProfScope ps(h, "rnn_step_fwd");
-        ps.launches = T;
-        for (int t = 0; t < T; ++t)
-          gemm::rnn_step(s, in + (int64_t)t * N * Din, Din, Din, h->dense + h->layer[l].Wi, h->dense + h->layer[l].bi,
-                         t > 0 ? hs + (int64_t)(t - 1) * N * H : nullptr, h->dense + h->layer[l].Wo, h->dense + h->layer[l].bo, mask + (int64_t)t * N,
-                         pre + (int64_t)t * N * H, hs + (int64_t)t * N * H, H, N, H, c.use_relu == 1 ? 1 : 0);
-        continue;
-      }
-      for (int t = 0; t < T; ++t) {
-        float* pre_t = pre + (int64_t)t * N * H;
-        if (t > 0) {
-          ProfScope ps(h, "gemm_o2g_fwd");
-          gemm::run(s, hs + (int64_t)(t - 1) * N * H, H, 1, h->dense + h->layer[l].Wo, 1, H, pre_t, H, N, H, H, true, nullptr, 1, bf);
-        }
-        ProfScope ps(h, "rnn_cell_fwd");
-        kk::rnn_cell_fwd(s, pre_t, h->dense + h->layer[l].bo, mask + (int64_t)t * N, hs + (int64_t)t * N * H, N, H, c.use_relu == 1 ? 1 : 0);
-      }
-      // the mask of the NEXT layer reads hs: it is complete here
-    }
-  } else
-  for (int l = 0; l < L; ++l) {
-    const int Din = h->layer[l].Din;
-    const float* in = (l == 0) ? w.X : w.Hs + (int64_t)(l - 1) * T * N * H;
-    float* act = w.ACT + (int64_t)l * T * N * 4 * H;
-    float* hs = w.Hs + (int64_t)l * T * N * H;
-    float* cs = w.Cs + (int64_t)l * T * N * H;
-    const float* Wi = h->dense + h->layer[l].Wi;
-    const float* bi = h->dense + h->layer[l].bi;
-    const float* Wo = h->dense + h->layer[l].Wo;
-    if (!bf && !no_step && h->persist_layers && lp32::supported(0, N, Din, H, h->persist_layers == 2)) {
-      // all T steps of the layer in ONE persistent launch: h and c never leave the CU (layer_f32_persist.hip)
-      ProfScope ps(h, "lstm_layer_fwd");
-      lp32::forward_layer(s, 0, in, N, T, Din, H, Wi, Wo, bi, nullptr, hs, cs, act, nullptr, 0, save, /*write_all_h=*/l < L - 1);
-      continue;
-    }
-    if (!bf && !no_step && gemm::step_supported(in, Din, Din, hs, H, H, Wi, Wo, N)) {
-      // one launch per step: [x_t | h_{t-1}] [W_i2g | W_o2g]^T + b with the FastLSTM cell in the epilogue (gemm_tiled.hip);
-      // gate values are written only when a backward follows
-      ProfScope ps(h, "lstm_step_fwd");
-      ps.launches = T;
-      for (int t = 0; t < T; ++t)
-        gemm::lstm_step(s, in + (int64_t)t * N * Din, Din, Din, Wi, bi, t > 0 ? hs + (int64_t)(t - 1) * N * H : nullptr, Wo,
-                        t > 0 ? cs + (int64_t)(t - 1) * N * H : nullptr, cs + (int64_t)t * N * H, hs + (int64_t)t * N * H, H,
-                        save ? act + (int64_t)t * N * 4 * H : nullptr, N, H);
-      continue;
-    }
-    {
-      ProfScope ps(h, "gemm_i2g_fwd");
-      gemm::run(s, in, Din, 1, Wi, 1, Din, act, 4 * H, (int64_t)T * N, 4 * H, Din, false, bi, 1, bf);
-    }
-    for (int t = 0; t < T; ++t) {
-      float* act_t = act + (int64_t)t * N * 4 * H;
-      if (t > 0) {
-        ProfScope ps(h, "gemm_o2g_fwd");
-        gemm::run(s, hs + (int64_t)(t - 1) * N * H, H, 1, Wo, 1, H, act_t, 4 * H, N, 4 * H, H, true, nullptr, 1, bf);
-      }
-      ProfScope ps(h, "lstm_gates_fwd");
-      kk::lstm_gates_fwd(s, act_t, t > 0 ? cs + (int64_t)(t - 1) * N * H : nullptr, cs + (int64_t)t * N * H, hs + (int64_t)t * N * H, N, H);
-    }
-  }
-  {
-    ProfScope ps(h, "gemm_head_fwd");
-    const float* hT = w.Hs + ((int64_t)(L - 1) * T + (T - 1)) * N * H;
-    gemm::run(s, hT, H, 1, h->dense + h->off_outW, 1, H, w.S, c.C, N, c.C, H, false, h->dense + h->off_outb, 1, bf);
-  }
-}
-
 // every_class: also pooled / probs of all C classes (what kprn_forward_batch can hand out); else the selected class only
 static void pool_stage(kprn_handle* h, const kprn_batch* b, int cid, bool every_class) {
   const kprn_config& c = h->cfg;
@@ -503,13 +276,16 @@ static void check_batch(kprn_handle* h, const kprn_batch* b, int class_id) {
   KPRN_REQUIRE(class_id >= 1 && class_id <= h->cfg.C, KPRN_E_ARG, "classId must be in 1..C (nn.Select(2,classId), MyOptimizer.lua:126)");
 }
 
+// A TRAINING call runs on the fused path (forward + backward): the one statement of it, for use_fused and for det_check.
+// compute_dtype 0 (f32 MFMA), 2 (f32x6: exact fp32 products from bf16 pieces on the matrix cores) and 3: fused forward + fp32 backward; 1 (bf16 products): the
+// fused matrix-core forward for scoring only, the generic or bf16 pipeline for training.  Embedding ablations (dt = 0 / de = 0) run on the generic pipeline.
+static bool trains_fused(const kprn_handle* h, int T) {
+  const kprn_config& c = h->cfg;
+  return h->impl == 0 && c.rnn_type == 0 && c.compute_dtype != 1 && c.dt != 0 && c.de != 0 && fused::fwd_supported(h, T) && fused::bwd_supported(h, T);
+}
 static bool use_fused(kprn_handle* h, const kprn_batch* b, bool save_for_backward) {
-  if (h->impl != 0 || h->cfg.rnn_type != 0 || !fused::fwd_supported(h, b->T)) return false;
-  if (h->cfg.dt == 0 || h->cfg.de == 0) return false;  // embedding ablations run on the generic pipeline
-  // compute_dtype 0 (f32 MFMA) and 2 (f32x6: exact fp32 products from bf16 pieces on the matrix cores): fused forward + backward;
-  // 1 (bf16 products): the fused matrix-core forward for scoring, the generic pipeline for training
-  if (h->cfg.compute_dtype == 1) return !save_for_backward;  // (2, 3: forward on the matrix cores, fp32 backward)
-  return !save_for_backward || fused::bwd_supported(h, b->T);
+  if (save_for_backward) return trains_fused(h, b->T);
+  return h->impl == 0 && h->cfg.rnn_type == 0 && h->cfg.dt != 0 && h->cfg.de != 0 && fused::fwd_supported(h, b->T);
 }
 
 // all_scores: the caller reads S itself, every column of it (path_scores).  The fused fp32 forward's head forms column classId alone unless a reader of the pass
@@ -547,7 +323,7 @@ static void forward_impl(kprn_handle* h, const kprn_batch* b, int class_id, bool
     bf16p::forward(h, b, save_for_backward);
   } else {
     ensure_ws_generic(h, N, b->T);
-    forward_generic(h, b, save_for_backward);
+    generic::forward(h, b, save_for_backward);
   }
   if (do_pool) pool_stage(h, b, class_id - 1, every_class);
   h->last_B = b->B;
@@ -595,305 +371,6 @@ static void zero_grads(kprn_handle* h) {
   h->dense_grads_clean = true;
 }
 
-// Layer 0 of the generic LSTM / rnn backward through the small-table identity (kprn_internal.h kk::onehot_cols): dx for the entity slice only, ONE dW
-// product over [S | x_e] (the one-hot selectors are written over the last ns type columns of the saved step input, next to the entity columns),
-// the type / relation blocks of gW_i2g and both table gradients from G.  GH = rows of W_i2g (4H FastLSTM, H rnn).  Returns false when the shape is not
-// covered (the caller then takes the dx product + table-gradient route).
-static int small_tables_ns(const kprn_handle* h, const kprn_batch* b) {
-  const kprn_config& c = h->cfg;
-  const int ns = (c.Vr + c.Vt + 3) & ~3;
-  // (a dropped x_t is no sum of table rows, and the route overwrites type columns of the saved input, which the dropped dW product reads: DESIGN.md 3.12)
-  const bool ok = !h->drop_live && h->small_tables && c.num_types == 1 && c.rnn_type != 2 && ns <= c.dt && ns <= 128 && c.de > 0 && c.dr > 0 && b->key_sorted != nullptr && !b->tile_k &&
-                  b->F >= 3;
-  return ok ? ns : 0;
-}
-// the generic pipeline's entity gradient from row-major dx over the occurrence index; option "deterministic" = "2": the partial sums of runs that straddle
-// 64-position segments leave with plain stores and the launch behind adds them in segment order, as "1" does for the fused path's compact slice
-static void entity_grad_rowmajor(kprn_handle* h, const kprn_batch* b, const float* dx, int D, int dt) {
-  const kprn_config& c = h->cfg;
-  if (h->deterministic != 2) {
-    bidx::entity_grad(h->stream, dx, /*frag_order=*/0, b->key_sorted, b->pos_sorted, b->n_index, b->N, b->T, D, dt, c.de, c.Ve, h->g_We);
-    return;
-  }
-  const int64_t need = (b->n_index + 63) / 64 * 2 * c.de;
-  if (need > h->det_seg_cap) {
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    dfree(h->det_seg);
-    h->det_seg = dalloc<float>(need);
-    h->det_seg_cap = need;
-  }
-  const bidx::DetEntity de_{h->det_seg, nullptr};
-  bidx::entity_grad(h->stream, dx, /*frag_order=*/0, b->key_sorted, b->pos_sorted, b->n_index, b->N, b->T, D, dt, c.de, c.Ve, h->g_We, nullptr, nullptr, &de_);
-  bidx::entity_grad_tail(h->stream, b->key_sorted, b->n_index, c.de, c.Ve, h->g_We, de_, nullptr);
-}
-
-static void backward_layer0_small_tables(kprn_handle* h, const kprn_batch* b, int ns, int GH, int split, bool bf) {
-  const kprn_config& c = h->cfg;
-  Workspace& w = h->ws;
-  const int D = h->D, T = b->T;
-  const int64_t N = b->N, TN = (int64_t)T * N;
-  hipStream_t s = h->stream;
-  float* gd = h->g_dense;
-  const float* Wi = h->dense + h->layer[0].Wi;
-  const int NZ = ns + c.de;
-  if ((int64_t)GH * NZ > h->st_ctmp_cap) {
-    HIP_TRY(hipStreamSynchronize(s));
-    dfree(h->st_ctmp);
-    h->st_ctmp = dalloc<float>((int64_t)GH * NZ);
-    h->st_ctmp_cap = (int64_t)GH * NZ;
-  }
-  {
-    ProfScope ps(h, "gemm_bwd_dw_merged");   // Ct [GH][ns + de] = dA^T [S | x_e]
-    kk::onehot_cols(s, b->idx, N, T, b->F, c.Vr, c.Vt, w.X, D, c.dt - ns, ns);
-    HIP_TRY(hipMemsetAsync(h->st_ctmp, 0, (size_t)GH * NZ * sizeof(float), s));
-    gemm::run(s, w.dA, 1, GH, w.X + (c.dt - ns), D, 1, h->st_ctmp, NZ, GH, NZ, TN, true, nullptr, split, bf, false, h->deterministic == 2 ? &h->det_slab : nullptr);
-  }
-  {
-    ProfScope ps(h, "gemm_i2g_bwd_dx_e");    // dx_e [T N][de] = dA W_i2g[:, entity columns], compact
-    gemm::run(s, w.dA, GH, 1, Wi + c.dt, D, 1, w.dIn, c.de, TN, c.de, GH, false, nullptr, 1, bf);
-  }
-  {
-    ProfScope ps(h, "small_tables_finish");
-    kk::small_tables_finish(s, h->st_ctmp, ns, GH, D, c.dt, c.de, c.dr, c.Vt, c.Vr, h->dense + h->off_Wt, h->dense + h->off_Wr, Wi, gd + h->layer[0].Wi, gd + h->off_Wt,
-                            gd + h->off_Wr);
-  }
-  {
-    ProfScope ps(h, "entity_grad");
-    entity_grad_rowmajor(h, b, w.dIn, c.de, 0);
-  }
-}
-
-// scratch for W_o2g^T of the persistent BPTT launch (grow-only)
-static float* lp_wot_buffer(kprn_handle* h, int H, int GH) {
-  const int64_t need = (int64_t)lp32::bptt_scratch_floats(H, GH);
-  if (need > h->lp_wot_cap) {
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    dfree(h->lp_wot);
-    h->lp_wot = dalloc<float>(need);
-    h->lp_wot_cap = need;
-  }
-  return h->lp_wot;
-}
-
-static void backward_generic(kprn_handle* h, const kprn_batch* b, int cid) {
-  const kprn_config& c = h->cfg;
-  const bool bf = c.compute_dtype == 1;
-  Workspace& w = h->ws;
-  const int H = c.H, L = c.L, D = h->D, T = b->T;
-  const int64_t N = b->N;
-  hipStream_t s = h->stream;
-  float* gd = h->g_dense;
-  const int st_ns = small_tables_ns(h, b);   // > 0: layer 0's input gradients through the small-table identity
-  // option "deterministic" = "2" (FastLSTM and rnn cells; det_check has refused the rest): every join of partial sums below takes its slab form -- the producer
-  // plain-stores one slab per workgroup or K split into det's scratch, kk::slab_join behind it adds the slabs in index order
-  DetScratch* const det = (h->deterministic == 2 && c.rnn_type != 2) ? &h->det_slab : nullptr;
-  {
-    ProfScope ps(h, "head_bwd");
-    const float* hT = w.Hs + ((int64_t)(L - 1) * T + (T - 1)) * N * H;
-    kk::head_bwd(s, w.dS, hT, h->dense + h->off_outW, N, H, cid, w.dH, gd + h->off_outW, gd + h->off_outb, det);
-  }
-  HIP_TRY(hipMemsetAsync(w.dC, 0, (size_t)N * H * sizeof(float), s));
-  const int split = (int)std::min<int64_t>(1024, std::max<int64_t>(1, (T * N) / 2048));
-  if (c.rnn_type == 2) {
-    for (int l = L - 1; l >= 0; --l) {
-      const int Din = h->layer[l].Din;
-      const float* in = (l == 0) ? w.X : w.Hs + (int64_t)(l - 1) * T * N * H;
-      const float* act = w.ACT + (int64_t)l * T * N * 4 * H;
-      const float* hs = w.Hs + (int64_t)l * T * N * H;
-      const float* Wi = h->dense + h->layer[l].Wi;
-      const float* Wo = h->dense + h->layer[l].Wo;
-      const float* Wc = h->dense + h->layer[l].Wc;
-      const float* Uc = h->dense + h->layer[l].Uc;
-      const bool has_up = (l < L - 1);
-      const bool bptt2 = !bf && h->persist_layers && lp32::bptt_supported(2, N, H, h->persist_layers == 2);
-      if (bptt2) {
-        // the cell backward of all T steps and both recurrent products of a step (d(r h') = d pre_n c_h2h; dh' += [d pre_r | d pre_z] o2g) in ONE launch
-        ProfScope ps(h, "gru_layer_bwd");
-        lp32::bptt_layer(s, 2, act, nullptr, hs, nullptr, has_up ? w.dIn : w.dH, has_up, Wo, lp_wot_buffer(h, H, 3 * H), w.dA, N, T, H, 0, Uc, gd + h->layer[l].bi, gd + h->layer[l].bc);
-      } else if (has_up) HIP_TRY(hipMemsetAsync(w.dH, 0, (size_t)N * H * sizeof(float), s));
-      for (int t = T - 1; t >= 0 && !bptt2; --t) {
-        float* dA_t = w.dA + (int64_t)t * N * 4 * H;
-        const float* a_t = act + (int64_t)t * N * 4 * H;
-        const float* hp = t > 0 ? hs + (int64_t)(t - 1) * N * H : nullptr;
-        {
-          ProfScope ps(h, "gru_cell_bwd");
-          kk::gru_bwd1(s, a_t, hp, w.dH, has_up ? w.dIn + (int64_t)t * N * H : nullptr, dA_t, w.dC /* direct dh' path */, N, H);
-        }
-        if (t > 0) {
-          ProfScope ps(h, "gemm_o2g_bwd_dh");  // d(r*h') = d pre_n * c_h2h
-          gemm::run(s, dA_t + 2 * H, 4 * H, 1, Uc, H, 1, dA_t + 3 * H, 4 * H, N, H, H, false, nullptr, 1, bf);
-        }
-        {
-          ProfScope ps(h, "gru_cell_bwd");
-          kk::gru_bwd2(s, a_t, hp, dA_t, w.dC, w.dH, N, H);
-        }
-        if (t > 0) {
-          ProfScope ps(h, "gemm_o2g_bwd_dh");  // dh' += [d pre_r | d pre_z] * o2g
-          gemm::run(s, dA_t, 4 * H, 1, Wo, H, 1, w.dH, H, N, H, 2 * H, true, nullptr, 1, bf);
-        }
-      }
-      if (T > 1) {
-        ProfScope ps(h, "gemm_o2g_bwd_dw");
-        gemm::run(s, w.dA + (int64_t)N * 4 * H, 1, 4 * H, hs, H, 1, gd + h->layer[l].Wo, H, 2 * H, H, (int64_t)(T - 1) * N, true, nullptr, split, bf, /*untiled=*/true);
-        // c_h2h += d pre_n[1..T-1]^T (r*h')[1..T-1]
-        gemm::run(s, w.dA + (int64_t)N * 4 * H + 2 * H, 1, 4 * H, act + (int64_t)N * 4 * H + 3 * H, 4 * H, 1, gd + h->layer[l].Uc, H, H, H,
-                  (int64_t)(T - 1) * N, true, nullptr, split, bf);
-      }
-      // The input maps of the gates and of the candidate are two arrays (i2g.weight [2H][Din], c_i2h.weight [H][Din]) but ONE operand of the record's first 3H columns:
-      // one dW product into a zeroed [3H][Din] image (added to the two gradients behind it) and one dx product on a packed copy -- the [H][Din] halves alone fall below
-      // the tiled kernel's 256 rows, and the second dx product was a read-modify-write pass over dIn.
-      const int64_t cat = (int64_t)3 * H * Din;
-      if (2 * cat > h->st_ctmp_cap) {
-        HIP_TRY(hipStreamSynchronize(s));
-        dfree(h->st_ctmp);
-        h->st_ctmp = dalloc<float>(2 * cat);
-        h->st_ctmp_cap = 2 * cat;
-      }
-      float* wcat = h->st_ctmp;
-      float* gcat = h->st_ctmp + cat;
-      {
-        ProfScope ps(h, "gemm_i2g_bwd_dw");
-        HIP_TRY(hipMemsetAsync(gcat, 0, (size_t)cat * sizeof(float), s));
-        gemm::run(s, w.dA, 1, 4 * H, in, Din, 1, gcat, Din, 3 * H, Din, (int64_t)T * N, true, nullptr, split, bf, /*untiled=*/true);
-        kk::add_into(s, gd + h->layer[l].Wi, gcat, (int64_t)2 * H * Din);
-        kk::add_into(s, gd + h->layer[l].Wc, gcat + (int64_t)2 * H * Din, (int64_t)H * Din);
-      }
-      if (!bptt2) {   // (the persistent BPTT launch forms the sums itself)
-        ProfScope ps(h, "bias_colsum");
-        kk::col_sum_add(s, w.dA, (int64_t)T * N, 2 * H, gd + h->layer[l].bi, 4 * H);
-        kk::col_sum_add(s, w.dA + 2 * H, (int64_t)T * N, H, gd + h->layer[l].bc, 4 * H);
-      }
-      {
-        ProfScope ps(h, "gemm_i2g_bwd_dx");
-        HIP_TRY(hipMemcpyAsync(wcat, Wi, (size_t)2 * H * Din * sizeof(float), hipMemcpyDeviceToDevice, s));
-        HIP_TRY(hipMemcpyAsync(wcat + (int64_t)2 * H * Din, Wc, (size_t)H * Din * sizeof(float), hipMemcpyDeviceToDevice, s));
-        gemm::run(s, w.dA, 4 * H, 1, wcat, Din, 1, w.dIn, Din, (int64_t)T * N, Din, 3 * H, false, nullptr, 1, bf);
-      }
-    }
-  } else if (c.rnn_type == 1) {
-    const int relu = c.use_relu == 1 ? 1 : 0;
-    for (int l = L - 1; l >= 0; --l) {
-      const int Din = h->layer[l].Din;
-      // (dropout: the input the layer saw is the dropped one -- X holds it for layer 0, HsD for the layers above)
-      const float* in = (l == 0) ? w.X : (h->drop_live ? w.HsD : w.Hs) + (int64_t)(l - 1) * T * N * H;
-      const float* pre = w.ACT + (int64_t)l * T * N * H;
-      const float* hs = w.Hs + (int64_t)l * T * N * H;
-      const float* mask = w.mask + (int64_t)l * T * N;
-      const float* Wi = h->dense + h->layer[l].Wi;
-      const float* Wo = h->dense + h->layer[l].Wo;
-      const bool has_up = (l < L - 1);
-      const bool bptt1 = !bf && h->persist_layers && lp32::bptt_supported(1, N, H, h->persist_layers == 2);
-      if (bptt1) {
-        // the cell backward of all T steps + the recurrent gradient in ONE persistent launch (layer_f32_persist.hip k_bptt): dh never leaves the CU
-        ProfScope ps(h, "rnn_layer_bwd");
-        // (det: no bias sums inside the launch -- its workgroups join them with atomics; the column sum over dA below takes them)
-        lp32::bptt_layer(s, 1, nullptr, nullptr, hs, mask, has_up ? w.dIn : w.dH, has_up, Wo, lp_wot_buffer(h, H, H), w.dA, N, T, H, relu, nullptr,
-                         det ? nullptr : gd + h->layer[l].bi, det ? nullptr : gd + h->layer[l].bo);
-      } else if (has_up) HIP_TRY(hipMemsetAsync(w.dH, 0, (size_t)N * H * sizeof(float), s));
-      for (int t = T - 1; t >= 0 && !bptt1; --t) {
-        float* dA_t = w.dA + (int64_t)t * N * H;
-        {
-          ProfScope ps(h, "rnn_cell_bwd");
-          kk::rnn_cell_bwd(s, pre + (int64_t)t * N * H, hs + (int64_t)t * N * H, mask + (int64_t)t * N, has_up ? w.dIn + (int64_t)t * N * H : nullptr,
-                           w.dH, dA_t, N, H, relu);
-        }
-        if (t > 0) {
-          ProfScope ps(h, "gemm_o2g_bwd_dh");
-          gemm::run(s, dA_t, H, 1, Wo, H, 1, w.dH, H, N, H, H, false, nullptr, 1, bf);
-        }
-      }
-      if (T > 1) {
-        ProfScope ps(h, "gemm_o2g_bwd_dw");
-        gemm::run(s, w.dA + (int64_t)N * H, 1, H, hs, H, 1, gd + h->layer[l].Wo, H, H, H, (int64_t)(T - 1) * N, true, nullptr, split, bf, false, det);
-      }
-      if (det || !(bptt1 && lp32::bptt_sums_bias(1, H))) {   // (the persistent BPTT launch forms the sums itself)
-        ProfScope ps(h, "bias_colsum");  // i2h.bias and h2h.bias see the same gradient (both are added to every pre-activation)
-        kk::col_sum_add(s, w.dA, (int64_t)T * N, H, gd + h->layer[l].bi, 0, gd + h->layer[l].bo, det);   // (one pass over dA for both)
-      }
-      if (l == 0 && st_ns > 0) {
-        backward_layer0_small_tables(h, b, st_ns, H, split, bf);
-        return;
-      }
-      {
-        ProfScope ps(h, "gemm_i2g_bwd_dw");
-        gemm::run(s, w.dA, 1, H, in, Din, 1, gd + h->layer[l].Wi, Din, H, Din, (int64_t)T * N, true, nullptr, split, bf, false, det);
-      }
-      {
-        ProfScope ps(h, "gemm_i2g_bwd_dx");
-        gemm::run(s, w.dA, H, 1, Wi, Din, 1, w.dIn, Din, (int64_t)T * N, Din, H, false, nullptr, 1, bf);
-      }
-      if (h->drop_live) {
-        // the product is the gradient wrt the DROPPED input: times the regenerated m s it is the gradient from above of layer l - 1, or what the table
-        // gradients of layer 0 are formed from
-        ProfScope ps(h, "drop_rows_bwd");
-        kk::drop_rows(s, w.dIn, w.dIn, N, T, Din, drop_args(h, l));
-      }
-    }
-  } else
-  for (int l = L - 1; l >= 0; --l) {
-    const int Din = h->layer[l].Din;
-    const float* in = (l == 0) ? w.X : w.Hs + (int64_t)(l - 1) * T * N * H;
-    const float* act = w.ACT + (int64_t)l * T * N * 4 * H;
-    const float* hs = w.Hs + (int64_t)l * T * N * H;
-    const float* cs = w.Cs + (int64_t)l * T * N * H;
-    const float* Wi = h->dense + h->layer[l].Wi;
-    const float* Wo = h->dense + h->layer[l].Wo;
-    const bool has_up = (l < L - 1);
-    const bool bptt0 = !bf && h->persist_layers && lp32::bptt_supported(0, N, H, h->persist_layers == 2);
-    if (bptt0) {
-      // the cell backward of all T steps + the recurrent gradient in ONE persistent launch (layer_f32_persist.hip k_bptt): dh / dc never leave the CU
-      ProfScope ps(h, "lstm_layer_bwd");
-      lp32::bptt_layer(s, 0, act, cs, nullptr, nullptr, has_up ? w.dIn : w.dH, has_up, Wo, lp_wot_buffer(h, H, 4 * H), w.dA, N, T, H, 0, nullptr,
-                       det ? nullptr : gd + h->layer[l].bi);   // (det: the column sum over dA below takes the bias)
-    } else if (has_up) {
-      HIP_TRY(hipMemsetAsync(w.dH, 0, (size_t)N * H * sizeof(float), s));
-      HIP_TRY(hipMemsetAsync(w.dC, 0, (size_t)N * H * sizeof(float), s));
-    }
-    for (int t = T - 1; t >= 0 && !bptt0; --t) {
-      float* dA_t = w.dA + (int64_t)t * N * 4 * H;
-      {
-        ProfScope ps(h, "lstm_gates_bwd");
-        kk::lstm_gates_bwd(s, act + (int64_t)t * N * 4 * H, cs + (int64_t)t * N * H, t > 0 ? cs + (int64_t)(t - 1) * N * H : nullptr,
-                           has_up ? w.dIn + (int64_t)t * N * H : nullptr, w.dH, w.dC, dA_t, N, H);
-      }
-      if (t > 0) {
-        ProfScope ps(h, "gemm_o2g_bwd_dh");
-        gemm::run(s, dA_t, 4 * H, 1, Wo, H, 1, w.dH, H, N, H, 4 * H, false, nullptr, 1, bf);
-      }
-    }
-    if (T > 1) {
-      ProfScope ps(h, "gemm_o2g_bwd_dw");
-      // gWo[4H,H] += dA[1..T-1]^T * h[0..T-2]
-      gemm::run(s, w.dA + (int64_t)N * 4 * H, 1, 4 * H, hs, H, 1, gd + h->layer[l].Wo, H, 4 * H, H, (int64_t)(T - 1) * N, true, nullptr, split, bf, false, det);
-    }
-    if (det || !(bptt0 && lp32::bptt_sums_bias(0, H))) {   // (the persistent BPTT launch forms the sums itself)
-      ProfScope ps(h, "bias_colsum");
-      kk::col_sum_add(s, w.dA, (int64_t)T * N, 4 * H, gd + h->layer[l].bi, 0, nullptr, det);
-    }
-    if (l == 0 && st_ns > 0) {
-      backward_layer0_small_tables(h, b, st_ns, 4 * H, split, bf);
-      return;
-    }
-    {
-      ProfScope ps(h, "gemm_i2g_bwd_dw");
-      gemm::run(s, w.dA, 1, 4 * H, in, Din, 1, gd + h->layer[l].Wi, Din, 4 * H, Din, (int64_t)T * N, true, nullptr, split, bf, false, det);
-    }
-    {
-      ProfScope ps(h, "gemm_i2g_bwd_dx");
-      gemm::run(s, w.dA, 4 * H, 1, Wi, Din, 1, w.dIn, Din, (int64_t)T * N, Din, 4 * H, false, nullptr, 1, bf);
-    }
-  }
-  {
-    ProfScope ps(h, "embed_scatter");
-    const bool have_index = b->key_sorted != nullptr && !b->tile_k;  // (an index built for a prefix plan lives in the reordered path space)
-    kk::embed_scatter(s, b->idx, N, T, b->F, c.num_types, w.dIn, c.dt, c.de, c.dr, c.Vt, c.Vr, gd + h->off_Wt, h->g_We, gd + h->off_Wr, have_index, det);
-  }
-  if (b->key_sorted != nullptr && !b->tile_k) {
-    ProfScope ps(h, "entity_grad");
-    entity_grad_rowmajor(h, b, w.dIn, D, c.dt);
-  }
-}
-
 // the loss of the last backward = fixed-order sum of the loss stage's per-workgroup partials, formed on demand
 static void form_loss(kprn_handle* h) {
   if (h->loss_pending <= 0) return;
@@ -916,40 +393,34 @@ static void det_check(const kprn_handle* h, int T, const kprn_batch* b = nullptr
   if (!h->deterministic) return;
   const kprn_config& c = h->cfg;
   const char* why = nullptr;
-  if (h->deterministic == 1) {
+  // the fused path trains where use_fused(.., true) says so, under "2" exactly as under "1"
+  if (trains_fused(h, T)) why = det_fused_why(h);
+  else if (h->deterministic == 1) {
     if (h->impl != 0) why = "the generic pipeline (impl = generic: split-K atomics in its weight-gradient products)";
     else if (c.rnn_type != 0) why = "the rnn / gru pipeline";
     else if (c.compute_dtype == 1) why = "the bf16 pipeline (compute_dtype 1)";
-    else if (!fused::fwd_supported(h, T) || !fused::bwd_supported(h, T) || c.dt == 0 || c.de == 0)
-      why = "the generic pipeline (this shape is not the fused D = H = 64 path's: wide persistent layers / split-K products)";
-    else why = det_fused_why(h);
-    if (why) throw KprnError{KPRN_E_UNSUPPORTED, std::string("deterministic = 1: training would run on ") + why + ", which has no deterministic form; set deterministic = 0"};
-    return;
+    else why = "the generic pipeline (this shape is not the fused D = H = 64 path's: wide persistent layers / split-K products)";
   }
-  // "2".  The fused path trains where use_fused(.., true) says so: the same refusals as under "1" there
-  const bool fusedp = h->impl == 0 && c.rnn_type == 0 && c.compute_dtype != 1 && c.dt != 0 && c.de != 0 && fused::fwd_supported(h, T) && fused::bwd_supported(h, T);
-  if (fusedp) why = det_fused_why(h);
   else if (c.rnn_type == 2) why = "the gru pipeline";
   else if (c.compute_dtype == 1) why = "the bf16 pipeline or the generic pipeline's bf16 products (compute_dtype 1)";
   else if (c.compute_dtype != 0) why = "the generic pipeline with a compute_dtype other than 0";
   else {
     // the generic fp32 pipeline.  Layer 0's table gradients: the small-table identity (no sums across workgroups but the split-K product's), or the scatter route,
-    // whose one-hot products take tables of at most 128 rows x 128 columns (kernels_basic.hip table_grad_mfma; the kernels behind it have no deterministic form)
-    const int ns = (c.Vr + c.Vt + 3) & ~3;
+    // whose one-hot products take tables of at most 128 rows x 128 columns (kernels_basic.hip table_grad_mfma; the kernels behind it have no deterministic form).
+    // The handle's facts: this call's forward drops iff the option is on; a batch without the index is refused below whichever route it would take
     const bool will_drop = h->dropout_p > 0.f && c.rnn_type == 1;
-    const bool ident = !will_drop && h->small_tables && c.num_types == 1 && ns <= c.dt && ns <= 128 && c.de > 0 && c.dr > 0 && (!b || b->F >= 3);
-    if (!ident && !kk::embed_scatter_det_ok(c.dt, c.dr, c.Vt, c.Vr))
+    if (!generic::small_tables_route(h, b ? b->F : 3, will_drop, /*have_index=*/true) && !kk::embed_scatter_det_ok(c.dt, c.dr, c.Vt, c.Vr))
       why = "the generic pipeline's general embedding scatter (a type / relation table of more than 128 rows or a slice of more than 128 columns)";
     else if (b && c.de > 0 && (b->key_sorted == nullptr || b->tile_k))
       why = "the generic pipeline's entity scatter (a batch without the occurrence index, or with an identical-prefix plan)";
   }
-  if (why) throw KprnError{KPRN_E_UNSUPPORTED, std::string("deterministic = 2: training would run on ") + why + ", which has no deterministic form; set deterministic = 0"};
+  if (why) throw KprnError{KPRN_E_UNSUPPORTED, std::string(h->deterministic == 1 ? "deterministic = 1" : "deterministic = 2") + ": training would run on " + why + ", which has no deterministic form; set deterministic = 0"};
 }
 
 static void backward_impl(kprn_handle* h, const kprn_batch* b, int class_id, int literal, float inv_batch) {
   check_batch(h, b, class_id);
   det_check(h, b->T, b);
-  drop_check(h, b);
+  generic::drop_check(h, b);
   KPRN_REQUIRE(b->labels != nullptr && b->has_index, KPRN_E_ARG, "batch has no labels (targets are required, MyOptimizer.lua:179)");
   const kprn_config& c = h->cfg;
   zero_grads(h);
@@ -996,7 +467,7 @@ static void backward_impl(kprn_handle* h, const kprn_batch* b, int class_id, int
   //  and making the main stream wait for the pass's last workgroups cost 3 % of the step; apply_update joins before it writes parameters)
   if (fusedp) fused::backward(h, b, cid);
   else if (bf16p::supported(h, b)) bf16p::backward(h, b, cid);
-  else backward_generic(h, b, cid);
+  else generic::backward(h, b, cid);
   h->ent_grads_dirty = true;
   h->grads_serial = b->serial;
 }
@@ -2615,7 +2086,7 @@ int kprn_train_step_batch(kprn_handle* h, const kprn_batch* b, int32_t class_id,
   KPRN_REQUIRE(opt, KPRN_E_ARG, "opt is NULL");
   check_batch(h, b, class_id);
   det_check(h, b->T, b);
-  drop_check(h, b);
+  generic::drop_check(h, b);
   catch_up(h, b);
   if (!h->pad_clean) { zero_pad_tokens(h); fused::params_changed(h); bf16p::params_changed(h, false); }  // MyOptimizer.lua:181 (a no-op when the last step left them zero)
   // the loss goes back as soon as the loss stage has run (option "train_step_return" = "loss"); profiling and "drain" wait for the whole step as before

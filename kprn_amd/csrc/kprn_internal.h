@@ -240,7 +240,7 @@ struct kprn_handle {
   int persist_layers = 1;     // option "persist_layers": generic fp32 LSTM / rnn layers as one persistent launch per layer where the shape allows (layer_f32_persist.hip)
   bool small_tables_fwd = true;   // option "small_tables_fwd": the fused D = H = 64 forward multiplies [S | x_e] by [Q ; W_i2g[:, e cols]^T] in layer 0 (lstm_fused_fwd.hip fwd_body IDENT)
   bool head_select = true;        // option "head_select": the fused fp32 forward's head forms column classId alone when no reader of the pass needs another (lstm_fused_fwd.hip head_tile_sel)
-  bool small_tables = true;       // option "small_tables": generic fp32 pipelines (LSTM / rnn cells) form the layer-0 type / relation gradients from G (kprn_api.hip backward_generic)
+  bool small_tables = true;       // option "small_tables": generic fp32 pipelines (LSTM / rnn cells) form the layer-0 type / relation gradients from G (generic_pipeline.hip small_tables_route)
   float* lp_wot = nullptr; int64_t lp_wot_cap = 0;     // layer_f32_persist.hip: W_o2g^T of the layer whose BPTT launch is queued
   float* st_ctmp = nullptr; int64_t st_ctmp_cap = 0;   //   ... its [GH][ns + de] product result
   bool bf16_small_tables = true;  // option "bf16_small_tables": configs[3] backward forms the type / relation gradients from G = dA^T [S_r | S_t] (lstm_bf16.hip)
@@ -293,7 +293,7 @@ struct kprn_handle {
   float dropout_p = 0.f;
   uint64_t dropout_seed = 0;   // default cfg.seed + cfg.rank (kprn_create)
   uint32_t drop_draw = 0, drop_draw_cur = 0;
-  bool drop_live = false;      // the state saved by the last generic training forward was dropped (what backward_generic must undo)
+  bool drop_live = false;      // the state saved by the last generic training forward was dropped (what generic::backward must undo)
   float* det_norm_part = nullptr;   // [kk::SUMSQ_DET_BLOCKS] per-workgroup partials of the gradient norm
 
   bool prof_on = false;
@@ -621,6 +621,37 @@ void set_t_pad(int elements);      // (process-wide) pad of the transposed image
 void set_gemm_pingpong(bool on);   // (process-wide) the split-K bf16 products on the two-group 256 x 256 kernel (opt-in) or on k_gemm16x (default)   // ms per launch (kprn_debug_gemm what 5 / 6)
 }  // namespace bf16p
 
+// ---- fused D = H = 64 path (lstm_fused_*.hip): the host entry points ------------------------------------------------------------------
+namespace fused {
+bool fwd_supported(const kprn_handle* h, int T);
+void forward(kprn_handle* h, const kprn_batch* b, bool save, int64_t tile_begin = 0, int64_t tile_end = -1, bool ignore_reserve = false, int sel = -1);
+// small batches: tiles of ONE 16-row m-tile (four times as many workgroups, a quarter of the latency per tile); no identical-prefix plan
+bool small_tiles(const kprn_handle* h, int64_t N, bool has_plan);
+bool bwd_supported(const kprn_handle* h, int T);
+void backward(kprn_handle* h, const kprn_batch* b, int cid);
+void params_changed(kprn_handle* h);
+bool transpose_job(kprn_handle* h, kk::TransposeJob* tj);
+void prefix_forward(kprn_handle* h, const kprn_batch* b);
+bool forward_dual(kprn_handle* h, const kprn_batch* bt, const kprn_batch* bs, float* S_score, int sel_train, int sel_score);
+bool catch_up_with_prefix(kprn_handle* h, const kprn_batch* b, float* W, float* g, float* m, float* v, int32_t* last, int32_t t_now, const float* step_tab,
+                          float b1, float b2, float eps);
+void mc_prepare(kprn_handle* h);
+void forward_mc(kprn_handle* h, const kprn_batch* b, bool save);                     // (between the fused files)
+bool prefix_backward(kprn_handle* h, const kprn_batch* b, int64_t n_tiles);         // (between the fused files)
+void release(kprn_handle* h);
+void handover_stats(kprn_handle* h, const kprn_batch* b, int64_t* out /*[4]: pairs, steps moved, longest workgroup in half steps without / with*/);
+}  // namespace fused
+
+// ---- generic fp32 pipeline (generic_pipeline.hip): every shape the two above do not take -- rnn, wide FastLSTM, gru, impl = generic ----------------
+namespace generic {
+void forward(kprn_handle* h, const kprn_batch* b, bool save);
+void backward(kprn_handle* h, const kprn_batch* b, int cid);
+// > 0: layer 0's input gradients take the small-table identity (the number of one-hot selector columns); the ONE statement of the route's conditions
+int small_tables_route(const kprn_handle* h, int F, bool dropped, bool have_index);
+void drop_check(const kprn_handle* h, const kprn_batch* b);   // option "dropout": the mask generator's addressing limits; throws before anything is launched
+}  // namespace generic
+void ensure_ws_generic(kprn_handle* h, int64_t N, int T);   // kprn_api.hip: the workspace the generic and the bf16 pipeline share
+
 // ---- once per DEVICE -----------------------------------------------------------------------------------------
 // hipFuncSetAttribute (the raised dynamic-LDS limit of a kernel) applies to the CURRENT device: a `static bool done` guard is per process, and the second
 // GPU of a process (the data-parallel loopback and multichip tests hold several) then launches the kernel without it.  One bit per device ordinal.
@@ -661,6 +692,32 @@ inline hipError_t kprn_dev_malloc(void** p, size_t bytes) {
   }
   return e;
 }
+
+template <typename T>
+inline T* dalloc(int64_t n) {
+  void* p = nullptr;
+  if (n <= 0) n = 1;
+  // 64 bytes of slack: the tiled GEMMs fetch 16-byte vectors that may straddle the end of a matrix's last row (gemm_tiled.hip)
+  hipError_t e = kprn_dev_malloc(&p, (size_t)n * sizeof(T) + 64);
+  if (e != hipSuccess) throw KprnError{KPRN_E_NOMEM, std::string("hipMalloc failed: ") + hipGetErrorString(e)};
+  return (T*)p;
+}
+template <typename T>
+inline void dfree(T*& p) { if (p) { hipFree(p); p = nullptr; } }
+// Grow-only device scratch of the host code: need > cap -> drain the stream whose launches may still read the old block, free it, allocate `need` elements
+// (dev_grow) or twice that (dev_grow2: lists whose length creeps up batch by batch), set the capacity.  Returns the buffer.
+template <typename T>
+inline T* dev_grow(hipStream_t s, T*& p, int64_t& cap, int64_t need, int factor = 1) {
+  if (need > cap) {
+    HIP_TRY(hipStreamSynchronize(s));
+    dfree(p);
+    p = dalloc<T>(need * factor);
+    cap = need * factor;
+  }
+  return p;
+}
+template <typename T>
+inline T* dev_grow2(hipStream_t s, T*& p, int64_t& cap, int64_t need) { return dev_grow(s, p, cap, need, 2); }
 
 namespace hostfeed {
 struct Shape { int B, P, T, F, nT, Vt, Ve, Vr; };

@@ -17,7 +17,7 @@
 //     read under the MFMAs of group g.  K is padded to whole pairs of groups (pad columns of the LDS tile are zero; a weight row read past its end
 //     delivers the next row's finite values, times zero).
 //   * Saves (training) in the generic backward's own layouts -- gates [T][N][4H], c, h [T][N][H] (rnn: pre-activations [T][N][H]) -- so the
-//     backward of kprn_api.hip runs unchanged.
+//     backward of generic_pipeline.hip runs unchanged.
 #include <string.h>
 
 #include <algorithm>
@@ -474,7 +474,7 @@ __global__ __launch_bounds__(NTHR, 1) void k_layer(LArgs a) {
 
 // =====================================================================================================================================================
 // BPTT through one layer as ONE persistent launch: the cell backward of all T steps + the recurrent gradient dh_{t-1} = dA_t W_o2g, replacing per step one
-// element-wise launch (kk::lstm_gates_bwd / rnn_cell_bwd: saves in, dH / dC in and out, dA out) and one dh product launch (kprn_api.hip backward_generic).
+// element-wise launch (kk::lstm_gates_bwd / rnn_cell_bwd: saves in, dH / dC in and out, dA out) and one dh product launch (generic_pipeline.hip backward_steps).
 // dW and dx stay products over the dA this launch writes ([T][N][GH], the generic layout).
 //   * A workgroup owns a 64-path tile for t = T-1 .. 0; dc_t and dh live in registers, in the SAME lane layout as the forward's cell (lane (arow, ag) of wave w:
 //     path 16 i + arow, hidden units 64 c + 16 w + 4 ag .. + 3 -- rnn: 64 w + 16 q + 4 ag), because the product is taken transposed with the weight

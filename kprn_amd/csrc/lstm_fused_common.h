@@ -455,20 +455,8 @@ static inline State* st(kprn_handle* h) {
   return (State*)h->fused_state;
 }
 
-bool fwd_supported(const kprn_handle* h, int T);
-// small batches: tiles of ONE 16-row m-tile (four times as many workgroups, a quarter of the latency per tile); no identical-prefix plan
-constexpr int64_t SMALL_TILES_MAX_PATHS = 8192;
-bool small_tiles(const kprn_handle* h, int64_t N, bool has_plan);
-void handover_stats(kprn_handle* h, const kprn_batch* b, int64_t* out /*[4]: pairs, steps moved, longest workgroup in half steps without / with*/);
+// (the host entry points are declared in kprn_internal.h; here: what needs this header's types)
+constexpr int64_t SMALL_TILES_MAX_PATHS = 8192;   // fused::small_tiles
 HoArgs handover_args(kprn_handle* h, int grid);   // this launch's hand-over context (epoch 0: off)
-void prefix_forward(kprn_handle* h, const kprn_batch* b);
-bool forward_dual(kprn_handle* h, const kprn_batch* bt, const kprn_batch* bs, float* S_score, int sel_train, int sel_score);
-bool catch_up_with_prefix(kprn_handle* h, const kprn_batch* b, float* W, float* g, float* m, float* v, int32_t* last, int32_t t_now, const float* step_tab,
-                          float b1, float b2, float eps);
-void forward_mc(kprn_handle* h, const kprn_batch* b, bool save);
-void mc_prepare(kprn_handle* h);
-bool prefix_backward(kprn_handle* h, const kprn_batch* b, int64_t n_tiles);
-bool bwd_supported(const kprn_handle* h, int T);
-bool transpose_job(kprn_handle* h, kk::TransposeJob* tj);
 
 }  // namespace fused

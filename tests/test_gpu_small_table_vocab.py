@@ -3,7 +3,7 @@
 The routes place relation v at one-hot column v and type v at column Vr + v, ids 1-based:
   fused D = H = 64: forward identity (lstm_fused_fwd.hip fwd_body IDENT) and BPTT identity (lstm_fused_bwd.hip bwd_body IDENT, kk::small_tables_finish) while
   Vt + Vr <= 16; one-hot MFMAs inside the bottom BPTT launch ("fused_small_tables") or the passenger job of the entity-gradient launch (bidx::SmallGrad) while
-  Vt <= 16 and Vr <= 16; the scatter kernel above; generic fp32: merged dW over [S | x_e] while roundup4(Vr + Vt) <= dt (kprn_api.hip small_tables_ns);
+  Vt <= 16 and Vr <= 16; the scatter kernel above; generic fp32: merged dW over [S | x_e] while roundup4(Vr + Vt) <= dt (generic_pipeline.hip small_tables_route);
   bf16: merged dW while Vt + Vr <= 128 (lstm_bf16.hip).
 The rest of the suite runs them at Vt = 6, Vr in {9, 100} on synth.make_paths inputs, which never draw type Vt nor relation Vr - 2 (the #UNK rows): the last
 one-hot column, a full 16-row accumulator tile and both sides of every cut-off were never live.  Here the inputs come from tests/vocab_inputs.py

@@ -240,7 +240,7 @@ def test_ids_beyond_2_pow_24_gather_bit_exact():
 def test_generic_small_table_gradients_match_the_dx_route(kind, dims, L, Vr):
     """Round 5, generic fp32 pipelines: layer 0's type / relation gradients (tables and the matching column blocks of W_i2g) from G = dA^T [S_r | S_t]
     -- the one-hot selectors written over the last type columns of the saved step input, ONE dW product over [S | x_e], dx for the entity slice only
-    (kprn_api.hip backward_layer0_small_tables).  Same engine, same batch: against the full dx product + table-gradient launches
+    (generic_pipeline.hip backward_layer0_small_tables).  Same engine, same batch: against the full dx product + table-gradient launches
     ("small_tables" = 0) every gradient agrees to fp32 reordering; against the float64 oracle inside the fp32 bar."""
     dt, de, dr, H = dims
     rt = 1 if kind == "rnn" else 0
