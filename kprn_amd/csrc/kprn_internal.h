@@ -3,6 +3,7 @@
 #include <stdlib.h>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <exception>
 #include <functional>
 #include <future>
 #include <string>
@@ -234,7 +235,7 @@ struct kprn_handle {
   // caller asked for the loss); the flag is consumed by the NEXT kprn_train_step (dropin_prev_waited_now: valid during that call's feed only) and set again
   // only by a call that succeeded, so a failed call never lends its predecessor's guarantee to its successor.
   bool dropin_prev_waited = false, dropin_prev_waited_now = false; int inline_upload_side = 1;
-  bool inline_side_ok = true;   // (feed_impl: false when the handle still referred to the slot being refilled -- its rows are copied out in stream order first)
+  bool inline_side_ok = true;   // (slots::feed: false when the handle still referred to the slot being refilled -- its rows are copied out in stream order first)
   bool score_pending = false;     // a pass is (possibly) still running on score_stream
   int bf16_bptt_dxe = 8;          // option "bf16_bptt_dxe": the persistent BPTT launch also forms dx for the entity slice (weight ring depth 8 | 16; 0: a separate product)
   int persist_layers = 1;     // option "persist_layers": generic fp32 LSTM / rnn layers as one persistent launch per layer where the shape allows (layer_f32_persist.hip)
@@ -316,6 +317,54 @@ struct ProfScope {
 hipStream_t make_concurrent_stream(kprn_handle* h, int* probes = nullptr);   // a stream whose work runs BESIDE the main stream's (kprn_api.hip: probed, not assumed)
 void prof_drain(kprn_handle* h);
 void join_score(kprn_handle* h);  // main stream waits for the scoring pass on the side stream, if any
+
+// ---- the C ABI's frame: device selected, the hand-over fault checked, exceptions -> status + kprn_last_error ----------------
+#define API_BEGIN(h)                                   \
+  if (!(h)) return KPRN_E_ARG;                         \
+  try {                                                \
+    HIP_TRY(hipSetDevice((h)->cfg.device_id));         \
+    if ((h)->ho_fault && *(volatile int*)(h)->ho_fault) throw KprnError{KPRN_E_DEVICE, "a fused kernel's tile hand-over wait timed out: results since then are invalid"};
+#define API_END(h)                                                                        \
+  }                                                                                       \
+  catch (const KprnError& e) { (h)->err = e.msg; return e.code; }                         \
+  catch (const std::exception& e) { (h)->err = e.what(); return KPRN_E_DEVICE; }          \
+  catch (...) { (h)->err = "unknown error"; return KPRN_E_DEVICE; }                       \
+  return KPRN_OK;
+
+// ---- host waits for the handle's streams, each set named once.  nothrow: the destroy routes and the profiler ignore a failed wait ----
+inline void sync_stream(hipStream_t s, bool nothrow) { const hipError_t e = hipStreamSynchronize(s); if (!nothrow) HIP_TRY(e); }
+inline void sync_side_streams(kprn_handle* h, bool nothrow = false) {   // scoring, rest: where passes run beside the main stream
+  for (hipStream_t s : {h->score_stream, h->rest_stream}) if (s) sync_stream(s, nothrow);
+}
+inline void sync_compute_streams(kprn_handle* h, bool nothrow = false) { sync_side_streams(h, nothrow); sync_stream(h->stream, nothrow); }   // ... and main
+inline void sync_all_streams(kprn_handle* h, bool nothrow = false) {    // ... and the two that fill slots: nothing queued anywhere reads a slot afterwards
+  sync_compute_streams(h, nothrow);
+  for (hipStream_t s : {h->feed_stream, h->upload_stream}) if (s) sync_stream(s, nothrow);
+}
+// a non-blocking stream of the highest or the lowest priority (each priority class has hardware queues of its own)
+inline hipStream_t make_priority_stream(bool high) {
+  int lo = 0, hi = 0;   // (lo = the numerically largest value = the LOWEST priority)
+  hipStream_t s = nullptr;
+  HIP_TRY(hipDeviceGetStreamPriorityRange(&lo, &hi));
+  HIP_TRY(hipStreamCreateWithPriority(&s, hipStreamNonBlocking, high ? hi : lo));
+  return s;
+}
+
+// ---- kprn_api.hip, for the slot code ----------------------------------------------------------------------
+bool use_fused(kprn_handle* h, const kprn_batch* b, bool save_for_backward);   // this pass over b runs on the fused D = H = 64 path
+void launch_score_rest(kprn_handle* h);      // the deferred part of a split scoring pass goes out now (no-op when there is none)
+void materialize_step_rows(kprn_handle* h);  // the optimiser's row list stops being a view of a batch: copied to the handle's own storage
+// ---- batches and feed slots (batch_slots.hip): the lifecycle of a kprn_batch and the kprn_batch_* / kprn_host_* entry points ----------------
+namespace slots {
+// a new batch, ready on return (kprn_batch_create / _create_ragged); counts != null: ragged, N paths (P ignored); else B * P paths
+void create(kprn_handle* h, const int32_t* idx, const int32_t* counts, const float* labels, int32_t B, int32_t P, int64_t N, int32_t T, int32_t F, kprn_batch** out);
+// (re)fills *slot asynchronously (kprn_batch_feed_*_async); inline_now: derived on the calling thread (the host-buffer entry points)
+void feed(kprn_handle* h, kprn_batch** slot, const int32_t* idx, const float* labels, const int64_t* rows, int32_t B, int32_t P, int32_t T, int32_t F,
+          bool inline_now = false, const int32_t* counts = nullptr, int64_t n_ragged = 0);
+void ready(kprn_handle* h, const kprn_batch* b);   // first use of a fed slot: waits for its feed, takes the summary over; KPRN_E_INDEX for a bad id
+void release(kprn_batch* b);                       // frees a slot the handle no longer refers to, behind drained streams
+void scratch_reserve(void** scratch, size_t* bytes, size_t need);   // grow-only device scratch (twice the need); the caller has drained its stream
+}  // namespace slots
 
 // ---- kernels (kernels_basic.hip) -----------------------------------------------------------
 namespace kk {
