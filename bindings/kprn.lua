@@ -17,6 +17,7 @@ local ffi = require 'ffi'
 ffi.cdef[[
 typedef struct kprn_handle kprn_handle;
 typedef struct kprn_batch kprn_batch;
+typedef struct kprn_graph kprn_graph;
 typedef struct {
   int32_t Vt, Ve, Vr, dt, de, dr, F, num_types, H, L, C, rnn_type, use_relu, rnn_init, compute_dtype, reducer, K, device_id, rank, world;
   float param_init; uint64_t seed; void* stream;
@@ -83,6 +84,13 @@ int kprn_explain_batch(kprn_handle*, const kprn_batch*, int32_t, const int32_t*,
 int kprn_recommend_explain_ragged(kprn_handle*, const int32_t*, const int32_t*, int32_t, int64_t, int32_t, int32_t, int32_t, const int32_t*, int32_t, int32_t, int32_t, int32_t, int32_t*, float*, int32_t*, float*, float*, float*);
 int kprn_host_explain(const float*, const int32_t*, int32_t, int32_t, int32_t, int32_t, int32_t, const int32_t*, int32_t, int32_t, int32_t*, float*, float*, float*, float*);
 int kprn_host_dropout_keep(uint64_t, unsigned int, int32_t, int32_t, int64_t, int32_t, float, unsigned char*);
+/* path finder: a knowledge graph in HBM, a pair's paths as a ragged batch, the batch's ids back (include/kprn.h "finding a pair's paths") */
+int kprn_graph_create(kprn_handle*, const int32_t*, const int32_t*, const int32_t*, int64_t, const int32_t*, int32_t, kprn_graph**);
+void kprn_graph_destroy(kprn_handle*, kprn_graph*);
+int kprn_graph_num_edges(kprn_handle*, const kprn_graph*, int64_t*);
+int kprn_find_paths(kprn_handle*, const kprn_graph*, const int32_t*, const float*, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t*, int64_t*, kprn_batch**);
+int kprn_batch_read_idx(kprn_handle*, const kprn_batch*, int32_t*);
+int kprn_host_find_paths(const int32_t*, const int32_t*, const int32_t*, int64_t, const int32_t*, int32_t, int32_t, int32_t, int32_t, int32_t, const int32_t*, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t*, int64_t*, int32_t*);
 ]]
 
 local C = ffi.load('kprn')

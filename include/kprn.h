@@ -45,6 +45,7 @@ extern "C" {
 
 typedef struct kprn_handle kprn_handle;
 typedef struct kprn_batch kprn_batch;
+typedef struct kprn_graph kprn_graph;
 
 typedef enum {
   KPRN_OK = 0,
@@ -317,6 +318,46 @@ int kprn_recommend_explain_ragged(kprn_handle* h, const int32_t* idx, const int3
 int kprn_host_explain(const float* path_scores, const int32_t* offsets /* [B+1] */, int32_t B, int32_t C, int32_t class_id, int32_t reducer,
                       int32_t K_reducer, const int32_t* pairs, int32_t n_pairs, int32_t M, int32_t* path_idx, float* path_score, float* path_weight,
                       float* pooled, float* probs);
+
+/* ---- finding a pair's paths (an extension: the reference mines paths offline, data_prepare/path_find_depth_3.py, by random walks) ----
+ * From a knowledge graph to a ragged batch on the device: the graph lives in HBM as CSR, and kprn_find_paths enumerates -- exhaustively and
+ * deterministically, no sampling -- every path between B (user, item) pairs and lays the kept ones out as the rows of a ragged kprn_batch, which is
+ * accepted wherever a ragged batch is (scoring, kprn_explain_batch, board puts and ranking, training).
+ *  - vocabulary: nodes are the entity ids 1 .. Ve-1 (Ve is the pad row), relations 1 .. Vr, type ids 1 .. Vt, all the handle's.
+ *  - graph: directed edges (src[e], rel[e], dst[e]), e < E <= 2^31 - 1, in any order; the caller supplies inverse edges itself (rate / _rate, ...).  The build
+ *    sorts them by (src, dst, rel) and drops exact duplicates and self-loops.  node_types [Ve][num_types]: row e - 1 = the type-slot ids of entity e exactly as
+ *    the formatter prints them for a step (slots already padded with the type table's pad id); the pad entity's row (the last) is ignored.  end_relation: the
+ *    id of #END_RELATION.  An id outside its vocabulary is KPRN_E_INDEX and leaves no graph behind.
+ *  - path of h hops: u = n0 -> n1 -> ... -> nh = i, every (n_k, r_k, n_k+1) an edge, all nodes pairwise distinct (the miner's `mid_node not in path_set`);
+ *    u == i has no paths; two relations between the same two nodes give two paths.  1 <= min_hops <= max_hops <= 3: three hops is the reference's "depth 3"
+ *    (user-item-user-item).  Four and five hops need sampling to stay bounded and are NOT built: max_hops > 3 is KPRN_E_ARG.  min_hops = 2 keeps the direct
+ *    u-i edge out of a positive pair's paths.
+ *  - order within a pair (canonical): hops ascending, then the integer sequence (n1, r0, n2, r1, ..., r_{h-1}) ascending lexicographically.
+ *  - cap: found[b] = the number of paths that exist; the kept ones are the first counts[b] = min(found[b], max_paths) in that order, 1 <= max_paths <= 4096.
+ *    Nothing depends on timing: ranks come from a counting pass and prefix sums, never from an atomic counter.
+ *  - row of a kept path, [T][F], T >= max_hops + 1, as pathformat.py lays it out: T - (h + 1) steps of left padding (Vt x num_types, Ve, Vr), then step k < h =
+ *    (node_types[n_k], n_k, r_k) and the last step (node_types[i], i, end_relation).  Where F > num_types + 2 the leading columns, which no kernel reads and
+ *    the id validation does not look at, are written as Vt.
+ *  - result: counts [B] (zeros allowed) and found [B] on the host (either may be NULL); *out = a ragged batch of the B' pairs with counts > 0 in input order,
+ *    labels [B] (or NULL) compacted the same way; B' == 0: *out = NULL with KPRN_OK.  Synchronous.  A pair's node outside 1 .. Ve-1 is KPRN_E_INDEX.  If the
+ *    fill pass places another number of rows than the counting pass allotted a pair, the call returns KPRN_E_DEVICE and no batch; no write leaves the
+ *    pair's rows in either case.                                                                                                                    */
+int kprn_graph_create(kprn_handle* h, const int32_t* src, const int32_t* dst, const int32_t* rel, int64_t E, const int32_t* node_types /* [Ve][num_types] */,
+                      int32_t end_relation, kprn_graph** out);
+/* kprn_destroy frees the graphs still alive */
+void kprn_graph_destroy(kprn_handle* h, kprn_graph* g);
+/* edges the graph stores: E less the duplicates and self-loops */
+int kprn_graph_num_edges(kprn_handle* h, const kprn_graph* g, int64_t* n);
+int kprn_find_paths(kprn_handle* h, const kprn_graph* g, const int32_t* pairs /* [B][2] = (u, i) */, const float* labels /* [B] or NULL */, int32_t B,
+                    int32_t min_hops, int32_t max_hops, int32_t max_paths, int32_t T, int32_t* counts /* [B] */, int64_t* found /* [B] */, kprn_batch** out);
+/* a batch's ids [N][T][F] in the caller's path order, back on the host (to print the paths an explanation names); any batch, rectangular ([B*P][T][F]) or ragged */
+int kprn_batch_read_idx(kprn_handle* h, const kprn_batch* b, int32_t* idx_out);
+/* the same rule on the host cores over the graph's raw arrays (no handle, no GPU), on `threads` threads: counts [B], found [B] (or NULL), and idx = the
+ * [sum(counts)][T][F] rows of the pairs with counts > 0 in input order -- the ids kprn_batch_read_idx returns for kprn_find_paths' batch.  idx == NULL: it only
+ * counts (call it once for the sizes, once for the rows).  The refusals are kprn_graph_create's and kprn_find_paths'; F < num_types + 2 is KPRN_E_ARG.    */
+int kprn_host_find_paths(const int32_t* src, const int32_t* dst, const int32_t* rel, int64_t E, const int32_t* node_types, int32_t Ve, int32_t Vr, int32_t Vt,
+                         int32_t num_types, int32_t end_relation, const int32_t* pairs, int32_t B, int32_t min_hops, int32_t max_hops, int32_t max_paths,
+                         int32_t T, int32_t F, int32_t threads, int32_t* counts, int64_t* found, int32_t* idx);
 
 /* ---- training ---------------------------------------------------------------------- */
 /* fEval of MyOptimizer.lua:184-195: zeroGradParameters; forward; BCE; backward.

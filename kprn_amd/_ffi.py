@@ -177,6 +177,51 @@ def host_dropout_keep(seed, draw, layer, T, N, Din, p):
     return keep
 
 
+FIND_MAX_HOPS, FIND_MAX_PATHS = 3, 4096   # kprn_find_paths: hops per path, kept paths per pair
+
+
+def _graph_arrays(src, dst, rel, node_types):
+    src, dst, rel = (np.ascontiguousarray(a, np.int32).reshape(-1) for a in (src, dst, rel))
+    nt = np.ascontiguousarray(node_types, np.int32)
+    if not (src.shape == dst.shape == rel.shape) or nt.ndim != 2:
+        raise KprnError(E_ARG, "a graph is src / dst / rel [E] and node_types [Ve, num_types]")
+    return src, dst, rel, nt
+
+
+def _pairs_array(pairs, labels):
+    pr = np.ascontiguousarray(pairs, np.int32)
+    if pr.ndim != 2 or pr.shape[1] != 2 or pr.shape[0] < 1:
+        raise KprnError(E_ARG, "pairs must be [B, 2] = (user, item)")
+    lab = None if labels is None else np.ascontiguousarray(labels, np.float32)
+    if lab is not None and lab.shape != (pr.shape[0],):
+        raise KprnError(E_ARG, "labels must be [B]")
+    return pr, lab
+
+
+def host_find_paths(src, dst, rel, node_types, Vr, Vt, end_relation, pairs, min_hops, max_hops, max_paths, T, F=None, threads=1, want_idx=True):
+    """kprn_host_find_paths (no handle, no GPU): the finder's rule of include/kprn.h over the graph's raw arrays; Ve and num_types are node_types' shape ->
+    (idx [N,T,F] of the pairs with counts > 0 in input order, or None with want_idx=False; counts [B]; found [B])"""
+    src, dst, rel, nt = _graph_arrays(src, dst, rel, node_types)
+    pr, _ = _pairs_array(pairs, None)
+    Ve, num_types = int(nt.shape[0]), int(nt.shape[1])
+    F = num_types + 2 if F is None else int(F)
+    B = int(pr.shape[0])
+    counts, found = np.zeros(B, np.int32), np.zeros(B, np.int64)
+
+    def call(idx):
+        rc = lib().kprn_host_find_paths(_fp(src), _fp(dst), _fp(rel), C.c_int64(int(src.shape[0])), _fp(nt), Ve, int(Vr), int(Vt), num_types, int(end_relation),
+                                        _fp(pr), B, int(min_hops), int(max_hops), int(max_paths), int(T), F, int(threads), _fp(counts), _fp(found), _fp(idx))
+        if rc != 0:
+            raise KprnError(rc, "kprn_host_find_paths: bad graph ids / pairs / hops / max_paths / T / F")
+    call(None)
+    if not want_idx:
+        return None, counts, found
+    idx = np.zeros((int(counts.astype(np.int64).sum()), int(T), F), np.int32)
+    if idx.size:
+        call(idx)
+    return idx, counts, found
+
+
 def format_score_lines(counter0, probs, labels):
     """bytes of the scoring writer's lines for pairs counter0 .. (kprn_format_score_lines; host-only)"""
     L = lib()
@@ -219,6 +264,8 @@ def lib():
     L.kprn_destroy.argtypes = [C.c_void_p]
     L.kprn_batch_destroy.restype = None
     L.kprn_batch_destroy.argtypes = [C.c_void_p, C.c_void_p]
+    L.kprn_graph_destroy.restype = None
+    L.kprn_graph_destroy.argtypes = [C.c_void_p, C.c_void_p]
     L.kprn_host_alloc.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]
     L.kprn_host_free.argtypes = [C.c_void_p, C.c_void_p]
     _lib = L
@@ -351,9 +398,27 @@ class Batch:
                                                                    self.B, self.P, self.T, self.F))
         return self
 
+    @classmethod
+    def _adopt(cls, engine, ptr, counts, T, F, has_labels):
+        """the ragged batch a library call made (kprn_find_paths)"""
+        self = cls.__new__(cls)
+        self._attach(engine)
+        self.ptr = ptr
+        self.B, self.P = int(counts.shape[0]), 0
+        self.N, self.T, self.F = int(counts.astype(np.int64).sum()), int(T), int(F)
+        self.counts = counts
+        self.has_labels = has_labels
+        return self
+
     @property
     def n_paths(self):
         return self.N if getattr(self, "counts", None) is not None else self.B * self.P
+
+    def read_idx(self):
+        """kprn_batch_read_idx: the batch's ids [N,T,F] in the caller's path order, back on the host"""
+        out = np.empty((self.n_paths, self.T, self.F), np.int32)
+        self.engine._ck(self.engine.L.kprn_batch_read_idx(self.engine.h, self.ptr, _fp(out)))
+        return out
 
     @property
     def n_uniq(self):
@@ -389,6 +454,38 @@ class Batch:
             pass
 
 
+class Graph:
+    """A knowledge graph resident in HBM as CSR (kprn_graph_create): the input of Engine.find_paths."""
+
+    def __init__(self, engine, src, dst, rel, node_types, end_relation):
+        src, dst, rel, nt = _graph_arrays(src, dst, rel, node_types)
+        if nt.shape != (engine.cfg.Ve, engine.cfg.num_types):
+            raise KprnError(E_ARG, "node_types must be [Ve, num_types] of the engine")
+        self.engine = engine
+        self.ptr = C.c_void_p()
+        engine._graphs.add(self)
+        engine._ck(engine.L.kprn_graph_create(engine.h, _fp(src), _fp(dst), _fp(rel), C.c_int64(int(src.shape[0])), _fp(nt), int(end_relation), C.byref(self.ptr)))
+
+    @property
+    def n_edges(self):
+        """edges stored: the input's less duplicates and self-loops"""
+        n = C.c_int64()
+        self.engine._ck(self.engine.L.kprn_graph_num_edges(self.engine.h, self.ptr, C.byref(n)))
+        return int(n.value)
+
+    def free(self):
+        if self.ptr:
+            self.engine.L.kprn_graph_destroy(self.engine.h, self.ptr)
+            self.ptr = C.c_void_p()
+
+    def __del__(self):
+        try:
+            if self.engine.h:
+                self.free()
+        except Exception:
+            pass
+
+
 STREAM_LEGACY_DEFAULT = C.c_void_p(-1).value   # kprn_config.stream: queue on the legacy default (null) stream (KPRN_STREAM_LEGACY_DEFAULT)
 
 
@@ -400,6 +497,7 @@ class Engine:
                  rank=0, world=1, param_init=0.1, seed=12345, stream=None, use_relu=1, rnn_init=0, compute_dtype=0):
         self.L = lib()
         self._batches = weakref.WeakSet()
+        self._graphs = weakref.WeakSet()
         self.cfg = Config(Vt, Ve, Vr, dt, de, dr, F, num_types, H, L, C_, rnn_type, use_relu, rnn_init, compute_dtype, reducer, K, device_id, rank, world,
                           param_init, seed, stream)
         self.h = C.c_void_p()
@@ -423,6 +521,8 @@ class Engine:
         if self.h:
             for b in list(self._batches):   # (device blocks, page-locked images and events of batches the caller still holds)
                 b.free()
+            for g in list(self._graphs):
+                g.free()
             for p in getattr(self, "_pinned", []):
                 self.L.kprn_host_free(self.h, p)
             self._pinned = []
@@ -644,6 +744,24 @@ class Engine:
         self._ck(self.L.kprn_recommend_ragged(self.h, _fp(idx), _fp(counts), B, C.c_int64(int(idx.shape[0])), int(idx.shape[1]), int(idx.shape[2]),
                                               int(class_id), _fp(gc), G, int(mode), int(K), _fp(ti), _fp(ts), _fp(probs)))
         return ti, ts, probs
+
+    # -- path finder (include/kprn.h "finding a pair's paths") ---------------------------------
+    def graph(self, src, dst, rel, node_types, end_relation):
+        """kprn_graph_create: directed edges (src, rel, dst) [E] with 1-based ids, node_types [Ve, num_types] (row e - 1 = entity e's type slots)"""
+        return Graph(self, src, dst, rel, node_types, end_relation)
+
+    def find_paths(self, graph, pairs, min_hops, max_hops, max_paths, T, labels=None):
+        """kprn_find_paths: every path of min_hops .. max_hops (<= 3) hops between the pairs [B,2] = (user, item), the first max_paths per pair in the
+        canonical order -> (ragged Batch of the pairs that have paths, or None when none has; counts [B]; found [B])"""
+        pr, lab = _pairs_array(pairs, labels)
+        B = int(pr.shape[0])
+        counts, found = np.zeros(B, np.int32), np.zeros(B, np.int64)
+        ptr = C.c_void_p()
+        self._ck(self.L.kprn_find_paths(self.h, graph.ptr, _fp(pr), _fp(lab), B, int(min_hops), int(max_hops), int(max_paths), int(T), _fp(counts), _fp(found),
+                                        C.byref(ptr)))
+        if not ptr:
+            return None, counts, found
+        return Batch._adopt(self, ptr, counts[counts > 0].copy(), T, self.cfg.F, lab is not None), counts, found
 
     # -- explanation (include/kprn.h "explaining a recommendation") ---------------------------
     def explain_batch(self, batch, M, class_id=1, pairs=None, out=None):

@@ -120,11 +120,14 @@ void scratch_reserve(void** scratch, size_t* bytes, size_t need) {
 
 // upload + validation + identical-prefix plan + occurrence index on stream s; the host-side summary (validation flag, distinct
 // rows, plan header, per-tile prefix lengths) lands in the slot's pinned block behind them.  Nothing here waits for the device.
-static void enqueue(kprn_handle* h, kprn_batch* b, const int32_t* idx, const float* labels, hipStream_t s, void* scratch, size_t scratch_bytes) {
+// idx == null: the ids are produced on the device by fill, straight into the slot's idx block
+static void enqueue(kprn_handle* h, kprn_batch* b, const int32_t* idx, const float* labels, hipStream_t s, void* scratch, size_t scratch_bytes,
+                    const DeviceFill* fill = nullptr) {
   const int32_t B = b->B, T = b->T, F = b->F;
   const int64_t N = b->N, nsteps = N * T;
   const bool plan = b->kcap > 0;
-  HIP_TRY(hipMemcpyAsync(b->idx, idx, (size_t)nsteps * F * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  if (idx) HIP_TRY(hipMemcpyAsync(b->idx, idx, (size_t)nsteps * F * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  else (*fill)(b->idx, s);
   if (b->off) {   // ragged: offsets + workgroup table as the host derived them (kk::ragged_plan)
     HIP_TRY(hipMemcpyAsync(b->off, b->hrag.data(), (size_t)(B + 1) * sizeof(int32_t), hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(b->wg, b->hrag.data() + (B + 1), (size_t)(b->n_wg + 1) * sizeof(int32_t), hipMemcpyHostToDevice, s));
@@ -189,8 +192,9 @@ void ready(kprn_handle* h, const kprn_batch* cb) {
 
 // a fill's arguments, checked before a slot is touched.  counts != null: a ragged batch of N paths (P is ignored and comes back 0); its plan is derived here
 struct RaggedPlan { std::vector<int32_t> tab; int32_t sum[3] = {0, 0, 0}; };   // offsets [B+1] | workgroup table, and kk::ragged_plan's summary words
-static void check_fill(kprn_handle* h, const int32_t* idx, const int32_t* counts, int32_t B, int32_t* P, int64_t N, int32_t T, int32_t F, RaggedPlan* rp) {
-  KPRN_REQUIRE(idx, KPRN_E_ARG, "idx is NULL");
+static void check_fill(kprn_handle* h, const int32_t* idx, const int32_t* counts, int32_t B, int32_t* P, int64_t N, int32_t T, int32_t F, RaggedPlan* rp,
+                       bool on_device = false) {
+  KPRN_REQUIRE(idx || on_device, KPRN_E_ARG, "idx is NULL");
   if (!counts) KPRN_REQUIRE(B > 0 && *P > 0 && T > 0, KPRN_E_ARG, "B, P, T must be positive");
   else KPRN_REQUIRE(B > 0 && N >= B && T > 0, KPRN_E_ARG, "B, T must be positive and N >= B");
   KPRN_REQUIRE(F == h->cfg.F, KPRN_E_ARG, "F does not match numFeatureTemplates");
@@ -207,11 +211,12 @@ static void set_ragged(kprn_batch* b, RaggedPlan* rp) {
 }
 
 // a new batch, ready on return: built by the device kernels on the handle's stream.  counts != null: ragged, N paths (P is ignored); else B * P paths
+// fill != null (and idx null): the ids come from the device (kprn_internal.h DeviceFill)
 void create(kprn_handle* h, const int32_t* idx, const int32_t* counts, const float* labels, int32_t B, int32_t P, int64_t N, int32_t T, int32_t F,
-            kprn_batch** out) {
+            kprn_batch** out, const DeviceFill* fill) {
   *out = nullptr;
   RaggedPlan rp;
-  check_fill(h, idx, counts, B, &P, N, T, F, &rp);
+  check_fill(h, idx, counts, B, &P, N, T, F, &rp, fill != nullptr);
   if (!counts) N = (int64_t)B * P;
   kprn_batch* b = new kprn_batch();
   try {
@@ -219,7 +224,7 @@ void create(kprn_handle* h, const int32_t* idx, const int32_t* counts, const flo
     if (counts) set_ragged(b, &rp);
     b->has_index = true; b->idx_valid = true;
     scratch_reserve(&h->bidx_scratch, &h->bidx_scratch_bytes, std::max(bidx::scratch_bytes(b->n_index, h->cfg.Ve), bidx::prefix_scratch_bytes(N, fused::KCAP)));
-    enqueue(h, b, idx, labels, h->stream, h->bidx_scratch, h->bidx_scratch_bytes);
+    enqueue(h, b, idx, labels, h->stream, h->bidx_scratch, h->bidx_scratch_bytes, fill);
     HIP_TRY(hipStreamSynchronize(h->stream));
     finish(h, b);
   } catch (...) {
@@ -477,6 +482,26 @@ int kprn_batch_num_paths(kprn_handle* h, const kprn_batch* b, int64_t* n) {
   API_BEGIN(h)
   KPRN_REQUIRE(b && n, KPRN_E_ARG, "NULL argument");
   *n = b->N;
+  API_END(h)
+}
+
+int kprn_batch_read_idx(kprn_handle* h, const kprn_batch* b, int32_t* idx_out) {
+  API_BEGIN(h)
+  KPRN_REQUIRE(b && idx_out, KPRN_E_ARG, "NULL argument");
+  slots::ready(h, b);
+  const int64_t N = b->N, row = (int64_t)b->T * b->F;
+  if (b->idx_valid) {
+    HIP_TRY(hipMemcpyAsync(idx_out, b->idx, (size_t)(N * row) * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+  } else {
+    // (a label-less fed batch with a plan keeps the reordered ids only: path perm[s] is row s of idx_s)
+    KPRN_REQUIRE(b->idx_s && b->perm, KPRN_E_ARG, "the batch holds no ids");
+    std::vector<int32_t> rows((size_t)(N * row)), perm((size_t)N);
+    HIP_TRY(hipMemcpyAsync(rows.data(), b->idx_s, rows.size() * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(perm.data(), b->perm, perm.size() * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    for (int64_t s = 0; s < N; ++s) memcpy(idx_out + (int64_t)perm[s] * row, rows.data() + s * row, (size_t)row * sizeof(int32_t));
+  }
   API_END(h)
 }
 

@@ -75,6 +75,8 @@ struct DetScratch { float* p = nullptr; int64_t cap = 0; };
 
 namespace fused { constexpr int KCAP = 8; }  // longest identical prefix the fused kernels skip (lstm_fused_common.h)
 
+struct kprn_graph;   // path_find.hip
+
 struct kprn_batch {
   int32_t B, P, T, F;
   int64_t N = 0;              // paths of the batch: B*P, or sum of the counts of a ragged batch
@@ -282,6 +284,8 @@ struct kprn_handle {
   void* rank_pin = nullptr; size_t rank_pin_bytes = 0, rank_pin_off[2] = {0, 0};   // page-locked group table and top-K rows of kprn_recommend_ragged
   void* explain_buf = nullptr; size_t explain_buf_bytes = 0;   // device pair list and results of one kprn_explain_batch call
   void* explain_pin = nullptr; size_t explain_pin_bytes = 0;   // page-locked explanation rows of kprn_recommend_explain_ragged
+  std::vector<kprn_graph*> graphs;                     // path_find.hip: the knowledge graphs alive on this handle (kprn_destroy frees what is left)
+  void* pf_buf = nullptr; size_t pf_buf_bytes = 0;     // device arguments of one kprn_find_paths call (pairs, totals, first rows, counts, flag)
 
   // option "deterministic": every float sum of a training step whose addends come from different waves or workgroups of one launch is formed in an order that
   // depends on the batch and the launch geometry only; pipelines that cannot do that refuse to train
@@ -356,8 +360,12 @@ void launch_score_rest(kprn_handle* h);      // the deferred part of a split sco
 void materialize_step_rows(kprn_handle* h);  // the optimiser's row list stops being a view of a batch: copied to the handle's own storage
 // ---- batches and feed slots (batch_slots.hip): the lifecycle of a kprn_batch and the kprn_batch_* / kprn_host_* entry points ----------------
 namespace slots {
-// a new batch, ready on return (kprn_batch_create / _create_ragged); counts != null: ragged, N paths (P ignored); else B * P paths
-void create(kprn_handle* h, const int32_t* idx, const int32_t* counts, const float* labels, int32_t B, int32_t P, int64_t N, int32_t T, int32_t F, kprn_batch** out);
+// ids that are already on the device: fill(idx_dev, s) queues on s whatever writes the batch's [N,T,F] ids into the slot's idx block (kprn_find_paths)
+typedef std::function<void(int32_t* idx_dev, hipStream_t s)> DeviceFill;
+// a new batch, ready on return (kprn_batch_create / _create_ragged); counts != null: ragged, N paths (P ignored); else B * P paths.  idx == null with
+// fill: nothing is uploaded, fill writes the ids, and validation, prefix plan and occurrence index run over them where they are
+void create(kprn_handle* h, const int32_t* idx, const int32_t* counts, const float* labels, int32_t B, int32_t P, int64_t N, int32_t T, int32_t F, kprn_batch** out,
+            const DeviceFill* fill = nullptr);
 // (re)fills *slot asynchronously (kprn_batch_feed_*_async); inline_now: derived on the calling thread (the host-buffer entry points)
 void feed(kprn_handle* h, kprn_batch** slot, const int32_t* idx, const float* labels, const int64_t* rows, int32_t B, int32_t P, int32_t T, int32_t F,
           bool inline_now = false, const int32_t* counts = nullptr, int64_t n_ragged = 0);
@@ -485,6 +493,11 @@ int validate(int64_t n_scores, const int64_t* members, const int64_t* goff, cons
              int* max_n, std::string* why);
 void launch(hipStream_t s, const Args& a, int max_n);   // hist must be zero; every group is ranked by exactly one of the two kernels
 }  // namespace rk
+
+// ---- path finder (path_find.hip): kprn_graph_* / kprn_find_paths / kprn_host_find_paths ---------------
+namespace pf {
+void release_all(kprn_handle* h);   // kprn_destroy: the graphs still alive and the finder's argument buffer
+}  // namespace pf
 
 // ---- explanation stage (explain_paths.hip) -------------------------------------------------------
 namespace ex {

@@ -1,0 +1,607 @@
+// Path finder (include/kprn.h "finding a pair's paths"): a knowledge graph as CSR in HBM, and for B (user, item) pairs every path of min_hops .. max_hops <= 3
+// hops between them, laid out as the rows of a ragged kprn_batch.  Integers only; no float, no atomics that hand out output slots, no LDS beyond the
+// workgroup's scan.
+//
+// One definition of the rule serves the kernels and the host twin (namespace pf, __host__ __device__):
+//   graph   edges sorted by (src, dst, rel), exact duplicates and self-loops dropped; rowptr [Ve + 1] by 1-based node id
+//   path    u = n0 -> n1 -> ... -> nh = i over edges, all nodes pairwise distinct (u == i: none); two relations between the same nodes are two paths
+//   order   hops ascending, then (n1, r0, n2, r1, ..., r_{h-1}) lexicographically = the depth-first order of the sorted CSR.  The paths of h >= 2 hops are
+//           grouped by their first edge e0 (u's adjacency, in order): subtree_count gives the group's sizes, subtree_fill writes its rows in order
+//   rank    of a path = (paths of fewer hops) + (paths of the same hops under earlier first edges) + its place under its own first edge
+// Device: one 256-thread workgroup per pair.  In a user-item graph u's adjacency is short and n1's (a popular item's raters) is long, so the 3-hop work is
+// spread over the SECOND edges: every closing-edge search (edge_range of n2 -> i) is one lane's.
+//   k_count   the pair's totals per hop -> tot [B][4] = {1 hop, 2 hops, 3 hops, found}: 2 hops a thread per first edge, 3 hops a wave per first edge with its
+//             lanes over the second edges.  The host turns them into counts = min(found, max_paths), compacts the pairs that have paths and scans the
+//             counts into each pair's first row
+//   k_fill    ranks by prefix sums in the workgroup (Hillis-Steele in LDS, int64): 2 hops over 256 first edges at a time; 3 hops first edge by first edge,
+//             256 second edges at a time, a running rank carried from chunk to chunk.  A thread writes the rows of its own first / second edge at their ranks
+//             while rank < counts[b] -- the range the pair was allotted -- and a hop's chunks stop once the running rank reaches it (with a cap of 28 the fill
+//             pass touches a few chunks, whatever found is).  The rows a workgroup placed are summed and compared with counts[b]: a disagreement between
+//             the passes sets the flag (KPRN_E_DEVICE), and no write leaves the pair's range either way.
+// The host twin walks the same primitives (edge_range, mid_range, write_row) pair by pair on its threads.
+#include "kprn_internal.h"
+
+#include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_select.hpp>
+
+#include <algorithm>
+#include <atomic>
+#include <thread>
+#include <tuple>
+
+struct kprn_graph {
+  int32_t Ve = 0, Vr = 0, Vt = 0, nT = 0, end_rel = 0;
+  int64_t E = 0;                 // stored edges (after duplicates and self-loops are gone)
+  int32_t* rowptr = nullptr;     // device [Ve + 1]: edges of node n = rowptr[n] .. rowptr[n + 1] - 1 (n = 0 has none)
+  int32_t* col = nullptr;        // device [E] destination
+  int32_t* rel = nullptr;        // device [E] relation
+  int32_t* types = nullptr;      // device [Ve][nT]: row e - 1 = the type slots of entity e
+};
+
+namespace pf {
+
+struct Csr { const int32_t* rowptr; const int32_t* col; const int32_t* rel; };
+struct Fmt { const int32_t* types; int nT, Vt, Ve, Vr, T, F, end_rel; };
+constexpr int TPB = 256;
+
+// the edges n -> target: [lo, hi) (contiguous, relation ascending)
+__host__ __device__ static inline void edge_range(const Csr& g, int n, int target, int& lo, int& hi) {
+  const int a = g.rowptr[n], b = g.rowptr[n + 1];
+  int l = a, r = b;
+  while (l < r) { const int m = l + ((r - l) >> 1); if (g.col[m] < target) l = m + 1; else r = m; }
+  lo = l;
+  r = b;
+  while (l < r) { const int m = l + ((r - l) >> 1); if (g.col[m] <= target) l = m + 1; else r = m; }
+  hi = l;
+}
+
+// the closing edges of the 3-hop paths u -> n1 -> col[e1] -> i: their number, the first one in lo; none when the middle node repeats u, i or n1
+__host__ __device__ static inline int mid_range(const Csr& g, int u, int i, int n1, int e1, int& lo) {
+  const int n2 = g.col[e1];
+  lo = 0;
+  if (n2 == u || n2 == i || n2 == n1) return 0;
+  int hi;
+  edge_range(g, n2, i, lo, hi);
+  return hi - lo;
+}
+
+// paths of 2 / 3 hops whose first edge is e0 (want2 / want3: the hop is asked for)
+__host__ __device__ static inline void subtree_count(const Csr& g, int u, int i, int e0, bool want2, bool want3, int64_t& c2, int64_t& c3) {
+  c2 = 0; c3 = 0;
+  const int n1 = g.col[e0];
+  if (n1 == u || n1 == i) return;
+  int lo, hi;
+  if (want2) { edge_range(g, n1, i, lo, hi); c2 = hi - lo; }
+  if (!want3) return;
+  const int end = g.rowptr[n1 + 1];
+  for (int e1 = g.rowptr[n1]; e1 < end; ++e1) c3 += mid_range(g, u, i, n1, e1, lo);
+}
+
+// one path's [T][F] row: left padding (Vt .., Ve, Vr), then (types of n_k, n_k, r_k), the last step with #END_RELATION; leading columns = Vt
+__host__ __device__ static inline void write_row(const Fmt& f, int32_t* row, int h, const int* nodes, const int* rels) {
+  const int pad = f.T - (h + 1), lead = f.F - f.nT - 2;
+  for (int t = 0; t < f.T; ++t) {
+    int32_t* s = row + t * f.F;
+    const int k = t - pad;
+    for (int c = 0; c < lead; ++c) s[c] = f.Vt;
+    if (k < 0) {
+      for (int c = 0; c < f.nT; ++c) s[lead + c] = f.Vt;
+      s[f.F - 2] = f.Ve; s[f.F - 1] = f.Vr;
+    } else {
+      const int n = nodes[k];
+      for (int c = 0; c < f.nT; ++c) s[lead + c] = f.types[(int64_t)(n - 1) * f.nT + c];
+      s[f.F - 2] = n; s[f.F - 1] = k < h ? rels[k] : f.end_rel;
+    }
+  }
+}
+
+// the first room1 paths of 1 hop among the edges lo + first, lo + first + step, ... of [lo, hi), each at its rank; returns the rows written
+__host__ __device__ static inline int hop1_fill(const Csr& g, const Fmt& f, int u, int i, int lo, int hi, int first, int step, int64_t room1, int32_t* out) {
+  int placed = 0;
+  const int64_t row = (int64_t)f.T * f.F;
+  for (int64_t j = first; j < hi - lo && j < room1; j += step) {
+    const int nodes[2] = {u, i}, rels[1] = {g.rel[lo + j]};
+    write_row(f, out + j * row, 1, nodes, rels);
+    ++placed;
+  }
+  return placed;
+}
+
+// the rows of first edge e0 in order: at most room2 paths of 2 hops from out2 on, at most room3 of 3 hops from out3 on; returns the rows written
+__host__ __device__ static inline int subtree_fill(const Csr& g, const Fmt& f, int u, int i, int e0, int64_t room2, int64_t room3, int32_t* out2, int32_t* out3) {
+  const int n1 = g.col[e0];
+  if (n1 == u || n1 == i) return 0;
+  const int64_t row = (int64_t)f.T * f.F;
+  int placed = 0, lo, hi;
+  if (room2 > 0) {
+    edge_range(g, n1, i, lo, hi);
+    for (int e = lo; e < hi && room2 > 0; ++e, --room2) {
+      const int nodes[3] = {u, n1, i}, rels[2] = {g.rel[e0], g.rel[e]};
+      write_row(f, out2, 2, nodes, rels);
+      out2 += row; ++placed;
+    }
+  }
+  if (room3 > 0) {
+    const int end = g.rowptr[n1 + 1];
+    for (int e1 = g.rowptr[n1]; e1 < end && room3 > 0; ++e1) {
+      hi = mid_range(g, u, i, n1, e1, lo) + lo;
+      for (int e = lo; e < hi && room3 > 0; ++e, --room3) {
+        const int nodes[4] = {u, n1, g.col[e1], i}, rels[3] = {g.rel[e0], g.rel[e1], g.rel[e]};
+        write_row(f, out3, 3, nodes, rels);
+        out3 += row; ++placed;
+      }
+    }
+  }
+  return placed;
+}
+
+__host__ __device__ static inline int64_t room(int64_t cap, int64_t rank) { return rank < cap ? cap - rank : 0; }
+
+// ---- kernels ---------------------------------------------------------------------------------------------------------------------------------
+// sum over the workgroup; every thread gets it.  sh [TPB]
+__device__ static inline int64_t block_sum(int64_t v, int64_t* sh) {
+  __syncthreads();   // (sh may still be read from the previous use)
+  sh[threadIdx.x] = v;
+  __syncthreads();
+  for (int d = TPB / 2; d > 0; d >>= 1) {
+    if ((int)threadIdx.x < d) sh[threadIdx.x] += sh[threadIdx.x + d];
+    __syncthreads();
+  }
+  return sh[0];
+}
+// exclusive prefix over the workgroup in thread order; total = the sum.  sh [TPB]
+__device__ static inline int64_t block_scan_excl(int64_t v, int64_t* sh, int64_t& total) {
+  __syncthreads();
+  sh[threadIdx.x] = v;
+  __syncthreads();
+  for (int d = 1; d < TPB; d <<= 1) {
+    const int64_t t = (int)threadIdx.x >= d ? sh[threadIdx.x - d] : 0;
+    __syncthreads();
+    sh[threadIdx.x] += t;
+    __syncthreads();
+  }
+  total = sh[TPB - 1];
+  return sh[threadIdx.x] - v;
+}
+
+__global__ __launch_bounds__(TPB) void k_count(Csr g, const int32_t* __restrict__ pairs, int hmask, int64_t* __restrict__ tot) {
+  __shared__ int64_t sh[TPB];
+  const int b = blockIdx.x, u = pairs[2 * b], i = pairs[2 * b + 1];
+  int64_t c1 = 0, c2 = 0, c3 = 0;
+  if (u != i) {   // (workgroup-uniform)
+    int lo, hi;
+    if (hmask & 1) { edge_range(g, u, i, lo, hi); c1 = hi - lo; }
+    const int end = g.rowptr[u + 1];
+    if (hmask & 2) {   // a thread per first edge: one search each
+      for (int e0 = g.rowptr[u] + threadIdx.x; e0 < end; e0 += TPB) {
+        int64_t a2, a3;
+        subtree_count(g, u, i, e0, true, false, a2, a3);
+        c2 += a2;
+      }
+      c2 = block_sum(c2, sh);
+    }
+    if (hmask & 4) {   // a wave per first edge, its lanes over the second edges: the long adjacency of a popular n1 is 64 searches wide
+      const int lane = threadIdx.x & 63;
+      for (int e0 = g.rowptr[u] + (threadIdx.x >> 6); e0 < end; e0 += TPB / 64) {
+        const int n1 = g.col[e0];
+        if (n1 == u || n1 == i) continue;   // (wave-uniform)
+        const int end1 = g.rowptr[n1 + 1];
+        for (int e1 = g.rowptr[n1] + lane; e1 < end1; e1 += 64) { int lo; c3 += mid_range(g, u, i, n1, e1, lo); }
+      }
+      c3 = block_sum(c3, sh);
+    }
+  }
+  if (threadIdx.x == 0) { tot[4 * (int64_t)b] = c1; tot[4 * (int64_t)b + 1] = c2; tot[4 * (int64_t)b + 2] = c3; tot[4 * (int64_t)b + 3] = c1 + c2 + c3; }
+}
+
+// first [b]: the pair's first row in idx (-1: the pair has no paths and owns nothing); cnt [b]: the rows it was allotted
+__global__ __launch_bounds__(TPB) void k_fill(Csr g, Fmt f, const int32_t* __restrict__ pairs, int hmask, const int64_t* __restrict__ tot,
+                                              const int64_t* __restrict__ first, const int32_t* __restrict__ cnt, int32_t* __restrict__ idx, int32_t* flag) {
+  __shared__ int64_t sh[TPB];
+  const int b = blockIdx.x;
+  const int64_t off = first[b];
+  if (off < 0) return;   // (workgroup-uniform)
+  const int u = pairs[2 * b], i = pairs[2 * b + 1];
+  const int64_t cap = cnt[b], row = (int64_t)f.T * f.F;
+  const int64_t base2 = tot[4 * (int64_t)b], base3 = base2 + tot[4 * (int64_t)b + 1];
+  int32_t* out = idx + off * row;
+  int64_t placed = 0;
+  if (hmask & 1) {
+    int lo, hi;
+    edge_range(g, u, i, lo, hi);
+    placed += hop1_fill(g, f, u, i, lo, hi, threadIdx.x, TPB, cap, out);
+  }
+  const int end = g.rowptr[u + 1];
+  // 2 hops: a thread per first edge, 256 first edges at a time; done2 = the paths under earlier chunks (workgroup-uniform, like every loop bound below)
+  if ((hmask & 2) && base2 < cap) {
+    int64_t done2 = 0;
+    for (int e_base = g.rowptr[u]; e_base < end && base2 + done2 < cap; e_base += TPB) {
+      const int e0 = e_base + threadIdx.x;
+      int64_t c2 = 0, c3, sum2;
+      if (e0 < end) subtree_count(g, u, i, e0, true, false, c2, c3);
+      const int64_t r2 = base2 + done2 + block_scan_excl(c2, sh, sum2);
+      // (a rank at or past the cap has no room; out + rank * row is formed only for a rank below it)
+      if (c2 && r2 < cap) placed += subtree_fill(g, f, u, i, e0, cap - r2, 0, out + r2 * row, out);
+      done2 += sum2;
+    }
+  }
+  // 3 hops: the first edges in order, the workgroup's threads over the second edges 256 at a time; a thread writes the paths through its second edge
+  if ((hmask & 4) && base3 < cap) {
+    int64_t run3 = base3;   // rank of the next chunk's first path
+    for (int e0 = g.rowptr[u]; e0 < end && run3 < cap; ++e0) {
+      const int n1 = g.col[e0];
+      if (n1 == u || n1 == i) continue;
+      const int end1 = g.rowptr[n1 + 1];
+      for (int e1_base = g.rowptr[n1]; e1_base < end1 && run3 < cap; e1_base += TPB) {
+        const int e1 = e1_base + threadIdx.x;
+        int lo = 0;
+        const int64_t c = e1 < end1 ? mid_range(g, u, i, n1, e1, lo) : 0;
+        int64_t sum3;
+        const int64_t r3 = run3 + block_scan_excl(c, sh, sum3);
+        for (int64_t k = 0; k < c && r3 + k < cap; ++k) {
+          const int nodes[4] = {u, n1, g.col[e1], i}, rels[3] = {g.rel[e0], g.rel[e1], g.rel[lo + k]};
+          write_row(f, out + (r3 + k) * row, 3, nodes, rels);
+          ++placed;
+        }
+        run3 += sum3;
+      }
+    }
+  }
+  placed = block_sum(placed, sh);
+  if (threadIdx.x == 0 && placed != cap) atomicOr(flag, 1);
+}
+
+// ---- graph build -----------------------------------------------------------------------------------------------------------------------------
+__global__ void k_edge_keys(const int32_t* __restrict__ src, const int32_t* __restrict__ dst, int64_t E, unsigned long long* __restrict__ key) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e < E) key[e] = ((unsigned long long)(uint32_t)src[e] << 32) | (uint32_t)dst[e];
+}
+// keep [e]: edge e of the sorted list is no self-loop and differs from the one before it; col [e] = its destination
+__global__ void k_keep(const unsigned long long* __restrict__ key, const int32_t* __restrict__ rel, int64_t E, int32_t* __restrict__ keep, int32_t* __restrict__ col) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= E) return;
+  const unsigned long long k = key[e];
+  const bool loop = (uint32_t)(k >> 32) == (uint32_t)k;
+  const bool dup = e > 0 && key[e - 1] == k && rel[e - 1] == rel[e];
+  keep[e] = (!loop && !dup) ? 1 : 0;
+  col[e] = (int32_t)(uint32_t)k;
+}
+// rowptr [n] = the first stored edge whose source is >= n, n = 0 .. Ve
+__global__ void k_rowptr(const unsigned long long* __restrict__ key, int64_t E, int32_t Ve, int32_t* __restrict__ rowptr) {
+  const int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (n > Ve) return;
+  const unsigned long long want = (unsigned long long)n << 32;
+  int64_t l = 0, r = E;
+  while (l < r) { const int64_t m = l + ((r - l) >> 1); if (key[m] < want) l = m + 1; else r = m; }
+  rowptr[n] = (int32_t)l;
+}
+
+static int bits_for(int64_t v) { int b = 1; while (b < 63 && ((int64_t)1 << b) <= v) ++b; return b; }
+static unsigned blocks_for(int64_t n) { return (unsigned)((n + TPB - 1) / TPB); }
+
+// temporaries of one build, freed whatever happens
+struct Tmp {
+  std::vector<void*> v;
+  ~Tmp() { for (void* p : v) hipFree(p); }
+  template <typename T> T* get(int64_t n) {
+    void* p = nullptr;
+    if (kprn_dev_malloc(&p, (size_t)std::max<int64_t>(n, 1) * sizeof(T)) != hipSuccess) throw KprnError{KPRN_E_NOMEM, "hipMalloc failed (graph build)"};
+    v.push_back(p);
+    return (T*)p;
+  }
+};
+
+// the refusals shared by kprn_graph_create and the host twin
+static int validate_graph(const int32_t* src, const int32_t* dst, const int32_t* rel, int64_t E, const int32_t* node_types, int32_t Ve, int32_t Vr, int32_t Vt,
+                          int32_t nT, int32_t end_rel, std::string* why) {
+  auto bad = [&](int code, const char* t) { if (why) *why = t; return code; };
+  if (E < 0 || E > 0x7fffffffLL) return bad(KPRN_E_ARG, "E must be in 0 .. 2^31 - 1");
+  if ((E > 0 && (!src || !dst || !rel)) || !node_types) return bad(KPRN_E_ARG, "src / dst / rel / node_types is NULL");
+  if (Ve < 2 || Vr < 1 || Vt < 1 || nT < 1) return bad(KPRN_E_ARG, "the vocabularies need Ve >= 2, Vr >= 1, Vt >= 1, num_types >= 1");
+  if (end_rel < 1 || end_rel > Vr) return bad(KPRN_E_INDEX, "end_relation is outside 1..Vr");
+  for (int64_t e = 0; e < E; ++e) {
+    if (src[e] < 1 || src[e] >= Ve || dst[e] < 1 || dst[e] >= Ve) return bad(KPRN_E_INDEX, "an edge's node is outside 1..Ve-1 (Ve is the pad row)");
+    if (rel[e] < 1 || rel[e] > Vr) return bad(KPRN_E_INDEX, "an edge's relation is outside 1..Vr");
+  }
+  for (int64_t k = 0; k < (int64_t)(Ve - 1) * nT; ++k)
+    if (node_types[k] < 1 || node_types[k] > Vt) return bad(KPRN_E_INDEX, "a type id is outside 1..Vt");
+  return KPRN_OK;
+}
+static int validate_find(const int32_t* pairs, int32_t B, int32_t Ve, int32_t min_hops, int32_t max_hops, int32_t max_paths, int32_t T, std::string* why) {
+  auto bad = [&](int code, const char* t) { if (why) *why = t; return code; };
+  if (!pairs || B < 1) return bad(KPRN_E_ARG, "pairs is NULL or B < 1");
+  if (min_hops < 1 || min_hops > max_hops || max_hops > 3) return bad(KPRN_E_ARG, "hops: 1 <= min_hops <= max_hops <= 3");
+  if (max_paths < 1 || max_paths > kk::RAGGED_MAX_SEG) return bad(KPRN_E_ARG, "max_paths must be in 1..4096");
+  if (T < max_hops + 1) return bad(KPRN_E_ARG, "T must be at least max_hops + 1");
+  for (int64_t k = 0; k < 2 * (int64_t)B; ++k)
+    if (pairs[k] < 1 || pairs[k] >= Ve) return bad(KPRN_E_INDEX, "a pair's node is outside 1..Ve-1");
+  return KPRN_OK;
+}
+static int hop_mask(int min_hops, int max_hops) { int m = 0; for (int h = min_hops; h <= max_hops; ++h) m |= 1 << (h - 1); return m; }
+
+static kprn_graph* build_graph(kprn_handle* h, const int32_t* src, const int32_t* dst, const int32_t* rel, int64_t E, const int32_t* node_types, int32_t end_rel) {
+  const kprn_config& c = h->cfg;
+  hipStream_t s = h->stream;
+  kprn_graph* g = new kprn_graph();
+  g->Ve = c.Ve; g->Vr = c.Vr; g->Vt = c.Vt; g->nT = c.num_types; g->end_rel = end_rel;
+  try {
+    g->rowptr = dalloc<int32_t>((int64_t)c.Ve + 1);
+    g->types = dalloc<int32_t>((int64_t)c.Ve * c.num_types);
+    HIP_TRY(hipMemcpyAsync(g->types, node_types, (size_t)c.Ve * c.num_types * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    if (E == 0) {
+      HIP_TRY(hipMemsetAsync(g->rowptr, 0, ((size_t)c.Ve + 1) * sizeof(int32_t), s));
+      g->col = dalloc<int32_t>(1); g->rel = dalloc<int32_t>(1);
+      HIP_TRY(hipStreamSynchronize(s));
+      return g;
+    }
+    Tmp tmp;
+    int32_t* d_src = tmp.get<int32_t>(E); int32_t* d_dst = tmp.get<int32_t>(E); int32_t* d_rel = tmp.get<int32_t>(E);
+    unsigned long long* key0 = tmp.get<unsigned long long>(E); unsigned long long* key1 = tmp.get<unsigned long long>(E);
+    unsigned long long* key2 = tmp.get<unsigned long long>(E);
+    int32_t* rel1 = tmp.get<int32_t>(E); int32_t* rel2 = tmp.get<int32_t>(E);
+    int32_t* keep = tmp.get<int32_t>(E); int32_t* col2 = tmp.get<int32_t>(E);
+    int32_t* d_n = tmp.get<int32_t>(4);
+    HIP_TRY(hipMemcpyAsync(d_src, src, (size_t)E * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_dst, dst, (size_t)E * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_rel, rel, (size_t)E * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_edge_keys, dim3(blocks_for(E)), dim3(TPB), 0, s, d_src, d_dst, E, key0);
+    HIP_TRY(hipGetLastError());
+    // (src, dst, rel) order from two stable passes: by relation, then by (src, dst)
+    const int rbits = bits_for(c.Vr), kbits = 32 + bits_for(c.Ve);
+    size_t need1 = 0, need2 = 0, need3 = 0;
+    HIP_TRY(rocprim::radix_sort_pairs(nullptr, need1, (uint32_t*)d_rel, (uint32_t*)rel1, key0, key1, (size_t)E, 0, rbits, s));
+    HIP_TRY(rocprim::radix_sort_pairs(nullptr, need2, key1, key2, rel1, rel2, (size_t)E, 0, kbits, s));
+    HIP_TRY(rocprim::select(nullptr, need3, key2, keep, key0, d_n, (size_t)E, s));
+    size_t need4 = 0;
+    HIP_TRY(rocprim::select(nullptr, need4, col2, keep, d_src, d_n, (size_t)E, s));
+    const size_t need = std::max(std::max(need1, need2), std::max(need3, need4));
+    char* work = tmp.get<char>((int64_t)need);
+    size_t nb = need;
+    HIP_TRY(rocprim::radix_sort_pairs(work, nb, (uint32_t*)d_rel, (uint32_t*)rel1, key0, key1, (size_t)E, 0, rbits, s));
+    nb = need;
+    HIP_TRY(rocprim::radix_sort_pairs(work, nb, key1, key2, rel1, rel2, (size_t)E, 0, kbits, s));
+    hipLaunchKernelGGL(k_keep, dim3(blocks_for(E)), dim3(TPB), 0, s, key2, rel2, E, keep, col2);
+    HIP_TRY(hipGetLastError());
+    // compaction: the stored key (for rowptr), destination and relation of every kept edge (d_src / d_dst are free again)
+    nb = need; HIP_TRY(rocprim::select(work, nb, key2, keep, key0, d_n, (size_t)E, s));
+    nb = need; HIP_TRY(rocprim::select(work, nb, col2, keep, d_src, d_n, (size_t)E, s));
+    nb = need; HIP_TRY(rocprim::select(work, nb, rel2, keep, d_dst, d_n, (size_t)E, s));
+    int32_t n_kept = 0;
+    HIP_TRY(hipMemcpyAsync(&n_kept, d_n, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    KPRN_REQUIRE(n_kept >= 0 && n_kept <= E, KPRN_E_DEVICE, "graph build: the compaction returned an impossible edge count");
+    g->E = n_kept;
+    g->col = dalloc<int32_t>(n_kept); g->rel = dalloc<int32_t>(n_kept);
+    if (n_kept > 0) {
+      HIP_TRY(hipMemcpyAsync(g->col, d_src, (size_t)n_kept * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+      HIP_TRY(hipMemcpyAsync(g->rel, d_dst, (size_t)n_kept * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    }
+    hipLaunchKernelGGL(k_rowptr, dim3(blocks_for((int64_t)c.Ve + 1)), dim3(TPB), 0, s, key0, (int64_t)n_kept, c.Ve, g->rowptr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(s));
+  } catch (...) {
+    dfree(g->rowptr); dfree(g->col); dfree(g->rel); dfree(g->types);
+    delete g;
+    throw;
+  }
+  return g;
+}
+
+static void free_graph(kprn_graph* g) {
+  dfree(g->rowptr); dfree(g->col); dfree(g->rel); dfree(g->types);
+  delete g;
+}
+
+void release_all(kprn_handle* h) {
+  for (kprn_graph* g : h->graphs) free_graph(g);
+  h->graphs.clear();
+  if (h->pf_buf) { hipFree(h->pf_buf); h->pf_buf = nullptr; h->pf_buf_bytes = 0; }
+}
+
+// ---- host twin: the same rule over a CSR built by std::sort ---------------------------------------------------------------------------------
+struct HostCsr { std::vector<int32_t> rowptr, col, rel; };
+static HostCsr host_csr(const int32_t* src, const int32_t* dst, const int32_t* rel, int64_t E, int32_t Ve) {
+  std::vector<std::tuple<int32_t, int32_t, int32_t>> ed;
+  ed.reserve((size_t)E);
+  for (int64_t e = 0; e < E; ++e) if (src[e] != dst[e]) ed.emplace_back(src[e], dst[e], rel[e]);
+  std::sort(ed.begin(), ed.end());
+  ed.erase(std::unique(ed.begin(), ed.end()), ed.end());
+  HostCsr g;
+  g.rowptr.assign((size_t)Ve + 2, 0);
+  g.col.resize(ed.size() + 1); g.rel.resize(ed.size() + 1);
+  for (size_t e = 0; e < ed.size(); ++e) { g.rowptr[(size_t)std::get<0>(ed[e]) + 1]++; g.col[e] = std::get<1>(ed[e]); g.rel[e] = std::get<2>(ed[e]); }
+  for (size_t n = 0; n + 1 < g.rowptr.size(); ++n) g.rowptr[n + 1] += g.rowptr[n];
+  return g;
+}
+
+template <class Fn>
+static void parallel_pairs(int32_t B, int threads, Fn&& fn) {
+  const int nth = std::max(1, std::min(threads, (int)B));
+  if (nth == 1) { for (int32_t b = 0; b < B; ++b) fn(b); return; }
+  std::atomic<int32_t> next{0};   // (which thread takes a pair changes nothing a pair computes)
+  std::vector<std::thread> th;
+  for (int t = 0; t < nth; ++t)
+    th.emplace_back([&] { for (int32_t b = next.fetch_add(1); b < B; b = next.fetch_add(1)) fn(b); });
+  for (auto& t : th) t.join();
+}
+
+static void host_pair_totals(const Csr& g, int u, int i, int hmask, int64_t* t4) {
+  int64_t c1 = 0, c2 = 0, c3 = 0;
+  if (u != i) {
+    int lo, hi;
+    if (hmask & 1) { edge_range(g, u, i, lo, hi); c1 = hi - lo; }
+    if (hmask & 6)
+      for (int e0 = g.rowptr[u]; e0 < g.rowptr[u + 1]; ++e0) {
+        int64_t a2, a3;
+        subtree_count(g, u, i, e0, (hmask & 2) != 0, (hmask & 4) != 0, a2, a3);
+        c2 += a2; c3 += a3;
+      }
+  }
+  t4[0] = c1; t4[1] = c2; t4[2] = c3; t4[3] = c1 + c2 + c3;
+}
+
+static int64_t host_pair_fill(const Csr& g, const Fmt& f, int u, int i, int hmask, const int64_t* t4, int64_t cap, int32_t* out) {
+  const int64_t row = (int64_t)f.T * f.F, base2 = t4[0], base3 = t4[0] + t4[1];
+  int64_t placed = 0, done2 = 0, done3 = 0;
+  int lo, hi;
+  if (hmask & 1) { edge_range(g, u, i, lo, hi); placed += hop1_fill(g, f, u, i, lo, hi, 0, 1, cap, out); }
+  for (int e0 = g.rowptr[u]; e0 < g.rowptr[u + 1]; ++e0) {
+    const bool go2 = (hmask & 2) && base2 + done2 < cap, go3 = (hmask & 4) && base3 + done3 < cap;
+    if (!go2 && !go3) break;
+    int64_t c2, c3;
+    subtree_count(g, u, i, e0, go2, go3, c2, c3);
+    const int64_t r2 = base2 + done2, r3 = base3 + done3;
+    const int64_t room2 = c2 ? room(cap, r2) : 0, room3 = c3 ? room(cap, r3) : 0;
+    placed += subtree_fill(g, f, u, i, e0, room2, room3, room2 ? out + r2 * row : out, room3 ? out + r3 * row : out);
+    done2 += c2; done3 += c3;
+  }
+  return placed;
+}
+
+}  // namespace pf
+
+extern "C" {
+
+int kprn_graph_create(kprn_handle* h, const int32_t* src, const int32_t* dst, const int32_t* rel, int64_t E, const int32_t* node_types, int32_t end_relation,
+                      kprn_graph** out) {
+  API_BEGIN(h)
+  KPRN_REQUIRE(out, KPRN_E_ARG, "out is NULL");
+  *out = nullptr;
+  std::string why;
+  const int rc = pf::validate_graph(src, dst, rel, E, node_types, h->cfg.Ve, h->cfg.Vr, h->cfg.Vt, h->cfg.num_types, end_relation, &why);
+  if (rc != KPRN_OK) throw KprnError{rc, why};
+  kprn_graph* g = pf::build_graph(h, src, dst, rel, E, node_types, end_relation);
+  h->graphs.push_back(g);
+  *out = g;
+  API_END(h)
+}
+
+void kprn_graph_destroy(kprn_handle* h, kprn_graph* g) {
+  if (!h || !g) return;
+  auto it = std::find(h->graphs.begin(), h->graphs.end(), g);
+  if (it == h->graphs.end()) return;   // (not this handle's, or destroyed already)
+  hipSetDevice(h->cfg.device_id);
+  sync_stream(h->stream, /*nothrow=*/true);   // (a finder launch may still read it)
+  h->graphs.erase(it);
+  pf::free_graph(g);
+}
+
+int kprn_graph_num_edges(kprn_handle* h, const kprn_graph* g, int64_t* n) {
+  API_BEGIN(h)
+  KPRN_REQUIRE(g && n, KPRN_E_ARG, "NULL argument");
+  *n = g->E;
+  API_END(h)
+}
+
+int kprn_find_paths(kprn_handle* h, const kprn_graph* g, const int32_t* pairs, const float* labels, int32_t B, int32_t min_hops, int32_t max_hops,
+                    int32_t max_paths, int32_t T, int32_t* counts, int64_t* found, kprn_batch** out) {
+  API_BEGIN(h)
+  KPRN_REQUIRE(out, KPRN_E_ARG, "out is NULL");
+  *out = nullptr;
+  KPRN_REQUIRE(g && std::find(h->graphs.begin(), h->graphs.end(), g) != h->graphs.end(), KPRN_E_ARG, "g is not a graph of this handle");
+  std::string why;
+  const int rc = pf::validate_find(pairs, B, g->Ve, min_hops, max_hops, max_paths, T, &why);
+  if (rc != KPRN_OK) throw KprnError{rc, why};
+  const kprn_config& c = h->cfg;
+  KPRN_REQUIRE(c.F >= c.num_types + 2, KPRN_E_ARG, "F must hold num_types + 2 columns");
+  hipStream_t s = h->stream;
+  const int hmask = pf::hop_mask(min_hops, max_hops);
+  // device arguments of the two passes: pairs [2B] | cnt [B] | flag [4] (int32), then tot [4B] | first [B] (int64)
+  const size_t w32 = ((size_t)3 * B + 4 + 1) & ~(size_t)1, total = w32 * 4 + (size_t)5 * B * 8;
+  if (total > h->pf_buf_bytes) {
+    HIP_TRY(hipStreamSynchronize(s));
+    if (h->pf_buf) { hipFree(h->pf_buf); h->pf_buf = nullptr; h->pf_buf_bytes = 0; }
+    hipError_t e = kprn_dev_malloc(&h->pf_buf, total + total / 4 + 64);
+    if (e != hipSuccess) throw KprnError{KPRN_E_NOMEM, std::string("hipMalloc failed: ") + hipGetErrorString(e)};
+    h->pf_buf_bytes = total + total / 4;
+  }
+  int32_t* d_pairs = (int32_t*)h->pf_buf;
+  int32_t* d_cnt = d_pairs + 2 * (size_t)B;
+  int32_t* d_flag = d_cnt + B;
+  int64_t* d_tot = (int64_t*)((char*)h->pf_buf + w32 * 4);
+  int64_t* d_first = d_tot + 4 * (size_t)B;
+  const pf::Csr csr{g->rowptr, g->col, g->rel};
+  HIP_TRY(hipMemcpyAsync(d_pairs, pairs, (size_t)2 * B * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  {
+    ProfScope ps(h, "find_paths_count");
+    hipLaunchKernelGGL(pf::k_count, dim3((unsigned)B), dim3(pf::TPB), 0, s, csr, d_pairs, hmask, d_tot);
+    HIP_TRY(hipGetLastError());
+  }
+  std::vector<int64_t> tot((size_t)4 * B), first((size_t)B);
+  HIP_TRY(hipMemcpyAsync(tot.data(), d_tot, tot.size() * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  // the scan over the pairs: counts, the pairs that have paths, each one's first row
+  std::vector<int32_t> cnt((size_t)B), kept;
+  std::vector<float> lab;
+  int64_t N = 0;
+  for (int32_t b = 0; b < B; ++b) {
+    const int64_t f = tot[4 * (size_t)b + 3];
+    KPRN_REQUIRE(f >= 0, KPRN_E_DEVICE, "find_paths: the counting pass returned a negative count");
+    cnt[b] = (int32_t)std::min<int64_t>(f, max_paths);
+    first[b] = cnt[b] > 0 ? N : -1;
+    if (cnt[b] > 0) { kept.push_back(cnt[b]); if (labels) lab.push_back(labels[b]); }
+    N += cnt[b];
+  }
+  if (!kept.empty()) {
+    HIP_TRY(hipMemcpyAsync(d_cnt, cnt.data(), (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_first, first.data(), (size_t)B * sizeof(int64_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(d_flag, 0, sizeof(int32_t), s));
+    const pf::Fmt fmt{g->types, g->nT, g->Vt, g->Ve, g->Vr, T, c.F, g->end_rel};
+    const slots::DeviceFill fill = [&](int32_t* idx_dev, hipStream_t st) {
+      ProfScope ps(h, "find_paths_fill", st);
+      hipLaunchKernelGGL(pf::k_fill, dim3((unsigned)B), dim3(pf::TPB), 0, st, csr, fmt, d_pairs, hmask, d_tot, d_first, d_cnt, idx_dev, d_flag);
+      HIP_TRY(hipGetLastError());
+    };
+    kprn_batch* nb = nullptr;
+    slots::create(h, nullptr, kept.data(), labels ? lab.data() : nullptr, (int32_t)kept.size(), 0, N, T, c.F, &nb, &fill);
+    int32_t flag = 0;
+    const hipError_t e = hipMemcpy(&flag, d_flag, sizeof(int32_t), hipMemcpyDeviceToHost);   // (create has drained the stream)
+    if (e != hipSuccess || flag != 0) {
+      kprn_batch_destroy(h, nb);
+      HIP_TRY(e);
+      throw KprnError{KPRN_E_DEVICE, "find_paths: the fill pass placed a different number of paths than the counting pass allotted"};
+    }
+    *out = nb;
+  }
+  for (int32_t b = 0; b < B; ++b) {
+    if (counts) counts[b] = cnt[b];
+    if (found) found[b] = tot[4 * (size_t)b + 3];
+  }
+  API_END(h)
+}
+
+int kprn_host_find_paths(const int32_t* src, const int32_t* dst, const int32_t* rel, int64_t E, const int32_t* node_types, int32_t Ve, int32_t Vr, int32_t Vt,
+                         int32_t num_types, int32_t end_relation, const int32_t* pairs, int32_t B, int32_t min_hops, int32_t max_hops, int32_t max_paths,
+                         int32_t T, int32_t F, int32_t threads, int32_t* counts, int64_t* found, int32_t* idx) {
+  int rc = pf::validate_graph(src, dst, rel, E, node_types, Ve, Vr, Vt, num_types, end_relation, nullptr);
+  if (rc != KPRN_OK) return rc;
+  rc = pf::validate_find(pairs, B, Ve, min_hops, max_hops, max_paths, T, nullptr);
+  if (rc != KPRN_OK) return rc;
+  if (F < num_types + 2 || !counts) return KPRN_E_ARG;
+  try {
+    const pf::HostCsr hg = pf::host_csr(src, dst, rel, E, Ve);
+    const pf::Csr g{hg.rowptr.data(), hg.col.data(), hg.rel.data()};
+    const pf::Fmt f{node_types, num_types, Vt, Ve, Vr, T, F, end_relation};
+    const int hmask = pf::hop_mask(min_hops, max_hops);
+    std::vector<int64_t> tot((size_t)4 * B), first((size_t)B);
+    pf::parallel_pairs(B, threads, [&](int32_t b) { pf::host_pair_totals(g, pairs[2 * b], pairs[2 * b + 1], hmask, &tot[4 * (size_t)b]); });
+    int64_t N = 0;
+    for (int32_t b = 0; b < B; ++b) {
+      counts[b] = (int32_t)std::min<int64_t>(tot[4 * (size_t)b + 3], max_paths);
+      if (found) found[b] = tot[4 * (size_t)b + 3];
+      first[b] = N;
+      N += counts[b];
+    }
+    if (!idx) return KPRN_OK;
+    std::atomic<int> wrong{0};
+    pf::parallel_pairs(B, threads, [&](int32_t b) {
+      if (counts[b] == 0) return;
+      const int64_t placed = pf::host_pair_fill(g, f, pairs[2 * b], pairs[2 * b + 1], hmask, &tot[4 * (size_t)b], counts[b], idx + first[b] * T * F);
+      if (placed != counts[b]) wrong = 1;
+    });
+    if (wrong) return KPRN_E_DEVICE;
+  } catch (...) { return KPRN_E_NOMEM; }
+  return KPRN_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,124 @@
+"""From a knowledge graph to a recommendation: the arrays of kprn_graph_create built with the formatter's own id rules, and the chain
+find paths -> score -> rank -> explain -> read the winning paths back, all on the device (include/kprn.h "finding a pair's paths").
+
+The reference mines paths offline (release/data_prepare/path_find_depth_3.py: random walks over pickled dictionaries); here the finder is exhaustive
+and deterministic, and its output is a ragged batch, so nothing downstream changes.
+
+Ids: the vocab files are 0-based and the engine's ids are those + 1 (int2torch.lua:60-63), like everything the formatter prints.  The finder pads a
+path on the left with the engine's pad rows (Vt, Ve, Vr: the last row of each table); `from_triples(strict=True)` refuses a vocabulary whose
+#PAD_TOKEN is not the last id of its table, because the rows would then differ from the formatter's.
+"""
+import numpy as np
+
+from . import _ffi
+from .pathformat import PathFormatter
+
+
+class KnowledgeGraph:
+    """src / dst / rel [E] (1-based ids), node_types [Ve, num_types] (row e - 1 = entity e), end_relation, the table sizes Ve / Vr / Vt."""
+
+    def __init__(self, src, dst, rel, node_types, end_relation, Vr, Vt, vocabs=None):
+        self.src, self.dst, self.rel = (np.ascontiguousarray(a, np.int32) for a in (src, dst, rel))
+        self.node_types = np.ascontiguousarray(node_types, np.int32)
+        self.Ve, self.num_types = (int(x) for x in self.node_types.shape)
+        self.Vr, self.Vt, self.end_relation = int(Vr), int(Vt), int(end_relation)
+        self.vocabs = vocabs
+        self._names = None
+        self._device = {}   # id(engine) -> _ffi.Graph
+
+    @classmethod
+    def from_triples(cls, triples, vocabs, num_types, strict=True):
+        """triples: (head name, relation name, tail name), directed -- inverse edges are the caller's, as in the reference's data.  Names the vocabularies do
+        not know fall back to #UNK_ENTITY / #UNK_RELATION, a node's type slots are what PathFormatter prints for a step that leaves it (sorted as strings,
+        truncated, reversed, left-padded with the type table's #PAD_TOKEN; #UNK_ENTITY_TYPE where the entity has no type entry).  Entities that share an id
+        (several unknown names) share the first one's type row."""
+        fmt = PathFormatter(vocabs, 0, num_types)
+        one = lambda v: int(v) + 1
+        Ve = max(int(v) for v in vocabs.entity.values()) + 1
+        Vr = max(int(v) for v in vocabs.relation.values()) + 1
+        Vt = max(int(v) for v in vocabs.entity_type.values()) + 1
+        pads = (one(vocabs.entity_type["#PAD_TOKEN"]), one(vocabs.entity["#PAD_TOKEN"]), one(vocabs.relation["#PAD_TOKEN"]))
+        if strict and pads != (Vt, Ve, Vr):
+            raise ValueError("the finder pads with the last row of each table (%d, %d, %d); this vocabulary's #PAD_TOKEN ids are %s" % (Vt, Ve, Vr, pads))
+        node_types = np.full((Ve, num_types), pads[0], np.int32)
+        seen = set()
+
+        def node(name):
+            feat = fmt._feature(name, "#END_RELATION").split(",")
+            e = int(feat[num_types]) + 1
+            if e not in seen:
+                seen.add(e)
+                node_types[e - 1] = [int(t) + 1 for t in feat[:num_types]]
+            return e
+
+        src, dst, rel = [], [], []
+        unk_rel = one(vocabs.relation["#UNK_RELATION"])
+        for head, r, tail in triples:
+            src.append(node(head)); dst.append(node(tail))
+            rel.append(one(vocabs.relation[r]) if r in vocabs.relation else unk_rel)
+        return cls(src, dst, rel, node_types, one(vocabs.relation["#END_RELATION"]), Vr, Vt, vocabs)
+
+    def entity_id(self, name):
+        v = self.vocabs.entity
+        return int(v[name] if name in v else v["#UNK_ENTITY"]) + 1
+
+    def entity_name(self, e):
+        if self._names is None:
+            self._names = {int(i) + 1: n for n, i in self.vocabs.entity.items()}
+        return self._names.get(int(e), str(e))
+
+    def on(self, eng):
+        """the graph in this engine's HBM (built once per engine)"""
+        g = self._device.get(id(eng))
+        if g is None or not g.ptr:
+            g = self._device[id(eng)] = eng.graph(self.src, self.dst, self.rel, self.node_types, self.end_relation)
+        return g
+
+    def host_find_paths(self, pairs, min_hops, max_hops, max_paths, T, F=None, threads=1, want_idx=True):
+        return _ffi.host_find_paths(self.src, self.dst, self.rel, self.node_types, self.Vr, self.Vt, self.end_relation, pairs, min_hops, max_hops, max_paths,
+                                    T, F=F, threads=threads, want_idx=want_idx)
+
+
+def read_triples(path):
+    """a TSV of `head \\t relation \\t tail` names, one directed edge per line"""
+    with open(path) as f:
+        for line in f:
+            parts = line.rstrip("\n").split("\t")
+            if len(parts) >= 3:
+                yield parts[0], parts[1], parts[2]
+
+
+def recommend(eng, kg, user, items, K, M, min_hops=1, max_hops=3, max_paths=28, T=None, class_id=1, mode=_ffi.RANK_PRINTED):
+    """Which of `items` for `user` (entity ids), and why: find every pair's paths on the device, score the batch, put the scores on the board, rank the
+    one group, explain the K winners and read their paths' ids back.  kg: a KnowledgeGraph, or an _ffi.Graph already on the engine.  The board is
+    resized to the candidates that have paths (kprn_board_reserve keeps nothing).
+    -> the K best items, best first: dict(item, rank, score, n_paths, found, paths = the M strongest as (ids [T,F], weight, score)); items without any
+    path are not candidates, so the list may be shorter than K -- empty when no item is reachable."""
+    graph = kg.on(eng) if isinstance(kg, KnowledgeGraph) else kg
+    items = np.asarray(items, np.int32).reshape(-1)
+    pairs = np.stack([np.full(items.shape, int(user), np.int32), items], axis=1)
+    T = max_hops + 1 if T is None else int(T)
+    batch, counts, found = eng.find_paths(graph, pairs, min_hops, max_hops, max_paths, T)
+    if batch is None:
+        return []
+    try:
+        cand = np.nonzero(counts)[0]            # pair b of the batch is items[cand[b]]
+        eng.forward_async(batch, class_id)      # the scoring pass; its probabilities stay on the device
+        eng.board_reserve(batch.B)
+        eng.board_put(0, batch.B)
+        kk = min(int(K), _ffi.RANK_MAX_K)
+        top = eng.rank_groups(np.array([0, batch.B], np.int64), K=kk, mode=mode)
+        win = top["topk_idx"][0]
+        win = win[win >= 0]
+        ex = eng.explain_batch(batch, M, class_id, pairs=win)
+        idx = batch.read_idx()
+        off = np.concatenate([[0], np.cumsum(batch.counts, dtype=np.int64)])
+        out = []
+        for place, b in enumerate(win):
+            paths = [(idx[off[b] + q], float(ex["path_weight"][place, r]), float(ex["path_score"][place, r]))
+                     for r, q in enumerate(ex["path_idx"][place]) if q >= 0]
+            out.append(dict(item=int(items[cand[b]]), rank=place, score=float(top["topk_score"][0, place]), n_paths=int(batch.counts[b]),
+                            found=int(found[cand[b]]), paths=paths))
+        return out
+    finally:
+        batch.free()

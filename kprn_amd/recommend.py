@@ -1,0 +1,54 @@
+"""`python -m kprn_amd.recommend <flags>`: which of the items in -items for -user, from a knowledge graph and a checkpoint, and why (an extension;
+the reference mines paths offline and scores files).  A thin command line over graph.recommend.
+
+Flags: those of `python -m kprn_amd.score` that shape and load the model (-model_path, -top_k, -gpu_id and the OneModel flags; the TopK reducer's K is the
+model flag -K here, because -k is the number of items to return), plus
+  -kg triples.tsv      the graph: `head \\t relation \\t tail` names per line, directed (list inverse edges yourself)
+  -vocab_dir DIR       entity_type_id.txt, all_relation_id.txt, all_entity_id.txt, entity_to_type.txt, domain-label
+  -user U  -items FILE the user's entity name; candidate item names, one per line
+  -k K                 items to return;  -explain_paths M  strongest paths printed per item
+  -min_hops / -max_hops / -max_paths   the finder's limits (1, 3, 28)
+Output, tab separated: one line `rank, item, %.5f score, paths kept, paths found` per item, then one line `rank, place, %.5f weight, %.6g score, path`
+per explained path (the path as scoring.format_path prints it)."""
+import argparse
+import sys
+
+from . import graph, model, scoring
+from .pathformat import Vocabs
+
+
+def main(argv=None, out=sys.stdout):
+    p = argparse.ArgumentParser()
+    p.add_argument("-model_path", default=""); p.add_argument("-gpu_id", type=int, default=-1); p.add_argument("-top_k", type=int, default=2)
+    p.add_argument("-kg", required=True); p.add_argument("-vocab_dir", required=True)
+    p.add_argument("-user", required=True); p.add_argument("-items", required=True)
+    p.add_argument("-k", type=int, default=10); p.add_argument("-explain_paths", type=int, default=3)
+    p.add_argument("-min_hops", type=int, default=1); p.add_argument("-max_hops", type=int, default=3); p.add_argument("-max_paths", type=int, default=28)
+    args, rest = p.parse_known_args(argv)
+    if not 1 <= args.explain_paths <= 32:
+        sys.exit("-explain_paths must be in 1..32")
+    if not 1 <= args.k <= 64:
+        sys.exit("-k must be in 1..64")
+    params = model.parse_flags(rest)
+    params.reducer, params.initModel, params.gpuid = model.reducer_of_score_flag(args.top_k), args.model_path, args.gpu_id
+    kg = graph.KnowledgeGraph.from_triples(graph.read_triples(args.kg), Vocabs(args.vocab_dir), params.numEntityTypes)
+    if (kg.Vt, kg.Ve, kg.Vr) != (params.entityTypeVocabSize, params.entityVocabSize, params.relationVocabSize):
+        sys.exit("the vocabularies hold %d types, %d entities, %d relations; the model flags say %d, %d, %d"
+                 % (kg.Vt, kg.Ve, kg.Vr, params.entityTypeVocabSize, params.entityVocabSize, params.relationVocabSize))
+    with open(args.items) as f:
+        names = [l.strip() for l in f if l.strip()]
+    eng = model.build_engine(params)
+    try:
+        res = graph.recommend(eng, kg, kg.entity_id(args.user), [kg.entity_id(n) for n in names], args.k, args.explain_paths, args.min_hops, args.max_hops,
+                              args.max_paths)
+    finally:
+        eng.close()
+    for r in res:
+        out.write("%d\t%s\t%.5f\t%d\t%d\n" % (r["rank"], kg.entity_name(r["item"]), r["score"], r["n_paths"], r["found"]))
+        for place, (ids, w, s) in enumerate(r["paths"]):
+            out.write("%d\t%d\t%.5f\t%.6g\t%s\n" % (r["rank"], place, w, s, scoring.format_path(ids, kg.Ve)))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -1,0 +1,67 @@
+"""Times kprn_find_paths against its host twin on one synthetic graph: a user-item graph with skewed item popularity,
+n_users + n_items nodes, n_ratings `rate` edges and their inverses, random (user, item) pairs, 3 hops, a cap per pair.
+
+  python scripts/gpu_path_find_bench.py [--users 80000 --items 20000 --ratings 1000000 --pairs 4096 --cap 28 --threads 16 --reps 5]
+
+Prints one JSON line: the graph build, the finder call (counting pass + slot creation with the fill pass, validation, plan and index: what a caller
+waits for; median of --reps calls after one warm-up), the two finder kernels from the engine's profiler, and the twin on --threads host threads."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from kprn_amd import _ffi  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--users", type=int, default=80000); ap.add_argument("--items", type=int, default=20000)
+    ap.add_argument("--ratings", type=int, default=1000000); ap.add_argument("--pairs", type=int, default=4096)
+    ap.add_argument("--cap", type=int, default=28); ap.add_argument("--threads", type=int, default=16); ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--skip_device", type=int, default=0)
+    a = ap.parse_args()
+    rng = np.random.RandomState(7)
+    pop = 1.0 / (np.arange(a.items) + 10.0) ** 0.8
+    u = rng.randint(1, a.users + 1, size=a.ratings).astype(np.int32)
+    it = (a.users + 1 + rng.choice(a.items, size=a.ratings, p=pop / pop.sum())).astype(np.int32)
+    src, dst = np.concatenate([u, it]), np.concatenate([it, u])
+    rel = np.concatenate([np.full(a.ratings, 1, np.int32), np.full(a.ratings, 2, np.int32)])
+    Ve, Vr, Vt, end_rel = a.users + a.items + 1, 4, 4, 3
+    nt = np.ones((Ve, 1), np.int32)
+    nt[a.users:] = 2
+    pairs = np.stack([rng.randint(1, a.users + 1, size=a.pairs), a.users + 1 + rng.randint(0, a.items, size=a.pairs)], axis=1).astype(np.int32)
+    out = dict(nodes=Ve - 1, edges_in=int(src.shape[0]), pairs=a.pairs, hops=3, cap=a.cap, threads=a.threads)
+    t0 = time.perf_counter()
+    idx, counts, found = _ffi.host_find_paths(src, dst, rel, nt, Vr, Vt, end_rel, pairs, 1, 3, a.cap, 4, threads=a.threads)
+    out["twin_s"] = time.perf_counter() - t0
+    out.update(paths_kept=int(counts.sum()), paths_found=int(found.sum()), pairs_with_paths=int((counts > 0).sum()), found_max=int(found.max()))
+    if not a.skip_device:
+        eng = _ffi.Engine(Vt, Ve, Vr, 16, 32, 16, 64, 2)
+        t0 = time.perf_counter()
+        gr = eng.graph(src, dst, rel, nt, end_rel)
+        out["graph_build_s"] = time.perf_counter() - t0
+        out["edges_stored"] = gr.n_edges
+        ts = []
+        for rep in range(a.reps + 1):
+            if rep == a.reps:
+                eng.profile(True)
+            t0 = time.perf_counter()
+            b, c, f = eng.find_paths(gr, pairs, 1, 3, a.cap, 4)
+            ts.append(time.perf_counter() - t0)
+            if rep == 0:
+                out["equal_to_twin"] = bool(np.array_equal(c, counts) and np.array_equal(f, found) and np.array_equal(b.read_idx(), idx))
+            b.free()
+        out["find_paths_s"] = float(np.median(ts[1:a.reps]))
+        out["find_paths_all_s"] = [round(t, 5) for t in ts]
+        eng.sync()
+        out["kernels_ms"] = {k: round(v[0], 4) for k, v in eng.profile_get().items() if k.startswith("find_paths")}
+        eng.close()
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
