@@ -18,6 +18,7 @@ ffi.cdef[[
 typedef struct kprn_handle kprn_handle;
 typedef struct kprn_batch kprn_batch;
 typedef struct kprn_graph kprn_graph;
+typedef struct kprn_sampler kprn_sampler;
 typedef struct {
   int32_t Vt, Ve, Vr, dt, de, dr, F, num_types, H, L, C, rnn_type, use_relu, rnn_init, compute_dtype, reducer, K, device_id, rank, world;
   float param_init; uint64_t seed; void* stream;
@@ -91,6 +92,12 @@ int kprn_graph_num_edges(kprn_handle*, const kprn_graph*, int64_t*);
 int kprn_find_paths(kprn_handle*, const kprn_graph*, const int32_t*, const float*, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t*, int64_t*, kprn_batch**);
 int kprn_batch_read_idx(kprn_handle*, const kprn_batch*, int32_t*);
 int kprn_host_find_paths(const int32_t*, const int32_t*, const int32_t*, int64_t, const int32_t*, int32_t, int32_t, int32_t, int32_t, int32_t, const int32_t*, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t*, int64_t*, int32_t*);
+/* negative sampler: a weighted candidate list in HBM, negatives per user slot, positives -> sampled pair list -> ragged batch (include/kprn.h "sampling negatives") */
+int kprn_sampler_create(kprn_handle*, const int32_t*, const float*, int64_t, kprn_sampler**);
+void kprn_sampler_destroy(kprn_handle*, kprn_sampler*);
+int kprn_sample_negatives(kprn_handle*, const kprn_graph*, const kprn_sampler*, const int32_t*, int32_t, int32_t, int32_t, uint64_t, unsigned int, int32_t*, int32_t*);
+int kprn_host_sample_negatives(const int32_t*, const int32_t*, const int32_t*, int64_t, int32_t, const int32_t*, const float*, int64_t, const int32_t*, int32_t, int32_t, int32_t, uint64_t, unsigned int, int32_t, int32_t*, int32_t*);
+int kprn_find_training_paths(kprn_handle*, const kprn_graph*, const kprn_sampler*, const int32_t*, int32_t, int32_t, int32_t, uint64_t, unsigned int, int32_t, int32_t, int32_t, int32_t, int32_t*, int32_t*, int64_t*, kprn_batch**);
 ]]
 
 local C = ffi.load('kprn')

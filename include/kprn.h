@@ -46,6 +46,7 @@ extern "C" {
 typedef struct kprn_handle kprn_handle;
 typedef struct kprn_batch kprn_batch;
 typedef struct kprn_graph kprn_graph;
+typedef struct kprn_sampler kprn_sampler;
 
 typedef enum {
   KPRN_OK = 0,
@@ -358,6 +359,43 @@ int kprn_batch_read_idx(kprn_handle* h, const kprn_batch* b, int32_t* idx_out);
 int kprn_host_find_paths(const int32_t* src, const int32_t* dst, const int32_t* rel, int64_t E, const int32_t* node_types, int32_t Ve, int32_t Vr, int32_t Vt,
                          int32_t num_types, int32_t end_relation, const int32_t* pairs, int32_t B, int32_t min_hops, int32_t max_hops, int32_t max_paths,
                          int32_t T, int32_t F, int32_t threads, int32_t* counts, int64_t* found, int32_t* idx);
+
+/* ---- sampling negatives (an extension: the reference draws them offline, data_prepare/sample.py:18-26,101-117 -- distinct non-interacted items, uniform at
+ * alpha = 0, else weighted by frequency^alpha; its draws, numpy.random.multinomial and Python's random, cannot be reproduced and are not restated) ----
+ * For B user slots, n_neg items per slot from a weighted candidate list, on the device and fully specified, so that any id can be rebuilt anywhere:
+ *  - candidate list: items [M], entity ids in 1 .. Ve-1, strictly ascending, 1 <= M < 2^31; weights [M] fp32, finite and >= 0, NULL = all 1; at least one
+ *    weight > 0.  Anything else is KPRN_E_ARG (KPRN_E_INDEX for an id outside the table), decided on the host before anything is allocated.
+ *  - thresholds, built on the host in double in index order: cum_j = cum_{j-1} + (double)w_j, thr[j] = (uint64) floor(cum_j / cum_{M-1} * 4294967296.0), hence
+ *    thr[M-1] = 2^32.  pick(r) of a 32-bit word r = the number of j with thr[j] <= r (an upper bound by binary search); an item of weight 0 is never picked.
+ *  - words: Philox4x32-10 (the generator of the dropout rule above), key = (seed & 0xffffffff, seed >> 32), counter = (a / 4, n, b, draw); word a % 4 of that
+ *    call belongs to attempt a of negative n of user slot b.  The counter holds the SLOT b, not the user id: the same user in two slots draws different items.
+ *  - acceptance: for slot b, u = users[b], the negatives are settled in the order n = 0 .. n_neg-1.  Negative n = items[pick(word)] of its first attempt
+ *    a < max_attempts whose candidate c satisfies all of: c != u; the stored graph has no edge u -> c of any relation; c is not one of the negatives already
+ *    accepted for this slot.  No attempt qualifies: slot n is 0, and the later n still try.
+ *  - limits: n_neg in 1..256, max_attempts in 1..64 (else KPRN_E_ARG); n_found[b] = the slot's non-zero entries.
+ * A positive item is adjacent to its user, so it is never drawn as that user's negative.  Nothing depends on timing: no atomic hands out a slot.
+ * A sampler is independent of any graph (the graph is an argument of the sampling calls); kprn_destroy frees the samplers still alive.                   */
+int kprn_sampler_create(kprn_handle* h, const int32_t* items, const float* weights /* [M] or NULL */, int64_t M, kprn_sampler** out);
+void kprn_sampler_destroy(kprn_handle* h, kprn_sampler* s);
+/* neg: host [B][n_neg]; n_found: host [B] or NULL.  Synchronous.  A user outside 1 .. Ve-1 is KPRN_E_INDEX, bad limits KPRN_E_ARG; a refused call writes nothing. */
+int kprn_sample_negatives(kprn_handle* h, const kprn_graph* g, const kprn_sampler* s, const int32_t* users /* [B] */, int32_t B, int32_t n_neg,
+                          int32_t max_attempts, uint64_t seed, unsigned int draw /* uint32 */, int32_t* neg, int32_t* n_found);
+/* the same rule on the host cores over the graph's raw edge arrays (no handle, no GPU), on `threads` threads; rel is not looked at (an edge of any relation
+ * counts).  The same refusals, plus kprn_graph_create's for E and the edges' nodes.                                                                        */
+int kprn_host_sample_negatives(const int32_t* src, const int32_t* dst, const int32_t* rel, int64_t E, int32_t Ve, const int32_t* items, const float* weights,
+                               int64_t M, const int32_t* users, int32_t B, int32_t n_neg, int32_t max_attempts, uint64_t seed, unsigned int draw,
+                               int32_t threads, int32_t* neg, int32_t* n_found);
+/* A training minibatch from B positives in one call: every positive's n_neg negatives are sampled on the device with slot b = the positive's index, the
+ * sampling kernel writes the pair list where the finder reads it -- row b * (1 + n_neg) = (u, i) with label 1, then (u, negative k) with label 0, k = 0 ..
+ * n_neg-1 -- and the finder's count and fill passes run over that list; the list never visits the host on the way.  The call waits where kprn_find_paths
+ * waits (for the counts, for the finished batch); sampling adds no wait.  An empty negative slot (item 0) is a pair of 0 paths, not an error; pairs without
+ * paths are dropped and the labels compacted exactly as kprn_find_paths does.  pairs_out (host [B * (1 + n_neg)][2], or NULL), counts and found
+ * [B * (1 + n_neg)] (or NULL) and the batch -- ids, counts, labels -- equal those of kprn_sample_negatives followed by kprn_find_paths on the same pair list
+ * and labels, the rows of item 0 left out of that call and counted as 0 paths.  A node of pos outside 1 .. Ve-1 is KPRN_E_INDEX; the limits are the two
+ * calls'; B * (1 + n_neg) must stay below 2^31.  No pair has a path: *out = NULL with KPRN_OK.                                                          */
+int kprn_find_training_paths(kprn_handle* h, const kprn_graph* g, const kprn_sampler* s, const int32_t* pos /* [B][2] = (u, i) */, int32_t B, int32_t n_neg,
+                             int32_t max_attempts, uint64_t seed, unsigned int draw /* uint32 */, int32_t min_hops, int32_t max_hops, int32_t max_paths,
+                             int32_t T, int32_t* pairs_out, int32_t* counts, int64_t* found, kprn_batch** out);
 
 /* ---- training ---------------------------------------------------------------------- */
 /* fEval of MyOptimizer.lua:184-195: zeroGradParameters; forward; BCE; backward.

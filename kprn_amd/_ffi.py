@@ -222,6 +222,39 @@ def host_find_paths(src, dst, rel, node_types, Vr, Vt, end_relation, pairs, min_
     return idx, counts, found
 
 
+SAMPLE_MAX_NEG, SAMPLE_MAX_ATTEMPTS = 256, 64   # kprn_sample_negatives: negatives per user slot, attempts per negative
+
+
+def _sampler_arrays(items, weights):
+    it = np.ascontiguousarray(items, np.int32).reshape(-1)
+    w = None if weights is None else np.ascontiguousarray(weights, np.float32).reshape(-1)
+    if w is not None and w.shape != it.shape:
+        raise KprnError(E_ARG, "weights must be [M] like items")
+    return it, w
+
+
+def _seed_draw(seed, draw):
+    return C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), C.c_uint32(int(draw) & 0xFFFFFFFF)
+
+
+def host_sample_negatives(src, dst, rel, Ve, items, weights, users, n_neg, seed, draw, max_attempts=16, threads=1, out=None):
+    """kprn_host_sample_negatives (no handle, no GPU): the sampling rule of include/kprn.h over the graph's raw edge arrays -> (neg [B, n_neg], n_found [B]);
+    `out` = (neg, n_found) arrays to write into (a refused call leaves them as they are)"""
+    src, dst, rel = (np.ascontiguousarray(a, np.int32).reshape(-1) for a in (src, dst, rel))
+    if not (src.shape == dst.shape == rel.shape):
+        raise KprnError(E_ARG, "a graph is src / dst / rel [E]")
+    it, w = _sampler_arrays(items, weights)
+    us = np.ascontiguousarray(users, np.int32).reshape(-1)
+    B = int(us.shape[0])
+    neg, nf = out if out is not None else (np.zeros((B, max(int(n_neg), 0)), np.int32), np.zeros(B, np.int32))
+    sd, dr = _seed_draw(seed, draw)
+    rc = lib().kprn_host_sample_negatives(_fp(src), _fp(dst), _fp(rel), C.c_int64(int(src.shape[0])), int(Ve), _fp(it), _fp(w), C.c_int64(int(it.shape[0])), _fp(us),
+                                          B, int(n_neg), int(max_attempts), sd, dr, int(threads), _fp(neg), _fp(nf))
+    if rc != 0:
+        raise KprnError(rc, "kprn_host_sample_negatives: bad edges / items / weights / users / n_neg / max_attempts")
+    return neg, nf
+
+
 def format_score_lines(counter0, probs, labels):
     """bytes of the scoring writer's lines for pairs counter0 .. (kprn_format_score_lines; host-only)"""
     L = lib()
@@ -266,6 +299,8 @@ def lib():
     L.kprn_batch_destroy.argtypes = [C.c_void_p, C.c_void_p]
     L.kprn_graph_destroy.restype = None
     L.kprn_graph_destroy.argtypes = [C.c_void_p, C.c_void_p]
+    L.kprn_sampler_destroy.restype = None
+    L.kprn_sampler_destroy.argtypes = [C.c_void_p, C.c_void_p]
     L.kprn_host_alloc.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]
     L.kprn_host_free.argtypes = [C.c_void_p, C.c_void_p]
     _lib = L
@@ -486,6 +521,30 @@ class Graph:
             pass
 
 
+class Sampler:
+    """A weighted candidate list resident in HBM (kprn_sampler_create): the input of Engine.sample_negatives / find_training_paths."""
+
+    def __init__(self, engine, items, weights=None):
+        it, w = _sampler_arrays(items, weights)
+        self.engine = engine
+        self.ptr = C.c_void_p()
+        self.M = int(it.shape[0])
+        engine._samplers.add(self)
+        engine._ck(engine.L.kprn_sampler_create(engine.h, _fp(it), _fp(w), C.c_int64(self.M), C.byref(self.ptr)))
+
+    def free(self):
+        if self.ptr:
+            self.engine.L.kprn_sampler_destroy(self.engine.h, self.ptr)
+            self.ptr = C.c_void_p()
+
+    def __del__(self):
+        try:
+            if self.engine.h:
+                self.free()
+        except Exception:
+            pass
+
+
 STREAM_LEGACY_DEFAULT = C.c_void_p(-1).value   # kprn_config.stream: queue on the legacy default (null) stream (KPRN_STREAM_LEGACY_DEFAULT)
 
 
@@ -498,6 +557,7 @@ class Engine:
         self.L = lib()
         self._batches = weakref.WeakSet()
         self._graphs = weakref.WeakSet()
+        self._samplers = weakref.WeakSet()
         self.cfg = Config(Vt, Ve, Vr, dt, de, dr, F, num_types, H, L, C_, rnn_type, use_relu, rnn_init, compute_dtype, reducer, K, device_id, rank, world,
                           param_init, seed, stream)
         self.h = C.c_void_p()
@@ -521,7 +581,7 @@ class Engine:
         if self.h:
             for b in list(self._batches):   # (device blocks, page-locked images and events of batches the caller still holds)
                 b.free()
-            for g in list(self._graphs):
+            for g in list(self._graphs) + list(self._samplers):
                 g.free()
             for p in getattr(self, "_pinned", []):
                 self.L.kprn_host_free(self.h, p)
@@ -762,6 +822,36 @@ class Engine:
         if not ptr:
             return None, counts, found
         return Batch._adopt(self, ptr, counts[counts > 0].copy(), T, self.cfg.F, lab is not None), counts, found
+
+    # -- negative sampler (include/kprn.h "sampling negatives") -------------------------------
+    def sampler(self, items, weights=None):
+        """kprn_sampler_create: candidate items [M] (entity ids, strictly ascending) and their weights (None = uniform)"""
+        return Sampler(self, items, weights)
+
+    def sample_negatives(self, graph, sampler, users, n_neg, seed, draw, max_attempts=16, out=None):
+        """kprn_sample_negatives: n_neg distinct items per user slot, none the user or adjacent to it in `graph` -> (neg [B, n_neg] with 0 = no item found,
+        n_found [B]); `out` = (neg, n_found) arrays to write into"""
+        us = np.ascontiguousarray(users, np.int32).reshape(-1)
+        B = int(us.shape[0])
+        neg, nf = out if out is not None else (np.zeros((B, max(int(n_neg), 0)), np.int32), np.zeros(B, np.int32))
+        sd, dr = _seed_draw(seed, draw)
+        self._ck(self.L.kprn_sample_negatives(self.h, graph.ptr, sampler.ptr, _fp(us), B, int(n_neg), int(max_attempts), sd, dr, _fp(neg), _fp(nf)))
+        return neg, nf
+
+    def find_training_paths(self, graph, sampler, positives, n_neg, seed, draw, min_hops, max_hops, max_paths, T, max_attempts=16):
+        """kprn_find_training_paths: the positives [B,2] = (user, item), each with n_neg negatives sampled on the device, through the finder ->
+        (ragged Batch with labels 1 / 0 of the pairs that have paths, or None; pairs [B * (1 + n_neg), 2]; counts; found)"""
+        pos, _ = _pairs_array(positives, None)
+        B = int(pos.shape[0])
+        n = B * (1 + max(int(n_neg), 0))
+        pairs, counts, found = np.zeros((n, 2), np.int32), np.zeros(n, np.int32), np.zeros(n, np.int64)
+        ptr = C.c_void_p()
+        sd, dr = _seed_draw(seed, draw)
+        self._ck(self.L.kprn_find_training_paths(self.h, graph.ptr, sampler.ptr, _fp(pos), B, int(n_neg), int(max_attempts), sd, dr, int(min_hops), int(max_hops),
+                                                 int(max_paths), int(T), _fp(pairs), _fp(counts), _fp(found), C.byref(ptr)))
+        if not ptr:
+            return None, pairs, counts, found
+        return Batch._adopt(self, ptr, counts[counts > 0].copy(), T, self.cfg.F, True), pairs, counts, found
 
     # -- explanation (include/kprn.h "explaining a recommendation") ---------------------------
     def explain_batch(self, batch, M, class_id=1, pairs=None, out=None):

@@ -75,7 +75,8 @@ struct DetScratch { float* p = nullptr; int64_t cap = 0; };
 
 namespace fused { constexpr int KCAP = 8; }  // longest identical prefix the fused kernels skip (lstm_fused_common.h)
 
-struct kprn_graph;   // path_find.hip
+struct kprn_graph;   // path_find_dev.h
+struct kprn_sampler; // neg_sample.hip
 
 struct kprn_batch {
   int32_t B, P, T, F;
@@ -286,6 +287,8 @@ struct kprn_handle {
   void* explain_pin = nullptr; size_t explain_pin_bytes = 0;   // page-locked explanation rows of kprn_recommend_explain_ragged
   std::vector<kprn_graph*> graphs;                     // path_find.hip: the knowledge graphs alive on this handle (kprn_destroy frees what is left)
   void* pf_buf = nullptr; size_t pf_buf_bytes = 0;     // device arguments of one kprn_find_paths call (pairs, totals, first rows, counts, flag)
+  std::vector<kprn_sampler*> samplers;                 // neg_sample.hip: the negative samplers alive on this handle (kprn_destroy frees what is left)
+  void* ns_buf = nullptr; size_t ns_buf_bytes = 0;     // device arguments and results of one sampling call (users or positives, negatives, n_found)
 
   // option "deterministic": every float sum of a training step whose addends come from different waves or workgroups of one launch is formed in an order that
   // depends on the batch and the launch geometry only; pipelines that cannot do that refuse to train
@@ -498,6 +501,10 @@ void launch(hipStream_t s, const Args& a, int max_n);   // hist must be zero; ev
 namespace pf {
 void release_all(kprn_handle* h);   // kprn_destroy: the graphs still alive and the finder's argument buffer
 }  // namespace pf
+// ---- negative sampler (neg_sample.hip): kprn_sampler_* / kprn_sample_negatives / kprn_find_training_paths / kprn_host_sample_negatives ----
+namespace ns {
+void release_all(kprn_handle* h);   // kprn_destroy: the samplers still alive and the sampling calls' buffer
+}  // namespace ns
 
 // ---- explanation stage (explain_paths.hip) -------------------------------------------------------
 namespace ex {

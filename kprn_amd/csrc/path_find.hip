@@ -18,42 +18,17 @@
 //             while rank < counts[b] -- the range the pair was allotted -- and a hop's chunks stop once the running rank reaches it (with a cap of 28 the fill
 //             pass touches a few chunks, whatever found is).  The rows a workgroup placed are summed and compared with counts[b]: a disagreement between
 //             the passes sets the flag (KPRN_E_DEVICE), and no write leaves the pair's range either way.
-// The host twin walks the same primitives (edge_range, mid_range, write_row) pair by pair on its threads.
-#include "kprn_internal.h"
+// The host twin walks the same primitives (edge_range, mid_range, write_row) pair by pair on its threads.  The graph, the CSR view and edge_range are in
+// path_find_dev.h, shared with neg_sample.hip; find_staged runs the two passes over a pair list that is staged into HBM by its caller.
+#include "path_find_dev.h"
 
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_select.hpp>
 
-#include <algorithm>
-#include <atomic>
-#include <thread>
-#include <tuple>
-
-struct kprn_graph {
-  int32_t Ve = 0, Vr = 0, Vt = 0, nT = 0, end_rel = 0;
-  int64_t E = 0;                 // stored edges (after duplicates and self-loops are gone)
-  int32_t* rowptr = nullptr;     // device [Ve + 1]: edges of node n = rowptr[n] .. rowptr[n + 1] - 1 (n = 0 has none)
-  int32_t* col = nullptr;        // device [E] destination
-  int32_t* rel = nullptr;        // device [E] relation
-  int32_t* types = nullptr;      // device [Ve][nT]: row e - 1 = the type slots of entity e
-};
-
 namespace pf {
 
-struct Csr { const int32_t* rowptr; const int32_t* col; const int32_t* rel; };
 struct Fmt { const int32_t* types; int nT, Vt, Ve, Vr, T, F, end_rel; };
 constexpr int TPB = 256;
-
-// the edges n -> target: [lo, hi) (contiguous, relation ascending)
-__host__ __device__ static inline void edge_range(const Csr& g, int n, int target, int& lo, int& hi) {
-  const int a = g.rowptr[n], b = g.rowptr[n + 1];
-  int l = a, r = b;
-  while (l < r) { const int m = l + ((r - l) >> 1); if (g.col[m] < target) l = m + 1; else r = m; }
-  lo = l;
-  r = b;
-  while (l < r) { const int m = l + ((r - l) >> 1); if (g.col[m] <= target) l = m + 1; else r = m; }
-  hi = l;
-}
 
 // the closing edges of the 3-hop paths u -> n1 -> col[e1] -> i: their number, the first one in lo; none when the middle node repeats u, i or n1
 __host__ __device__ static inline int mid_range(const Csr& g, int u, int i, int n1, int e1, int& lo) {
@@ -307,12 +282,19 @@ static int validate_graph(const int32_t* src, const int32_t* dst, const int32_t*
     if (node_types[k] < 1 || node_types[k] > Vt) return bad(KPRN_E_INDEX, "a type id is outside 1..Vt");
   return KPRN_OK;
 }
-static int validate_find(const int32_t* pairs, int32_t B, int32_t Ve, int32_t min_hops, int32_t max_hops, int32_t max_paths, int32_t T, std::string* why) {
+int validate_find_limits(int32_t B, int32_t min_hops, int32_t max_hops, int32_t max_paths, int32_t T, std::string* why) {
   auto bad = [&](int code, const char* t) { if (why) *why = t; return code; };
-  if (!pairs || B < 1) return bad(KPRN_E_ARG, "pairs is NULL or B < 1");
+  if (B < 1) return bad(KPRN_E_ARG, "pairs is NULL or B < 1");
   if (min_hops < 1 || min_hops > max_hops || max_hops > 3) return bad(KPRN_E_ARG, "hops: 1 <= min_hops <= max_hops <= 3");
   if (max_paths < 1 || max_paths > kk::RAGGED_MAX_SEG) return bad(KPRN_E_ARG, "max_paths must be in 1..4096");
   if (T < max_hops + 1) return bad(KPRN_E_ARG, "T must be at least max_hops + 1");
+  return KPRN_OK;
+}
+static int validate_find(const int32_t* pairs, int32_t B, int32_t Ve, int32_t min_hops, int32_t max_hops, int32_t max_paths, int32_t T, std::string* why) {
+  auto bad = [&](int code, const char* t) { if (why) *why = t; return code; };
+  if (!pairs) return bad(KPRN_E_ARG, "pairs is NULL or B < 1");
+  const int rc = validate_find_limits(B, min_hops, max_hops, max_paths, T, why);
+  if (rc != KPRN_OK) return rc;
   for (int64_t k = 0; k < 2 * (int64_t)B; ++k)
     if (pairs[k] < 1 || pairs[k] >= Ve) return bad(KPRN_E_INDEX, "a pair's node is outside 1..Ve-1");
   return KPRN_OK;
@@ -398,33 +380,7 @@ void release_all(kprn_handle* h) {
   if (h->pf_buf) { hipFree(h->pf_buf); h->pf_buf = nullptr; h->pf_buf_bytes = 0; }
 }
 
-// ---- host twin: the same rule over a CSR built by std::sort ---------------------------------------------------------------------------------
-struct HostCsr { std::vector<int32_t> rowptr, col, rel; };
-static HostCsr host_csr(const int32_t* src, const int32_t* dst, const int32_t* rel, int64_t E, int32_t Ve) {
-  std::vector<std::tuple<int32_t, int32_t, int32_t>> ed;
-  ed.reserve((size_t)E);
-  for (int64_t e = 0; e < E; ++e) if (src[e] != dst[e]) ed.emplace_back(src[e], dst[e], rel[e]);
-  std::sort(ed.begin(), ed.end());
-  ed.erase(std::unique(ed.begin(), ed.end()), ed.end());
-  HostCsr g;
-  g.rowptr.assign((size_t)Ve + 2, 0);
-  g.col.resize(ed.size() + 1); g.rel.resize(ed.size() + 1);
-  for (size_t e = 0; e < ed.size(); ++e) { g.rowptr[(size_t)std::get<0>(ed[e]) + 1]++; g.col[e] = std::get<1>(ed[e]); g.rel[e] = std::get<2>(ed[e]); }
-  for (size_t n = 0; n + 1 < g.rowptr.size(); ++n) g.rowptr[n + 1] += g.rowptr[n];
-  return g;
-}
-
-template <class Fn>
-static void parallel_pairs(int32_t B, int threads, Fn&& fn) {
-  const int nth = std::max(1, std::min(threads, (int)B));
-  if (nth == 1) { for (int32_t b = 0; b < B; ++b) fn(b); return; }
-  std::atomic<int32_t> next{0};   // (which thread takes a pair changes nothing a pair computes)
-  std::vector<std::thread> th;
-  for (int t = 0; t < nth; ++t)
-    th.emplace_back([&] { for (int32_t b = next.fetch_add(1); b < B; b = next.fetch_add(1)) fn(b); });
-  for (auto& t : th) t.join();
-}
-
+// ---- host twin: the same rule over the host CSR (path_find_dev.h) ---------------------------------------------------------------------------
 static void host_pair_totals(const Csr& g, int u, int i, int hmask, int64_t* t4) {
   int64_t c1 = 0, c2 = 0, c3 = 0;
   if (u != i) {
@@ -456,6 +412,76 @@ static int64_t host_pair_fill(const Csr& g, const Fmt& f, int u, int i, int hmas
     done2 += c2; done3 += c3;
   }
   return placed;
+}
+
+void find_staged(kprn_handle* h, const kprn_graph* g, const StagePairs& stage, const float* labels, int32_t B, int32_t min_hops, int32_t max_hops,
+                 int32_t max_paths, int32_t T, int32_t* pairs_out, int32_t* counts, int64_t* found, kprn_batch** out) {
+  const kprn_config& c = h->cfg;
+  KPRN_REQUIRE(c.F >= c.num_types + 2, KPRN_E_ARG, "F must hold num_types + 2 columns");
+  hipStream_t s = h->stream;
+  const int hmask = hop_mask(min_hops, max_hops);
+  // device arguments of the two passes: pairs [2B] | cnt [B] | flag [4] (int32), then tot [4B] | first [B] (int64)
+  const size_t w32 = ((size_t)3 * B + 4 + 1) & ~(size_t)1, total = w32 * 4 + (size_t)5 * B * 8;
+  if (total > h->pf_buf_bytes) {
+    HIP_TRY(hipStreamSynchronize(s));
+    if (h->pf_buf) { hipFree(h->pf_buf); h->pf_buf = nullptr; h->pf_buf_bytes = 0; }
+    hipError_t e = kprn_dev_malloc(&h->pf_buf, total + total / 4 + 64);
+    if (e != hipSuccess) throw KprnError{KPRN_E_NOMEM, std::string("hipMalloc failed: ") + hipGetErrorString(e)};
+    h->pf_buf_bytes = total + total / 4;
+  }
+  int32_t* d_pairs = (int32_t*)h->pf_buf;
+  int32_t* d_cnt = d_pairs + 2 * (size_t)B;
+  int32_t* d_flag = d_cnt + B;
+  int64_t* d_tot = (int64_t*)((char*)h->pf_buf + w32 * 4);
+  int64_t* d_first = d_tot + 4 * (size_t)B;
+  const Csr csr{g->rowptr, g->col, g->rel};
+  stage(d_pairs, s);
+  {
+    ProfScope ps(h, "find_paths_count");
+    hipLaunchKernelGGL(k_count, dim3((unsigned)B), dim3(TPB), 0, s, csr, d_pairs, hmask, d_tot);
+    HIP_TRY(hipGetLastError());
+  }
+  std::vector<int64_t> tot((size_t)4 * B), first((size_t)B);
+  HIP_TRY(hipMemcpyAsync(tot.data(), d_tot, tot.size() * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+  if (pairs_out) HIP_TRY(hipMemcpyAsync(pairs_out, d_pairs, (size_t)2 * B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  // the scan over the pairs: counts, the pairs that have paths, each one's first row
+  std::vector<int32_t> cnt((size_t)B), kept;
+  std::vector<float> lab;
+  int64_t N = 0;
+  for (int32_t b = 0; b < B; ++b) {
+    const int64_t f = tot[4 * (size_t)b + 3];
+    KPRN_REQUIRE(f >= 0, KPRN_E_DEVICE, "find_paths: the counting pass returned a negative count");
+    cnt[b] = (int32_t)std::min<int64_t>(f, max_paths);
+    first[b] = cnt[b] > 0 ? N : -1;
+    if (cnt[b] > 0) { kept.push_back(cnt[b]); if (labels) lab.push_back(labels[b]); }
+    N += cnt[b];
+  }
+  if (!kept.empty()) {
+    HIP_TRY(hipMemcpyAsync(d_cnt, cnt.data(), (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_first, first.data(), (size_t)B * sizeof(int64_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(d_flag, 0, sizeof(int32_t), s));
+    const Fmt fmt{g->types, g->nT, g->Vt, g->Ve, g->Vr, T, c.F, g->end_rel};
+    const slots::DeviceFill fill = [&](int32_t* idx_dev, hipStream_t st) {
+      ProfScope ps(h, "find_paths_fill", st);
+      hipLaunchKernelGGL(k_fill, dim3((unsigned)B), dim3(TPB), 0, st, csr, fmt, d_pairs, hmask, d_tot, d_first, d_cnt, idx_dev, d_flag);
+      HIP_TRY(hipGetLastError());
+    };
+    kprn_batch* nb = nullptr;
+    slots::create(h, nullptr, kept.data(), labels ? lab.data() : nullptr, (int32_t)kept.size(), 0, N, T, c.F, &nb, &fill);
+    int32_t flag = 0;
+    const hipError_t e = hipMemcpy(&flag, d_flag, sizeof(int32_t), hipMemcpyDeviceToHost);   // (create has drained the stream)
+    if (e != hipSuccess || flag != 0) {
+      kprn_batch_destroy(h, nb);
+      HIP_TRY(e);
+      throw KprnError{KPRN_E_DEVICE, "find_paths: the fill pass placed a different number of paths than the counting pass allotted"};
+    }
+    *out = nb;
+  }
+  for (int32_t b = 0; b < B; ++b) {
+    if (counts) counts[b] = cnt[b];
+    if (found) found[b] = tot[4 * (size_t)b + 3];
+  }
 }
 
 }  // namespace pf
@@ -502,71 +528,10 @@ int kprn_find_paths(kprn_handle* h, const kprn_graph* g, const int32_t* pairs, c
   std::string why;
   const int rc = pf::validate_find(pairs, B, g->Ve, min_hops, max_hops, max_paths, T, &why);
   if (rc != KPRN_OK) throw KprnError{rc, why};
-  const kprn_config& c = h->cfg;
-  KPRN_REQUIRE(c.F >= c.num_types + 2, KPRN_E_ARG, "F must hold num_types + 2 columns");
-  hipStream_t s = h->stream;
-  const int hmask = pf::hop_mask(min_hops, max_hops);
-  // device arguments of the two passes: pairs [2B] | cnt [B] | flag [4] (int32), then tot [4B] | first [B] (int64)
-  const size_t w32 = ((size_t)3 * B + 4 + 1) & ~(size_t)1, total = w32 * 4 + (size_t)5 * B * 8;
-  if (total > h->pf_buf_bytes) {
-    HIP_TRY(hipStreamSynchronize(s));
-    if (h->pf_buf) { hipFree(h->pf_buf); h->pf_buf = nullptr; h->pf_buf_bytes = 0; }
-    hipError_t e = kprn_dev_malloc(&h->pf_buf, total + total / 4 + 64);
-    if (e != hipSuccess) throw KprnError{KPRN_E_NOMEM, std::string("hipMalloc failed: ") + hipGetErrorString(e)};
-    h->pf_buf_bytes = total + total / 4;
-  }
-  int32_t* d_pairs = (int32_t*)h->pf_buf;
-  int32_t* d_cnt = d_pairs + 2 * (size_t)B;
-  int32_t* d_flag = d_cnt + B;
-  int64_t* d_tot = (int64_t*)((char*)h->pf_buf + w32 * 4);
-  int64_t* d_first = d_tot + 4 * (size_t)B;
-  const pf::Csr csr{g->rowptr, g->col, g->rel};
-  HIP_TRY(hipMemcpyAsync(d_pairs, pairs, (size_t)2 * B * sizeof(int32_t), hipMemcpyHostToDevice, s));
-  {
-    ProfScope ps(h, "find_paths_count");
-    hipLaunchKernelGGL(pf::k_count, dim3((unsigned)B), dim3(pf::TPB), 0, s, csr, d_pairs, hmask, d_tot);
-    HIP_TRY(hipGetLastError());
-  }
-  std::vector<int64_t> tot((size_t)4 * B), first((size_t)B);
-  HIP_TRY(hipMemcpyAsync(tot.data(), d_tot, tot.size() * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  // the scan over the pairs: counts, the pairs that have paths, each one's first row
-  std::vector<int32_t> cnt((size_t)B), kept;
-  std::vector<float> lab;
-  int64_t N = 0;
-  for (int32_t b = 0; b < B; ++b) {
-    const int64_t f = tot[4 * (size_t)b + 3];
-    KPRN_REQUIRE(f >= 0, KPRN_E_DEVICE, "find_paths: the counting pass returned a negative count");
-    cnt[b] = (int32_t)std::min<int64_t>(f, max_paths);
-    first[b] = cnt[b] > 0 ? N : -1;
-    if (cnt[b] > 0) { kept.push_back(cnt[b]); if (labels) lab.push_back(labels[b]); }
-    N += cnt[b];
-  }
-  if (!kept.empty()) {
-    HIP_TRY(hipMemcpyAsync(d_cnt, cnt.data(), (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d_first, first.data(), (size_t)B * sizeof(int64_t), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemsetAsync(d_flag, 0, sizeof(int32_t), s));
-    const pf::Fmt fmt{g->types, g->nT, g->Vt, g->Ve, g->Vr, T, c.F, g->end_rel};
-    const slots::DeviceFill fill = [&](int32_t* idx_dev, hipStream_t st) {
-      ProfScope ps(h, "find_paths_fill", st);
-      hipLaunchKernelGGL(pf::k_fill, dim3((unsigned)B), dim3(pf::TPB), 0, st, csr, fmt, d_pairs, hmask, d_tot, d_first, d_cnt, idx_dev, d_flag);
-      HIP_TRY(hipGetLastError());
-    };
-    kprn_batch* nb = nullptr;
-    slots::create(h, nullptr, kept.data(), labels ? lab.data() : nullptr, (int32_t)kept.size(), 0, N, T, c.F, &nb, &fill);
-    int32_t flag = 0;
-    const hipError_t e = hipMemcpy(&flag, d_flag, sizeof(int32_t), hipMemcpyDeviceToHost);   // (create has drained the stream)
-    if (e != hipSuccess || flag != 0) {
-      kprn_batch_destroy(h, nb);
-      HIP_TRY(e);
-      throw KprnError{KPRN_E_DEVICE, "find_paths: the fill pass placed a different number of paths than the counting pass allotted"};
-    }
-    *out = nb;
-  }
-  for (int32_t b = 0; b < B; ++b) {
-    if (counts) counts[b] = cnt[b];
-    if (found) found[b] = tot[4 * (size_t)b + 3];
-  }
+  const pf::StagePairs stage = [&](int32_t* d_pairs, hipStream_t s) {
+    HIP_TRY(hipMemcpyAsync(d_pairs, pairs, (size_t)2 * B * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  };
+  pf::find_staged(h, g, stage, labels, B, min_hops, max_hops, max_paths, T, nullptr, counts, found, out);
   API_END(h)
 }
 

@@ -8,6 +8,9 @@ Ids: the vocab files are 0-based and the engine's ids are those + 1 (int2torch.l
 path on the left with the engine's pad rows (Vt, Ve, Vr: the last row of each table); `from_triples(strict=True)` refuses a vocabulary whose
 #PAD_TOKEN is not the last id of its table, because the rows would then differ from the formatter's.
 """
+import sys
+import time
+
 import numpy as np
 
 from . import _ffi
@@ -74,6 +77,23 @@ class KnowledgeGraph:
             g = self._device[id(eng)] = eng.graph(self.src, self.dst, self.rel, self.node_types, self.end_relation)
         return g
 
+    def relation_id(self, relation_name):
+        if self.vocabs is None or relation_name not in self.vocabs.relation:
+            raise ValueError("the relation vocabulary has no %r" % (relation_name,))
+        return int(self.vocabs.relation[relation_name]) + 1
+
+    def interactions(self, relation_name):
+        """the distinct (user, item) pairs joined by an edge of that relation, [n, 2] int32, sorted by (user, item): the positives to train on"""
+        m = self.rel == self.relation_id(relation_name)
+        pr = np.stack([self.src[m], self.dst[m]], axis=1).astype(np.int32)
+        return np.unique(pr, axis=0) if len(pr) else pr.reshape(0, 2)
+
+    def item_weights(self, items, alpha, relation_name):
+        """(in-degree over that relation) ^ alpha for each of `items`, fp32 computed in double: the reference's generate_fq_dict (data_prepare/sample.py)
+        without its normalisation, which the sampler's thresholds do.  alpha = 0: all ones (uniform)"""
+        deg = np.bincount(self.interactions(relation_name)[:, 1], minlength=self.Ve + 1).astype(np.float64)
+        return np.power(deg[np.asarray(items, np.int64)], float(alpha)).astype(np.float32)
+
     def host_find_paths(self, pairs, min_hops, max_hops, max_paths, T, F=None, threads=1, want_idx=True):
         return _ffi.host_find_paths(self.src, self.dst, self.rel, self.node_types, self.Vr, self.Vt, self.end_relation, pairs, min_hops, max_hops, max_paths,
                                     T, F=F, threads=threads, want_idx=want_idx)
@@ -122,3 +142,71 @@ def recommend(eng, kg, user, items, K, M, min_hops=1, max_hops=3, max_paths=28, 
         return out
     finally:
         batch.free()
+
+
+def train_from_graph(eng, kg, positives, opt, minibatch, n_neg, num_epochs, seed, sampler=None, max_attempts=16, min_hops=2, max_hops=3, max_paths=28, T=None,
+                     class_id=1, epoch_hooks=(), start_iteration=1, gradient_step_counter=100, out=None, stats=None):
+    """Training from a knowledge graph alone: every step samples its negatives, finds the paths and trains, all on the device.
+    positives [n, 2] = (user, item) entity ids (KnowledgeGraph.interactions); sampler: an _ffi.Sampler (None: the positives' distinct items, uniform).
+    Each epoch e shuffles the positives with np.random.RandomState(seed + e) and walks them `minibatch` at a time; a step is
+    Engine.find_training_paths (seed, draw = the global step number) -> train_step -> free.  A minibatch in which no pair has a path is skipped and counted.
+    Losses are summed on the device (option "loss_accumulate"); the epoch lines and hooks (OptimizerCallback) are MyOptimizer's.
+    -> the epochs' average losses; stats (a dict, optional) receives steps / skipped / pairs."""
+    out = sys.stdout if out is None else out
+    graph = kg.on(eng) if isinstance(kg, KnowledgeGraph) else kg
+    pos = np.ascontiguousarray(positives, np.int32).reshape(-1, 2)
+    if len(pos) == 0:
+        raise ValueError("no positives to train on")
+    own = sampler is None
+    if own:
+        sampler = eng.sampler(np.unique(pos[:, 1]))
+    T = max_hops + 1 if T is None else int(T)
+    st = dict(steps=0, skipped=0, pairs=0)
+    history = []
+    for hook in epoch_hooks:
+        if hook.epochHookFreq == 1:
+            hook.hook(0)
+    eng.set_option("loss_accumulate", "1")
+    eng.loss_sum(reset=True)
+    try:
+        draw = 0
+        prev = time.time()
+        for i in range(int(start_iteration), int(num_epochs) + 1):
+            order = np.random.RandomState((int(seed) + i) & 0xFFFFFFFF).permutation(len(pos))
+            total, batches, processed, since = 0.0, 0, 0, 0
+            for k in range(0, len(pos), int(minibatch)):
+                mb = pos[order[k:k + int(minibatch)]]
+                batch, _, counts, _ = eng.find_training_paths(graph, sampler, mb, n_neg, seed, draw, min_hops, max_hops, max_paths, T, max_attempts=max_attempts)
+                draw += 1
+                if batch is None:
+                    st["skipped"] += 1
+                    continue
+                try:
+                    eng.train_step(batch, opt, class_id, want_loss=False)
+                finally:
+                    batch.free()
+                batches += 1
+                since += 1
+                processed += len(mb)
+                st["steps"] += 1
+                st["pairs"] += batch.B
+                if since % int(gradient_step_counter) == 0:
+                    total += eng.loss_sum(reset=True)[0]
+                    print("Printing after %d gradient steps\navg loss in epoch = %f\n" % (gradient_step_counter, total / since), file=out)
+            total += eng.loss_sum(reset=True)[0]
+            avg = total / max(batches, 1)
+            now = time.time()
+            elapsed, prev = now - prev, now
+            print("\nIter: %d\navg loss in epoch = %f\ntotal elapsed = %f\ntime per batch = %f" % (i, avg, elapsed, elapsed / max(batches, 1)), file=out)
+            print("examples/sec = %f" % (processed / max(elapsed, 1e-9)), file=out)
+            history.append(avg)
+            for hook in epoch_hooks:
+                if i % hook.epochHookFreq == 0:
+                    hook.hook(i)
+    finally:
+        eng.set_option("loss_accumulate", "0")
+        if own:
+            sampler.free()
+    if stats is not None:
+        stats.update(st)
+    return history

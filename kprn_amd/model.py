@@ -49,11 +49,21 @@ def flag_parser():
     # evaluation during training (the slot OneModel.lua:389 left commented out): every -evaluationFrequency epochs the pairs of -testList are scored
     # and the groups of -rank_samples ranked on the device (scoring.rank_test_set); without -rank_samples nothing is evaluated
     a("-rank_samples", default=""); a("-rank_entity", default=""); a("-rank_users", default=""); a("-testList", default="test.list")
+    # training from a knowledge graph (python -m kprn_amd.train; not in the reference): negatives sampled and paths found on the device, step by step
+    a("-kg", default="", help="triples.tsv (head, relation, tail names per line, directed): train from this graph instead of -dataDir; needs -vocab_dir and -interaction_rel")
+    a("-vocab_dir", default=""); a("-interaction_rel", default="", help="the relation whose (user, item) edges are the positives")
+    a("-negatives", type=int, default=4); a("-neg_alpha", type=float, default=0.0, help="negatives are drawn with weight (item's interactions)^neg_alpha; 0 = uniform")
+    a("-neg_attempts", type=int, default=16); a("-min_hops", type=int, default=2); a("-max_hops", type=int, default=3); a("-max_paths", type=int, default=28)
+    a("-sampleSeed", type=int, default=1)
     return p
 
 
 def parse_flags(argv=None):
-    return flag_parser().parse_args(argv)
+    p = flag_parser()
+    params = p.parse_args(argv)
+    if params.kg and not (params.vocab_dir and params.interaction_rel):
+        p.error("-kg needs -vocab_dir DIR (the vocabulary files) and -interaction_rel NAME (the relation of the user-item edges to train on)")
+    return params
 
 
 RNN_TYPES = {"lstm": 0, "rnn": 1, "gru": 2}

@@ -3,9 +3,16 @@
 Same flags (OneModel.lua:27-87), same data layout (dataDir/train.list naming .torch / .int / .npz
 files), same epoch log lines, checkpoint "<model>-latest" every saveFrequency epochs
 (OneModel.lua:392-408; native format, kprn_save).
+
+With `-kg triples.tsv -vocab_dir DIR -interaction_rel NAME` (an extension) there are no path files: the (user, item) edges of that relation are the
+positives, and every step samples -negatives items per positive (an item's weight is its number of interactions to the power -neg_alpha's value, 0 =
+uniform; at most -neg_attempts draws per negative), finds the pairs' paths of -min_hops .. -max_hops hops (at most -max_paths each) and trains, all on the device (graph.train_from_graph); -sampleSeed seeds the shuffles
+and the draws.  Same epoch lines, same -model / -saveFrequency.
 """
 import os
 import sys
+
+import numpy as np
 
 from . import model
 from .batcher import BatcherFileList
@@ -40,8 +47,36 @@ def make_evaluator(eng, params, log=None):
     return evaluator
 
 
+def train_from_kg(params, eng, callbacks):
+    from . import graph
+    from .pathformat import Vocabs
+    kg = graph.KnowledgeGraph.from_triples(graph.read_triples(params.kg), Vocabs(params.vocab_dir), params.numEntityTypes)
+    positives = kg.interactions(params.interaction_rel)
+    if len(positives) == 0:
+        sys.exit("the graph has no edge of relation %s" % params.interaction_rel)
+    items = np.unique(positives[:, 1])
+    sampler = eng.sampler(items, kg.item_weights(items, params.neg_alpha, params.interaction_rel))
+    print("Training from the graph: %d positives, %d candidate items, %d negatives each" % (len(positives), len(items), params.negatives))
+    graph.train_from_graph(eng, kg, positives, model.opt_from_flags(params), params.minibatch, params.negatives, params.numEpochs, params.sampleSeed,
+                           sampler=sampler, max_attempts=params.neg_attempts, min_hops=params.min_hops, max_hops=params.max_hops, max_paths=params.max_paths,
+                           epoch_hooks=callbacks, start_iteration=params.startIteration, gradient_step_counter=params.gradientStepCounter)
+    return 0
+
+
+def check_kg_vocabulary(params):
+    """before the engine exists: the vocabulary files must be the ones the model flags describe (as python -m kprn_amd.recommend checks)"""
+    from .pathformat import Vocabs
+    voc = Vocabs(params.vocab_dir)
+    sizes = tuple(max(int(v) for v in d.values()) + 1 for d in (voc.entity_type, voc.entity, voc.relation))
+    if sizes != (params.entityTypeVocabSize, params.entityVocabSize, params.relationVocabSize):
+        sys.exit("the vocabularies hold %d types, %d entities, %d relations; the model flags say %d, %d, %d"
+                 % (sizes + (params.entityTypeVocabSize, params.entityVocabSize, params.relationVocabSize)))
+
+
 def main(argv=None):
     params = model.parse_flags(argv)
+    if params.kg:
+        check_kg_vocabulary(params)
     if params.createExptDir == 1 and params.exptDir:
         os.makedirs(params.exptDir, exist_ok=True)
         with open(os.path.join(params.exptDir, "config.txt"), "w") as f:  # OneModel.lua:128-170
@@ -50,7 +85,7 @@ def main(argv=None):
     eng = model.build_engine(params)
     print(model.REDUCER_NAME[model.reducer_of_train_flag(params.topK)])
     print("Using Adam!" if params.useAdam == 1 else "Using adagrad!")
-    trainBatcher = BatcherFileList(params.dataDir, params.minibatch, True, 100, params.gpuid != -1, "train.list", seed=params.seed, check_ids=False)   # (the engine validates every id)
+    trainBatcher = None if params.kg else BatcherFileList(params.dataDir, params.minibatch, True, 100, params.gpuid != -1, "train.list", seed=params.seed, check_ids=False)   # (the engine validates every id)
     callbacks = []
     if params.model:
         def saver(i):
@@ -65,6 +100,8 @@ def main(argv=None):
             print("WARNING! - createExptDir is NOT set!")
     if params.rank_samples:
         callbacks.append(OptimizerCallback(params.evaluationFrequency, make_evaluator(eng, params), "evaluation"))   # (OneModel.lua:389)
+    if params.kg:
+        return train_from_kg(params, eng, callbacks)
     opt = model.opt_from_flags(params)
     optimizer = MyOptimizer(eng, {"numEpochs": params.numEpochs, "epochHooks": callbacks, "minibatchsize": params.minibatch},
                             opt, startIteration=params.startIteration, gradientStepCounter=params.gradientStepCounter)
