@@ -110,14 +110,6 @@ static void reserve(kprn_handle* h, kprn_batch* b, int32_t B, int32_t P, int32_t
   }
 }
 
-void scratch_reserve(void** scratch, size_t* bytes, size_t need) {
-  if (need <= *bytes) return;
-  if (*scratch) hipFree(*scratch);
-  *scratch = nullptr; *bytes = 0;
-  HIP_TRY(kprn_dev_malloc(scratch, need * 2));
-  *bytes = need * 2;
-}
-
 // upload + validation + identical-prefix plan + occurrence index on stream s; the host-side summary (validation flag, distinct
 // rows, plan header, per-tile prefix lengths) lands in the slot's pinned block behind them.  Nothing here waits for the device.
 // idx == null: the ids are produced on the device by fill, straight into the slot's idx block
@@ -223,7 +215,8 @@ void create(kprn_handle* h, const int32_t* idx, const int32_t* counts, const flo
     reserve(h, b, B, P, T, F, labels != nullptr, 0, 0, counts ? N : 0);
     if (counts) set_ragged(b, &rp);
     b->has_index = true; b->idx_valid = true;
-    scratch_reserve(&h->bidx_scratch, &h->bidx_scratch_bytes, std::max(bidx::scratch_bytes(b->n_index, h->cfg.Ve), bidx::prefix_scratch_bytes(N, fused::KCAP)));
+    const size_t need = std::max(bidx::scratch_bytes(b->n_index, h->cfg.Ve), bidx::prefix_scratch_bytes(N, fused::KCAP));
+    grow_device(h->bidx_scratch, h->bidx_scratch_bytes, need, need * 2, need * 2, {});   // (no wait, as before: the users of this scratch drain the stream)
     enqueue(h, b, idx, labels, h->stream, h->bidx_scratch, h->bidx_scratch_bytes, fill);
     HIP_TRY(hipStreamSynchronize(h->stream));
     finish(h, b);
@@ -424,10 +417,7 @@ void feed(kprn_handle* h, kprn_batch** slot, const int32_t* idx, const float* la
       b->host_built = false; b->has_index = true; b->idx_valid = true;
       const int64_t N = b->N;
       const size_t need = std::max(bidx::scratch_bytes(b->n_index, h->cfg.Ve), bidx::prefix_scratch_bytes(N, fused::KCAP));
-      if (need > h->feed_scratch_bytes) {
-        HIP_TRY(hipStreamSynchronize(h->feed_stream));
-        scratch_reserve(&h->feed_scratch, &h->feed_scratch_bytes, need);
-      }
+      grow_device(h->feed_scratch, h->feed_scratch_bytes, need, need * 2, need * 2, {h->feed_stream}, /*wait_if_empty=*/true);
       // everything enqueued on the handle so far (the last readers of this slot among it) comes first
       HIP_TRY(hipEventRecord(h->ev_feed_fork, h->stream));
       HIP_TRY(hipStreamWaitEvent(h->feed_stream, h->ev_feed_fork, 0));

@@ -122,23 +122,6 @@ static void step_tab_reserve(kprn_handle* h, int64_t need) {
   h->step_tab = nd; h->step_tab_host = nh; h->step_tab_cap = cap;
 }
 
-// scoring overlap: the main stream waits for the pass running on the side stream (before anything that changes what that pass
-// reads -- parameters, the prefix table -- and before the backward kernels, which want the chip to themselves)
-void join_score(kprn_handle* h) {
-  if (h->score_rest_batch) launch_score_rest(h);   // (a split pass whose second part nobody placed: it goes now)
-  if (!h->score_pending) return;
-  HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_score_done, 0));
-  h->score_pending = false;
-}
-
-// ranking stage: the main stream waits for the board puts queued on the scoring stream (before it reads the board, and before a pass that runs on the
-// main stream writes the side buffers those puts read: "score_dual")
-static void join_put(kprn_handle* h) {
-  if (!h->put_side) return;
-  HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_put, 0));
-  h->put_side = false;
-}
-
 // bring every entity row up to opt_step (needed before anything reads the whole table)
 static void flush_lazy(kprn_handle* h) {
   join_score(h);
@@ -185,7 +168,7 @@ void materialize_step_rows(kprn_handle* h) {
   h->rows_view = h->step_rows; h->count_view = h->step_count; h->view_batch = nullptr;
 }
 
-static void ensure_ws_common(kprn_handle* h, int64_t N, int64_t B, int64_t n_wg = 0) {
+void ensure_ws_common(kprn_handle* h, int64_t N, int64_t B, int64_t n_wg) {
   const int64_t np = std::max<int64_t>(kk::loss_partials((int)B), n_wg);   // (n_wg: the loss-stage workgroups of a ragged batch)
   dev_grow2(h->stream, h->loss_partial, h->loss_partial_cap, np);
   Workspace& w = h->ws;
@@ -232,7 +215,7 @@ void ensure_ws_generic(kprn_handle* h, int64_t N, int T) {
 }
 
 // rows of this batch that are behind opt_step are replayed before the forward reads them
-static void catch_up(kprn_handle* h, const kprn_batch* b) {
+void catch_up(kprn_handle* h, const kprn_batch* b) {
   if (h->lazy_pending && !b->has_index) { flush_lazy(h); return; }   // (no row list: bring the whole table up to date instead)
   if (!h->lazy_pending || b->n_uniq == 0) return;
   if (h->caught_serial == b->serial && h->caught_step == h->opt_step) return;  // this batch's rows are already current
@@ -250,7 +233,7 @@ static void catch_up(kprn_handle* h, const kprn_batch* b) {
 }
 
 // every_class: also pooled / probs of all C classes (what kprn_forward_batch can hand out); else the selected class only
-static void pool_stage(kprn_handle* h, const kprn_batch* b, int cid, bool every_class) {
+void pool_stage(kprn_handle* h, const kprn_batch* b, int cid, bool every_class) {
   const kprn_config& c = h->cfg;
   Workspace& w = h->ws;
   ProfScope ps(h, "pool_sigmoid");
@@ -262,7 +245,7 @@ static void pool_stage(kprn_handle* h, const kprn_batch* b, int cid, bool every_
   kk::pool_sigmoid(h->stream, w.S, b->B, b->P, c.C, c.reducer, c.K, every_class ? w.pooled : nullptr, every_class ? w.probs : nullptr, cid, w.sel, h->sel_host_armed);
 }
 
-static void check_batch(kprn_handle* h, const kprn_batch* b, int class_id) {
+void check_batch(kprn_handle* h, const kprn_batch* b, int class_id) {
   KPRN_REQUIRE(b != nullptr, KPRN_E_ARG, "batch is NULL");
   slots::ready(h, b);  // (a slot filled by kprn_batch_feed_async: its feed was issued a step ago)
   KPRN_REQUIRE(class_id >= 1 && class_id <= h->cfg.C, KPRN_E_ARG, "classId must be in 1..C (nn.Select(2,classId), MyOptimizer.lua:126)");
@@ -283,8 +266,7 @@ bool use_fused(kprn_handle* h, const kprn_batch* b, bool save_for_backward) {
 // all_scores: the caller reads S itself, every column of it (path_scores).  The fused fp32 forward's head forms column classId alone unless a reader of the pass
 // needs other columns (option "head_select"): the training forward never does (the loss stage and the BPTT launches read S[:, cid] and W_out[cid]), a scoring
 // pass does when its pooling stage runs for every class or the caller copies S.
-static void forward_impl(kprn_handle* h, const kprn_batch* b, int class_id, bool save_for_backward, bool do_pool = true, bool every_class = true,
-                         bool all_scores = false) {
+void forward_impl(kprn_handle* h, const kprn_batch* b, int class_id, bool save_for_backward, bool do_pool, bool every_class, bool all_scores) {
   check_batch(h, b, class_id);
   const int64_t N = b->N;
   const int sel = (save_for_backward || !(every_class || all_scores)) ? class_id - 1 : -1;
@@ -296,7 +278,7 @@ static void forward_impl(kprn_handle* h, const kprn_batch* b, int class_id, bool
       // a deferred scoring pass ("score_dual") rides in this training forward's launch; its pooling stage follows on this stream, and the event the
       // pass's readers wait for is recorded here
       const kprn_batch* sb = h->score_rest_batch;
-      join_put(h);   // (a board put queued on the scoring stream still reads sel2, which this pass's pooling stage writes from THIS stream)
+      score::join_put(h);   // (a board put queued on the scoring stream still reads sel2, which this pass's pooling stage writes from THIS stream)
       dual = fused::forward_dual(h, b, sb, h->S2, sel, h->score_rest_cid - 1);   // (the pass's pooling stage reads its own class's column)
       if (dual) {
         h->score_rest_batch = nullptr;
@@ -333,10 +315,7 @@ static void materialize_union(kprn_handle* h) {
   h->dp_union_pending = false;
   const int64_t n = (int64_t)h->dp_world * h->dp_cap;
   const size_t need = bidx::merge_scratch_bytes(n, h->cfg.Ve);
-  if (need > h->bidx_scratch_bytes) {
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    slots::scratch_reserve(&h->bidx_scratch, &h->bidx_scratch_bytes, need);
-  }
+  grow_device(h->bidx_scratch, h->bidx_scratch_bytes, need, need * 2, need * 2, {h->stream}, /*wait_if_empty=*/true);
   if (!h->dp_mark) {
     h->dp_mark = dalloc<int32_t>(h->cfg.Ve);
     HIP_TRY(hipMemsetAsync(h->dp_mark, 0, (size_t)h->cfg.Ve * sizeof(int32_t), h->stream));
@@ -846,226 +825,10 @@ int kprn_zero_pad_tokens(kprn_handle* h) {
   API_END(h)
 }
 
-// ---- batches and feed slots: batch_slots.hip --------------------------------------------------------------------------------
-// ---- a side stream that really runs beside the main stream ---------------------------------------------------------------------
-// HIP multiplexes its streams onto a few hardware queues (GPU_MAX_HW_QUEUES, 4 by default; assigned round-robin as streams are made),
-// and two streams that land on the same queue execute IN ORDER.  In a process that also holds torch's and RCCL's streams the scoring
-// pass's stream shared the main stream's queue in about every other run: the pass then ran strictly before the training forward
-// (profiles/r03: 0.41 + 0.41 ms instead of 0.74 ms for the overlapped pair).  So the stream is probed: a kernel on the main stream
-// waits (bounded, 200 us) for a flag that a kernel on the candidate sets; if the flag never arrives the two share a queue and the
-// next candidate is tried (every new stream advances the round-robin).
-__global__ void k_probe_wait(int* flag, int* seen, long long max_ticks) {
-  const long long t0 = wall_clock64();   // (100 MHz)
-  int f = 0;
-  while (!(f = __hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) && wall_clock64() - t0 < max_ticks) __builtin_amdgcn_s_sleep(32);
-  *seen = f;
-}
-__global__ void k_probe_set(int* flag) { __hip_atomic_store(flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-}  // extern "C"
-hipStream_t make_concurrent_stream(kprn_handle* h, int* probes) {
-  const int kTries = 8;
-  hipStream_t cand[kTries] = {};
-  int32_t* d = dalloc<int32_t>(2);   // {flag, seen}
-  hipStream_t pick = nullptr;
-  int made = 0;
-  try {
-    for (int i = 0; i < kTries && !pick; ++i) {
-      HIP_TRY(hipStreamCreateWithFlags(&cand[i], hipStreamNonBlocking));
-      made = i + 1;
-      HIP_TRY(hipMemsetAsync(d, 0, 2 * sizeof(int32_t), h->stream));
-      HIP_TRY(hipStreamSynchronize(h->stream));
-      hipLaunchKernelGGL(k_probe_wait, dim3(1), dim3(1), 0, h->stream, d, d + 1, (long long)20000);
-      hipLaunchKernelGGL(k_probe_set, dim3(1), dim3(1), 0, cand[i], d);
-      HIP_TRY(hipGetLastError());
-      HIP_TRY(hipStreamSynchronize(h->stream));
-      HIP_TRY(hipStreamSynchronize(cand[i]));
-      int32_t seen = 0;
-      HIP_TRY(hipMemcpy(&seen, d + 1, sizeof(int32_t), hipMemcpyDeviceToHost));
-      if (seen) pick = cand[i];
-    }
-  } catch (...) {
-    for (int i = 0; i < made; ++i) if (cand[i]) hipStreamDestroy(cand[i]);
-    dfree(d);
-    throw;
-  }
-  if (probes) *probes = made; else h->side_stream_probes = made;   // (default: the scoring stream's count, what kprn_get_stat reports)
-  if (!pick) pick = cand[0];   // (every candidate shares the main stream's queue: correct anyway, just not concurrent)
-  for (int i = 0; i < made; ++i) if (cand[i] && cand[i] != pick) hipStreamDestroy(cand[i]);
-  dfree(d);
-  return pick;
-}
-extern "C" {
-
-int kprn_forward_batch_async(kprn_handle* h, const kprn_batch* b, int32_t class_id) {
-  API_BEGIN(h)
-  if (h->score_rest_batch) launch_score_rest(h);   // (the second part of an earlier split pass that nobody placed: before its buffers are reused)
-  h->pool_defer_batch = nullptr;
-  h->last_forward_side = false;
-  if (h->score_overlap && b && use_fused(h, b, false)) {
-    // the pass goes to the side stream with its own output buffers; everything it reads is final on the main stream first
-    check_batch(h, b, class_id);
-    const int64_t N = b->N;
-    catch_up(h, b);
-    ensure_ws_common(h, N, b->B);
-    if (!h->score_stream) {
-      h->score_stream = make_concurrent_stream(h);
-      HIP_TRY(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
-      HIP_TRY(hipEventCreateWithFlags(&h->ev_score_done, hipEventDisableTiming));
-    }
-    if (N > h->cap_N2 || b->B > h->cap_B2) {
-      sync_side_streams(h);
-      dfree(h->S2); dfree(h->sel2);
-      h->cap_N2 = std::max(N, h->cap_N2); h->cap_B2 = std::max<int64_t>(b->B, h->cap_B2);
-      h->S2 = dalloc<float>(h->cap_N2 * h->cfg.C);
-      h->sel2 = dalloc<float>(h->cap_B2);
-    }
-    fused::prefix_forward(h, b);  // (main stream; cached for the pass below and for the training forward of the same batch)
-    fused::mc_prepare(h);         // (likewise: the split weights of the matrix-core forward)
-    if ((h->score_dual == 1 || (h->score_dual == 2 && fused::small_tiles(h, N, b->tile_k != nullptr))) && h->cfg.compute_dtype == 0 && h->cfg.L == 2 &&
-        !(h->score_split > 0.f)) {
-      // "score_dual": the WHOLE pass waits for the training forward that usually comes next and rides in its launch (forward_impl, fused::forward_dual) --
-      // deferred like the second part of a split pass (tile 0 on): whoever needs its result, its buffers or the parameters it reads first runs it the usual
-      // way (join_score -> launch_score_rest)
-      if (h->score_pending && h->ev_score_done) HIP_TRY(hipStreamWaitEvent(h->score_stream, h->ev_score_done, 0));   // (an earlier pass wrote the same S2 / sel2)
-      h->score_rest_batch = b; h->score_rest_cid = class_id; h->score_rest_tile0 = 0;
-      h->score_on_main = false;
-      h->score_pending = true;
-      h->last_forward_side = true;
-      h->last_B = b->B;
-      return KPRN_OK;
-    }
-    h->score_on_main = false;
-    HIP_TRY(hipEventRecord(h->ev_fork, h->stream));
-    HIP_TRY(hipStreamWaitEvent(h->score_stream, h->ev_fork, 0));
-    // an earlier pass (or its deferred part, which may have run on the rest stream: "score_rest_before_bptt") writes the same S2 / sel2: this pass
-    // starts behind it whichever stream it finished on
-    if (h->score_pending && h->ev_score_done) HIP_TRY(hipStreamWaitEvent(h->score_stream, h->ev_score_done, 0));
-    Workspace& w = h->ws;
-    hipStream_t main_stream = h->stream;
-    float* S0 = w.S; float* sel0 = w.sel;
-    h->stream = h->score_stream; w.S = h->S2; w.sel = h->sel2;
-    // "score_split" f: the last f of the batch's tiles wait for kprn_forward_batch_async_rest (a data-parallel step places them under its
-    // collective); the first part runs now, beside whatever is queued next, on the whole chip
-    const int64_t n_tiles = (N + 63) / 64;
-    const int64_t t_split = (h->score_split > 0.f && h->cfg.compute_dtype == 0 && n_tiles >= 64 && !fused::small_tiles(h, N, b->tile_k != nullptr))
-                                ? std::max<int64_t>(1, std::min<int64_t>(n_tiles - 1, (int64_t)((1.0 - h->score_split) * n_tiles + 0.5))) : n_tiles;
-    try {
-      fused::forward(h, b, false, 0, t_split < n_tiles ? t_split : -1, t_split < n_tiles, class_id - 1);   // (kprn_read_probs / kprn_board_put: the selected class)
-      if (t_split == n_tiles) pool_stage(h, b, class_id - 1, false);
-    } catch (...) { h->stream = main_stream; w.S = S0; w.sel = sel0; throw; }
-    h->stream = main_stream; w.S = S0; w.sel = sel0;
-    if (t_split < n_tiles) {
-      h->score_rest_batch = b; h->score_rest_cid = class_id; h->score_rest_tile0 = t_split;
-      if (h->score_rest_before_bptt) {   // (the rest runs on another stream: its pooling stage reads this part's scores)
-        if (!h->ev_part1) HIP_TRY(hipEventCreateWithFlags(&h->ev_part1, hipEventDisableTiming));
-        HIP_TRY(hipEventRecord(h->ev_part1, h->score_stream));
-      }
-    } else HIP_TRY(hipEventRecord(h->ev_score_done, h->score_stream));
-    h->score_pending = true;
-    h->last_forward_side = true;
-    h->last_B = b->B;
-    return KPRN_OK;
-  }
-  forward_impl(h, b, class_id, false, true, /*every_class=*/false);  // kprn_read_probs hands out the selected class
-  API_END(h)
-}
-
-// the second part of a split scoring pass (kprn_set_option "score_split"): the remaining tiles + the pooling stage, behind everything queued
-// on the main stream so far
-extern "C++" void launch_score_rest(kprn_handle* h) {   // (declared in kprn_internal.h: batch_slots.hip calls it)
-  const kprn_batch* b = h->score_rest_batch;
-  h->score_rest_batch = nullptr;
-  if (!b) return;
-  hipStream_t rs = h->score_stream;
-  if (h->score_rest_before_bptt && h->ev_part1) {
-    if (!h->rest_stream) h->rest_stream = make_priority_stream(/*high=*/false);
-    rs = h->rest_stream;
-    HIP_TRY(hipStreamWaitEvent(rs, h->ev_part1, 0));
-  }
-  HIP_TRY(hipEventRecord(h->ev_fork, h->stream));
-  HIP_TRY(hipStreamWaitEvent(rs, h->ev_fork, 0));
-  Workspace& w = h->ws;
-  hipStream_t main_stream = h->stream;
-  float* S0 = w.S; float* sel0 = w.sel;
-  h->stream = rs; w.S = h->S2; w.sel = h->sel2;
-  try {
-    fused::forward(h, b, false, h->score_rest_tile0, -1, false, h->score_rest_cid - 1);
-    pool_stage(h, b, h->score_rest_cid - 1, false);
-  } catch (...) {
-    // the pass cannot finish: nobody may wait for it on a stale event, or hand out its half-filled S2 / sel2 as a finished pass
-    h->stream = main_stream; w.S = S0; w.sel = sel0;
-    h->score_pending = false; h->last_forward_side = false; h->last_B = 0;
-    (void)hipStreamSynchronize(rs);
-    throw;
-  }
-  h->stream = main_stream; w.S = S0; w.sel = sel0;
-  HIP_TRY(hipEventRecord(h->ev_score_done, rs));
-}
-
-static void score_rest_hook(kprn_handle* h) {
-  if (h->score_rest_in_backward && h->score_rest_batch) launch_score_rest(h);
-}
-
-int kprn_forward_batch_async_rest(kprn_handle* h) {
-  API_BEGIN(h)
-  launch_score_rest(h);
-  API_END(h)
-}
-
-int kprn_read_probs(kprn_handle* h, float* probs, int32_t B) {
-  API_BEGIN(h)
-  KPRN_REQUIRE(probs && B > 0 && B <= h->last_B, KPRN_E_ARG, "bad probs buffer / B");
-  if (h->last_forward_side) {
-    if (h->score_rest_batch) launch_score_rest(h);
-    // (the second part of a split pass may have run on the rest stream, and a join may already have cleared score_pending: the pass's event orders this copy)
-    if (h->score_on_main) {   // ("score_dual": the pass ran in a training forward's launch on the main stream)
-      HIP_TRY(hipEventRecord(h->ev_fork, h->stream));
-      HIP_TRY(hipStreamWaitEvent(h->score_stream, h->ev_fork, 0));
-    } else
-    if (h->ev_score_done) HIP_TRY(hipStreamWaitEvent(h->score_stream, h->ev_score_done, 0));
-    HIP_TRY(hipMemcpyAsync(probs, h->sel2, (size_t)B * sizeof(float), hipMemcpyDeviceToHost, h->score_stream));
-    HIP_TRY(hipStreamSynchronize(h->score_stream));
-  } else {
-    HIP_TRY(hipMemcpyAsync(probs, h->ws.sel, (size_t)B * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-  }
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  prof_drain(h);
-  API_END(h)
-}
-
-int kprn_forward_batch(kprn_handle* h, const kprn_batch* b, int32_t class_id, float* probs, float* all_probs, float* pooled, float* path_scores) {
-  API_BEGIN(h)
-  KPRN_REQUIRE(b != nullptr, KPRN_E_ARG, "batch is NULL");
-  // the selected class's probabilities (what model:forward hands test_from_checkpoint.lua:109) come back through a page-locked mirror the pool kernel
-  // writes: no copy operation between the pass and the caller; the other outputs are copied as before and cost the all-class reduction only when asked for
-  struct Disarm { kprn_handle* h; ~Disarm() { h->sel_host_armed = nullptr; } } disarm{h};
-  const bool mirror = probs != nullptr && !h->prof_on;
-  if (mirror) {
-    if ((int64_t)b->B > h->probs_mirror_cap) {
-      if (h->probs_mirror) { HIP_TRY(hipStreamSynchronize(h->stream)); HIP_TRY(hipHostFree(h->probs_mirror)); h->probs_mirror = nullptr; h->probs_mirror_cap = 0; }
-      HIP_TRY(hipHostMalloc((void**)&h->probs_mirror, (size_t)(2 * (int64_t)b->B + 64) * sizeof(float)));
-      h->probs_mirror_cap = 2 * (int64_t)b->B + 64;
-    }
-    h->sel_host_armed = h->probs_mirror;
-  }
-  forward_impl(h, b, class_id, false, /*do_pool=*/true, /*every_class=*/all_probs != nullptr || pooled != nullptr, /*all_scores=*/path_scores != nullptr);
-  const int C = h->cfg.C;
-  hipStream_t s = h->stream;
-  if (probs && !mirror) HIP_TRY(hipMemcpyAsync(probs, h->ws.sel, (size_t)b->B * sizeof(float), hipMemcpyDeviceToHost, s));
-  if (all_probs) HIP_TRY(hipMemcpyAsync(all_probs, h->ws.probs, (size_t)b->B * C * sizeof(float), hipMemcpyDeviceToHost, s));
-  if (pooled) HIP_TRY(hipMemcpyAsync(pooled, h->ws.pooled, (size_t)b->B * C * sizeof(float), hipMemcpyDeviceToHost, s));
-  if (path_scores)
-    HIP_TRY(hipMemcpyAsync(path_scores, h->score_buf, (size_t)b->N * C * sizeof(float), hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  if (mirror) memcpy(probs, h->probs_mirror, (size_t)b->B * sizeof(float));
-  prof_drain(h);
-  API_END(h)
-}
-
+// ---- batches and feed slots: batch_slots.hip; scoring, ranking and explaining: score_stages.hip ----------------------------------------------
 // the host-buffer entry points' minibatch -> an engine-owned slot (0 / 1: training, 2 / 3: scoring), derived on the calling thread
-static int dropin_feed(kprn_handle* h, bool score, const int32_t* idx, const float* labels, int32_t B, int32_t P, int32_t T, int32_t F,
-                       const int32_t* counts = nullptr, int64_t n_ragged = 0) {
+extern "C++" int dropin_feed(kprn_handle* h, bool score, const int32_t* idx, const float* labels, int32_t B, int32_t P, int32_t T, int32_t F,
+                             const int32_t* counts, int64_t n_ragged) {
   API_BEGIN(h)
   int& nx = score ? h->dropin_next_score : h->dropin_next_train;
   const int si = (score ? 2 : 0) + nx;
@@ -1077,329 +840,6 @@ static int dropin_feed(kprn_handle* h, bool score, const int32_t* idx, const flo
     slots::feed(h, &h->dropin_slot[si], idx, labels, nullptr, B, P, T, F, /*inline_now=*/true, counts, n_ragged);
   }
   h->dropin_last = si;
-  API_END(h)
-}
-
-int kprn_forward(kprn_handle* h, const int32_t* idx, int32_t B, int32_t P, int32_t T, int32_t F, int32_t class_id, float* probs, float* all_probs) {
-  if (!h) return KPRN_E_ARG;
-  int rc = dropin_feed(h, /*score=*/true, idx, nullptr, B, P, T, F);   // (engine-owned feed slots: see kprn_train_step)
-  if (rc != KPRN_OK) return rc;
-  return kprn_forward_batch(h, h->dropin_slot[h->dropin_last], class_id, probs, all_probs, nullptr, nullptr);
-}
-
-int kprn_forward_ragged(kprn_handle* h, const int32_t* idx, const int32_t* counts, int32_t B, int64_t N, int32_t T, int32_t F, int32_t class_id, float* probs,
-                        float* all_probs) {
-  if (!h) return KPRN_E_ARG;
-  if (!counts) { h->err = "counts is NULL"; return KPRN_E_ARG; }
-  int rc = dropin_feed(h, /*score=*/true, idx, nullptr, B, 0, T, F, counts, N);
-  if (rc != KPRN_OK) return rc;
-  return kprn_forward_batch(h, h->dropin_slot[h->dropin_last], class_id, probs, all_probs, nullptr, nullptr);
-}
-
-// ---- ranking stage: the score board, kprn_rank_groups, kprn_recommend_ragged (kernels: rank_groups.hip) ---------------------------------------
-int kprn_board_reserve(kprn_handle* h, int64_t n) {
-  API_BEGIN(h)
-  KPRN_REQUIRE(n >= 1 && n < (1ll << 40), KPRN_E_ARG, "board size must be >= 1");
-  sync_compute_streams(h);   // (queued puts and a ranking call's reads of the old board)
-  h->put_side = false;
-  dfree(h->board);
-  h->board_n = 0;
-  h->board = dalloc<float>(n);
-  h->board_n = n;
-  for (int64_t o = 0; o < n; o += (1ll << 30))   // every entry NaN: ranking counts an entry nothing wrote as invalid
-    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)(h->board + o), 0x7fc00000, (size_t)std::min<int64_t>(n - o, 1ll << 30), h->stream));
-  API_END(h)
-}
-
-int kprn_board_put(kprn_handle* h, int64_t offset, int32_t B) {
-  API_BEGIN(h)
-  KPRN_REQUIRE(h->board, KPRN_E_ARG, "no board: call kprn_board_reserve first");
-  KPRN_REQUIRE(B > 0 && h->last_B > 0 && B <= h->last_B, KPRN_E_ARG, "no scoring pass to read from, or B beyond its pairs");
-  KPRN_REQUIRE(offset >= 0 && offset <= h->board_n - B, KPRN_E_INDEX, "the range leaves the board");
-  if (h->last_forward_side) {
-    // the order of kprn_read_probs, with the copy staying on the device and nobody waiting on the host
-    if (h->score_rest_batch) launch_score_rest(h);
-    if (h->score_on_main) {   // ("score_dual": the pass ran in a training forward's launch on the main stream)
-      HIP_TRY(hipEventRecord(h->ev_fork, h->stream));
-      HIP_TRY(hipStreamWaitEvent(h->score_stream, h->ev_fork, 0));
-    } else if (h->ev_score_done) HIP_TRY(hipStreamWaitEvent(h->score_stream, h->ev_score_done, 0));
-    HIP_TRY(hipMemcpyAsync(h->board + offset, h->sel2, (size_t)B * sizeof(float), hipMemcpyDeviceToDevice, h->score_stream));
-    // later passes on the scoring stream follow the copy in stream order, one on the rest stream starts behind its first part there; a pass that writes
-    // sel2 from the main stream, and every reader of the board, waits for this event (join_put)
-    if (!h->ev_put) HIP_TRY(hipEventCreateWithFlags(&h->ev_put, hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(h->ev_put, h->score_stream));
-    h->put_side = true;
-  } else {
-    HIP_TRY(hipMemcpyAsync(h->board + offset, h->ws.sel, (size_t)B * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
-  }
-  API_END(h)
-}
-
-int kprn_board_write(kprn_handle* h, int64_t offset, const float* src, int64_t n) {
-  API_BEGIN(h)
-  KPRN_REQUIRE(h->board, KPRN_E_ARG, "no board: call kprn_board_reserve first");
-  KPRN_REQUIRE(src && n > 0, KPRN_E_ARG, "bad source / n");
-  KPRN_REQUIRE(offset >= 0 && offset <= h->board_n - n, KPRN_E_INDEX, "the range leaves the board");
-  join_put(h);
-  HIP_TRY(hipMemcpyAsync(h->board + offset, src, (size_t)n * sizeof(float), hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  API_END(h)
-}
-
-int kprn_board_read(kprn_handle* h, int64_t offset, float* dst, int64_t n) {
-  API_BEGIN(h)
-  KPRN_REQUIRE(h->board, KPRN_E_ARG, "no board: call kprn_board_reserve first");
-  KPRN_REQUIRE(dst && n > 0, KPRN_E_ARG, "bad destination / n");
-  KPRN_REQUIRE(offset >= 0 && offset <= h->board_n - n, KPRN_E_INDEX, "the range leaves the board");
-  join_put(h);
-  HIP_TRY(hipMemcpyAsync(dst, h->board + offset, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  API_END(h)
-}
-
-// arguments up, one or two launches, results down, all on the main stream; the caller has validated everything (rk::validate) and synchronises
-// The one-call route (kprn_recommend_ragged) moves nothing with copy operations: the group table is read, and the top-K rows are written, by the kernel itself in
-// page-locked host memory (as kprn_forward_batch's probabilities are), so the call is the pass, the pooling stage, one ranking launch and one wait; the rows are
-// handed out after that wait (rank_pinned_fetch).  Measured with copies: 95 us a user against 68 us for kprn_forward_ragged + the host rule (profiles/rank).
-static void rank_run_pinned(kprn_handle* h, const float* dev_scores, const int64_t* goff, int32_t G, int32_t mode, int32_t K, int max_n) {
-  const size_t o_ti = ((size_t)(G + 1) * 8 + 15) & ~(size_t)15, o_ts = o_ti + (((size_t)G * K * 4 + 15) & ~(size_t)15), total = o_ts + (size_t)G * K * 4;
-  if (total > h->rank_pin_bytes) {
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    if (h->rank_pin) { HIP_TRY(hipHostFree(h->rank_pin)); h->rank_pin = nullptr; h->rank_pin_bytes = 0; }
-    HIP_TRY(hipHostMalloc(&h->rank_pin, 2 * total + 256));
-    h->rank_pin_bytes = 2 * total + 256;
-  }
-  char* base = (char*)h->rank_pin;
-  memcpy(base, goff, (size_t)(G + 1) * 8);
-  h->rank_pin_off[0] = o_ti; h->rank_pin_off[1] = o_ts;
-  rk::Args a;
-  a.scores = dev_scores; a.members = nullptr; a.goff = (const int64_t*)base; a.pos = nullptr;
-  a.G = G; a.mode = mode; a.K = K; a.hist_len = 1;
-  a.ranks = nullptr; a.tk_idx = (int32_t*)(base + o_ti); a.tk_score = (float*)(base + o_ts); a.hist = nullptr;
-  a.sort_min = h->rank_sort_min;
-  ProfScope ps(h, "rank_groups");
-  rk::launch(h->stream, a, max_n);
-}
-static void rank_pinned_fetch(kprn_handle* h, int32_t G, int32_t K, int32_t* topk_idx, float* topk_score) {
-  memcpy(topk_idx, (char*)h->rank_pin + h->rank_pin_off[0], (size_t)G * K * 4);
-  memcpy(topk_score, (char*)h->rank_pin + h->rank_pin_off[1], (size_t)G * K * 4);
-}
-
-static void rank_run(kprn_handle* h, const float* dev_scores, const int64_t* members, const int64_t* goff, const int32_t* pos, int32_t G, int32_t mode, int32_t K,
-                     int max_n, int32_t* ranks, int32_t* topk_idx, float* topk_score, int64_t* hist, int32_t hist_len) {
-  const int64_t m0 = goff[0], M = members ? goff[G] - m0 : 0;
-  auto up8 = [](size_t b) { return (b + 15) & ~(size_t)15; };
-  const size_t o_goff = 0, o_mem = o_goff + up8((size_t)(G + 1) * 8), o_hist = o_mem + up8((size_t)M * 8), o_pos = o_hist + up8((size_t)(hist_len + 4) * 8),
-               o_ranks = o_pos + up8((size_t)G * 4), o_ti = o_ranks + up8((size_t)G * 4), o_ts = o_ti + up8((size_t)G * K * 4), total = o_ts + up8((size_t)G * K * 4);
-  if (total > h->rank_buf_bytes) {
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    if (h->rank_buf) { hipFree(h->rank_buf); h->rank_buf = nullptr; h->rank_buf_bytes = 0; }
-    hipError_t e = kprn_dev_malloc(&h->rank_buf, total + total / 4 + 64);
-    if (e != hipSuccess) throw KprnError{KPRN_E_NOMEM, std::string("hipMalloc failed: ") + hipGetErrorString(e)};
-    h->rank_buf_bytes = total + total / 4;
-  }
-  char* base = (char*)h->rank_buf;
-  hipStream_t s = h->stream;
-  std::vector<int64_t> rebased;
-  const int64_t* goff_up = goff;
-  if (members && m0 != 0) {   // (the kernels index the uploaded slice of members from 0)
-    rebased.assign(goff, goff + G + 1);
-    for (auto& v : rebased) v -= m0;
-    goff_up = rebased.data();
-  }
-  HIP_TRY(hipMemcpyAsync(base + o_goff, goff_up, (size_t)(G + 1) * 8, hipMemcpyHostToDevice, s));
-  if (members) HIP_TRY(hipMemcpyAsync(base + o_mem, members + m0, (size_t)M * 8, hipMemcpyHostToDevice, s));
-  if (pos) HIP_TRY(hipMemcpyAsync(base + o_pos, pos, (size_t)G * 4, hipMemcpyHostToDevice, s));
-  if (rebased.size()) HIP_TRY(hipStreamSynchronize(s));   // (the copy's source is a local)
-  if (hist) HIP_TRY(hipMemsetAsync(base + o_hist, 0, (size_t)(hist_len + 4) * 8, s));
-  rk::Args a;
-  a.scores = dev_scores; a.members = members ? (const int64_t*)(base + o_mem) : nullptr; a.goff = (const int64_t*)(base + o_goff);
-  a.pos = pos ? (const int32_t*)(base + o_pos) : nullptr;
-  a.G = G; a.mode = mode; a.K = K; a.hist_len = hist_len;
-  a.ranks = ranks ? (int32_t*)(base + o_ranks) : nullptr;
-  a.tk_idx = topk_idx ? (int32_t*)(base + o_ti) : nullptr; a.tk_score = topk_idx ? (float*)(base + o_ts) : nullptr;
-  a.hist = hist ? (unsigned long long*)(base + o_hist) : nullptr;
-  a.sort_min = h->rank_sort_min;
-  {
-    ProfScope ps(h, "rank_groups");
-    rk::launch(s, a, max_n);
-  }
-  if (ranks) HIP_TRY(hipMemcpyAsync(ranks, base + o_ranks, (size_t)G * 4, hipMemcpyDeviceToHost, s));
-  if (topk_idx) {
-    HIP_TRY(hipMemcpyAsync(topk_idx, base + o_ti, (size_t)G * K * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(topk_score, base + o_ts, (size_t)G * K * 4, hipMemcpyDeviceToHost, s));
-  }
-  if (hist) HIP_TRY(hipMemcpyAsync(hist, base + o_hist, (size_t)(hist_len + 4) * 8, hipMemcpyDeviceToHost, s));
-}
-
-int kprn_rank_groups(kprn_handle* h, const int64_t* members, const int64_t* group_offsets, const int32_t* pos, int32_t G, int32_t mode, int32_t K,
-                     int32_t* ranks, int32_t* topk_idx, float* topk_score, int64_t* hist, int32_t hist_len) {
-  API_BEGIN(h)
-  KPRN_REQUIRE(h->board, KPRN_E_ARG, "no board: call kprn_board_reserve first");
-  KPRN_REQUIRE((topk_idx == nullptr) == (topk_score == nullptr), KPRN_E_ARG, "topk_idx and topk_score go together");
-  int max_n = 0;
-  std::string why;
-  const int rc = rk::validate(h->board_n, members, group_offsets, pos, G, mode, K, hist_len, &max_n, &why);
-  if (rc != KPRN_OK) throw KprnError{rc, why};
-  join_put(h);
-  rank_run(h, h->board, members, group_offsets, pos, G, mode, K, max_n, ranks, topk_idx, topk_score, hist, hist_len);
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  prof_drain(h);
-  API_END(h)
-}
-
-// the refusals of kprn_recommend_ragged that need no device work, before anything is fed
-static int recommend_check(kprn_handle* h, const int32_t* counts, int32_t B, const int32_t* group_counts, int32_t G, int32_t mode, int32_t K,
-                           const int32_t* topk_idx, const float* topk_score, std::vector<int64_t>& goff, int* max_n) {
-  API_BEGIN(h)
-  KPRN_REQUIRE(counts && group_counts && topk_idx && topk_score && G >= 1 && B >= 1, KPRN_E_ARG, "NULL argument, or G / B < 1");
-  goff.assign((size_t)G + 1, 0);
-  for (int32_t g = 0; g < G; ++g) goff[g + 1] = goff[g] + group_counts[g];
-  KPRN_REQUIRE(goff[G] == B, KPRN_E_ARG, "group_counts do not add up to B");
-  std::string why;
-  const int rc = rk::validate(B, nullptr, goff.data(), nullptr, G, mode, K, 1, max_n, &why);
-  if (rc != KPRN_OK) throw KprnError{rc, why};
-  API_END(h)
-}
-
-int kprn_recommend_ragged(kprn_handle* h, const int32_t* idx, const int32_t* counts, int32_t B, int64_t N, int32_t T, int32_t F, int32_t class_id,
-                          const int32_t* group_counts, int32_t G, int32_t mode, int32_t K, int32_t* topk_idx, float* topk_score, float* probs) {
-  if (!h) return KPRN_E_ARG;
-  std::vector<int64_t> goff;
-  int max_n = 0;
-  int rc = recommend_check(h, counts, B, group_counts, G, mode, K, topk_idx, topk_score, goff, &max_n);
-  if (rc != KPRN_OK) return rc;
-  rc = dropin_feed(h, /*score=*/true, idx, nullptr, B, 0, T, F, counts, N);
-  if (rc != KPRN_OK) return rc;
-  API_BEGIN(h)
-  // the pass of kprn_forward_ragged, the ranking kernel behind it on the same stream over the pass's own output, one wait for both; the probabilities come
-  // back through the pool kernel's page-locked mirror as in kprn_forward_batch
-  struct Disarm { kprn_handle* h; ~Disarm() { h->sel_host_armed = nullptr; } } disarm{h};
-  const bool mirror = probs != nullptr && !h->prof_on;
-  if (mirror) {
-    if ((int64_t)B > h->probs_mirror_cap) {
-      if (h->probs_mirror) { HIP_TRY(hipStreamSynchronize(h->stream)); HIP_TRY(hipHostFree(h->probs_mirror)); h->probs_mirror = nullptr; h->probs_mirror_cap = 0; }
-      HIP_TRY(hipHostMalloc((void**)&h->probs_mirror, (size_t)(2 * (int64_t)B + 64) * sizeof(float)));
-      h->probs_mirror_cap = 2 * (int64_t)B + 64;
-    }
-    h->sel_host_armed = h->probs_mirror;
-  }
-  forward_impl(h, h->dropin_slot[h->dropin_last], class_id, false, /*do_pool=*/true, /*every_class=*/false);
-  rank_run_pinned(h, h->ws.sel, goff.data(), G, mode, K, max_n);
-  if (probs && !mirror) HIP_TRY(hipMemcpyAsync(probs, h->ws.sel, (size_t)B * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  rank_pinned_fetch(h, G, K, topk_idx, topk_score);
-  if (mirror) memcpy(probs, h->probs_mirror, (size_t)B * sizeof(float));
-  prof_drain(h);
-  API_END(h)
-}
-
-// ---- explanation stage: kprn_explain_batch, kprn_recommend_explain_ragged (kernels: explain_paths.hip) ---------------------------------------
-static ex::Args explain_args(kprn_handle* h, const kprn_batch* b, int class_id, int M) {
-  const kprn_config& c = h->cfg;
-  ex::Args a;
-  a.S = h->score_buf; a.off = b->off; a.B = b->B; a.P = b->P; a.seg_wave = b->off ? b->seg_wave : 0;
-  a.C = c.C; a.cid = class_id - 1; a.reducer = c.reducer; a.K = c.K; a.M = M;
-  a.pairs = nullptr; a.goff = nullptr; a.per_group = 1; a.n = 0;
-  a.idx = nullptr; a.score = nullptr; a.weight = nullptr; a.pooled = nullptr; a.prob = nullptr;
-  return a;
-}
-
-int kprn_explain_batch(kprn_handle* h, const kprn_batch* b, int32_t class_id, const int32_t* pairs, int32_t n_pairs, int32_t M, int32_t* path_idx,
-                       float* path_score, float* path_weight, float* pooled, float* probs) {
-  API_BEGIN(h)
-  KPRN_REQUIRE(b != nullptr, KPRN_E_ARG, "batch is NULL");
-  KPRN_REQUIRE(path_idx && path_score && path_weight, KPRN_E_ARG, "path_idx, path_score and path_weight are required");
-  std::string why;
-  const int rc = ex::validate(b->B, pairs, n_pairs, M, &why);
-  if (rc != KPRN_OK) throw KprnError{rc, why};
-  forward_impl(h, b, class_id, false, /*do_pool=*/true, /*every_class=*/false);   // (refuses a bad class_id / an id out of range before anything is queued)
-  const int64_t n = n_pairs;
-  auto up = [](size_t x) { return (x + 15) & ~(size_t)15; };
-  const size_t rows = up((size_t)n * M * 4), o_pairs = 0, o_idx = up((size_t)n * 4), o_score = o_idx + rows, o_weight = o_score + rows,
-               o_pooled = o_weight + rows, o_prob = o_pooled + up((size_t)n * 4), total = o_prob + up((size_t)n * 4);
-  if (total > h->explain_buf_bytes) {
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    if (h->explain_buf) { hipFree(h->explain_buf); h->explain_buf = nullptr; h->explain_buf_bytes = 0; }
-    hipError_t e = kprn_dev_malloc(&h->explain_buf, total + total / 4 + 64);
-    if (e != hipSuccess) throw KprnError{KPRN_E_NOMEM, std::string("hipMalloc failed: ") + hipGetErrorString(e)};
-    h->explain_buf_bytes = total + total / 4;
-  }
-  char* base = (char*)h->explain_buf;
-  hipStream_t s = h->stream;
-  if (pairs) HIP_TRY(hipMemcpyAsync(base + o_pairs, pairs, (size_t)n * 4, hipMemcpyHostToDevice, s));
-  ex::Args a = explain_args(h, b, class_id, M);
-  a.pairs = pairs ? (const int32_t*)(base + o_pairs) : nullptr;
-  a.n = n;
-  a.idx = (int32_t*)(base + o_idx); a.score = (float*)(base + o_score); a.weight = (float*)(base + o_weight);
-  a.pooled = pooled ? (float*)(base + o_pooled) : nullptr; a.prob = probs ? (float*)(base + o_prob) : nullptr;
-  {
-    ProfScope ps(h, "explain_paths");
-    ex::launch(s, a, b->off ? b->max_cnt : b->P);
-  }
-  HIP_TRY(hipMemcpyAsync(path_idx, a.idx, (size_t)n * M * 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(path_score, a.score, (size_t)n * M * 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(path_weight, a.weight, (size_t)n * M * 4, hipMemcpyDeviceToHost, s));
-  if (pooled) HIP_TRY(hipMemcpyAsync(pooled, a.pooled, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-  if (probs) HIP_TRY(hipMemcpyAsync(probs, a.prob, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  prof_drain(h);
-  API_END(h)
-}
-
-int kprn_recommend_explain_ragged(kprn_handle* h, const int32_t* idx, const int32_t* counts, int32_t B, int64_t N, int32_t T, int32_t F, int32_t class_id,
-                                  const int32_t* group_counts, int32_t G, int32_t mode, int32_t K, int32_t M, int32_t* topk_idx, float* topk_score,
-                                  int32_t* path_idx, float* path_score, float* path_weight, float* probs) {
-  if (!h) return KPRN_E_ARG;
-  if (!path_idx || !path_score || !path_weight) { h->err = "path_idx, path_score and path_weight are required"; return KPRN_E_ARG; }
-  if (M < 1 || M > KPRN_EXPLAIN_MAX_M) { h->err = "M must be in 1..32"; return KPRN_E_ARG; }
-  std::vector<int64_t> goff;
-  int max_n = 0;
-  int rc = recommend_check(h, counts, B, group_counts, G, mode, K, topk_idx, topk_score, goff, &max_n);
-  if (rc != KPRN_OK) return rc;
-  rc = dropin_feed(h, /*score=*/true, idx, nullptr, B, 0, T, F, counts, N);
-  if (rc != KPRN_OK) return rc;
-  API_BEGIN(h)
-  // kprn_recommend_ragged, and one more launch behind the ranking kernel: its pair list is the top-K rows that kernel wrote (page-locked memory the device
-  // reads in place), its own rows land in page-locked memory too: still one wait, no copy operation
-  struct Disarm { kprn_handle* h; ~Disarm() { h->sel_host_armed = nullptr; } } disarm{h};
-  const bool mirror = probs != nullptr && !h->prof_on;
-  if (mirror) {
-    if ((int64_t)B > h->probs_mirror_cap) {
-      if (h->probs_mirror) { HIP_TRY(hipStreamSynchronize(h->stream)); HIP_TRY(hipHostFree(h->probs_mirror)); h->probs_mirror = nullptr; h->probs_mirror_cap = 0; }
-      HIP_TRY(hipHostMalloc((void**)&h->probs_mirror, (size_t)(2 * (int64_t)B + 64) * sizeof(float)));
-      h->probs_mirror_cap = 2 * (int64_t)B + 64;
-    }
-    h->sel_host_armed = h->probs_mirror;
-  }
-  const int64_t n = (int64_t)G * K;
-  const size_t rows = ((size_t)n * M * 4 + 15) & ~(size_t)15;
-  if (3 * rows > h->explain_pin_bytes) {
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    if (h->explain_pin) { HIP_TRY(hipHostFree(h->explain_pin)); h->explain_pin = nullptr; h->explain_pin_bytes = 0; }
-    HIP_TRY(hipHostMalloc(&h->explain_pin, 6 * rows + 256));
-    h->explain_pin_bytes = 6 * rows + 256;
-  }
-  const kprn_batch* b = h->dropin_slot[h->dropin_last];
-  forward_impl(h, b, class_id, false, /*do_pool=*/true, /*every_class=*/false);
-  rank_run_pinned(h, h->ws.sel, goff.data(), G, mode, K, max_n);
-  ex::Args a = explain_args(h, b, class_id, M);
-  char* pin = (char*)h->explain_pin;
-  a.pairs = (const int32_t*)((char*)h->rank_pin + h->rank_pin_off[0]); a.goff = (const int64_t*)h->rank_pin; a.per_group = K;
-  a.n = n;
-  a.idx = (int32_t*)pin; a.score = (float*)(pin + rows); a.weight = (float*)(pin + 2 * rows);
-  {
-    ProfScope ps(h, "explain_paths");
-    ex::launch(h->stream, a, b->max_cnt);
-  }
-  if (probs && !mirror) HIP_TRY(hipMemcpyAsync(probs, h->ws.sel, (size_t)B * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  rank_pinned_fetch(h, G, K, topk_idx, topk_score);
-  memcpy(path_idx, pin, (size_t)n * M * 4);
-  memcpy(path_score, pin + rows, (size_t)n * M * 4);
-  memcpy(path_weight, pin + 2 * rows, (size_t)n * M * 4);
-  if (mirror) memcpy(probs, h->probs_mirror, (size_t)B * sizeof(float));
-  prof_drain(h);
   API_END(h)
 }
 
@@ -1456,11 +896,7 @@ int kprn_train_step_batch(kprn_handle* h, const kprn_batch* b, int32_t class_id,
   struct Disarm { kprn_handle* h; ~Disarm() { h->loss_early_armed = false; } } disarm{h};
   if (loss && !h->train_step_drain && !h->prof_on) {
     const int64_t np = std::max<int64_t>(kk::loss_partials(b->B), b->n_wg);   // (n_wg: the loss-stage workgroups of a ragged batch)
-    if (np > h->loss_mirror_cap) {
-      if (h->loss_mirror) { HIP_TRY(hipStreamSynchronize(h->stream)); HIP_TRY(hipHostFree(h->loss_mirror)); h->loss_mirror = nullptr; h->loss_mirror_cap = 0; }
-      HIP_TRY(hipHostMalloc((void**)&h->loss_mirror, (size_t)(2 * np + 64) * sizeof(float)));
-      h->loss_mirror_cap = 2 * np + 64;
-    }
+    grow_pinned(h->loss_mirror, h->loss_mirror_cap, np, (size_t)(2 * np + 64) * sizeof(float), 2 * np + 64, {h->stream});
     if (!h->ev_loss) HIP_TRY(hipEventCreateWithFlags(&h->ev_loss, hipEventDisableTiming));
     h->loss_early_armed = true;
   }
@@ -2025,7 +1461,7 @@ int kprn_set_option(kprn_handle* h, const char* key, const char* value) {
   } else if (strcmp(key, "score_rest_in_backward") == 0) {
     join_score(h);
     h->score_rest_in_backward = atoi(value) ? 1 : 0;
-    h->after_bptt_hook = h->score_rest_in_backward ? score_rest_hook : nullptr;
+    h->after_bptt_hook = h->score_rest_in_backward ? score::rest_hook : nullptr;
   } else if (strcmp(key, "score_split") == 0) {
     // kprn_forward_batch_async queues only the first (1 - f) of the batch's tiles; kprn_forward_batch_async_rest the others + the pooling
     join_score(h);

@@ -5,6 +5,7 @@
 #include <stdint.h>
 #include <exception>
 #include <functional>
+#include <initializer_list>
 #include <future>
 #include <string>
 #include <vector>
@@ -228,7 +229,7 @@ struct kprn_handle {
   int prefix_plan = 1;            // kprn_set_option "prefix_plan": build identical-prefix plans for new batches (fused path)
   int score_overlap = 0;
   hipStream_t score_stream = nullptr;
-  int side_stream_probes = 0;     // candidates tried before one ran beside the main stream (kprn_api.hip make_concurrent_stream)
+  int side_stream_probes = 0;     // candidates tried before one ran beside the main stream (score_stages.hip make_concurrent_stream)
   hipEvent_t ev_fork = nullptr, ev_score_done = nullptr;
   kprn_batch* dropin_slot[4] = {nullptr, nullptr, nullptr, nullptr};   // feed slots of the host-buffer entry points (kprn_train_step: 0 / 1, kprn_forward: 2 / 3)
   int dropin_next_train = 0, dropin_next_score = 0, dropin_last = 0;
@@ -268,7 +269,7 @@ struct kprn_handle {
   // finish inside the second launch's start-up skew -- a quarter of the scoring pass in time the step's schedule wastes anyway (the first part then ends 4 tile-steps earlier)
   int score_rest_before_bptt = 0;
   hipStream_t rest_stream = nullptr; hipEvent_t ev_part1 = nullptr;
-  void (*after_bptt_hook)(kprn_handle*) = nullptr;   // (set by kprn_api.hip: lstm_fused_bwd.hip cannot see launch_score_rest)
+  void (*after_bptt_hook)(kprn_handle*) = nullptr;   // (kprn_set_option installs score::rest_hook: lstm_fused_bwd.hip cannot see launch_score_rest)
   const kprn_batch* score_rest_batch = nullptr; int score_rest_cid = 1; int64_t score_rest_tile0 = 0;   // the deferred part of a split pass
   bool last_forward_side = false; // kprn_read_probs reads the side buffers
   bool score_on_main = false;     // ... which the last pass filled from the MAIN stream ("score_dual")
@@ -321,7 +322,7 @@ struct ProfScope {
   ProfScope(kprn_handle* h_, const char* n, hipStream_t on = nullptr);
   ~ProfScope();
 };
-hipStream_t make_concurrent_stream(kprn_handle* h, int* probes = nullptr);   // a stream whose work runs BESIDE the main stream's (kprn_api.hip: probed, not assumed)
+hipStream_t make_concurrent_stream(kprn_handle* h, int* probes = nullptr);   // a stream whose work runs BESIDE the main stream's (score_stages.hip: probed, not assumed)
 void prof_drain(kprn_handle* h);
 void join_score(kprn_handle* h);  // main stream waits for the scoring pass on the side stream, if any
 
@@ -357,10 +358,22 @@ inline hipStream_t make_priority_stream(bool high) {
   return s;
 }
 
-// ---- kprn_api.hip, for the slot code ----------------------------------------------------------------------
+// ---- kprn_api.hip, for the slot code and the scoring stage: what training and scoring share ---------------------
 bool use_fused(kprn_handle* h, const kprn_batch* b, bool save_for_backward);   // this pass over b runs on the fused D = H = 64 path
-void launch_score_rest(kprn_handle* h);      // the deferred part of a split scoring pass goes out now (no-op when there is none)
 void materialize_step_rows(kprn_handle* h);  // the optimiser's row list stops being a view of a batch: copied to the handle's own storage
+void check_batch(kprn_handle* h, const kprn_batch* b, int class_id);   // a fed slot is ready, class_id in 1..C
+void catch_up(kprn_handle* h, const kprn_batch* b);                    // the batch's entity rows that are behind opt_step are replayed
+void ensure_ws_common(kprn_handle* h, int64_t N, int64_t B, int64_t n_wg = 0);
+void pool_stage(kprn_handle* h, const kprn_batch* b, int cid, bool every_class);   // reducer + sigmoid + select on h->stream over ws.S into ws.sel (and the mirror, if armed)
+void forward_impl(kprn_handle* h, const kprn_batch* b, int class_id, bool save_for_backward, bool do_pool = true, bool every_class = true, bool all_scores = false);
+int dropin_feed(kprn_handle* h, bool score, const int32_t* idx, const float* labels, int32_t B, int32_t P, int32_t T, int32_t F, const int32_t* counts = nullptr,
+                int64_t n_ragged = 0);   // the host-buffer entry points' minibatch -> the feed slot h->dropin_slot[h->dropin_last]; a status, its text in h->err
+// ---- the scoring stage (score_stages.hip): passes beside the main stream, the score board, ranking and explanation calls ----------------
+void launch_score_rest(kprn_handle* h);      // the deferred part of a split scoring pass goes out now (no-op when there is none)
+namespace score {
+void join_put(kprn_handle* h);    // main stream waits for the board puts queued on the scoring stream, if any
+void rest_hook(kprn_handle* h);   // kprn_handle::after_bptt_hook under option "score_rest_in_backward"
+}  // namespace score
 // ---- batches and feed slots (batch_slots.hip): the lifecycle of a kprn_batch and the kprn_batch_* / kprn_host_* entry points ----------------
 namespace slots {
 // ids that are already on the device: fill(idx_dev, s) queues on s whatever writes the batch's [N,T,F] ids into the slot's idx block (kprn_find_paths)
@@ -374,7 +387,6 @@ void feed(kprn_handle* h, kprn_batch** slot, const int32_t* idx, const float* la
           bool inline_now = false, const int32_t* counts = nullptr, int64_t n_ragged = 0);
 void ready(kprn_handle* h, const kprn_batch* b);   // first use of a fed slot: waits for its feed, takes the summary over; KPRN_E_INDEX for a bad id
 void release(kprn_batch* b);                       // frees a slot the handle no longer refers to, behind drained streams
-void scratch_reserve(void** scratch, size_t* bytes, size_t need);   // grow-only device scratch (twice the need); the caller has drained its stream
 }  // namespace slots
 
 // ---- kernels (kernels_basic.hip) -----------------------------------------------------------
@@ -787,6 +799,26 @@ inline T* dev_grow(hipStream_t s, T*& p, int64_t& cap, int64_t need, int factor 
 }
 template <typename T>
 inline T* dev_grow2(hipStream_t s, T*& p, int64_t& cap, int64_t need) { return dev_grow(s, p, cap, need, 2); }
+// Grow-only raw blocks whose size is a rule of their own (argument blocks, page-locked mirrors): need > cap -> wait for the streams whose queued work may still
+// use the old block (only when there is one, or -- wait_if_empty -- whenever the block grows), free it, allocate alloc_bytes, record `record` (in cap's unit).
+template <bool PINNED, typename T, typename C>
+inline void grow_only(T*& p, C& cap, C need, size_t alloc_bytes, C record, std::initializer_list<hipStream_t> wait, bool wait_if_empty) {
+  if (need <= cap) return;
+  if (p || wait_if_empty) for (hipStream_t s : wait) HIP_TRY(hipStreamSynchronize(s));
+  if (p) { if (PINNED) HIP_TRY(hipHostFree(p)); else hipFree(p); }
+  p = nullptr; cap = 0;
+  void* q = nullptr;
+  if (PINNED) HIP_TRY(hipHostMalloc(&q, alloc_bytes));
+  else if (const hipError_t e = kprn_dev_malloc(&q, alloc_bytes); e != hipSuccess) throw KprnError{KPRN_E_NOMEM, std::string("hipMalloc failed: ") + hipGetErrorString(e)};
+  p = (T*)q; cap = record;
+}
+template <typename T, typename C> inline void grow_device(T*& p, C& cap, C need, size_t alloc_bytes, C record, std::initializer_list<hipStream_t> wait, bool wait_if_empty = false) { grow_only<false>(p, cap, need, alloc_bytes, record, wait, wait_if_empty); }
+template <typename T, typename C> inline void grow_pinned(T*& p, C& cap, C need, size_t alloc_bytes, C record, std::initializer_list<hipStream_t> wait, bool wait_if_empty = false) { grow_only<true>(p, cap, need, alloc_bytes, record, wait, wait_if_empty); }
+// the device arguments and results of ONE call (ranking, explanation, path finder, sampler): a quarter of headroom; s is drained whenever the block grows
+inline void* grow_call_block(hipStream_t s, void*& p, size_t& bytes, size_t total) {
+  grow_device(p, bytes, total, total + total / 4 + 64, total + total / 4, {s}, /*wait_if_empty=*/true);
+  return p;
+}
 
 namespace hostfeed {
 struct Shape { int B, P, T, F, nT, Vt, Ve, Vr; };

@@ -148,16 +148,7 @@ static int validate_users(const int32_t* users, int64_t n, int32_t Ve, std::stri
 static Rng rng_of(uint64_t seed, uint32_t draw) { return Rng{(uint32_t)(seed & 0xffffffffu), (uint32_t)(seed >> 32), draw}; }
 
 // grow-only device block of the sampling calls (the stream is drained before it is replaced)
-static void* reserve(kprn_handle* h, size_t bytes) {
-  if (bytes > h->ns_buf_bytes) {
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    if (h->ns_buf) { hipFree(h->ns_buf); h->ns_buf = nullptr; h->ns_buf_bytes = 0; }
-    const hipError_t e = kprn_dev_malloc(&h->ns_buf, bytes + bytes / 4 + 64);
-    if (e != hipSuccess) throw KprnError{KPRN_E_NOMEM, std::string("hipMalloc failed: ") + hipGetErrorString(e)};
-    h->ns_buf_bytes = bytes + bytes / 4;
-  }
-  return h->ns_buf;
-}
+static void* reserve(kprn_handle* h, size_t bytes) { return grow_call_block(h->stream, h->ns_buf, h->ns_buf_bytes, bytes); }
 
 static void launch(kprn_handle* h, const kprn_graph* g, const kprn_sampler* s, const Rng& rng, const int32_t* d_users, int ustride, int32_t B, int32_t n_neg,
                    int32_t max_attempts, int32_t* d_neg, int32_t* d_found, int32_t* d_pairs, hipStream_t st) {

@@ -422,13 +422,7 @@ void find_staged(kprn_handle* h, const kprn_graph* g, const StagePairs& stage, c
   const int hmask = hop_mask(min_hops, max_hops);
   // device arguments of the two passes: pairs [2B] | cnt [B] | flag [4] (int32), then tot [4B] | first [B] (int64)
   const size_t w32 = ((size_t)3 * B + 4 + 1) & ~(size_t)1, total = w32 * 4 + (size_t)5 * B * 8;
-  if (total > h->pf_buf_bytes) {
-    HIP_TRY(hipStreamSynchronize(s));
-    if (h->pf_buf) { hipFree(h->pf_buf); h->pf_buf = nullptr; h->pf_buf_bytes = 0; }
-    hipError_t e = kprn_dev_malloc(&h->pf_buf, total + total / 4 + 64);
-    if (e != hipSuccess) throw KprnError{KPRN_E_NOMEM, std::string("hipMalloc failed: ") + hipGetErrorString(e)};
-    h->pf_buf_bytes = total + total / 4;
-  }
+  grow_call_block(s, h->pf_buf, h->pf_buf_bytes, total);
   int32_t* d_pairs = (int32_t*)h->pf_buf;
   int32_t* d_cnt = d_pairs + 2 * (size_t)B;
   int32_t* d_flag = d_cnt + B;
