@@ -98,6 +98,10 @@ void kprn_sampler_destroy(kprn_handle*, kprn_sampler*);
 int kprn_sample_negatives(kprn_handle*, const kprn_graph*, const kprn_sampler*, const int32_t*, int32_t, int32_t, int32_t, uint64_t, unsigned int, int32_t*, int32_t*);
 int kprn_host_sample_negatives(const int32_t*, const int32_t*, const int32_t*, int64_t, int32_t, const int32_t*, const float*, int64_t, const int32_t*, int32_t, int32_t, int32_t, uint64_t, unsigned int, int32_t, int32_t*, int32_t*);
 int kprn_find_training_paths(kprn_handle*, const kprn_graph*, const kprn_sampler*, const int32_t*, int32_t, int32_t, int32_t, uint64_t, unsigned int, int32_t, int32_t, int32_t, int32_t, int32_t*, int32_t*, int64_t*, kprn_batch**);
+/* sampled paths of four and five hops behind the exhaustive ones (include/kprn.h "sampled paths of four and five hops") */
+int kprn_find_paths_sampled(kprn_handle*, const kprn_graph*, const int32_t*, const float*, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, uint64_t, unsigned int, int32_t*, int64_t*, kprn_batch**);
+int kprn_host_find_paths_sampled(const int32_t*, const int32_t*, const int32_t*, int64_t, const int32_t*, int32_t, int32_t, int32_t, int32_t, int32_t, const int32_t*, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, uint64_t, unsigned int, int32_t, int32_t*, int64_t*, int32_t*);
+int kprn_find_training_paths_sampled(kprn_handle*, const kprn_graph*, const kprn_sampler*, const int32_t*, int32_t, int32_t, int32_t, uint64_t, unsigned int, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t*, int32_t*, int64_t*, kprn_batch**);
 ]]
 
 local C = ffi.load('kprn')

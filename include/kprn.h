@@ -331,8 +331,8 @@ int kprn_host_explain(const float* path_scores, const int32_t* offsets /* [B+1] 
  *    id of #END_RELATION.  An id outside its vocabulary is KPRN_E_INDEX and leaves no graph behind.
  *  - path of h hops: u = n0 -> n1 -> ... -> nh = i, every (n_k, r_k, n_k+1) an edge, all nodes pairwise distinct (the miner's `mid_node not in path_set`);
  *    u == i has no paths; two relations between the same two nodes give two paths.  1 <= min_hops <= max_hops <= 3: three hops is the reference's "depth 3"
- *    (user-item-user-item).  Four and five hops need sampling to stay bounded and are NOT built: max_hops > 3 is KPRN_E_ARG.  min_hops = 2 keeps the direct
- *    u-i edge out of a positive pair's paths.
+ *    (user-item-user-item).  Four and five hops need sampling to stay bounded: kprn_find_paths refuses max_hops > 3 with KPRN_E_ARG, and
+ *    kprn_find_paths_sampled ("sampled paths of four and five hops" below) appends them.  min_hops = 2 keeps the direct u-i edge out of a positive pair's paths.
  *  - order within a pair (canonical): hops ascending, then the integer sequence (n1, r0, n2, r1, ..., r_{h-1}) ascending lexicographically.
  *  - cap: found[b] = the number of paths that exist; the kept ones are the first counts[b] = min(found[b], max_paths) in that order, 1 <= max_paths <= 4096.
  *    Nothing depends on timing: ranks come from a counting pass and prefix sums, never from an atomic counter.
@@ -359,6 +359,37 @@ int kprn_batch_read_idx(kprn_handle* h, const kprn_batch* b, int32_t* idx_out);
 int kprn_host_find_paths(const int32_t* src, const int32_t* dst, const int32_t* rel, int64_t E, const int32_t* node_types, int32_t Ve, int32_t Vr, int32_t Vt,
                          int32_t num_types, int32_t end_relation, const int32_t* pairs, int32_t B, int32_t min_hops, int32_t max_hops, int32_t max_paths,
                          int32_t T, int32_t F, int32_t threads, int32_t* counts, int64_t* found, int32_t* idx);
+
+/* ---- sampled paths of four and five hops (an extension: the reference extends a three-hop path twice, data_prepare/path_find_depth_5.py, by sampling a few
+ * neighbours of the last item and one random item behind each; its draws, Python's random, cannot be reproduced and are not restated) ----
+ * The *_sampled calls accept 1 <= min_hops <= max_hops <= 5.  Hops 1..3 stay exhaustive, exactly as above.  Hops h in {4, 5} are sampled: a random prefix of
+ * h - 2 hops out of the user, then an exhaustive close of the last two hops into the item (a prefix that had to hit i in one hop would almost never close).
+ * For the pair in row b of the call's pair list, (u, i) with u != i and i != 0, and each asked h in {4, 5}, walks w = 0 .. walks-1:
+ *  - words: r[0..3] = Philox4x32-10(counter = (w, 65536 + h, b, draw), key = (seed & 0xffffffff, seed >> 32)).  65536 + h keeps the counters apart from the
+ *    negative sampler's (a / 4, n, b, draw), n <= 255, under the same seed and draw.  The counter holds the ROW b, not the user id: the same pair in two rows
+ *    draws different walks.
+ *  - prefix: n_0 = u; for k = 0 .. h-3: deg = rowptr[n_k + 1] - rowptr[n_k] (the node's stored edges, in the graph's (dst, rel) order); deg == 0: the walk is dead;
+ *    else e_k = rowptr[n_k] + mulhi32(r[k], deg) (the high word of the 64-bit product), n_{k+1} = the edge's destination, r_k its relation: uniform over stored
+ *    edges, so a multi-edge counts once per relation.  If n_{k+1} equals i or any of n_0 .. n_k the walk is dead.  No retries.
+ *  - duplicates: walk w is dropped if a walk w' < w of the same h has the same edge sequence (e_0 .. e_{h-3}).  Stored edges are distinct, so equal edge
+ *    sequences are equal prefixes, and distinct prefixes give distinct paths: no path is found twice.
+ *  - paths of a live walk: every (e, c), e an edge n_{h-2} -> m with m not in {u, n_1, .., n_{h-2}, i}, c an edge m -> i; order: e ascending, then c ascending
+ *    (adjacency order, then the closing multi-edges by relation).
+ *  - order within a pair: hops ascending -- 1, 2, 3 in the canonical order above, then 4, then 5; inside a sampled hop count the walk index ascending, then
+ *    the order above.  Walk order, not lexicographic order: the cap keeps an unbiased prefix of the sample, not the lowest ids.
+ *  - found[b] = (the paths of hops <= 3 that exist) + (the distinct sampled paths of hops 4 and 5): for h > 3 found counts what was SAMPLED, not what
+ *    exists.  counts[b] = min(found[b], max_paths).
+ *  - limits: walks in 1..256 when max_hops > 3 (else KPRN_E_ARG); when max_hops <= 3, walks / seed / draw are ignored (walks may be 0) and the call returns
+ *    exactly what the unsampled call returns.  T >= max_hops + 1.  Everything else -- row layout, padding, leading columns, compaction of the pairs without
+ *    paths, labels, refusals, the KPRN_E_DEVICE check of the fill pass -- is kprn_find_paths'.  Nothing depends on timing: no atomic hands out a slot or a rank. */
+int kprn_find_paths_sampled(kprn_handle* h, const kprn_graph* g, const int32_t* pairs /* [B][2] = (u, i) */, const float* labels /* [B] or NULL */, int32_t B,
+                            int32_t min_hops, int32_t max_hops, int32_t max_paths, int32_t T, int32_t walks, uint64_t seed, unsigned int draw /* uint32 */,
+                            int32_t* counts /* [B] */, int64_t* found /* [B] */, kprn_batch** out);
+/* the same rule on the host cores (no handle, no GPU); the other arguments and the refusals as kprn_host_find_paths' */
+int kprn_host_find_paths_sampled(const int32_t* src, const int32_t* dst, const int32_t* rel, int64_t E, const int32_t* node_types, int32_t Ve, int32_t Vr,
+                                 int32_t Vt, int32_t num_types, int32_t end_relation, const int32_t* pairs, int32_t B, int32_t min_hops, int32_t max_hops,
+                                 int32_t max_paths, int32_t T, int32_t F, int32_t walks, uint64_t seed, unsigned int draw, int32_t threads, int32_t* counts,
+                                 int64_t* found, int32_t* idx);
 
 /* ---- sampling negatives (an extension: the reference draws them offline, data_prepare/sample.py:18-26,101-117 -- distinct non-interacted items, uniform at
  * alpha = 0, else weighted by frequency^alpha; its draws, numpy.random.multinomial and Python's random, cannot be reproduced and are not restated) ----
@@ -396,6 +427,13 @@ int kprn_host_sample_negatives(const int32_t* src, const int32_t* dst, const int
 int kprn_find_training_paths(kprn_handle* h, const kprn_graph* g, const kprn_sampler* s, const int32_t* pos /* [B][2] = (u, i) */, int32_t B, int32_t n_neg,
                              int32_t max_attempts, uint64_t seed, unsigned int draw /* uint32 */, int32_t min_hops, int32_t max_hops, int32_t max_paths,
                              int32_t T, int32_t* pairs_out, int32_t* counts, int64_t* found, kprn_batch** out);
+
+/* kprn_find_training_paths with the sampled hops: one seed / draw serves the negatives and the walks, and a walk's row b is the pair-list row
+ * b * (1 + n_neg) + k.  By definition the outputs equal kprn_sample_negatives followed by kprn_find_paths_sampled on the same pair list, the rows of item 0
+ * counted as 0 paths.  max_hops <= 3: exactly kprn_find_training_paths.                                                                               */
+int kprn_find_training_paths_sampled(kprn_handle* h, const kprn_graph* g, const kprn_sampler* s, const int32_t* pos /* [B][2] = (u, i) */, int32_t B,
+                                     int32_t n_neg, int32_t max_attempts, uint64_t seed, unsigned int draw /* uint32 */, int32_t min_hops, int32_t max_hops,
+                                     int32_t max_paths, int32_t T, int32_t walks, int32_t* pairs_out, int32_t* counts, int64_t* found, kprn_batch** out);
 
 /* ---- training ---------------------------------------------------------------------- */
 /* fEval of MyOptimizer.lua:184-195: zeroGradParameters; forward; BCE; backward.

@@ -178,6 +178,7 @@ def host_dropout_keep(seed, draw, layer, T, N, Din, p):
 
 
 FIND_MAX_HOPS, FIND_MAX_PATHS = 3, 4096   # kprn_find_paths: hops per path, kept paths per pair
+FIND_MAX_HOPS_SAMPLED, FIND_MAX_WALKS = 5, 256   # kprn_find_paths_sampled: hops per path, walks per pair and sampled hop count
 
 
 def _graph_arrays(src, dst, rel, node_types):
@@ -198,21 +199,22 @@ def _pairs_array(pairs, labels):
     return pr, lab
 
 
-def host_find_paths(src, dst, rel, node_types, Vr, Vt, end_relation, pairs, min_hops, max_hops, max_paths, T, F=None, threads=1, want_idx=True):
-    """kprn_host_find_paths (no handle, no GPU): the finder's rule of include/kprn.h over the graph's raw arrays; Ve and num_types are node_types' shape ->
-    (idx [N,T,F] of the pairs with counts > 0 in input order, or None with want_idx=False; counts [B]; found [B])"""
+def _seed_draw(seed, draw):
+    return C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), C.c_uint32(int(draw) & 0xFFFFFFFF)
+
+
+def _host_find(call_lib, what, src, dst, rel, node_types, pairs, T, F, want_idx):
+    """the two calls of a host finder: counts, then rows.  call_lib(arrays .., counts, found, idx) -> status"""
     src, dst, rel, nt = _graph_arrays(src, dst, rel, node_types)
     pr, _ = _pairs_array(pairs, None)
-    Ve, num_types = int(nt.shape[0]), int(nt.shape[1])
-    F = num_types + 2 if F is None else int(F)
+    F = int(nt.shape[1]) + 2 if F is None else int(F)
     B = int(pr.shape[0])
     counts, found = np.zeros(B, np.int32), np.zeros(B, np.int64)
 
     def call(idx):
-        rc = lib().kprn_host_find_paths(_fp(src), _fp(dst), _fp(rel), C.c_int64(int(src.shape[0])), _fp(nt), Ve, int(Vr), int(Vt), num_types, int(end_relation),
-                                        _fp(pr), B, int(min_hops), int(max_hops), int(max_paths), int(T), F, int(threads), _fp(counts), _fp(found), _fp(idx))
+        rc = call_lib(src, dst, rel, nt, pr, B, F, counts, found, idx)
         if rc != 0:
-            raise KprnError(rc, "kprn_host_find_paths: bad graph ids / pairs / hops / max_paths / T / F")
+            raise KprnError(rc, what + ": bad graph ids / pairs / hops / max_paths / T / F / walks")
     call(None)
     if not want_idx:
         return None, counts, found
@@ -220,6 +222,29 @@ def host_find_paths(src, dst, rel, node_types, Vr, Vt, end_relation, pairs, min_
     if idx.size:
         call(idx)
     return idx, counts, found
+
+
+def host_find_paths(src, dst, rel, node_types, Vr, Vt, end_relation, pairs, min_hops, max_hops, max_paths, T, F=None, threads=1, want_idx=True):
+    """kprn_host_find_paths (no handle, no GPU): the finder's rule of include/kprn.h over the graph's raw arrays; Ve and num_types are node_types' shape ->
+    (idx [N,T,F] of the pairs with counts > 0 in input order, or None with want_idx=False; counts [B]; found [B])"""
+    def call(src, dst, rel, nt, pr, B, F, counts, found, idx):
+        return lib().kprn_host_find_paths(_fp(src), _fp(dst), _fp(rel), C.c_int64(int(src.shape[0])), _fp(nt), int(nt.shape[0]), int(Vr), int(Vt), int(nt.shape[1]),
+                                          int(end_relation), _fp(pr), B, int(min_hops), int(max_hops), int(max_paths), int(T), F, int(threads), _fp(counts),
+                                          _fp(found), _fp(idx))
+    return _host_find(call, "kprn_host_find_paths", src, dst, rel, node_types, pairs, T, F, want_idx)
+
+
+def host_find_paths_sampled(src, dst, rel, node_types, Vr, Vt, end_relation, pairs, min_hops, max_hops, max_paths, T, walks, seed, draw, F=None, threads=1,
+                            want_idx=True):
+    """kprn_host_find_paths_sampled (no handle, no GPU): host_find_paths with max_hops up to 5, the hops past 3 sampled by `walks` walks per pair and hop
+    count (include/kprn.h "sampled paths of four and five hops") -> (idx, counts, found)"""
+    sd, dr = _seed_draw(seed, draw)
+
+    def call(src, dst, rel, nt, pr, B, F, counts, found, idx):
+        return lib().kprn_host_find_paths_sampled(_fp(src), _fp(dst), _fp(rel), C.c_int64(int(src.shape[0])), _fp(nt), int(nt.shape[0]), int(Vr), int(Vt),
+                                                  int(nt.shape[1]), int(end_relation), _fp(pr), B, int(min_hops), int(max_hops), int(max_paths), int(T), F,
+                                                  int(walks), sd, dr, int(threads), _fp(counts), _fp(found), _fp(idx))
+    return _host_find(call, "kprn_host_find_paths_sampled", src, dst, rel, node_types, pairs, T, F, want_idx)
 
 
 SAMPLE_MAX_NEG, SAMPLE_MAX_ATTEMPTS = 256, 64   # kprn_sample_negatives: negatives per user slot, attempts per negative
@@ -231,10 +256,6 @@ def _sampler_arrays(items, weights):
     if w is not None and w.shape != it.shape:
         raise KprnError(E_ARG, "weights must be [M] like items")
     return it, w
-
-
-def _seed_draw(seed, draw):
-    return C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), C.c_uint32(int(draw) & 0xFFFFFFFF)
 
 
 def host_sample_negatives(src, dst, rel, Ve, items, weights, users, n_neg, seed, draw, max_attempts=16, threads=1, out=None):
@@ -810,15 +831,21 @@ class Engine:
         """kprn_graph_create: directed edges (src, rel, dst) [E] with 1-based ids, node_types [Ve, num_types] (row e - 1 = entity e's type slots)"""
         return Graph(self, src, dst, rel, node_types, end_relation)
 
-    def find_paths(self, graph, pairs, min_hops, max_hops, max_paths, T, labels=None):
+    def find_paths(self, graph, pairs, min_hops, max_hops, max_paths, T, labels=None, walks=0, seed=0, draw=0):
         """kprn_find_paths: every path of min_hops .. max_hops (<= 3) hops between the pairs [B,2] = (user, item), the first max_paths per pair in the
-        canonical order -> (ragged Batch of the pairs that have paths, or None when none has; counts [B]; found [B])"""
+        canonical order -> (ragged Batch of the pairs that have paths, or None when none has; counts [B]; found [B]).  walks > 0:
+        kprn_find_paths_sampled, max_hops up to 5 with the hops past 3 sampled by `walks` walks per pair and hop count under (seed, draw)"""
         pr, lab = _pairs_array(pairs, labels)
         B = int(pr.shape[0])
         counts, found = np.zeros(B, np.int32), np.zeros(B, np.int64)
         ptr = C.c_void_p()
-        self._ck(self.L.kprn_find_paths(self.h, graph.ptr, _fp(pr), _fp(lab), B, int(min_hops), int(max_hops), int(max_paths), int(T), _fp(counts), _fp(found),
-                                        C.byref(ptr)))
+        if int(walks) != 0:
+            sd, dr = _seed_draw(seed, draw)
+            self._ck(self.L.kprn_find_paths_sampled(self.h, graph.ptr, _fp(pr), _fp(lab), B, int(min_hops), int(max_hops), int(max_paths), int(T), int(walks), sd, dr,
+                                                    _fp(counts), _fp(found), C.byref(ptr)))
+        else:
+            self._ck(self.L.kprn_find_paths(self.h, graph.ptr, _fp(pr), _fp(lab), B, int(min_hops), int(max_hops), int(max_paths), int(T), _fp(counts), _fp(found),
+                                            C.byref(ptr)))
         if not ptr:
             return None, counts, found
         return Batch._adopt(self, ptr, counts[counts > 0].copy(), T, self.cfg.F, lab is not None), counts, found
@@ -838,17 +865,22 @@ class Engine:
         self._ck(self.L.kprn_sample_negatives(self.h, graph.ptr, sampler.ptr, _fp(us), B, int(n_neg), int(max_attempts), sd, dr, _fp(neg), _fp(nf)))
         return neg, nf
 
-    def find_training_paths(self, graph, sampler, positives, n_neg, seed, draw, min_hops, max_hops, max_paths, T, max_attempts=16):
+    def find_training_paths(self, graph, sampler, positives, n_neg, seed, draw, min_hops, max_hops, max_paths, T, max_attempts=16, walks=0):
         """kprn_find_training_paths: the positives [B,2] = (user, item), each with n_neg negatives sampled on the device, through the finder ->
-        (ragged Batch with labels 1 / 0 of the pairs that have paths, or None; pairs [B * (1 + n_neg), 2]; counts; found)"""
+        (ragged Batch with labels 1 / 0 of the pairs that have paths, or None; pairs [B * (1 + n_neg), 2]; counts; found).  walks > 0:
+        kprn_find_training_paths_sampled, max_hops up to 5 (the same seed and draw serve the negatives and the walks)"""
         pos, _ = _pairs_array(positives, None)
         B = int(pos.shape[0])
         n = B * (1 + max(int(n_neg), 0))
         pairs, counts, found = np.zeros((n, 2), np.int32), np.zeros(n, np.int32), np.zeros(n, np.int64)
         ptr = C.c_void_p()
         sd, dr = _seed_draw(seed, draw)
-        self._ck(self.L.kprn_find_training_paths(self.h, graph.ptr, sampler.ptr, _fp(pos), B, int(n_neg), int(max_attempts), sd, dr, int(min_hops), int(max_hops),
-                                                 int(max_paths), int(T), _fp(pairs), _fp(counts), _fp(found), C.byref(ptr)))
+        if int(walks) != 0:
+            self._ck(self.L.kprn_find_training_paths_sampled(self.h, graph.ptr, sampler.ptr, _fp(pos), B, int(n_neg), int(max_attempts), sd, dr, int(min_hops),
+                                                             int(max_hops), int(max_paths), int(T), int(walks), _fp(pairs), _fp(counts), _fp(found), C.byref(ptr)))
+        else:
+            self._ck(self.L.kprn_find_training_paths(self.h, graph.ptr, sampler.ptr, _fp(pos), B, int(n_neg), int(max_attempts), sd, dr, int(min_hops),
+                                                     int(max_hops), int(max_paths), int(T), _fp(pairs), _fp(counts), _fp(found), C.byref(ptr)))
         if not ptr:
             return None, pairs, counts, found
         return Batch._adopt(self, ptr, counts[counts > 0].copy(), T, self.cfg.F, True), pairs, counts, found

@@ -287,7 +287,7 @@ struct kprn_handle {
   void* explain_buf = nullptr; size_t explain_buf_bytes = 0;   // device pair list and results of one kprn_explain_batch call
   void* explain_pin = nullptr; size_t explain_pin_bytes = 0;   // page-locked explanation rows of kprn_recommend_explain_ragged
   std::vector<kprn_graph*> graphs;                     // path_find.hip: the knowledge graphs alive on this handle (kprn_destroy frees what is left)
-  void* pf_buf = nullptr; size_t pf_buf_bytes = 0;     // device arguments of one kprn_find_paths call (pairs, totals, first rows, counts, flag)
+  void* pf_buf = nullptr; size_t pf_buf_bytes = 0;     // device arguments of one kprn_find_paths call (pairs, totals, first rows, counts, flag; per-walk counts)
   std::vector<kprn_sampler*> samplers;                 // neg_sample.hip: the negative samplers alive on this handle (kprn_destroy frees what is left)
   void* ns_buf = nullptr; size_t ns_buf_bytes = 0;     // device arguments and results of one sampling call (users or positives, negatives, n_found)
 

@@ -242,9 +242,12 @@ int kprn_sample_negatives(kprn_handle* h, const kprn_graph* g, const kprn_sample
   API_END(h)
 }
 
-int kprn_find_training_paths(kprn_handle* h, const kprn_graph* g, const kprn_sampler* s, const int32_t* pos, int32_t B, int32_t n_neg, int32_t max_attempts,
-                             uint64_t seed, unsigned int draw, int32_t min_hops, int32_t max_hops, int32_t max_paths, int32_t T, int32_t* pairs_out,
-                             int32_t* counts, int64_t* found, kprn_batch** out) {
+}  // extern "C"
+
+// kprn_find_training_paths (sm == NULL) and kprn_find_training_paths_sampled
+static int find_training_paths(kprn_handle* h, const kprn_graph* g, const kprn_sampler* s, const int32_t* pos, int32_t B, int32_t n_neg, int32_t max_attempts,
+                               uint64_t seed, unsigned int draw, int32_t min_hops, int32_t max_hops, int32_t max_paths, int32_t T, const pf::Sampling* sm,
+                               int32_t* pairs_out, int32_t* counts, int64_t* found, kprn_batch** out) {
   API_BEGIN(h)
   KPRN_REQUIRE(out, KPRN_E_ARG, "out is NULL");
   *out = nullptr;
@@ -253,7 +256,7 @@ int kprn_find_training_paths(kprn_handle* h, const kprn_graph* g, const kprn_sam
   int rc = ns::validate_limits(B, n_neg, max_attempts, &why);
   if (rc == KPRN_OK) rc = ns::validate_users(pos, 2 * (int64_t)B, g->Ve, &why);
   const int32_t n_pairs = rc == KPRN_OK ? B * (1 + n_neg) : 0;
-  if (rc == KPRN_OK) rc = pf::validate_find_limits(n_pairs, min_hops, max_hops, max_paths, T, &why);
+  if (rc == KPRN_OK) rc = pf::validate_find_limits(n_pairs, min_hops, max_hops, max_paths, T, sm, &why);
   if (rc != KPRN_OK) throw KprnError{rc, why};
   int32_t* d_pos = (int32_t*)ns::reserve(h, (size_t)2 * B * sizeof(int32_t));
   std::vector<float> labels((size_t)n_pairs, 0.f);
@@ -264,8 +267,23 @@ int kprn_find_training_paths(kprn_handle* h, const kprn_graph* g, const kprn_sam
     HIP_TRY(hipMemcpyAsync(d_pos, pos, (size_t)2 * B * sizeof(int32_t), hipMemcpyHostToDevice, st));
     ns::launch(h, g, s, rng, d_pos, 2, B, n_neg, max_attempts, nullptr, nullptr, d_pairs, st);
   };
-  pf::find_staged(h, g, stage, labels.data(), n_pairs, min_hops, max_hops, max_paths, T, pairs_out, counts, found, out);
+  pf::find_staged(h, g, stage, labels.data(), n_pairs, min_hops, max_hops, max_paths, T, sm, pairs_out, counts, found, out);
   API_END(h)
+}
+
+extern "C" {
+
+int kprn_find_training_paths(kprn_handle* h, const kprn_graph* g, const kprn_sampler* s, const int32_t* pos, int32_t B, int32_t n_neg, int32_t max_attempts,
+                             uint64_t seed, unsigned int draw, int32_t min_hops, int32_t max_hops, int32_t max_paths, int32_t T, int32_t* pairs_out,
+                             int32_t* counts, int64_t* found, kprn_batch** out) {
+  return find_training_paths(h, g, s, pos, B, n_neg, max_attempts, seed, draw, min_hops, max_hops, max_paths, T, nullptr, pairs_out, counts, found, out);
+}
+
+int kprn_find_training_paths_sampled(kprn_handle* h, const kprn_graph* g, const kprn_sampler* s, const int32_t* pos, int32_t B, int32_t n_neg,
+                                     int32_t max_attempts, uint64_t seed, unsigned int draw, int32_t min_hops, int32_t max_hops, int32_t max_paths, int32_t T,
+                                     int32_t walks, int32_t* pairs_out, int32_t* counts, int64_t* found, kprn_batch** out) {
+  const pf::Sampling sm = pf::sampling_of(walks, seed, draw);   // (one seed and draw for the negatives and the walks: their counters differ)
+  return find_training_paths(h, g, s, pos, B, n_neg, max_attempts, seed, draw, min_hops, max_hops, max_paths, T, &sm, pairs_out, counts, found, out);
 }
 
 int kprn_host_sample_negatives(const int32_t* src, const int32_t* dst, const int32_t* rel, int64_t E, int32_t Ve, const int32_t* items, const float* weights,

@@ -1,5 +1,5 @@
 // Path finder (include/kprn.h "finding a pair's paths"): a knowledge graph as CSR in HBM, and for B (user, item) pairs every path of min_hops .. max_hops <= 3
-// hops between them, laid out as the rows of a ragged kprn_batch.  Integers only; no float, no atomics that hand out output slots, no LDS beyond the
+// hops between them, laid out as the rows of a ragged kprn_batch; the sampled paths of 4 and 5 hops that may follow them in a pair's rows are path_walk.hip's.  Integers only; no float, no atomics that hand out output slots, no LDS beyond the
 // workgroup's scan.
 //
 // One definition of the rule serves the kernels and the host twin (namespace pf, __host__ __device__):
@@ -16,7 +16,8 @@
 //   k_fill    ranks by prefix sums in the workgroup (Hillis-Steele in LDS, int64): 2 hops over 256 first edges at a time; 3 hops first edge by first edge,
 //             256 second edges at a time, a running rank carried from chunk to chunk.  A thread writes the rows of its own first / second edge at their ranks
 //             while rank < counts[b] -- the range the pair was allotted -- and a hop's chunks stop once the running rank reaches it (with a cap of 28 the fill
-//             pass touches a few chunks, whatever found is).  The rows a workgroup placed are summed and compared with counts[b]: a disagreement between
+//             pass touches a few chunks, whatever found is).  The rows a workgroup placed are summed and compared with counts[b] (with the pair's exhaustive total
+//             where sampled rows follow, which path_walk.hip places and checks the same way): a disagreement between
 //             the passes sets the flag (KPRN_E_DEVICE), and no write leaves the pair's range either way.
 // The host twin walks the same primitives (edge_range, mid_range, write_row) pair by pair on its threads.  The graph, the CSR view and edge_range are in
 // path_find_dev.h, shared with neg_sample.hip; find_staged runs the two passes over a pair list that is staged into HBM by its caller.
@@ -26,9 +27,6 @@
 #include <rocprim/device/device_select.hpp>
 
 namespace pf {
-
-struct Fmt { const int32_t* types; int nT, Vt, Ve, Vr, T, F, end_rel; };
-constexpr int TPB = 256;
 
 // the closing edges of the 3-hop paths u -> n1 -> col[e1] -> i: their number, the first one in lo; none when the middle node repeats u, i or n1
 __host__ __device__ static inline int mid_range(const Csr& g, int u, int i, int n1, int e1, int& lo) {
@@ -50,24 +48,6 @@ __host__ __device__ static inline void subtree_count(const Csr& g, int u, int i,
   if (!want3) return;
   const int end = g.rowptr[n1 + 1];
   for (int e1 = g.rowptr[n1]; e1 < end; ++e1) c3 += mid_range(g, u, i, n1, e1, lo);
-}
-
-// one path's [T][F] row: left padding (Vt .., Ve, Vr), then (types of n_k, n_k, r_k), the last step with #END_RELATION; leading columns = Vt
-__host__ __device__ static inline void write_row(const Fmt& f, int32_t* row, int h, const int* nodes, const int* rels) {
-  const int pad = f.T - (h + 1), lead = f.F - f.nT - 2;
-  for (int t = 0; t < f.T; ++t) {
-    int32_t* s = row + t * f.F;
-    const int k = t - pad;
-    for (int c = 0; c < lead; ++c) s[c] = f.Vt;
-    if (k < 0) {
-      for (int c = 0; c < f.nT; ++c) s[lead + c] = f.Vt;
-      s[f.F - 2] = f.Ve; s[f.F - 1] = f.Vr;
-    } else {
-      const int n = nodes[k];
-      for (int c = 0; c < f.nT; ++c) s[lead + c] = f.types[(int64_t)(n - 1) * f.nT + c];
-      s[f.F - 2] = n; s[f.F - 1] = k < h ? rels[k] : f.end_rel;
-    }
-  }
 }
 
 // the first room1 paths of 1 hop among the edges lo + first, lo + first + step, ... of [lo, hi), each at its rank; returns the rows written
@@ -113,32 +93,6 @@ __host__ __device__ static inline int subtree_fill(const Csr& g, const Fmt& f, i
 __host__ __device__ static inline int64_t room(int64_t cap, int64_t rank) { return rank < cap ? cap - rank : 0; }
 
 // ---- kernels ---------------------------------------------------------------------------------------------------------------------------------
-// sum over the workgroup; every thread gets it.  sh [TPB]
-__device__ static inline int64_t block_sum(int64_t v, int64_t* sh) {
-  __syncthreads();   // (sh may still be read from the previous use)
-  sh[threadIdx.x] = v;
-  __syncthreads();
-  for (int d = TPB / 2; d > 0; d >>= 1) {
-    if ((int)threadIdx.x < d) sh[threadIdx.x] += sh[threadIdx.x + d];
-    __syncthreads();
-  }
-  return sh[0];
-}
-// exclusive prefix over the workgroup in thread order; total = the sum.  sh [TPB]
-__device__ static inline int64_t block_scan_excl(int64_t v, int64_t* sh, int64_t& total) {
-  __syncthreads();
-  sh[threadIdx.x] = v;
-  __syncthreads();
-  for (int d = 1; d < TPB; d <<= 1) {
-    const int64_t t = (int)threadIdx.x >= d ? sh[threadIdx.x - d] : 0;
-    __syncthreads();
-    sh[threadIdx.x] += t;
-    __syncthreads();
-  }
-  total = sh[TPB - 1];
-  return sh[threadIdx.x] - v;
-}
-
 __global__ __launch_bounds__(TPB) void k_count(Csr g, const int32_t* __restrict__ pairs, int hmask, int64_t* __restrict__ tot) {
   __shared__ int64_t sh[TPB];
   const int b = blockIdx.x, u = pairs[2 * b], i = pairs[2 * b + 1];
@@ -223,7 +177,8 @@ __global__ __launch_bounds__(TPB) void k_fill(Csr g, Fmt f, const int32_t* __res
     }
   }
   placed = block_sum(placed, sh);
-  if (threadIdx.x == 0 && placed != cap) atomicOr(flag, 1);
+  // (cap > the exhaustive total only where sampled paths follow: those rows are path_walk.hip's)
+  if (threadIdx.x == 0 && placed != min(cap, tot[4 * (int64_t)b + 3])) atomicOr(flag, 1);
 }
 
 // ---- graph build -----------------------------------------------------------------------------------------------------------------------------
@@ -282,18 +237,20 @@ static int validate_graph(const int32_t* src, const int32_t* dst, const int32_t*
     if (node_types[k] < 1 || node_types[k] > Vt) return bad(KPRN_E_INDEX, "a type id is outside 1..Vt");
   return KPRN_OK;
 }
-int validate_find_limits(int32_t B, int32_t min_hops, int32_t max_hops, int32_t max_paths, int32_t T, std::string* why) {
+int validate_find_limits(int32_t B, int32_t min_hops, int32_t max_hops, int32_t max_paths, int32_t T, const Sampling* sm, std::string* why) {
   auto bad = [&](int code, const char* t) { if (why) *why = t; return code; };
   if (B < 1) return bad(KPRN_E_ARG, "pairs is NULL or B < 1");
-  if (min_hops < 1 || min_hops > max_hops || max_hops > 3) return bad(KPRN_E_ARG, "hops: 1 <= min_hops <= max_hops <= 3");
+  if (!sm && (min_hops < 1 || min_hops > max_hops || max_hops > 3)) return bad(KPRN_E_ARG, "hops: 1 <= min_hops <= max_hops <= 3");
+  if (sm && (min_hops < 1 || min_hops > max_hops || max_hops > 5)) return bad(KPRN_E_ARG, "hops: 1 <= min_hops <= max_hops <= 5");
+  if (sm && max_hops > 3 && (sm->walks < 1 || sm->walks > MAX_WALKS)) return bad(KPRN_E_ARG, "walks must be in 1..256 when max_hops > 3");
   if (max_paths < 1 || max_paths > kk::RAGGED_MAX_SEG) return bad(KPRN_E_ARG, "max_paths must be in 1..4096");
   if (T < max_hops + 1) return bad(KPRN_E_ARG, "T must be at least max_hops + 1");
   return KPRN_OK;
 }
-static int validate_find(const int32_t* pairs, int32_t B, int32_t Ve, int32_t min_hops, int32_t max_hops, int32_t max_paths, int32_t T, std::string* why) {
+int validate_find(const int32_t* pairs, int32_t B, int32_t Ve, int32_t min_hops, int32_t max_hops, int32_t max_paths, int32_t T, const Sampling* sm, std::string* why) {
   auto bad = [&](int code, const char* t) { if (why) *why = t; return code; };
   if (!pairs) return bad(KPRN_E_ARG, "pairs is NULL or B < 1");
-  const int rc = validate_find_limits(B, min_hops, max_hops, max_paths, T, why);
+  const int rc = validate_find_limits(B, min_hops, max_hops, max_paths, T, sm, why);
   if (rc != KPRN_OK) return rc;
   for (int64_t k = 0; k < 2 * (int64_t)B; ++k)
     if (pairs[k] < 1 || pairs[k] >= Ve) return bad(KPRN_E_INDEX, "a pair's node is outside 1..Ve-1");
@@ -415,19 +372,23 @@ static int64_t host_pair_fill(const Csr& g, const Fmt& f, int u, int i, int hmas
 }
 
 void find_staged(kprn_handle* h, const kprn_graph* g, const StagePairs& stage, const float* labels, int32_t B, int32_t min_hops, int32_t max_hops,
-                 int32_t max_paths, int32_t T, int32_t* pairs_out, int32_t* counts, int64_t* found, kprn_batch** out) {
+                 int32_t max_paths, int32_t T, const Sampling* sm, int32_t* pairs_out, int32_t* counts, int64_t* found, kprn_batch** out) {
   const kprn_config& c = h->cfg;
   KPRN_REQUIRE(c.F >= c.num_types + 2, KPRN_E_ARG, "F must hold num_types + 2 columns");
   hipStream_t s = h->stream;
   const int hmask = hop_mask(min_hops, max_hops);
-  // device arguments of the two passes: pairs [2B] | cnt [B] | flag [4] (int32), then tot [4B] | first [B] (int64)
-  const size_t w32 = ((size_t)3 * B + 4 + 1) & ~(size_t)1, total = w32 * 4 + (size_t)5 * B * 8;
+  const bool sampled = (hmask & HOPS_SAMPLED) != 0;   // (validated: sm is there)
+  const size_t n_wc = sampled ? (size_t)2 * B * sm->walks : 0;
+  // device arguments of the two passes: pairs [2B] | cnt [B] | flag [4] (int32), then tot [4B] | first [B] (int64); sampled hops add wsum [2B] | wc [B][2][walks]
+  const size_t w32 = ((size_t)3 * B + 4 + 1) & ~(size_t)1, total = w32 * 4 + ((size_t)(sampled ? 7 : 5) * B + n_wc) * 8;
   grow_call_block(s, h->pf_buf, h->pf_buf_bytes, total);
   int32_t* d_pairs = (int32_t*)h->pf_buf;
   int32_t* d_cnt = d_pairs + 2 * (size_t)B;
   int32_t* d_flag = d_cnt + B;
   int64_t* d_tot = (int64_t*)((char*)h->pf_buf + w32 * 4);
   int64_t* d_first = d_tot + 4 * (size_t)B;
+  int64_t* d_wsum = d_first + B;
+  int64_t* d_wc = d_wsum + 2 * (size_t)B;
   const Csr csr{g->rowptr, g->col, g->rel};
   stage(d_pairs, s);
   {
@@ -435,17 +396,25 @@ void find_staged(kprn_handle* h, const kprn_graph* g, const StagePairs& stage, c
     hipLaunchKernelGGL(k_count, dim3((unsigned)B), dim3(TPB), 0, s, csr, d_pairs, hmask, d_tot);
     HIP_TRY(hipGetLastError());
   }
-  std::vector<int64_t> tot((size_t)4 * B), first((size_t)B);
+  std::vector<int64_t> tot((size_t)4 * B), first((size_t)B), wsum(sampled ? (size_t)2 * B : 0);
+  if (sampled) {
+    ProfScope ps(h, "find_paths_walk_count");
+    walk_count_launch(csr, d_pairs, B, hmask, *sm, d_wc, d_wsum, s);
+    HIP_TRY(hipMemcpyAsync(wsum.data(), d_wsum, wsum.size() * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+  }
   HIP_TRY(hipMemcpyAsync(tot.data(), d_tot, tot.size() * sizeof(int64_t), hipMemcpyDeviceToHost, s));
   if (pairs_out) HIP_TRY(hipMemcpyAsync(pairs_out, d_pairs, (size_t)2 * B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   // the scan over the pairs: counts, the pairs that have paths, each one's first row
   std::vector<int32_t> cnt((size_t)B), kept;
+  std::vector<int64_t> fnd((size_t)B);
   std::vector<float> lab;
   int64_t N = 0;
   for (int32_t b = 0; b < B; ++b) {
-    const int64_t f = tot[4 * (size_t)b + 3];
-    KPRN_REQUIRE(f >= 0, KPRN_E_DEVICE, "find_paths: the counting pass returned a negative count");
+    const int64_t fx = tot[4 * (size_t)b + 3], fs = sampled ? wsum[2 * (size_t)b] + wsum[2 * (size_t)b + 1] : 0, f = fx + fs;
+    KPRN_REQUIRE(fx >= 0 && fs >= 0 && (!sampled || (wsum[2 * (size_t)b] >= 0 && wsum[2 * (size_t)b + 1] >= 0)), KPRN_E_DEVICE,
+                 "find_paths: the counting pass returned a negative count");
+    fnd[b] = f;
     cnt[b] = (int32_t)std::min<int64_t>(f, max_paths);
     first[b] = cnt[b] > 0 ? N : -1;
     if (cnt[b] > 0) { kept.push_back(cnt[b]); if (labels) lab.push_back(labels[b]); }
@@ -457,9 +426,15 @@ void find_staged(kprn_handle* h, const kprn_graph* g, const StagePairs& stage, c
     HIP_TRY(hipMemsetAsync(d_flag, 0, sizeof(int32_t), s));
     const Fmt fmt{g->types, g->nT, g->Vt, g->Ve, g->Vr, T, c.F, g->end_rel};
     const slots::DeviceFill fill = [&](int32_t* idx_dev, hipStream_t st) {
-      ProfScope ps(h, "find_paths_fill", st);
-      hipLaunchKernelGGL(k_fill, dim3((unsigned)B), dim3(TPB), 0, st, csr, fmt, d_pairs, hmask, d_tot, d_first, d_cnt, idx_dev, d_flag);
-      HIP_TRY(hipGetLastError());
+      {
+        ProfScope ps(h, "find_paths_fill", st);
+        hipLaunchKernelGGL(k_fill, dim3((unsigned)B), dim3(TPB), 0, st, csr, fmt, d_pairs, hmask, d_tot, d_first, d_cnt, idx_dev, d_flag);
+        HIP_TRY(hipGetLastError());
+      }
+      if (sampled) {
+        ProfScope pw(h, "find_paths_walk_fill", st);
+        walk_fill_launch(csr, fmt, d_pairs, B, *sm, d_tot, d_wc, d_first, d_cnt, idx_dev, d_flag, st);
+      }
     };
     kprn_batch* nb = nullptr;
     slots::create(h, nullptr, kept.data(), labels ? lab.data() : nullptr, (int32_t)kept.size(), 0, N, T, c.F, &nb, &fill);
@@ -474,8 +449,50 @@ void find_staged(kprn_handle* h, const kprn_graph* g, const StagePairs& stage, c
   }
   for (int32_t b = 0; b < B; ++b) {
     if (counts) counts[b] = cnt[b];
-    if (found) found[b] = tot[4 * (size_t)b + 3];
+    if (found) found[b] = fnd[b];
   }
+}
+
+int host_find(const int32_t* src, const int32_t* dst, const int32_t* rel, int64_t E, const int32_t* node_types, int32_t Ve, int32_t Vr, int32_t Vt, int32_t num_types,
+              int32_t end_relation, const int32_t* pairs, int32_t B, int32_t min_hops, int32_t max_hops, int32_t max_paths, int32_t T, int32_t F, const Sampling* sm,
+              int32_t threads, int32_t* counts, int64_t* found, int32_t* idx) {
+  int rc = pf::validate_graph(src, dst, rel, E, node_types, Ve, Vr, Vt, num_types, end_relation, nullptr);
+  if (rc != KPRN_OK) return rc;
+  rc = pf::validate_find(pairs, B, Ve, min_hops, max_hops, max_paths, T, sm, nullptr);
+  if (rc != KPRN_OK) return rc;
+  if (F < num_types + 2 || !counts) return KPRN_E_ARG;
+  try {
+    const pf::HostCsr hg = pf::host_csr(src, dst, rel, E, Ve);
+    const pf::Csr g{hg.rowptr.data(), hg.col.data(), hg.rel.data()};
+    const pf::Fmt f{node_types, num_types, Vt, Ve, Vr, T, F, end_relation};
+    const int hmask = pf::hop_mask(min_hops, max_hops);
+    const bool sampled = (hmask & HOPS_SAMPLED) != 0;
+    const size_t per = sampled ? (size_t)2 * sm->walks : 0;   // a pair's per-walk counts
+    std::vector<int64_t> tot((size_t)4 * B), first((size_t)B), wc(per * B), wsum(sampled ? (size_t)2 * B : 0);
+    pf::parallel_pairs(B, threads, [&](int32_t b) {
+      pf::host_pair_totals(g, pairs[2 * b], pairs[2 * b + 1], hmask, &tot[4 * (size_t)b]);
+      if (sampled) host_walk_counts(g, pairs[2 * b], pairs[2 * b + 1], b, hmask, *sm, &wc[per * b], &wsum[2 * (size_t)b]);
+    });
+    int64_t N = 0;
+    for (int32_t b = 0; b < B; ++b) {
+      const int64_t f = tot[4 * (size_t)b + 3] + (sampled ? wsum[2 * (size_t)b] + wsum[2 * (size_t)b + 1] : 0);
+      counts[b] = (int32_t)std::min<int64_t>(f, max_paths);
+      if (found) found[b] = f;
+      first[b] = N;
+      N += counts[b];
+    }
+    if (!idx) return KPRN_OK;
+    std::atomic<int> wrong{0};
+    pf::parallel_pairs(B, threads, [&](int32_t b) {
+      if (counts[b] == 0) return;
+      int32_t* rows = idx + first[b] * T * F;
+      int64_t placed = pf::host_pair_fill(g, f, pairs[2 * b], pairs[2 * b + 1], hmask, &tot[4 * (size_t)b], counts[b], rows);
+      if (sampled) placed += host_walk_fill(g, f, pairs[2 * b], pairs[2 * b + 1], b, *sm, &wc[per * b], tot[4 * (size_t)b + 3], counts[b], rows);
+      if (placed != counts[b]) wrong = 1;
+    });
+    if (wrong) return KPRN_E_DEVICE;
+  } catch (...) { return KPRN_E_NOMEM; }
+  return KPRN_OK;
 }
 
 }  // namespace pf
@@ -513,54 +530,52 @@ int kprn_graph_num_edges(kprn_handle* h, const kprn_graph* g, int64_t* n) {
   API_END(h)
 }
 
-int kprn_find_paths(kprn_handle* h, const kprn_graph* g, const int32_t* pairs, const float* labels, int32_t B, int32_t min_hops, int32_t max_hops,
-                    int32_t max_paths, int32_t T, int32_t* counts, int64_t* found, kprn_batch** out) {
+}  // extern "C"
+
+// kprn_find_paths (sm == NULL) and kprn_find_paths_sampled
+static int find_paths(kprn_handle* h, const kprn_graph* g, const int32_t* pairs, const float* labels, int32_t B, int32_t min_hops, int32_t max_hops,
+                      int32_t max_paths, int32_t T, const pf::Sampling* sm, int32_t* counts, int64_t* found, kprn_batch** out) {
   API_BEGIN(h)
   KPRN_REQUIRE(out, KPRN_E_ARG, "out is NULL");
   *out = nullptr;
   KPRN_REQUIRE(g && std::find(h->graphs.begin(), h->graphs.end(), g) != h->graphs.end(), KPRN_E_ARG, "g is not a graph of this handle");
   std::string why;
-  const int rc = pf::validate_find(pairs, B, g->Ve, min_hops, max_hops, max_paths, T, &why);
+  const int rc = pf::validate_find(pairs, B, g->Ve, min_hops, max_hops, max_paths, T, sm, &why);
   if (rc != KPRN_OK) throw KprnError{rc, why};
   const pf::StagePairs stage = [&](int32_t* d_pairs, hipStream_t s) {
     HIP_TRY(hipMemcpyAsync(d_pairs, pairs, (size_t)2 * B * sizeof(int32_t), hipMemcpyHostToDevice, s));
   };
-  pf::find_staged(h, g, stage, labels, B, min_hops, max_hops, max_paths, T, nullptr, counts, found, out);
+  pf::find_staged(h, g, stage, labels, B, min_hops, max_hops, max_paths, T, sm, nullptr, counts, found, out);
   API_END(h)
+}
+
+extern "C" {
+
+int kprn_find_paths(kprn_handle* h, const kprn_graph* g, const int32_t* pairs, const float* labels, int32_t B, int32_t min_hops, int32_t max_hops,
+                    int32_t max_paths, int32_t T, int32_t* counts, int64_t* found, kprn_batch** out) {
+  return find_paths(h, g, pairs, labels, B, min_hops, max_hops, max_paths, T, nullptr, counts, found, out);
+}
+
+int kprn_find_paths_sampled(kprn_handle* h, const kprn_graph* g, const int32_t* pairs, const float* labels, int32_t B, int32_t min_hops, int32_t max_hops,
+                            int32_t max_paths, int32_t T, int32_t walks, uint64_t seed, unsigned int draw, int32_t* counts, int64_t* found, kprn_batch** out) {
+  const pf::Sampling sm = pf::sampling_of(walks, seed, draw);
+  return find_paths(h, g, pairs, labels, B, min_hops, max_hops, max_paths, T, &sm, counts, found, out);
 }
 
 int kprn_host_find_paths(const int32_t* src, const int32_t* dst, const int32_t* rel, int64_t E, const int32_t* node_types, int32_t Ve, int32_t Vr, int32_t Vt,
                          int32_t num_types, int32_t end_relation, const int32_t* pairs, int32_t B, int32_t min_hops, int32_t max_hops, int32_t max_paths,
                          int32_t T, int32_t F, int32_t threads, int32_t* counts, int64_t* found, int32_t* idx) {
-  int rc = pf::validate_graph(src, dst, rel, E, node_types, Ve, Vr, Vt, num_types, end_relation, nullptr);
-  if (rc != KPRN_OK) return rc;
-  rc = pf::validate_find(pairs, B, Ve, min_hops, max_hops, max_paths, T, nullptr);
-  if (rc != KPRN_OK) return rc;
-  if (F < num_types + 2 || !counts) return KPRN_E_ARG;
-  try {
-    const pf::HostCsr hg = pf::host_csr(src, dst, rel, E, Ve);
-    const pf::Csr g{hg.rowptr.data(), hg.col.data(), hg.rel.data()};
-    const pf::Fmt f{node_types, num_types, Vt, Ve, Vr, T, F, end_relation};
-    const int hmask = pf::hop_mask(min_hops, max_hops);
-    std::vector<int64_t> tot((size_t)4 * B), first((size_t)B);
-    pf::parallel_pairs(B, threads, [&](int32_t b) { pf::host_pair_totals(g, pairs[2 * b], pairs[2 * b + 1], hmask, &tot[4 * (size_t)b]); });
-    int64_t N = 0;
-    for (int32_t b = 0; b < B; ++b) {
-      counts[b] = (int32_t)std::min<int64_t>(tot[4 * (size_t)b + 3], max_paths);
-      if (found) found[b] = tot[4 * (size_t)b + 3];
-      first[b] = N;
-      N += counts[b];
-    }
-    if (!idx) return KPRN_OK;
-    std::atomic<int> wrong{0};
-    pf::parallel_pairs(B, threads, [&](int32_t b) {
-      if (counts[b] == 0) return;
-      const int64_t placed = pf::host_pair_fill(g, f, pairs[2 * b], pairs[2 * b + 1], hmask, &tot[4 * (size_t)b], counts[b], idx + first[b] * T * F);
-      if (placed != counts[b]) wrong = 1;
-    });
-    if (wrong) return KPRN_E_DEVICE;
-  } catch (...) { return KPRN_E_NOMEM; }
-  return KPRN_OK;
+  return pf::host_find(src, dst, rel, E, node_types, Ve, Vr, Vt, num_types, end_relation, pairs, B, min_hops, max_hops, max_paths, T, F, nullptr, threads, counts, found,
+                       idx);
+}
+
+int kprn_host_find_paths_sampled(const int32_t* src, const int32_t* dst, const int32_t* rel, int64_t E, const int32_t* node_types, int32_t Ve, int32_t Vr,
+                                 int32_t Vt, int32_t num_types, int32_t end_relation, const int32_t* pairs, int32_t B, int32_t min_hops, int32_t max_hops,
+                                 int32_t max_paths, int32_t T, int32_t F, int32_t walks, uint64_t seed, unsigned int draw, int32_t threads, int32_t* counts,
+                                 int64_t* found, int32_t* idx) {
+  const pf::Sampling sm = pf::sampling_of(walks, seed, draw);
+  return pf::host_find(src, dst, rel, E, node_types, Ve, Vr, Vt, num_types, end_relation, pairs, B, min_hops, max_hops, max_paths, T, F, &sm, threads, counts, found,
+                       idx);
 }
 
 }  // extern "C"

@@ -1,7 +1,8 @@
-// What the path finder (path_find.hip) and the negative sampler (neg_sample.hip) share: the graph in HBM, the CSR view both walk (namespace pf,
-// __host__ __device__), the host CSR of the twins and their thread loop.
+// What the path finder (path_find.hip), its sampled hops (path_walk.hip) and the negative sampler (neg_sample.hip) share: the graph in HBM, the CSR view they
+// walk and a path's row (namespace pf, __host__ __device__), the workgroup's sums, the host CSR of the twins and their thread loop.
 #pragma once
 #include "kprn_internal.h"
+#include "philox_dev.h"
 
 #include <algorithm>
 #include <atomic>
@@ -30,6 +31,53 @@ __host__ __device__ static inline void edge_range(const Csr& g, int n, int targe
   r = b;
   while (l < r) { const int m = l + ((r - l) >> 1); if (g.col[m] <= target) l = m + 1; else r = m; }
   hi = l;
+}
+
+struct Fmt { const int32_t* types; int nT, Vt, Ve, Vr, T, F, end_rel; };
+constexpr int TPB = 256;
+
+// one path's [T][F] row: left padding (Vt .., Ve, Vr), then (types of n_k, n_k, r_k), the last step with #END_RELATION; leading columns = Vt
+__host__ __device__ static inline void write_row(const Fmt& f, int32_t* row, int h, const int* nodes, const int* rels) {
+  const int pad = f.T - (h + 1), lead = f.F - f.nT - 2;
+  for (int t = 0; t < f.T; ++t) {
+    int32_t* s = row + t * f.F;
+    const int k = t - pad;
+    for (int c = 0; c < lead; ++c) s[c] = f.Vt;
+    if (k < 0) {
+      for (int c = 0; c < f.nT; ++c) s[lead + c] = f.Vt;
+      s[f.F - 2] = f.Ve; s[f.F - 1] = f.Vr;
+    } else {
+      const int n = nodes[k];
+      for (int c = 0; c < f.nT; ++c) s[lead + c] = f.types[(int64_t)(n - 1) * f.nT + c];
+      s[f.F - 2] = n; s[f.F - 1] = k < h ? rels[k] : f.end_rel;
+    }
+  }
+}
+
+// sum over the workgroup; every thread gets it.  sh [TPB]
+__device__ static inline int64_t block_sum(int64_t v, int64_t* sh) {
+  __syncthreads();   // (sh may still be read from the previous use)
+  sh[threadIdx.x] = v;
+  __syncthreads();
+  for (int d = TPB / 2; d > 0; d >>= 1) {
+    if ((int)threadIdx.x < d) sh[threadIdx.x] += sh[threadIdx.x + d];
+    __syncthreads();
+  }
+  return sh[0];
+}
+// exclusive prefix over the workgroup in thread order; total = the sum.  sh [TPB]
+__device__ static inline int64_t block_scan_excl(int64_t v, int64_t* sh, int64_t& total) {
+  __syncthreads();
+  sh[threadIdx.x] = v;
+  __syncthreads();
+  for (int d = 1; d < TPB; d <<= 1) {
+    const int64_t t = (int)threadIdx.x >= d ? sh[threadIdx.x - d] : 0;
+    __syncthreads();
+    sh[threadIdx.x] += t;
+    __syncthreads();
+  }
+  total = sh[TPB - 1];
+  return sh[threadIdx.x] - v;
 }
 
 // ---- host twins: the same rule over a CSR built by std::sort --------------------------------------------------------------------------------
@@ -62,10 +110,29 @@ static void parallel_pairs(int32_t B, int threads, Fn&& fn) {
 // The finder's two passes over B pairs whose list stage(d_pairs, s) queues into HBM on the handle's stream -- a copy from the host (kprn_find_paths) or the
 // kernels that form it there (kprn_find_training_paths); a pair's item may be 0 = no item (the pair counts no paths), its user is a node.  pairs_out
 // (or NULL): the list back on the host, [B][2].  Everything else as kprn_find_paths.
+// sm (or NULL = hops 1..3 only): the sampled hops 4 and 5 (path_walk.hip) follow the exhaustive ones in every pair's rows.
 typedef std::function<void(int32_t* d_pairs, hipStream_t s)> StagePairs;
+struct Sampling { int32_t walks; uint32_t k0, k1, draw; };   // walks per pair and hop count; Philox key = the seed's halves
+static inline Sampling sampling_of(int32_t walks, uint64_t seed, uint32_t draw) { return Sampling{walks, (uint32_t)(seed & 0xffffffffu), (uint32_t)(seed >> 32), draw}; }
+constexpr int MAX_WALKS = 256, HOPS_SAMPLED = 8 | 16;   // (bits of the hop mask: bit h - 1 = paths of h hops are asked for)
 void find_staged(kprn_handle* h, const kprn_graph* g, const StagePairs& stage, const float* labels, int32_t B, int32_t min_hops, int32_t max_hops,
-                 int32_t max_paths, int32_t T, int32_t* pairs_out, int32_t* counts, int64_t* found, kprn_batch** out);
-// hops / max_paths / T of a find call (KPRN_E_ARG), before anything is staged
-int validate_find_limits(int32_t B, int32_t min_hops, int32_t max_hops, int32_t max_paths, int32_t T, std::string* why);
+                 int32_t max_paths, int32_t T, const Sampling* sm, int32_t* pairs_out, int32_t* counts, int64_t* found, kprn_batch** out);
+// hops / max_paths / T of a find call (KPRN_E_ARG), before anything is staged; sm == NULL: max_hops <= 3, else max_hops <= 5 and walks in 1..256 past 3 hops
+int validate_find_limits(int32_t B, int32_t min_hops, int32_t max_hops, int32_t max_paths, int32_t T, const Sampling* sm, std::string* why);
+int validate_find(const int32_t* pairs, int32_t B, int32_t Ve, int32_t min_hops, int32_t max_hops, int32_t max_paths, int32_t T, const Sampling* sm, std::string* why);
+// the host twin's body (kprn_host_find_paths and kprn_host_find_paths_sampled)
+int host_find(const int32_t* src, const int32_t* dst, const int32_t* rel, int64_t E, const int32_t* node_types, int32_t Ve, int32_t Vr, int32_t Vt, int32_t num_types,
+              int32_t end_relation, const int32_t* pairs, int32_t B, int32_t min_hops, int32_t max_hops, int32_t max_paths, int32_t T, int32_t F, const Sampling* sm,
+              int32_t threads, int32_t* counts, int64_t* found, int32_t* idx);
+
+// ---- the sampled hops (path_walk.hip; include/kprn.h "sampled paths of four and five hops") ----
+// per-walk path counts wc [B][2][walks] (slot 0 = 4 hops, 1 = 5 hops; 0 for a dead or dropped walk or a hop count hmask leaves out) and their sums wsum [B][2]
+void walk_count_launch(const Csr& g, const int32_t* d_pairs, int32_t B, int hmask, const Sampling& sm, int64_t* d_wc, int64_t* d_wsum, hipStream_t s);
+// the sampled rows of every pair, from rank tot[4 b + 3] (the pair's exhaustive paths) up to cnt[b]; flag as k_fill's
+void walk_fill_launch(const Csr& g, const Fmt& f, const int32_t* d_pairs, int32_t B, const Sampling& sm, const int64_t* d_tot, const int64_t* d_wc,
+                      const int64_t* d_first, const int32_t* d_cnt, int32_t* idx, int32_t* d_flag, hipStream_t s);
+// the same on the host for row b: wc [2][walks] -> the two sums in s2; the rows from rank base up to cap -> the rows written
+void host_walk_counts(const Csr& g, int u, int i, int b, int hmask, const Sampling& sm, int64_t* wc, int64_t* s2);
+int64_t host_walk_fill(const Csr& g, const Fmt& f, int u, int i, int b, const Sampling& sm, const int64_t* wc, int64_t base, int64_t cap, int32_t* out);
 
 }  // namespace pf

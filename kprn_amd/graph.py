@@ -94,7 +94,11 @@ class KnowledgeGraph:
         deg = np.bincount(self.interactions(relation_name)[:, 1], minlength=self.Ve + 1).astype(np.float64)
         return np.power(deg[np.asarray(items, np.int64)], float(alpha)).astype(np.float32)
 
-    def host_find_paths(self, pairs, min_hops, max_hops, max_paths, T, F=None, threads=1, want_idx=True):
+    def host_find_paths(self, pairs, min_hops, max_hops, max_paths, T, F=None, threads=1, want_idx=True, walks=0, seed=0, draw=0):
+        """walks > 0: the hops past 3 sampled (_ffi.host_find_paths_sampled)"""
+        if int(walks) != 0:
+            return _ffi.host_find_paths_sampled(self.src, self.dst, self.rel, self.node_types, self.Vr, self.Vt, self.end_relation, pairs, min_hops, max_hops,
+                                                max_paths, T, walks, seed, draw, F=F, threads=threads, want_idx=want_idx)
         return _ffi.host_find_paths(self.src, self.dst, self.rel, self.node_types, self.Vr, self.Vt, self.end_relation, pairs, min_hops, max_hops, max_paths,
                                     T, F=F, threads=threads, want_idx=want_idx)
 
@@ -108,17 +112,18 @@ def read_triples(path):
                 yield parts[0], parts[1], parts[2]
 
 
-def recommend(eng, kg, user, items, K, M, min_hops=1, max_hops=3, max_paths=28, T=None, class_id=1, mode=_ffi.RANK_PRINTED):
+def recommend(eng, kg, user, items, K, M, min_hops=1, max_hops=3, max_paths=28, T=None, class_id=1, mode=_ffi.RANK_PRINTED, walks=0, seed=1, draw=0):
     """Which of `items` for `user` (entity ids), and why: find every pair's paths on the device, score the batch, put the scores on the board, rank the
     one group, explain the K winners and read their paths' ids back.  kg: a KnowledgeGraph, or an _ffi.Graph already on the engine.  The board is
-    resized to the candidates that have paths (kprn_board_reserve keeps nothing).
+    resized to the candidates that have paths (kprn_board_reserve keeps nothing).  walks > 0: max_hops may be 4 or 5, the hops past 3 sampled by `walks`
+    walks per item and hop count under (seed, draw) (include/kprn.h "sampled paths of four and five hops").
     -> the K best items, best first: dict(item, rank, score, n_paths, found, paths = the M strongest as (ids [T,F], weight, score)); items without any
     path are not candidates, so the list may be shorter than K -- empty when no item is reachable."""
     graph = kg.on(eng) if isinstance(kg, KnowledgeGraph) else kg
     items = np.asarray(items, np.int32).reshape(-1)
     pairs = np.stack([np.full(items.shape, int(user), np.int32), items], axis=1)
     T = max_hops + 1 if T is None else int(T)
-    batch, counts, found = eng.find_paths(graph, pairs, min_hops, max_hops, max_paths, T)
+    batch, counts, found = eng.find_paths(graph, pairs, min_hops, max_hops, max_paths, T, walks=walks, seed=seed, draw=draw)
     if batch is None:
         return []
     try:
@@ -145,11 +150,12 @@ def recommend(eng, kg, user, items, K, M, min_hops=1, max_hops=3, max_paths=28, 
 
 
 def train_from_graph(eng, kg, positives, opt, minibatch, n_neg, num_epochs, seed, sampler=None, max_attempts=16, min_hops=2, max_hops=3, max_paths=28, T=None,
-                     class_id=1, epoch_hooks=(), start_iteration=1, gradient_step_counter=100, out=None, stats=None):
+                     class_id=1, epoch_hooks=(), start_iteration=1, gradient_step_counter=100, out=None, stats=None, walks=0):
     """Training from a knowledge graph alone: every step samples its negatives, finds the paths and trains, all on the device.
     positives [n, 2] = (user, item) entity ids (KnowledgeGraph.interactions); sampler: an _ffi.Sampler (None: the positives' distinct items, uniform).
     Each epoch e shuffles the positives with np.random.RandomState(seed + e) and walks them `minibatch` at a time; a step is
     Engine.find_training_paths (seed, draw = the global step number) -> train_step -> free.  A minibatch in which no pair has a path is skipped and counted.
+    walks > 0: max_hops may be 4 or 5, the hops past 3 sampled by `walks` walks per pair and hop count under the same seed and draw.
     Losses are summed on the device (option "loss_accumulate"); the epoch lines and hooks (OptimizerCallback) are MyOptimizer's.
     -> the epochs' average losses; stats (a dict, optional) receives steps / skipped / pairs."""
     out = sys.stdout if out is None else out
@@ -176,7 +182,8 @@ def train_from_graph(eng, kg, positives, opt, minibatch, n_neg, num_epochs, seed
             total, batches, processed, since = 0.0, 0, 0, 0
             for k in range(0, len(pos), int(minibatch)):
                 mb = pos[order[k:k + int(minibatch)]]
-                batch, _, counts, _ = eng.find_training_paths(graph, sampler, mb, n_neg, seed, draw, min_hops, max_hops, max_paths, T, max_attempts=max_attempts)
+                batch, _, counts, _ = eng.find_training_paths(graph, sampler, mb, n_neg, seed, draw, min_hops, max_hops, max_paths, T, max_attempts=max_attempts,
+                                                              walks=walks)
                 draw += 1
                 if batch is None:
                     st["skipped"] += 1

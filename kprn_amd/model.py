@@ -55,7 +55,19 @@ def flag_parser():
     a("-negatives", type=int, default=4); a("-neg_alpha", type=float, default=0.0, help="negatives are drawn with weight (item's interactions)^neg_alpha; 0 = uniform")
     a("-neg_attempts", type=int, default=16); a("-min_hops", type=int, default=2); a("-max_hops", type=int, default=3); a("-max_paths", type=int, default=28)
     a("-sampleSeed", type=int, default=1)
+    a("-walks", type=int, default=0, help="walks per pair and hop count that sample the paths of 4 and 5 hops (1..256); needed when -max_hops is above 3")
     return p
+
+
+def check_walks(max_hops, walks, error):
+    """the finder's sampling limits, decided on the host before an engine exists: error(message) for a -max_hops above 3 without -walks"""
+    if max_hops > _ffi.FIND_MAX_HOPS_SAMPLED:
+        error("-max_hops must be at most %d" % _ffi.FIND_MAX_HOPS_SAMPLED)
+    if max_hops > _ffi.FIND_MAX_HOPS and not 1 <= walks <= _ffi.FIND_MAX_WALKS:
+        error("-max_hops %d needs -walks N (1..%d): paths of more than %d hops are sampled, N walks per pair and hop count"
+              % (max_hops, _ffi.FIND_MAX_WALKS, _ffi.FIND_MAX_HOPS))
+    if walks < 0 or walks > _ffi.FIND_MAX_WALKS:
+        error("-walks must be in 0..%d" % _ffi.FIND_MAX_WALKS)
 
 
 def parse_flags(argv=None):
@@ -63,6 +75,7 @@ def parse_flags(argv=None):
     params = p.parse_args(argv)
     if params.kg and not (params.vocab_dir and params.interaction_rel):
         p.error("-kg needs -vocab_dir DIR (the vocabulary files) and -interaction_rel NAME (the relation of the user-item edges to train on)")
+    check_walks(params.max_hops, params.walks, p.error)
     return params
 
 

@@ -8,6 +8,7 @@ model flag -K here, because -k is the number of items to return), plus
   -user U  -items FILE the user's entity name; candidate item names, one per line
   -k K                 items to return;  -explain_paths M  strongest paths printed per item
   -min_hops / -max_hops / -max_paths   the finder's limits (1, 3, 28)
+  -walks N [-sampleSeed 1]             -max_hops 4 or 5: the paths of more than 3 hops are sampled, N walks (1..256) per item and hop count
 Output, tab separated: one line `rank, item, %.5f score, paths kept, paths found` per item, then one line `rank, place, %.5f weight, %.6g score, path`
 per explained path (the path as scoring.format_path prints it)."""
 import argparse
@@ -24,7 +25,9 @@ def main(argv=None, out=sys.stdout):
     p.add_argument("-user", required=True); p.add_argument("-items", required=True)
     p.add_argument("-k", type=int, default=10); p.add_argument("-explain_paths", type=int, default=3)
     p.add_argument("-min_hops", type=int, default=1); p.add_argument("-max_hops", type=int, default=3); p.add_argument("-max_paths", type=int, default=28)
+    p.add_argument("-walks", type=int, default=0)
     args, rest = p.parse_known_args(argv)
+    model.check_walks(args.max_hops, args.walks, p.error)
     if not 1 <= args.explain_paths <= 32:
         sys.exit("-explain_paths must be in 1..32")
     if not 1 <= args.k <= 64:
@@ -40,7 +43,7 @@ def main(argv=None, out=sys.stdout):
     eng = model.build_engine(params)
     try:
         res = graph.recommend(eng, kg, kg.entity_id(args.user), [kg.entity_id(n) for n in names], args.k, args.explain_paths, args.min_hops, args.max_hops,
-                              args.max_paths)
+                              args.max_paths, walks=args.walks, seed=params.sampleSeed)
     finally:
         eng.close()
     for r in res:
