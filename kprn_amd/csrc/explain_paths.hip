@@ -151,7 +151,7 @@ __global__ __launch_bounds__(256) void k_explain_wave(Args a) {
     if (lane == 0) { idx[r] = bi; score[r] = best; weight[r] = place_weight(a.reducer, kk, r, best, m, sum); }
     lv = best; li = bi;
   }
-  if (a.pooled || a.prob) {   // (a rectangular batch pools every pair in reduce_col's order, whatever its P: k_pool_sel)
+  if (a.pooled || a.prob) {   // (a rectangular batch pools every pair in reduce_col's order, whatever its P: k_pool<false, ..>)
     const float y = a.seg_wave ? reduce_col_wave(s, cnt, C, a.reducer, a.K, lane) : reduce_col(s, cnt, C, a.reducer, a.K);
     if (lane == 0) emit_pooled(a, i, y);
   }

@@ -4,7 +4,7 @@
 #include <string.h>
 #include "kprn_internal.h"
 #include "adam_rows_dev.h"
-#include "reduce_dev.h"
+#include "reduce_dev.h"   // (sigmoidf_: the gate kernels)
 
 namespace {
 
@@ -307,356 +307,8 @@ __global__ void k_gru_bwd2(const float* __restrict__ a, const float* __restrict_
   dH[i] = dHdir[i] + drh * r;
 }
 
-
-// + nn.Select(2, classId) (MyOptimizer.lua:126 / test_from_checkpoint.lua:82): sel[b] = probs[b][cid]
-__global__ void k_pool(const float* __restrict__ S, int B, int P, int C, int reducer, int K, float* __restrict__ pooled, float* __restrict__ probs,
-                       int cid, float* __restrict__ sel, float* __restrict__ sel_host) {
-  int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (gid >= (int64_t)B * C) return;
-  int c = (int)(gid % C);
-  int64_t b = gid / C;
-  float y = reduce_col(S + b * P * C + c, P, C, reducer, K);
-  float pr = sigmoidf_(y);
-  pooled[gid] = y;
-  probs[gid] = pr;
-  if (sel && c == cid) sel[b] = pr;
-  if (sel_host && c == cid) sel_host[b] = pr;   // page-locked mirror (kprn_forward_batch hands the probabilities out without a copy operation)
-}
-
-// nn.Select(2, classId) first: only the selected class is reduced (what model:forward hands the caller, test_from_checkpoint.lua:82)
-__global__ void k_pool_sel(const float* __restrict__ S, int B, int P, int C, int reducer, int K, int cid, float* __restrict__ sel, float* __restrict__ sel_host) {
-  const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= B) return;
-  const float pr = sigmoidf_(reduce_col(S + (int64_t)b * P * C + cid, P, C, reducer, K));
-  sel[b] = pr;
-  if (sel_host) sel_host[b] = pr;
-}
-
 // ---------------------------------------------------------------------------------------
-// The whole loss stage of a training step in one launch:
-//   A  reducer over the P paths + nn.Sigmoid + nn.Select for every class          (OneModel.lua:284-294, MyOptimizer.lua:126)
-//   B  nn.BCECriterion forward / backward on column classId, back through sigmoid and reducer -> dS[n]   (MyOptimizer.lua:193-195)
-//   C  nn.Linear(H,46) backward restricted to that column: gW[cid][:] += sum_n dS[n] hT[n][:], gb[cid] += sum_n dS[n]
-//   D  loss = fixed-order sum of the per-pair terms: per-workgroup partials, summed in index order by the last workgroup
-// (was five launches: pool, select, bce, sum, head_bwd).  One workgroup = LOSS_PPW pairs.  hT may be null (generic pipeline: its own head backward).
-// d[q] = d loss / d s[q]; slot (nullable): the pair's q-th gradient goes to dS[slot[q]] instead (fused path: tile slot of the path)
-__device__ float bce_pair(const float* __restrict__ s, int P, int C, int reducer, int K, int literal, float invB, float t, float* __restrict__ dpair,
-                          float* __restrict__ dS, const int32_t* __restrict__ slot, float* lossterm) {
-  auto d = [&](int q) -> float& { return slot ? dS[slot[q]] : dpair[q]; };
-  const float eps = 1e-12f;
-  const float y = reduce_col(s, P, C, reducer, K);
-  const float p = sigmoidf_(y);
-  *lossterm = -(t * logf(p + eps) + (1.f - t) * logf(1.f - p + eps)) * invB;
-  float dy;
-  if (literal) {
-    float dp = -(t - p) / ((1.f - p + eps) * (p + eps)) * invB;
-    dy = dp * p * (1.f - p);
-  } else {
-    dy = (p - t) * invB;
-  }
-  if (reducer == 2) {
-    float m = s[0];
-    for (int q = 1; q < P; ++q) m = fmaxf(m, s[(int64_t)q * C]);
-    float sum = 0.f;
-    for (int q = 0; q < P; ++q) sum += expf(s[(int64_t)q * C] - m);
-    for (int q = 0; q < P; ++q) d(q) = expf(s[(int64_t)q * C] - m) / sum * dy;
-  } else if (reducer == 0) {
-    int arg = 0;
-    for (int q = 1; q < P; ++q) if (s[(int64_t)q * C] > s[(int64_t)arg * C]) arg = q;
-    for (int q = 0; q < P; ++q) d(q) = (q == arg) ? dy : 0.f;
-  } else {
-    int kk = K < P ? K : P;
-    for (int q = 0; q < P; ++q) d(q) = 0.f;
-    float last_v = INFINITY; int last_i = -1;
-    for (int r = 0; r < kk; ++r) {
-      float best = -INFINITY; int bi = -1;
-      for (int q = 0; q < P; ++q) {
-        float v = s[(int64_t)q * C];
-        bool after = (v < last_v) || (v == last_v && q > last_i);
-        if (after && (bi < 0 || v > best)) { best = v; bi = q; }
-      }
-      d(bi) = dy / (float)kk; last_v = best; last_i = bi;
-    }
-  }
-  return p;
-}
-
-constexpr int LOSS_PPW = 16;  // pairs per workgroup of the loss stage: small on purpose (latency-bound: many workgroups in flight)
-static_assert(LOSS_PPW == kk::RAGGED_WG_PAIRS && kk::RAGGED_WG_PATHS == LOSS_PPW * kk::RAGGED_THREAD_MAX, "the ragged cut restates the rectangular one");
-__global__ __launch_bounds__(256) void k_loss_stage(const float* __restrict__ S, const float* __restrict__ labels, const float* __restrict__ hT,
-                                                    int B, int P, int C, int H, int cid, int reducer, int K, int literal, float invB,
-                                                    float* __restrict__ pooled, float* __restrict__ probs, float* __restrict__ sel,
-                                                    float* __restrict__ dS, const int32_t* __restrict__ slot_of, float* __restrict__ gW_row,
-                                                    float* __restrict__ gb_c, float* __restrict__ partial, int n_loss_blocks, kk::TransposeJob tj, float* __restrict__ partial_host,
-                                                    kk::PoolJob pj) {
-  if ((int)blockIdx.x >= n_loss_blocks + 64 * tj.n) {  // (workgroup-uniform) passenger: the pooling stage of a scoring pass (k_pool_sel's arithmetic)
-    const int b = ((int)blockIdx.x - n_loss_blocks - 64 * tj.n) * 256 + (int)threadIdx.x;
-    if (b >= pj.B) return;
-    const float pr = sigmoidf_(reduce_col(pj.S + (int64_t)b * pj.P * C + pj.cid, pj.P, C, reducer, K));
-    pj.sel[b] = pr;
-    if (pj.sel_host) pj.sel_host[b] = pr;
-    return;
-  }
-  if ((int)blockIdx.x >= n_loss_blocks) {  // (workgroup-uniform) the passenger job: 256x64 weight transposes
-    const int rb = blockIdx.x - n_loss_blocks;
-    const int m = rb >> 6, i = (rb & 63) * 256 + threadIdx.x;  // over the 64*256 outputs of matrix m
-    tj.WT[m][i] = tj.W[m][(i & 255) * 64 + (i >> 8)];
-    return;
-  }
-  __shared__ float lossw[LOSS_PPW];
-  __shared__ float red[4][65];
-  const int tid = threadIdx.x;
-  const int b0 = blockIdx.x * LOSS_PPW;
-  const int nb = (B - b0 < LOSS_PPW) ? (B - b0) : LOSS_PPW;
-  // A (only when the caller wants every class: training needs column classId alone, which B computes)
-  if (pooled) for (int i = tid; i < nb * C; i += 256) {
-    const int b = b0 + i / C, c = i % C;
-    const float y = reduce_col(S + (int64_t)b * P * C + c, P, C, reducer, K);
-    const float pr = sigmoidf_(y);
-    pooled[(int64_t)b * C + c] = y;
-    probs[(int64_t)b * C + c] = pr;
-    if (c == cid) sel[b] = pr;
-  }
-  // B
-  if (tid < LOSS_PPW) {
-    float lt = 0.f;
-    if (tid < nb) {
-      const int b = b0 + tid;
-      const float pr = bce_pair(S + (int64_t)b * P * C + cid, P, C, reducer, K, literal, invB, labels[b], dS + (int64_t)b * P, dS,
-                                slot_of ? slot_of + (int64_t)b * P : nullptr, &lt);
-      if (!pooled) sel[b] = pr;
-    }
-    lossw[tid] = lt;
-  }
-  __syncthreads();  // this workgroup's dS rows are visible to it
-  // C
-  if (hT) {
-    const int64_t n0 = (int64_t)b0 * P, n1 = n0 + (int64_t)nb * P;
-    const int sub = tid >> 6, col = tid & 63;
-    for (int c0 = 0; c0 < H; c0 += 64) {
-      const int cc = c0 + col;
-      float acc = 0.f, sd = 0.f;
-      for (int64_t n = n0 + sub; n < n1; n += 4) {
-        const float d = dS[n];
-        sd += d;
-        if (cc < H) acc += d * hT[n * H + cc];
-      }
-      red[sub][col] = acc;
-      if (col == 0) red[sub][64] = sd;
-      __syncthreads();
-      if (sub == 0) {
-        if (cc < H) unsafeAtomicAdd(gW_row + cc, (red[0][col] + red[1][col]) + (red[2][col] + red[3][col]));
-        if (col == 0 && c0 == 0) unsafeAtomicAdd(gb_c, (red[0][64] + red[1][64]) + (red[2][64] + red[3][64]));
-      }
-      __syncthreads();
-    }
-  }
-  // D: per-workgroup partial, summed in index order by k_sum_partials when the loss is asked for (a last-workgroup
-  //    reduction here needs a device-scope release per workgroup = an L2 write-back each: measured 30 us)
-  if (tid == 0) {
-    float s = 0.f;
-    for (int i = 0; i < LOSS_PPW; ++i) s += lossw[i];
-    partial[blockIdx.x] = s;
-    if (partial_host) partial_host[blockIdx.x] = s;   // page-locked mirror: the host adds the partials itself (kprn_train_step's early loss)
-  }
-}
-
-// ---------------------------------------------------------------------------------------
-// Ragged batches (an extension; the reference has one path count per batch): pair b owns the paths off[b] .. off[b+1]-1 of the flat score
-// matrix.  Two ways to reduce a pair, chosen once per batch (kk::Segs::wave): a thread per pair -- reduce_col / bce_pair, the rectangular
-// kernels' arithmetic -- when no pair is longer than RAGGED_THREAD_MAX, else a wave per pair: lanes stride the segment, then a butterfly over the
-// 64 lanes (every lane ends with the same bits, so no broadcast and no LDS).  In the wave form a pair of at most RAGGED_THREAD_MAX paths still
-// takes reduce_col's order (all lanes read the same addresses), so equal short counts give the rectangular batch's bits either way.
-// bce_pair by one wave (cnt > RAGGED_THREAD_MAX).  Path q's gradient is written by lane q % 64 only, so the TopK form's zero-then-set is one
-// thread's program order.
-__device__ float bce_pair_wave(const float* __restrict__ s, int cnt, int C, int reducer, int K, int literal, float invB, float t, float* __restrict__ dpair,
-                               float* __restrict__ dS, const int32_t* __restrict__ slot, float* lossterm, int lane) {
-  auto d = [&](int q) -> float& { return slot ? dS[slot[q]] : dpair[q]; };
-  const float eps = 1e-12f;
-  const float y = reduce_col_wave(s, cnt, C, reducer, K, lane);
-  const float p = sigmoidf_(y);
-  *lossterm = -(t * logf(p + eps) + (1.f - t) * logf(1.f - p + eps)) * invB;
-  float dy;
-  if (literal) {
-    float dp = -(t - p) / ((1.f - p + eps) * (p + eps)) * invB;
-    dy = dp * p * (1.f - p);
-  } else {
-    dy = (p - t) * invB;
-  }
-  if (reducer == 2) {
-    float m = -INFINITY;
-    for (int q = lane; q < cnt; q += 64) m = fmaxf(m, s[(int64_t)q * C]);
-    m = wave_all_max(m);
-    float sum = 0.f;
-    for (int q = lane; q < cnt; q += 64) sum += expf(s[(int64_t)q * C] - m);
-    sum = wave_all_sum(sum);
-    for (int q = lane; q < cnt; q += 64) d(q) = expf(s[(int64_t)q * C] - m) / sum * dy;
-  } else if (reducer == 0) {
-    float best; int arg;
-    lane_best(s, cnt, C, lane, INFINITY, -1, best, arg);
-    wave_all_best(best, arg);
-    for (int q = lane; q < cnt; q += 64) d(q) = (q == arg) ? dy : 0.f;
-  } else {
-    const int kk = K < cnt ? K : cnt;
-    for (int q = lane; q < cnt; q += 64) d(q) = 0.f;
-    float last_v = INFINITY; int last_i = -1;
-    for (int r = 0; r < kk; ++r) {
-      float best; int bi;
-      lane_best(s, cnt, C, lane, last_v, last_i, best, bi);
-      wave_all_best(best, bi);
-      if ((bi & 63) == lane) d(bi) = dy / (float)kk;
-      last_v = best; last_i = bi;
-    }
-  }
-  return p;
-}
-
-// k_pool / k_pool_sel for a ragged batch.  pooled == null: the selected class only.  Thread form: one thread per (pair, class); wave form: one
-// wave per (pair, class), four to a workgroup.
-__global__ __launch_bounds__(256) void k_pool_ragged(const float* __restrict__ S, kk::Segs g, int C, int reducer, int K, float* __restrict__ pooled,
-                                                     float* __restrict__ probs, int cid, float* __restrict__ sel, float* __restrict__ sel_host) {
-  const int lane = threadIdx.x & 63;
-  const int64_t item = g.wave ? (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6) : (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const int64_t n_items = pooled ? (int64_t)g.B * C : (int64_t)g.B;
-  if (item >= n_items) return;   // (wave form: the whole wave leaves)
-  const int b = pooled ? (int)(item / C) : (int)item;
-  const int c = pooled ? (int)(item % C) : cid;
-  const float y = reduce_seg(S + seg_begin(g.off, g.P, b) * C + c, seg_count(g.off, g.P, b), C, reducer, K, g.wave, lane);
-  const float pr = sigmoidf_(y);
-  if (g.wave && lane != 0) return;
-  if (pooled) { pooled[item] = y; probs[item] = pr; }
-  if (c == cid) {
-    if (sel) sel[b] = pr;
-    if (sel_host) sel_host[b] = pr;
-  }
-}
-
-// k_loss_stage for a ragged batch (or a rectangular one that carries a ragged passenger, or the reverse: off == null means P paths per pair).
-// Workgroup w owns the pairs wg[w] .. wg[w+1]-1: at most LOSS_PPW of them and at most RAGGED_WG_PATHS paths unless it is a single longer pair
-// (kk::ragged_plan), which bounds the head backward loop C.  Stages as in k_loss_stage.
-__global__ __launch_bounds__(256) void k_loss_stage_ragged(const float* __restrict__ S, const float* __restrict__ labels, const float* __restrict__ hT,
-                                                           kk::Segs g, int C, int H, int cid, int reducer, int K, int literal, float invB,
-                                                           float* __restrict__ pooled, float* __restrict__ probs, float* __restrict__ sel,
-                                                           float* __restrict__ dS, const int32_t* __restrict__ slot_of, float* __restrict__ gW_row,
-                                                           float* __restrict__ gb_c, float* __restrict__ partial, int n_loss_blocks, kk::TransposeJob tj,
-                                                           float* __restrict__ partial_host, kk::PoolJob pj) {
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  if ((int)blockIdx.x >= n_loss_blocks + 64 * tj.n) {  // (workgroup-uniform) passenger: the pooling stage of a scoring pass
-    const int rb = (int)blockIdx.x - n_loss_blocks - 64 * tj.n;
-    const int b = pj.wave ? rb * 4 + wv : rb * 256 + tid;
-    if (b >= pj.B) return;
-    const float pr = sigmoidf_(reduce_seg(pj.S + seg_begin(pj.off, pj.P, b) * C + pj.cid, seg_count(pj.off, pj.P, b), C, reducer, K, pj.wave, lane));
-    if (pj.wave && lane != 0) return;
-    pj.sel[b] = pr;
-    if (pj.sel_host) pj.sel_host[b] = pr;
-    return;
-  }
-  if ((int)blockIdx.x >= n_loss_blocks) {  // (workgroup-uniform) the passenger job: 256x64 weight transposes
-    const int rb = blockIdx.x - n_loss_blocks;
-    const int m = rb >> 6, i = (rb & 63) * 256 + threadIdx.x;
-    tj.WT[m][i] = tj.W[m][(i & 255) * 64 + (i >> 8)];
-    return;
-  }
-  __shared__ float lossw[LOSS_PPW];
-  __shared__ float red[4][65];
-  const int b0 = g.wg ? g.wg[blockIdx.x] : (int)blockIdx.x * LOSS_PPW;
-  const int nb = g.wg ? g.wg[blockIdx.x + 1] - b0 : ((g.B - b0 < LOSS_PPW) ? (g.B - b0) : LOSS_PPW);
-  // A
-  if (pooled) {
-    const int step = g.wave ? 4 : 256;
-    for (int i = g.wave ? wv : tid; i < nb * C; i += step) {
-      const int b = b0 + i / C, c = i % C;
-      const float y = reduce_seg(S + seg_begin(g.off, g.P, b) * C + c, seg_count(g.off, g.P, b), C, reducer, K, g.wave, lane);
-      const float pr = sigmoidf_(y);
-      if (!g.wave || lane == 0) {
-        pooled[(int64_t)b * C + c] = y;
-        probs[(int64_t)b * C + c] = pr;
-        if (c == cid) sel[b] = pr;
-      }
-    }
-  }
-  // B
-  if (tid < LOSS_PPW) lossw[tid] = 0.f;
-  __syncthreads();
-  if (!g.wave) {
-    if (tid < nb) {
-      const int b = b0 + tid;
-      const int64_t n0 = seg_begin(g.off, g.P, b);
-      float lt = 0.f;
-      const float pr = bce_pair(S + n0 * C + cid, seg_count(g.off, g.P, b), C, reducer, K, literal, invB, labels[b], dS + n0, dS,
-                                slot_of ? slot_of + n0 : nullptr, &lt);
-      if (!pooled) sel[b] = pr;
-      lossw[tid] = lt;
-    }
-  } else {
-    for (int i = wv; i < nb; i += 4) {   // (wave-uniform)
-      const int b = b0 + i;
-      const int64_t n0 = seg_begin(g.off, g.P, b);
-      const int cnt = seg_count(g.off, g.P, b);
-      float lt = 0.f, pr = 0.f;
-      if (cnt > kk::RAGGED_THREAD_MAX) {
-        pr = bce_pair_wave(S + n0 * C + cid, cnt, C, reducer, K, literal, invB, labels[b], dS + n0, dS, slot_of ? slot_of + n0 : nullptr, &lt, lane);
-      } else if (lane == 0) {
-        pr = bce_pair(S + n0 * C + cid, cnt, C, reducer, K, literal, invB, labels[b], dS + n0, dS, slot_of ? slot_of + n0 : nullptr, &lt);
-      }
-      if (lane == 0) {
-        if (!pooled) sel[b] = pr;
-        lossw[i] = lt;
-      }
-    }
-  }
-  __syncthreads();  // this workgroup's dS rows are visible to it
-  // C
-  if (hT) {
-    const int64_t n0 = seg_begin(g.off, g.P, b0), n1 = seg_begin(g.off, g.P, b0 + nb - 1) + seg_count(g.off, g.P, b0 + nb - 1);
-    const int sub = tid >> 6, col = tid & 63;
-    for (int c0 = 0; c0 < H; c0 += 64) {
-      const int cc = c0 + col;
-      float acc = 0.f, sd = 0.f;
-      for (int64_t n = n0 + sub; n < n1; n += 4) {
-        const float d = dS[n];
-        sd += d;
-        if (cc < H) acc += d * hT[n * H + cc];
-      }
-      red[sub][col] = acc;
-      if (col == 0) red[sub][64] = sd;
-      __syncthreads();
-      if (sub == 0) {
-        if (cc < H) unsafeAtomicAdd(gW_row + cc, (red[0][col] + red[1][col]) + (red[2][col] + red[3][col]));
-        if (col == 0 && c0 == 0) unsafeAtomicAdd(gb_c, (red[0][64] + red[1][64]) + (red[2][64] + red[3][64]));
-      }
-      __syncthreads();
-    }
-  }
-  // D: the per-workgroup partial, pairs in index order (k_sum_partials adds the partials in index order)
-  if (tid == 0) {
-    float s = 0.f;
-    for (int i = 0; i < LOSS_PPW; ++i) s += lossw[i];
-    partial[blockIdx.x] = s;
-    if (partial_host) partial_host[blockIdx.x] = s;
-  }
-}
-
-// loss = fixed-order sum of the per-workgroup partials (reproducible)
-__global__ void k_sum_partials(const float* __restrict__ partial, int n, float* __restrict__ out, int accumulate) {
-  __shared__ float pl[256];
-  float s = 0.f;
-  for (int base = 0; base < n; base += 256) {
-    const int i = base + (int)threadIdx.x;
-    pl[threadIdx.x] = (i < n) ? partial[i] : 0.f;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      const int m = (n - base < 256) ? (n - base) : 256;
-      for (int k = 0; k < m; ++k) s += pl[k];
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    out[0] = s;
-    if (accumulate) { out[1] += s; out[2] += 1.0f; }   // running sum / count of the losses since the last kprn_read_loss_sum
-  }
-}
-
+// (pooling and the loss stage: loss_stage.hip)
 // nn.Linear(H,46) backward restricted to the selected column (OneModel.lua:275; Select at MyOptimizer.lua:126)
 // DET (option "deterministic" = "2"; instantiations of their own, here and in k_head_bwd_w): the workgroup's H sums and its bias sum leave with plain stores in
 // row blockIdx.x of gWout = slab [gridDim.x][H + 1] (gbout unused); kk::slab_join adds the rows in workgroup order
@@ -1231,89 +883,6 @@ void col_sum_add(hipStream_t s, const float* A, int64_t rows, int cols, float* o
   CHECK_LAUNCH();
 }
 
-void pool_sigmoid(hipStream_t s, const float* S, int B, int P, int C, int reducer, int K, float* pooled, float* probs, int cid, float* sel, float* sel_host) {
-  if (B <= 0) return;
-  if (!pooled) hipLaunchKernelGGL(k_pool_sel, dim3(nblocks((int64_t)B)), dim3(TPB), 0, s, S, B, P, C, reducer, K, cid, sel, sel_host);
-  else hipLaunchKernelGGL(k_pool, dim3(nblocks((int64_t)B * C)), dim3(TPB), 0, s, S, B, P, C, reducer, K, pooled, probs, cid, sel, sel_host);
-  CHECK_LAUNCH();
-}
-
-void loss_stage(hipStream_t s, const float* S, const float* labels, const float* hT, int B, int P, int C, int H, int cid, int reducer, int K,
-                int literal, float invB, float* pooled, float* probs, float* sel, float* dS, const int32_t* slot_of, float* gW_row, float* gb_c,
-                float* partial, const TransposeJob* tj, float* partial_host, const PoolJob* pj) {
-  if (B <= 0) return;
-  TransposeJob t;
-  memset(&t, 0, sizeof(t));
-  if (tj) t = *tj;
-  PoolJob pjob;
-  memset(&pjob, 0, sizeof(pjob));
-  if (pj) pjob = *pj;
-  const int nlb = (B + LOSS_PPW - 1) / LOSS_PPW;
-  const int npb = (pjob.B + 255) / 256;
-  hipLaunchKernelGGL(k_loss_stage, dim3((unsigned)(nlb + 64 * t.n + npb)), dim3(256), 0, s, S, labels, hT, B, P, C, H, cid, reducer, K, literal, invB,
-                     pooled, probs, sel, dS, slot_of, gW_row, gb_c, partial, nlb, t, partial_host, pjob);
-  CHECK_LAUNCH();
-}
-
-int loss_partials(int B) { return (B + LOSS_PPW - 1) / LOSS_PPW; }
-
-void pool_sigmoid_ragged(hipStream_t s, const float* S, const Segs& g, int C, int reducer, int K, float* pooled, float* probs, int cid, float* sel, float* sel_host) {
-  if (g.B <= 0) return;
-  const int64_t items = pooled ? (int64_t)g.B * C : (int64_t)g.B;
-  hipLaunchKernelGGL(k_pool_ragged, dim3(nblocks(items, g.wave ? 4 : 256)), dim3(256), 0, s, S, g, C, reducer, K, pooled, probs, cid, sel, sel_host);
-  CHECK_LAUNCH();
-}
-
-int loss_stage_ragged(hipStream_t s, const float* S, const float* labels, const float* hT, const Segs& g, int C, int H, int cid, int reducer, int K,
-                      int literal, float invB, float* pooled, float* probs, float* sel, float* dS, const int32_t* slot_of, float* gW_row, float* gb_c,
-                      float* partial, const TransposeJob* tj, float* partial_host, const PoolJob* pj) {
-  if (g.B <= 0) return 0;
-  TransposeJob t;
-  memset(&t, 0, sizeof(t));
-  if (tj) t = *tj;
-  PoolJob pjob;
-  memset(&pjob, 0, sizeof(pjob));
-  if (pj) pjob = *pj;
-  const int nlb = g.wg ? g.n_wg : (g.B + LOSS_PPW - 1) / LOSS_PPW;
-  const int npb = pjob.wave ? (pjob.B + 3) / 4 : (pjob.B + 255) / 256;
-  hipLaunchKernelGGL(k_loss_stage_ragged, dim3((unsigned)(nlb + 64 * t.n + npb)), dim3(256), 0, s, S, labels, hT, g, C, H, cid, reducer, K, literal, invB,
-                     pooled, probs, sel, dS, slot_of, gW_row, gb_c, partial, nlb, t, partial_host, pjob);
-  CHECK_LAUNCH();
-  return nlb;
-}
-
-// Offsets, loss-stage workgroup table and the reducer form of a ragged batch (no device, no handle: kprn_host_ragged_plan).  A workgroup takes
-// consecutive pairs while it holds fewer than LOSS_PPW pairs and the next pair keeps it within RAGGED_WG_PATHS paths; a pair longer than that
-// is a workgroup of its own.  Equal counts <= 28 therefore cut as the rectangular loss stage does (LOSS_PPW pairs each).
-bool ragged_plan(const int32_t* counts, int32_t B, int64_t N, int32_t* off, int32_t* wg, int32_t* summary) {
-  if (!counts || B <= 0 || N < B || N > 0x7fffffffLL || !off || !wg || !summary) return false;
-  int64_t o = 0;
-  int32_t mx = 0, nw = 0, wpairs = 0;
-  int64_t wpaths = 0;
-  for (int32_t b = 0; b < B; ++b) {
-    const int32_t c = counts[b];
-    if (c < 1 || c > RAGGED_MAX_SEG) return false;
-    if (wpairs == 0 || wpairs == LOSS_PPW || wpaths + c > RAGGED_WG_PATHS) { wg[nw++] = b; wpairs = 0; wpaths = 0; }
-    ++wpairs; wpaths += c;
-    off[b] = (int32_t)o;
-    o += c;
-    if (o > N) return false;
-    if (c > mx) mx = c;
-  }
-  if (o != N) return false;
-  off[B] = (int32_t)o;
-  wg[nw] = B;
-  summary[0] = nw; summary[1] = mx; summary[2] = mx > RAGGED_THREAD_MAX ? 1 : 0;
-  return true;
-}
-
-void sum_partials(hipStream_t s, const float* partial, int n, float* out, int accumulate) {
-  hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, s, partial, n, out, accumulate);
-  CHECK_LAUNCH();
-}
-
-
-
 void head_bwd(hipStream_t s, const float* dS, const float* hT, const float* Wout, int64_t N, int H, int cid, float* dH, float* gWout, float* gbout, DetScratch* det) {
   if (N <= 0) return;
   if (det) {   // the same two kernels' det forms (same grids, same sums inside a workgroup), slab [workgroup][H + 1], then the join: the row, then the bias
@@ -1754,8 +1323,8 @@ void sumsq_rows(hipStream_t s, const float* G, const int32_t* rows, const int32_
 void sumsq_det(hipStream_t s, const float* x, int64_t n, const float* G, const int32_t* rows, const int32_t* count, int d, float* partial, float* out) {
   const int nb = SUMSQ_DET_BLOCKS / 2;
   hipLaunchKernelGGL(k_sumsq_det, dim3(2 * nb), dim3(256), 0, s, x, n, G, rows, count, d, nb, partial);
-  hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, s, partial, 2 * nb, out, 0);
   CHECK_LAUNCH();
+  sum_partials(s, partial, 2 * nb, out, 0);
 }
 
 static AdamDenseJob dense_job(float* x, float* g, float* m, float* v, int64_t n, float step, float b1, float b2, float eps,

@@ -237,12 +237,8 @@ void pool_stage(kprn_handle* h, const kprn_batch* b, int cid, bool every_class) 
   const kprn_config& c = h->cfg;
   Workspace& w = h->ws;
   ProfScope ps(h, "pool_sigmoid");
-  if (b->off) {
-    const kk::Segs g{b->B, 0, b->off, b->wg, b->n_wg, b->seg_wave};
-    kk::pool_sigmoid_ragged(h->stream, w.S, g, c.C, c.reducer, c.K, every_class ? w.pooled : nullptr, every_class ? w.probs : nullptr, cid, w.sel, h->sel_host_armed);
-    return;
-  }
-  kk::pool_sigmoid(h->stream, w.S, b->B, b->P, c.C, c.reducer, c.K, every_class ? w.pooled : nullptr, every_class ? w.probs : nullptr, cid, w.sel, h->sel_host_armed);
+  const kk::Segs g{b->B, b->P, b->off, b->wg, b->n_wg, b->seg_wave};
+  kk::pool_sigmoid(h->stream, w.S, g, c.C, c.reducer, c.K, every_class ? w.pooled : nullptr, every_class ? w.probs : nullptr, cid, w.sel, h->sel_host_armed);
 }
 
 void check_batch(kprn_handle* h, const kprn_batch* b, int class_id) {
@@ -405,7 +401,6 @@ static void backward_impl(kprn_handle* h, const kprn_batch* b, int class_id, int
     // pooling + sigmoid + select + BCE + reducer backward in one launch (the nn.Linear head's weight gradient is formed by the
     // top layer's backward kernel, fused path, or by the generic pipeline's own head backward)
     ProfScope ps(h, "loss_stage");
-    float* gd = h->g_dense;
     kk::TransposeJob tj;  // fused path: the backward's W^T copies, stale after an update, are rebuilt by passenger workgroups
     const bool have_tj = fusedp && fused::transpose_job(h, &tj);
     kk::PoolJob pj{h->S2, 0, 0, 0, h->sel2, nullptr};
@@ -413,18 +408,9 @@ static void backward_impl(kprn_handle* h, const kprn_batch* b, int class_id, int
       const kprn_batch* sb = h->pool_defer_batch;
       pj.B = sb->B; pj.P = sb->P; pj.off = sb->off; pj.wave = sb->seg_wave; pj.cid = h->pool_defer_cid; h->pool_defer_batch = nullptr;
     }
-    if (b->off || pj.off) {   // a ragged batch, or a ragged passenger: the segmented loss stage (a rectangular batch launches what it always did)
-      const kk::Segs g{b->B, b->P, b->off, b->wg, b->n_wg, b->seg_wave};
-      h->loss_pending = kk::loss_stage_ragged(h->stream, h->score_buf, b->labels, /*hT=*/nullptr, g, c.C, c.H, cid, c.reducer, c.K, literal, invB, /*pooled=*/nullptr,
-                                              /*probs=*/nullptr, w.sel, w.dS, fusedp ? b->slot_of : nullptr, gd + h->off_outW + (int64_t)cid * c.H,
-                                              gd + h->off_outb + cid, h->loss_partial, have_tj ? &tj : nullptr,
-                                              h->loss_early_armed ? h->loss_mirror : nullptr, pj.B > 0 ? &pj : nullptr);
-    } else {
-      kk::loss_stage(h->stream, h->score_buf, b->labels, /*hT=*/nullptr, b->B, b->P, c.C, c.H, cid, c.reducer, c.K, literal,
-                     invB, /*pooled=*/nullptr, /*probs=*/nullptr, w.sel, w.dS, fusedp ? b->slot_of : nullptr, gd + h->off_outW + (int64_t)cid * c.H, gd + h->off_outb + cid, h->loss_partial,
-                     have_tj ? &tj : nullptr, h->loss_early_armed ? h->loss_mirror : nullptr, pj.B > 0 ? &pj : nullptr);
-      h->loss_pending = kk::loss_partials(b->B);
-    }
+    const kk::Segs g{b->B, b->P, b->off, b->wg, b->n_wg, b->seg_wave};   // (a ragged batch or a ragged passenger: the launcher takes the segmented form)
+    h->loss_pending = kk::loss_stage(h->stream, h->score_buf, b->labels, g, c.C, cid, c.reducer, c.K, literal, invB, w.sel, w.dS, fusedp ? b->slot_of : nullptr,
+                                     h->loss_partial, have_tj ? &tj : nullptr, h->loss_early_armed ? h->loss_mirror : nullptr, pj.B > 0 ? &pj : nullptr);
     if (h->loss_early_armed) {   // what kprn_train_step_batch waits for instead of the end of the step
       h->loss_early_n = h->loss_pending;
       HIP_TRY(hipEventRecord(h->ev_loss, h->stream));

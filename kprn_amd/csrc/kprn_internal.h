@@ -419,35 +419,30 @@ void gru_gates_fwd(hipStream_t s, float* a, const float* hp, int64_t N, int H);
 void gru_out_fwd(hipStream_t s, float* a, const float* hp, float* h, int64_t N, int H);
 void gru_bwd1(hipStream_t s, const float* a, const float* hp, const float* dH, const float* dH_up, float* dA, float* dHdir, int64_t N, int H);
 void gru_bwd2(hipStream_t s, const float* a, const float* hp, float* dA, const float* dHdir, float* dH, int64_t N, int H);
-void pool_sigmoid(hipStream_t s, const float* S, int B, int P, int C, int reducer, int K, float* pooled, float* probs, int cid, float* sel, float* sel_host = nullptr);
 // A second, independent job the loss-stage launch can carry in extra workgroups: WT[m] = W[m]^T for up to four [256][64]
 // matrices (the fused backward's transposed LSTM weights, stale after every update).
 struct TransposeJob { const float* W[4]; float* WT[4]; int n; };
 // ... and the pooling stage of a scoring pass that ran in the training forward's launch ("score_dual"): reducer + sigmoid + select of ITS batch, as more
 // workgroups of the loss stage's launch (B = 0: none)
 struct PoolJob { const float* S; int B, P, cid; float* sel; float* sel_host; const int32_t* off = nullptr; int wave = 0; };
-// a batch as the reducer sees it: B pairs of P paths each, or (off != null) pair b = paths off[b] .. off[b+1]-1; wg / n_wg: the loss stage's
-// workgroup table of a ragged batch; wave: a wave per pair instead of a thread per pair
+// a batch as the reducer sees it: B pairs of P paths each (rectangular: Segs{B, P, nullptr, nullptr, 0, 0}), or (off != null) pair b = paths
+// off[b] .. off[b+1]-1; wg / n_wg: the loss stage's workgroup table of a ragged batch; wave: a wave per pair instead of a thread per pair
 struct Segs { int B, P; const int32_t* off; const int32_t* wg; int n_wg; int wave; };
-void pool_sigmoid_ragged(hipStream_t s, const float* S, const Segs& g, int C, int reducer, int K, float* pooled, float* probs, int cid, float* sel,
-                         float* sel_host = nullptr);
-// the loss stage when the batch or the passenger pooling job is ragged (either may also be rectangular: off == null); returns the number of partials
-int loss_stage_ragged(hipStream_t s, const float* S, const float* labels, const float* hT, const Segs& g, int C, int H, int cid, int reducer, int K,
-                      int literal, float invB, float* pooled, float* probs, float* sel, float* dS, const int32_t* slot_of, float* gW_row, float* gb_c,
-                      float* partial, const TransposeJob* tj = nullptr, float* partial_host = nullptr, const PoolJob* pj = nullptr);
 // segment limits of a ragged batch (DESIGN.md 'ragged batches')
 constexpr int RAGGED_MAX_SEG = 4096;     // longest pair kprn_host_ragged_plan accepts
 constexpr int RAGGED_THREAD_MAX = 28;    // longest pair a single thread reduces (the reference's largest path count: reduce_col's range)
-constexpr int RAGGED_WG_PAIRS = 16;     // pairs per loss-stage workgroup (= LOSS_PPW of the rectangular loss stage)
+constexpr int RAGGED_WG_PAIRS = 16;      // pairs per loss-stage workgroup, rectangular or ragged
 constexpr int RAGGED_WG_PATHS = 448;     // paths per loss-stage workgroup (16 pairs of 28); a longer pair has a workgroup to itself
 // offsets [B+1], workgroup table wg [<= B+1], summary {n_wg, max_cnt, wave}; false: a count < 1 or > RAGGED_MAX_SEG, or sum != N
 bool ragged_plan(const int32_t* counts, int32_t B, int64_t N, int32_t* off, int32_t* wg, int32_t* summary);
-// (partial_host: optional page-locked mirror of the per-workgroup loss partials)
-void loss_stage(hipStream_t s, const float* S, const float* labels, const float* hT, int B, int P, int C, int H, int cid, int reducer, int K,
-                int literal, float invB, float* pooled, float* probs, float* sel, float* dS, const int32_t* slot_of /*nullable: dS[slot_of[n]]*/,
-                float* gW_row, float* gb_c, float* partial, const TransposeJob* tj = nullptr, float* partial_host = nullptr, const PoolJob* pj = nullptr);
+// loss_stage.hip.  Reducer + sigmoid + select of a scoring pass; pooled / probs null: the selected class only.  The ragged forms launch when g.off is set
+void pool_sigmoid(hipStream_t s, const float* S, const Segs& g, int C, int reducer, int K, float* pooled, float* probs, int cid, float* sel, float* sel_host = nullptr);
+// the loss stage of a training step; the ragged form launches when the batch or the passenger pooling job is ragged.  Returns the number of partials
+// (slot_of nullable: dS[slot_of[n]]; partial_host: optional page-locked mirror of the per-workgroup loss partials)
+int loss_stage(hipStream_t s, const float* S, const float* labels, const Segs& g, int C, int cid, int reducer, int K, int literal, float invB, float* sel,
+               float* dS, const int32_t* slot_of, float* partial, const TransposeJob* tj = nullptr, float* partial_host = nullptr, const PoolJob* pj = nullptr);
 void sum_partials(hipStream_t s, const float* partial, int n, float* out, int accumulate);
-int loss_partials(int B);  // number of per-workgroup loss partials the loss stage writes for B pairs
+int loss_partials(int B);  // number of per-workgroup loss partials the loss stage writes for B pairs of a rectangular batch (sizes the partial buffer)
 void zero_pad3(hipStream_t s, float* a, int na, float* b, int nb, float* c, int nc);
 void head_bwd(hipStream_t s, const float* dS, const float* hT, const float* Wout, int64_t N, int H, int cid, float* dH, float* gWout, float* gbout,
               DetScratch* det = nullptr);

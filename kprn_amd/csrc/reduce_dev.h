@@ -1,4 +1,4 @@
-// The reducer over a pair's paths as device functions, shared by the pooling / loss kernels (kernels_basic.hip) and the explanation stage
+// The reducer over a pair's paths as device functions, shared by the pooling / loss kernels (loss_stage.hip) and the explanation stage
 // (explain_paths.hip): one definition, so that both produce the same bits for the same pair.
 #pragma once
 #include "kprn_internal.h"
