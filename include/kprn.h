@@ -118,6 +118,9 @@ typedef struct {
                                     touched; bit-identical to the dense update of optim.adam
                                 1 = dense: every row every step, as the reference does          */
 } kprn_opt;
+/* Every field but method may change from one step to the next and the result stays that of the dense update with the same per-step values: lr costs
+ * nothing; a change of beta1 / beta2 / eps, of entity_update 0 -> 1 or of regularize 0 -> 1 while entity rows lag costs one whole-table flush.  method
+ * stays what the handle's first step used (KPRN_E_ARG otherwise): both methods keep their state in optimiser slot 0.                              */
 
 /* ---- lifetime -------------------------------------------------------------------- */
 /* OneModel.lua:204-309: build predictor_net + reducer, init uniform(-paramInit,paramInit) */

@@ -428,9 +428,19 @@ static void backward_impl(kprn_handle* h, const kprn_batch* b, int class_id, int
   h->grads_serial = b->serial;
 }
 
-static void apply_update_impl(kprn_handle* h, const kprn_opt* o) {
+// What a kprn_opt may not ask of this handle, checked before a step launches or writes anything.  The method stays what the handle's first step used: optimiser
+// slot 0 holds Adam's first moments or Adagrad's sums of squares, one or the other -- Adagrad's square root over Adam's negative moments is NaN, Adam would
+// read the sums as momentum -- and an Adagrad step leaves no step size for a lagging row's replay.
+static void opt_check(const kprn_handle* h, const kprn_opt* o) {
   KPRN_REQUIRE(o != nullptr, KPRN_E_ARG, "opt is NULL");
   KPRN_REQUIRE(o->method == 0 || o->method == 1, KPRN_E_ARG, "opt.method must be 0 (adagrad) or 1 (adam)");
+  KPRN_REQUIRE(h->opt_method < 0 || o->method == h->opt_method, KPRN_E_ARG,
+               std::string("opt.method changed from ") + (h->opt_method == 1 ? "adam to adagrad" : "adagrad to adam") +
+                   " on a handle that has taken steps: the two methods keep different state in optimiser slot 0 (first moments / sums of squares); use a new handle");
+}
+
+static void apply_update_impl(kprn_handle* h, const kprn_opt* o) {
+  opt_check(h, o);
   const kprn_config& c = h->cfg;
   join_score(h);
   hipStream_t s = h->stream;
@@ -462,6 +472,8 @@ static void apply_update_impl(kprn_handle* h, const kprn_opt* o) {
   const int64_t pad_row = (int64_t)c.Ve - 1;
   bool pad_done = false;
   if (o->method == 1) {
+    // rows that lag replay their skipped steps with the constants those steps ran with: new ones are adopted only once the table is current
+    if (h->lazy_pending && (o->beta1 != h->last_b1 || o->beta2 != h->last_b2 || o->eps != h->last_eps)) flush_lazy(h);
     h->last_b1 = o->beta1; h->last_b2 = o->beta2; h->last_eps = o->eps;
     if (dense_ent && !h->ent_dense_mode) { flush_lazy(h); h->ent_dense_mode = true; }
     if (!dense_ent && h->ent_dense_mode) {
@@ -872,7 +884,7 @@ int kprn_apply_update(kprn_handle* h, const kprn_opt* opt) {
 
 int kprn_train_step_batch(kprn_handle* h, const kprn_batch* b, int32_t class_id, const kprn_opt* opt, float* loss) {
   API_BEGIN(h)
-  KPRN_REQUIRE(opt, KPRN_E_ARG, "opt is NULL");
+  opt_check(h, opt);
   check_batch(h, b, class_id);
   det_check(h, b->T, b);
   generic::drop_check(h, b);
@@ -906,7 +918,7 @@ int kprn_train_step(kprn_handle* h, const int32_t* idx, int32_t B, int32_t P, in
                     const kprn_opt* opt, float* loss) {
   if (!h) return KPRN_E_ARG;
   if (!labels) { h->err = "assert(targets) (MyOptimizer.lua:179)"; return KPRN_E_ARG; }
-  try { det_check(h, T); } catch (const KprnError& e) { h->err = e.msg; return e.code; }   // (before the feed: a refused call uploads nothing)
+  try { opt_check(h, opt); det_check(h, T); } catch (const KprnError& e) { h->err = e.msg; return e.code; }   // (before the feed: a refused call uploads nothing)
   // The minibatch goes through one of two engine-owned feed slots (grow-only capacity, page-locked staging: steady state allocates nothing and
   // frees nothing; alternating, so that the rows the lazy optimiser still names belong to the OTHER slot) instead of a batch created and
   // destroyed per call (two device allocations, a device-side index build with its synchronisations and three stream drains per step:
