@@ -102,6 +102,11 @@ int kprn_find_training_paths(kprn_handle*, const kprn_graph*, const kprn_sampler
 int kprn_find_paths_sampled(kprn_handle*, const kprn_graph*, const int32_t*, const float*, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, uint64_t, unsigned int, int32_t*, int64_t*, kprn_batch**);
 int kprn_host_find_paths_sampled(const int32_t*, const int32_t*, const int32_t*, int64_t, const int32_t*, int32_t, int32_t, int32_t, int32_t, int32_t, const int32_t*, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, uint64_t, unsigned int, int32_t, int32_t*, int64_t*, int32_t*);
 int kprn_find_training_paths_sampled(kprn_handle*, const kprn_graph*, const kprn_sampler*, const int32_t*, int32_t, int32_t, int32_t, uint64_t, unsigned int, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t*, int32_t*, int64_t*, kprn_batch**);
+/* candidates of a user: the catalogue items the graph reaches, found on the device (include/kprn.h "candidates of a user") */
+int kprn_find_candidates(kprn_handle*, const kprn_graph*, const kprn_sampler*, const int32_t*, int32_t, int32_t, int32_t, int32_t, int32_t*, int64_t*);
+int kprn_read_candidates(kprn_handle*, int32_t*, int64_t);
+int kprn_find_paths_of_candidates(kprn_handle*, const kprn_graph*, int32_t, int32_t, int32_t, int32_t, int32_t, uint64_t, unsigned int, int32_t*, int64_t*, kprn_batch**);
+int kprn_host_find_candidates(const int32_t*, const int32_t*, const int32_t*, int64_t, int32_t, const int32_t*, int64_t, const int32_t*, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t*, int32_t*);
 ]]
 
 local C = ffi.load('kprn')

@@ -438,6 +438,45 @@ int kprn_find_training_paths_sampled(kprn_handle* h, const kprn_graph* g, const 
                                      int32_t n_neg, int32_t max_attempts, uint64_t seed, unsigned int draw /* uint32 */, int32_t min_hops, int32_t max_hops,
                                      int32_t max_paths, int32_t T, int32_t walks, int32_t* pairs_out, int32_t* counts, int64_t* found, kprn_batch** out);
 
+/* ---- candidates of a user (an extension: the reference takes its candidates from files of 100 sampled negatives per user, data_prepare/sample.py, which
+ * are not restated; here the candidates are the catalogue items the graph reaches from the user) ----
+ * "What should this user get" without a candidate list from the caller: the walk runs from the user outward on the device, deg(u) * deg(a) * deg(b) steps,
+ * and leaves the (user, item) rows in HBM, where the finder reads them.
+ *  - catalogue: the item list of a kprn_sampler, items [M], ascending entity ids.  Its weights are not looked at: an item of weight 0 is still a member.
+ *    (The sampler already holds exactly this list in HBM; training from a graph and recommending can share one object.)
+ *  - candidates of a user u (a node, 1 .. Ve-1), for 1 <= min_hops <= max_hops <= 3: a catalogue member c is a candidate iff c != u; at least one path of
+ *    min_hops .. max_hops hops leads from u to c in the finder's sense (stored edges only, all nodes pairwise distinct); and, if exclude_adjacent != 0, the
+ *    stored graph has no edge u -> c of any relation (the items the user already has, by the negative sampler's own test).  Stored edges hold no
+ *    self-loops, so the path condition is: 1 hop u -> c; 2 hops u -> a -> c with c != u; 3 hops u -> a -> b -> c with b != u, c != u, c != a.
+ *    By definition the candidates are exactly the members for which kprn_find_paths over the same hops would report found > 0, less the exclusions.
+ *  - order within a user: entity id ascending.  Nothing depends on timing: membership is a bitmap (a set), ranks come from popcounts and prefix sums, and
+ *    no atomic hands out a slot or a rank.
+ *  - result: B users in one call give B groups; group_counts [B] (zeros allowed) and *total = sum(group_counts) on the host.  The pair list,
+ *    [total][2] = (u, c), users in input order, stays in HBM as THE HANDLE'S CANDIDATE LIST: it is replaced by the next successful call, freed by
+ *    kprn_destroy, and read by kprn_read_candidates and kprn_find_paths_of_candidates.
+ *  - refusals: hops outside 1..3, B < 1, B * ceil(M / 32) >= 2^31 or total >= 2^31 are KPRN_E_ARG; a user outside 1 .. Ve-1 is KPRN_E_INDEX.  A refused
+ *    call writes nothing and leaves the handle's previous list as it was.  If the fill pass places another number of rows than the counting pass allotted
+ *    a user, the call returns KPRN_E_DEVICE (no write leaves the user's rows in either case) and the previous list stays.
+ * Synchronous: the call waits once for the counts (the list's size) and once for the fill pass's verdict.                                             */
+int kprn_find_candidates(kprn_handle* h, const kprn_graph* g, const kprn_sampler* catalogue, const int32_t* users /* [B] */, int32_t B,
+                         int32_t min_hops, int32_t max_hops, int32_t exclude_adjacent, int32_t* group_counts /* [B] */, int64_t* total);
+/* the handle's candidate list back on the host; total must equal the list's, else KPRN_E_ARG (as is a handle that has no list yet) */
+int kprn_read_candidates(kprn_handle* h, int32_t* pairs_out /* [total][2] */, int64_t total);
+/* The finder's two passes over the handle's candidate list, copied device to device: the list never visits the host on the way.  labels = NULL; counts and
+ * found [total] (or NULL); row b of the sampled walks' Philox counter is the list's row b.  walks == 0: the limits are kprn_find_paths'; otherwise
+ * kprn_find_paths_sampled's (max_hops up to 5).  By definition the outputs equal those of kprn_find_paths (kprn_find_paths_sampled) on the pair list
+ * kprn_read_candidates returns.  No list yet: KPRN_E_ARG.  An empty list: *out = NULL with KPRN_OK.  A graph whose Ve differs from that of the graph the list
+ * was made on: KPRN_E_INDEX.  When the call asks for the same exhaustive hops that produced the list, every pair has found > 0, no pair is dropped, and
+ * the batch's pair p is the list's row p.                                                                                                           */
+int kprn_find_paths_of_candidates(kprn_handle* h, const kprn_graph* g, int32_t min_hops, int32_t max_hops, int32_t max_paths, int32_t T, int32_t walks,
+                                  uint64_t seed, unsigned int draw /* uint32 */, int32_t* counts /* [total] */, int64_t* found /* [total] */, kprn_batch** out);
+/* the same rule on the host cores over the graph's raw edge arrays and the item list (no handle, no GPU), on `threads` threads; rel is not looked at.
+ * group_counts [B]; cand = the [sum(group_counts)] candidate entity ids, users in input order, or NULL = counts only (call it once for the sizes, once
+ * for the ids).  The same refusals, plus kprn_sampler_create's for the item list and kprn_graph_create's for E and the edges' nodes.                    */
+int kprn_host_find_candidates(const int32_t* src, const int32_t* dst, const int32_t* rel, int64_t E, int32_t Ve, const int32_t* items, int64_t M,
+                              const int32_t* users, int32_t B, int32_t min_hops, int32_t max_hops, int32_t exclude_adjacent, int32_t threads,
+                              int32_t* group_counts, int32_t* cand /* [sum] entity ids, or NULL = counts only */);
+
 /* ---- training ---------------------------------------------------------------------- */
 /* fEval of MyOptimizer.lua:184-195: zeroGradParameters; forward; BCE; backward.
  * inv_batch = 0 -> 1/B; data-parallel callers pass 1/B_global.  loss may be NULL (async). */

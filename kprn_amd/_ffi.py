@@ -276,6 +276,29 @@ def host_sample_negatives(src, dst, rel, Ve, items, weights, users, n_neg, seed,
     return neg, nf
 
 
+def host_find_candidates(src, dst, rel, Ve, items, users, min_hops, max_hops, exclude_adjacent=True, threads=1):
+    """kprn_host_find_candidates (no handle, no GPU): the rule of include/kprn.h "candidates of a user" over the graph's raw edge arrays and the catalogue
+    `items` -> (cand [sum(group_counts)] entity ids, users in input order; group_counts [B]).  Two calls: the counts, then the ids"""
+    src, dst, rel = (np.ascontiguousarray(a, np.int32).reshape(-1) for a in (src, dst, rel))
+    if not (src.shape == dst.shape == rel.shape):
+        raise KprnError(E_ARG, "a graph is src / dst / rel [E]")
+    it, _ = _sampler_arrays(items, None)
+    us = np.ascontiguousarray(users, np.int32).reshape(-1)
+    B = int(us.shape[0])
+    gc = np.zeros(B, np.int32)
+
+    def call(counts, cand):
+        rc = lib().kprn_host_find_candidates(_fp(src), _fp(dst), _fp(rel), C.c_int64(int(src.shape[0])), int(Ve), _fp(it), C.c_int64(int(it.shape[0])), _fp(us), B,
+                                             int(min_hops), int(max_hops), int(bool(exclude_adjacent)), int(threads), _fp(counts), _fp(cand))
+        if rc != 0:
+            raise KprnError(rc, "kprn_host_find_candidates: bad edges / items / users / hops")
+    call(gc, None)
+    cand = np.zeros(int(gc.astype(np.int64).sum()), np.int32)
+    if cand.size:
+        call(np.zeros(B, np.int32), cand)
+    return cand, gc
+
+
 def format_score_lines(counter0, probs, labels):
     """bytes of the scoring writer's lines for pairs counter0 .. (kprn_format_score_lines; host-only)"""
     L = lib()
@@ -884,6 +907,37 @@ class Engine:
         if not ptr:
             return None, pairs, counts, found
         return Batch._adopt(self, ptr, counts[counts > 0].copy(), T, self.cfg.F, True), pairs, counts, found
+
+    # -- candidates of a user (include/kprn.h "candidates of a user") ---------------------------
+    def find_candidates(self, graph, sampler, users, min_hops, max_hops, exclude_adjacent=True):
+        """kprn_find_candidates + kprn_read_candidates: the members of the sampler's item list that min_hops .. max_hops (<= 3) hops reach from each of
+        `users`, less the user and (exclude_adjacent) the items it has an edge to -> (pairs [total, 2] = (user, item), users in input order and items
+        ascending; group_counts [B]).  The list stays on the device for find_paths_of_candidates"""
+        us = np.ascontiguousarray(users, np.int32).reshape(-1)
+        B = int(us.shape[0])
+        gc = np.zeros(B, np.int32)
+        total = C.c_int64()
+        self._ck(self.L.kprn_find_candidates(self.h, graph.ptr, sampler.ptr, _fp(us), B, int(min_hops), int(max_hops), int(bool(exclude_adjacent)), _fp(gc),
+                                             C.byref(total)))
+        self._cand_total = int(total.value)
+        pairs = np.zeros((int(total.value), 2), np.int32)
+        self._ck(self.L.kprn_read_candidates(self.h, _fp(pairs), C.c_int64(int(total.value))))
+        return pairs, gc
+
+    def find_paths_of_candidates(self, graph, total, min_hops, max_hops, max_paths, T, walks=0, seed=0, draw=0):
+        """kprn_find_paths_of_candidates: find_paths over the engine's candidate list (`total` rows, as find_candidates returned them), which never visits
+        the host -> (ragged Batch of the pairs that have paths, or None; counts [total]; found [total])"""
+        total = int(total)
+        if total != getattr(self, "_cand_total", total):   # (the library writes counts / found [the list's total])
+            raise KprnError(E_ARG, "total is not the candidate list's")
+        counts, found = np.zeros(total, np.int32), np.zeros(total, np.int64)
+        ptr = C.c_void_p()
+        sd, dr = _seed_draw(seed, draw)
+        self._ck(self.L.kprn_find_paths_of_candidates(self.h, graph.ptr, int(min_hops), int(max_hops), int(max_paths), int(T), int(walks), sd, dr, _fp(counts),
+                                                      _fp(found), C.byref(ptr)))
+        if not ptr:
+            return None, counts, found
+        return Batch._adopt(self, ptr, counts[counts > 0].copy(), T, self.cfg.F, False), counts, found
 
     # -- explanation (include/kprn.h "explaining a recommendation") ---------------------------
     def explain_batch(self, batch, M, class_id=1, pairs=None, out=None):

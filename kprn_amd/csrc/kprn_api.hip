@@ -663,6 +663,7 @@ void kprn_destroy(kprn_handle* h) {
   if (h->explain_pin) { hipHostFree(h->explain_pin); h->explain_pin = nullptr; }
   pf::release_all(h);
   ns::release_all(h);
+  cd::release_all(h);
   if (h->feed_pool) { hostfeed::free_pool((hostfeed::Pool*)h->feed_pool); h->feed_pool = nullptr; }  // (joins the workers)
   if (h->upload_pool) { hostfeed::free_pool((hostfeed::Pool*)h->upload_pool); h->upload_pool = nullptr; }
   if (h->upload_stream) { hipStreamSynchronize(h->upload_stream); hipStreamDestroy(h->upload_stream); h->upload_stream = nullptr; }

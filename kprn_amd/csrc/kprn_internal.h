@@ -290,6 +290,9 @@ struct kprn_handle {
   void* pf_buf = nullptr; size_t pf_buf_bytes = 0;     // device arguments of one kprn_find_paths call (pairs, totals, first rows, counts, flag; per-walk counts)
   std::vector<kprn_sampler*> samplers;                 // neg_sample.hip: the negative samplers alive on this handle (kprn_destroy frees what is left)
   void* ns_buf = nullptr; size_t ns_buf_bytes = 0;     // device arguments and results of one sampling call (users or positives, negatives, n_found)
+  // candidates.hip: the handle's candidate list = the (user, item) rows of the last successful kprn_find_candidates, [cand_total][2] (cand_total < 0: none yet)
+  int32_t* cand_list = nullptr; int64_t cand_total = -1; int32_t cand_Ve = 0;
+  void* cand_buf = nullptr; size_t cand_buf_bytes = 0; // device arguments of one kprn_find_candidates call (first rows, users, counts, flag, the users' bitmaps)
 
   // option "deterministic": every float sum of a training step whose addends come from different waves or workgroups of one launch is formed in an order that
   // depends on the batch and the launch geometry only; pipelines that cannot do that refuse to train
@@ -512,6 +515,10 @@ void release_all(kprn_handle* h);   // kprn_destroy: the graphs still alive and 
 namespace ns {
 void release_all(kprn_handle* h);   // kprn_destroy: the samplers still alive and the sampling calls' buffer
 }  // namespace ns
+// ---- candidates of a user (candidates.hip): kprn_find_candidates / kprn_read_candidates / kprn_find_paths_of_candidates / kprn_host_find_candidates ----
+namespace cd {
+void release_all(kprn_handle* h);   // kprn_destroy: the handle's candidate list and the call's buffer
+}  // namespace cd
 
 // ---- explanation stage (explain_paths.hip) -------------------------------------------------------
 namespace ex {

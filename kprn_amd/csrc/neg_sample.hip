@@ -17,12 +17,6 @@
 
 #include <cmath>
 
-struct kprn_sampler {
-  int32_t M = 0;
-  int32_t* items = nullptr;            // device [M]
-  unsigned long long* thr = nullptr;   // device [M], thr[M - 1] = 2^32
-};
-
 namespace ns {
 
 constexpr int TPB = 256, WAVES = TPB / 64, MAX_NEG = 256, MAX_ATTEMPTS = 64;
@@ -102,7 +96,7 @@ __global__ __launch_bounds__(TPB) void k_sample(pf::Csr g, Table t, Rng rng, con
 // ---- host side -------------------------------------------------------------------------------------------------------------------------------
 static int bad(std::string* why, int code, const char* t) { if (why) *why = t; return code; }
 
-static int validate_table(const int32_t* items, const float* weights, int64_t M, int32_t Ve, std::string* why) {
+int validate_table(const int32_t* items, const float* weights, int64_t M, int32_t Ve, std::string* why) {
   if (!items || M < 1 || M > 0x7fffffffLL) return bad(why, KPRN_E_ARG, "items is NULL or M is outside 1 .. 2^31 - 1");
   if (Ve < 2) return bad(why, KPRN_E_ARG, "Ve must be at least 2");
   bool any = weights == nullptr;
@@ -138,7 +132,7 @@ static int validate_limits(int64_t B, int32_t n_neg, int32_t max_attempts, std::
   if (B * (1 + (int64_t)n_neg) > 0x7fffffffLL) return bad(why, KPRN_E_ARG, "B * (1 + n_neg) must stay below 2^31");
   return KPRN_OK;
 }
-static int validate_users(const int32_t* users, int64_t n, int32_t Ve, std::string* why) {
+int validate_users(const int32_t* users, int64_t n, int32_t Ve, std::string* why) {
   if (!users) return bad(why, KPRN_E_ARG, "users is NULL");
   for (int64_t k = 0; k < n; ++k)
     if (users[k] < 1 || users[k] >= Ve) return bad(why, KPRN_E_INDEX, "a user (or a positive's item) is outside 1..Ve-1");

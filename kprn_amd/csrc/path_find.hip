@@ -256,7 +256,6 @@ int validate_find(const int32_t* pairs, int32_t B, int32_t Ve, int32_t min_hops,
     if (pairs[k] < 1 || pairs[k] >= Ve) return bad(KPRN_E_INDEX, "a pair's node is outside 1..Ve-1");
   return KPRN_OK;
 }
-static int hop_mask(int min_hops, int max_hops) { int m = 0; for (int h = min_hops; h <= max_hops; ++h) m |= 1 << (h - 1); return m; }
 
 static kprn_graph* build_graph(kprn_handle* h, const int32_t* src, const int32_t* dst, const int32_t* rel, int64_t E, const int32_t* node_types, int32_t end_rel) {
   const kprn_config& c = h->cfg;

@@ -1,4 +1,4 @@
-// What the path finder (path_find.hip), its sampled hops (path_walk.hip) and the negative sampler (neg_sample.hip) share: the graph in HBM, the CSR view they
+// What the path finder (path_find.hip), its sampled hops (path_walk.hip), the negative sampler (neg_sample.hip) and the candidates (candidates.hip) share: the graph in HBM, the CSR view they
 // walk and a path's row (namespace pf, __host__ __device__), the workgroup's sums, the host CSR of the twins and their thread loop.
 #pragma once
 #include "kprn_internal.h"
@@ -17,6 +17,17 @@ struct kprn_graph {
   int32_t* rel = nullptr;        // device [E] relation
   int32_t* types = nullptr;      // device [Ve][nT]: row e - 1 = the type slots of entity e
 };
+
+struct kprn_sampler {
+  int32_t M = 0;
+  int32_t* items = nullptr;            // device [M] ascending entity ids: the negative sampler's candidate list and the catalogue of candidates.hip
+  unsigned long long* thr = nullptr;   // device [M], thr[M - 1] = 2^32
+};
+
+namespace ns {   // (neg_sample.hip) the refusals of an item list and of a user list, shared with candidates.hip
+int validate_table(const int32_t* items, const float* weights, int64_t M, int32_t Ve, std::string* why);
+int validate_users(const int32_t* users, int64_t n, int32_t Ve, std::string* why);
+}  // namespace ns
 
 namespace pf {
 
@@ -115,6 +126,7 @@ typedef std::function<void(int32_t* d_pairs, hipStream_t s)> StagePairs;
 struct Sampling { int32_t walks; uint32_t k0, k1, draw; };   // walks per pair and hop count; Philox key = the seed's halves
 static inline Sampling sampling_of(int32_t walks, uint64_t seed, uint32_t draw) { return Sampling{walks, (uint32_t)(seed & 0xffffffffu), (uint32_t)(seed >> 32), draw}; }
 constexpr int MAX_WALKS = 256, HOPS_SAMPLED = 8 | 16;   // (bits of the hop mask: bit h - 1 = paths of h hops are asked for)
+static inline int hop_mask(int min_hops, int max_hops) { int m = 0; for (int h = min_hops; h <= max_hops; ++h) m |= 1 << (h - 1); return m; }
 void find_staged(kprn_handle* h, const kprn_graph* g, const StagePairs& stage, const float* labels, int32_t B, int32_t min_hops, int32_t max_hops,
                  int32_t max_paths, int32_t T, const Sampling* sm, int32_t* pairs_out, int32_t* counts, int64_t* found, kprn_batch** out);
 // hops / max_paths / T of a find call (KPRN_E_ARG), before anything is staged; sm == NULL: max_hops <= 3, else max_hops <= 5 and walks in 1..256 past 3 hops

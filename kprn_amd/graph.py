@@ -112,13 +112,19 @@ def read_triples(path):
                 yield parts[0], parts[1], parts[2]
 
 
-def recommend(eng, kg, user, items, K, M, min_hops=1, max_hops=3, max_paths=28, T=None, class_id=1, mode=_ffi.RANK_PRINTED, walks=0, seed=1, draw=0):
+def recommend(eng, kg, user, items, K, M, min_hops=1, max_hops=3, max_paths=28, T=None, class_id=1, mode=_ffi.RANK_PRINTED, walks=0, seed=1, draw=0, sampler=None,
+              exclude_adjacent=True):
     """Which of `items` for `user` (entity ids), and why: find every pair's paths on the device, score the batch, put the scores on the board, rank the
     one group, explain the K winners and read their paths' ids back.  kg: a KnowledgeGraph, or an _ffi.Graph already on the engine.  The board is
     resized to the candidates that have paths (kprn_board_reserve keeps nothing).  walks > 0: max_hops may be 4 or 5, the hops past 3 sampled by `walks`
     walks per item and hop count under (seed, draw) (include/kprn.h "sampled paths of four and five hops").
     -> the K best items, best first: dict(item, rank, score, n_paths, found, paths = the M strongest as (ids [T,F], weight, score)); items without any
-    path are not candidates, so the list may be shorter than K -- empty when no item is reachable."""
+    path are not candidates, so the list may be shorter than K -- empty when no item is reachable.
+    items=None: the candidates are found on the device among the items of `sampler` (an _ffi.Sampler: the catalogue), recommend_users for the one user."""
+    if items is None:
+        if sampler is None:
+            raise ValueError("recommend needs items, or a sampler whose item list is the catalogue")
+        return recommend_users(eng, kg, sampler, [user], K, M, min_hops, max_hops, max_paths, T, class_id, mode, walks, seed, draw, exclude_adjacent)[0]
     graph = kg.on(eng) if isinstance(kg, KnowledgeGraph) else kg
     items = np.asarray(items, np.int32).reshape(-1)
     pairs = np.stack([np.full(items.shape, int(user), np.int32), items], axis=1)
@@ -144,6 +150,80 @@ def recommend(eng, kg, user, items, K, M, min_hops=1, max_hops=3, max_paths=28, 
                      for r, q in enumerate(ex["path_idx"][place]) if q >= 0]
             out.append(dict(item=int(items[cand[b]]), rank=place, score=float(top["topk_score"][0, place]), n_paths=int(batch.counts[b]),
                             found=int(found[cand[b]]), paths=paths))
+        return out
+    finally:
+        batch.free()
+
+
+def _rank_key(scores, mode):
+    """the ranking stage's key (include/kprn.h "ranking"): what "%.5f" prints, times 1e5, in mode PRINTED; the fp32 value in mode RAW; an invalid member
+    sorts below every valid one"""
+    s = np.asarray(scores, np.float32)
+    if mode == _ffi.RANK_PRINTED:
+        valid = (s >= 0) & (s <= 1)
+        return np.where(valid, np.rint(np.where(valid, s, 0).astype(np.float64) * 1e5), -np.inf)
+    return np.where(np.isnan(s), -np.inf, s.astype(np.float64))
+
+
+def recommend_users(eng, kg, sampler, users, K, M=0, min_hops=1, max_hops=3, max_paths=28, T=None, class_id=1, mode=_ffi.RANK_PRINTED, walks=0, seed=1, draw=0,
+                    exclude_adjacent=True):
+    """What should each of `users` (entity ids) get, and why, without a candidate list: one chain for all of them.  The candidates -- the items of
+    `sampler` (an _ffi.Sampler: the catalogue) that min_hops .. min(max_hops, 3) hops reach from the user, less the user and, with exclude_adjacent, the
+    items it already has an edge to -- are found on the device (include/kprn.h "candidates of a user"), the finder reads that list where it lies, the
+    batch is scored and put on the board, one rank_groups call ranks every user's group, the winners are explained (M > 0) and their paths read back.
+    A group of more than 4096 surviving pairs (kprn_rank_groups' limit) is ranked as consecutive sub-groups of at most 4096 in the same call, whose
+    top-K rows are merged here by (key descending, index within the user's group ascending): what a single group would have given.
+    -> per user, the list of dicts `recommend` returns."""
+    graph = kg.on(eng) if isinstance(kg, KnowledgeGraph) else kg
+    users = np.asarray(users, np.int32).reshape(-1)
+    T = max_hops + 1 if T is None else int(T)
+    out = [[] for _ in users]
+    pairs, gc = eng.find_candidates(graph, sampler, users, min_hops, min(int(max_hops), _ffi.FIND_MAX_HOPS), exclude_adjacent)
+    if len(pairs) == 0:
+        return out
+    batch, counts, found = eng.find_paths_of_candidates(graph, len(pairs), min_hops, max_hops, max_paths, T, walks=walks, seed=seed, draw=draw)
+    if batch is None:
+        return out
+    try:
+        cand = np.nonzero(counts)[0]            # pair b of the batch is row cand[b] of the candidate list
+        ends = np.cumsum(gc, dtype=np.int64)
+        uoff = np.searchsorted(cand, np.concatenate([[0], ends]))   # user g's surviving pairs = the batch's pairs uoff[g] .. uoff[g + 1]
+        eng.forward_async(batch, class_id)
+        eng.board_reserve(batch.B)
+        eng.board_put(0, batch.B)
+        kk = min(int(K), _ffi.RANK_MAX_K)
+        goff, owner = [0], []                   # the sub-groups of at most RANK_MAX_GROUP members, and the user each belongs to
+        for g in range(len(users)):
+            for lo in range(int(uoff[g]), int(uoff[g + 1]), _ffi.RANK_MAX_GROUP):
+                goff.append(min(lo + _ffi.RANK_MAX_GROUP, int(uoff[g + 1])))
+                owner.append(g)
+        owner = np.array(owner)
+        top = eng.rank_groups(np.array(goff, np.int64), pos=np.full(len(owner), -1, np.int32), K=kk, mode=mode)
+        wins, scores = [], []                   # per user with candidates: the winners as pairs of the batch, best first
+        for g in range(len(users)):
+            rows = np.nonzero(owner == g)[0]
+            if len(rows) == 0:
+                wins.append(np.zeros(0, np.int64)); scores.append(np.zeros(0, np.float32))
+                continue
+            ti, ts = top["topk_idx"][rows], top["topk_score"][rows]
+            b = (ti.astype(np.int64) + np.array(goff, np.int64)[rows][:, None])[ti >= 0]
+            sc = ts[ti >= 0]
+            if len(rows) > 1:
+                order = np.lexsort((b, -_rank_key(sc, mode)))[:kk]
+                b, sc = b[order], sc[order]
+            wins.append(b); scores.append(sc)
+        win = np.concatenate(wins).astype(np.int32)
+        ex = eng.explain_batch(batch, M, class_id, pairs=win) if int(M) > 0 and len(win) else None
+        idx = batch.read_idx()
+        off = np.concatenate([[0], np.cumsum(batch.counts, dtype=np.int64)])
+        at = 0
+        for g in range(len(users)):
+            for place, (b, sc) in enumerate(zip(wins[g], scores[g])):
+                paths = [] if ex is None else [(idx[off[b] + q], float(ex["path_weight"][at, r]), float(ex["path_score"][at, r]))
+                                               for r, q in enumerate(ex["path_idx"][at]) if q >= 0]
+                out[g].append(dict(item=int(pairs[cand[b], 1]), rank=place, score=float(sc), n_paths=int(batch.counts[b]), found=int(found[cand[b]]),
+                                   paths=paths))
+                at += 1
         return out
     finally:
         batch.free()

@@ -1,11 +1,13 @@
-"""`python -m kprn_amd.recommend <flags>`: which of the items in -items for -user, from a knowledge graph and a checkpoint, and why (an extension;
-the reference mines paths offline and scores files).  A thin command line over graph.recommend.
+"""`python -m kprn_amd.recommend <flags>`: which of the items in -items -- or, without -items, which items of the whole catalogue -- for -user, from a
+knowledge graph and a checkpoint, and why (an extension; the reference mines paths offline and scores files).  A thin command line over graph.recommend.
 
 Flags: those of `python -m kprn_amd.score` that shape and load the model (-model_path, -top_k, -gpu_id and the OneModel flags; the TopK reducer's K is the
 model flag -K here, because -k is the number of items to return), plus
   -kg triples.tsv      the graph: `head \\t relation \\t tail` names per line, directed (list inverse edges yourself)
   -vocab_dir DIR       entity_type_id.txt, all_relation_id.txt, all_entity_id.txt, entity_to_type.txt, domain-label
   -user U  -items FILE the user's entity name; candidate item names, one per line
+  -interaction_rel R [-seen 0]   without -items: the catalogue is every item an edge of relation R leads to, and the candidates are those the graph
+                       reaches from the user in -min_hops .. min(-max_hops, 3) hops, found on the device; -seen 1 keeps the items the user already has an edge to
   -k K                 items to return;  -explain_paths M  strongest paths printed per item
   -min_hops / -max_hops / -max_paths   the finder's limits (1, 3, 28)
   -walks N [-sampleSeed 1]             -max_hops 4 or 5: the paths of more than 3 hops are sampled, N walks (1..256) per item and hop count
@@ -13,6 +15,8 @@ Output, tab separated: one line `rank, item, %.5f score, paths kept, paths found
 per explained path (the path as scoring.format_path prints it)."""
 import argparse
 import sys
+
+import numpy as np
 
 from . import graph, model, scoring
 from .pathformat import Vocabs
@@ -22,12 +26,15 @@ def main(argv=None, out=sys.stdout):
     p = argparse.ArgumentParser()
     p.add_argument("-model_path", default=""); p.add_argument("-gpu_id", type=int, default=-1); p.add_argument("-top_k", type=int, default=2)
     p.add_argument("-kg", required=True); p.add_argument("-vocab_dir", required=True)
-    p.add_argument("-user", required=True); p.add_argument("-items", required=True)
+    p.add_argument("-user", required=True); p.add_argument("-items", default="")
     p.add_argument("-k", type=int, default=10); p.add_argument("-explain_paths", type=int, default=3)
     p.add_argument("-min_hops", type=int, default=1); p.add_argument("-max_hops", type=int, default=3); p.add_argument("-max_paths", type=int, default=28)
     p.add_argument("-walks", type=int, default=0)
+    p.add_argument("-interaction_rel", default=""); p.add_argument("-seen", type=int, default=0, choices=(0, 1))
     args, rest = p.parse_known_args(argv)
     model.check_walks(args.max_hops, args.walks, p.error)
+    if not args.items and not args.interaction_rel:
+        p.error("-kg needs -vocab_dir DIR (the vocabulary files) and -interaction_rel NAME (the relation of the user-item edges to train on)")   # (train -kg's)
     if not 1 <= args.explain_paths <= 32:
         sys.exit("-explain_paths must be in 1..32")
     if not 1 <= args.k <= 64:
@@ -38,12 +45,20 @@ def main(argv=None, out=sys.stdout):
     if (kg.Vt, kg.Ve, kg.Vr) != (params.entityTypeVocabSize, params.entityVocabSize, params.relationVocabSize):
         sys.exit("the vocabularies hold %d types, %d entities, %d relations; the model flags say %d, %d, %d"
                  % (kg.Vt, kg.Ve, kg.Vr, params.entityTypeVocabSize, params.entityVocabSize, params.relationVocabSize))
-    with open(args.items) as f:
-        names = [l.strip() for l in f if l.strip()]
+    items, catalogue = None, None
+    if args.items:
+        with open(args.items) as f:
+            items = [kg.entity_id(l.strip()) for l in f if l.strip()]
+    else:
+        positives = kg.interactions(args.interaction_rel)
+        if len(positives) == 0:
+            sys.exit("the graph has no edge of relation %s" % args.interaction_rel)
+        catalogue = np.unique(positives[:, 1])
     eng = model.build_engine(params)
     try:
-        res = graph.recommend(eng, kg, kg.entity_id(args.user), [kg.entity_id(n) for n in names], args.k, args.explain_paths, args.min_hops, args.max_hops,
-                              args.max_paths, walks=args.walks, seed=params.sampleSeed)
+        sampler = None if catalogue is None else eng.sampler(catalogue)
+        res = graph.recommend(eng, kg, kg.entity_id(args.user), items, args.k, args.explain_paths, args.min_hops, args.max_hops,
+                              args.max_paths, walks=args.walks, seed=params.sampleSeed, sampler=sampler, exclude_adjacent=not args.seen)
     finally:
         eng.close()
     for r in res:
