@@ -505,6 +505,40 @@ int kprn_read_loss(kprn_handle* h, float* loss);
 int kprn_read_loss_sum(kprn_handle* h, float* sum, int32_t* steps, int32_t reset);
 int kprn_sync(kprn_handle* h);
 
+/* ---- pairwise loss (an extension: Bayesian personalised ranking over groups of pairs, in place of nn.BCECriterion on each pair by itself) ----
+ * kprn_set_option(h, "loss", "bpr") makes kprn_backward_batch and kprn_train_step_batch train on this rule; the batch needs a group table
+ * (kprn_batch_set_groups).  For a batch of B pairs, rectangular or ragged:
+ *   y_b = the reducer's fp32 output for the selected class (what the pooling stage calls pooled, before the sigmoid); t_b = the batch's labels;
+ *   go[0 .. G] = a group table over consecutive pairs: go[0] = 0, go[G] = B, non-decreasing (an empty group is allowed).
+ * Terms.  Group g contributes one term per ordered pair (i, j) of its members with t_i > 0.5 and t_j <= 0.5.  Positives need not come first and there may
+ *   be several; a group without a positive, or without a negative, contributes nothing.  n_terms = the batch's term count.
+ * Loss.  L = s * sum over the terms of softplus(-(y_i - y_j)), softplus(x) = max(x, 0) + log1p(exp(-|x|)): -log sigmoid(y_i - y_j) in its stable form.
+ *   s = inv_batch where the caller passes inv_batch > 0, else 1 / n_terms.  (The reference's criterion/BPRLoss.lua adds 1e-4 inside its logarithm; that
+ *   criterion belongs to the reference's entity-type task, which is out of scope here, and its gradient is not the derivative of its value: it is NOT
+ *   restated.)
+ * Gradient.  With sigma_ij = 1 / (1 + exp(y_i - y_j)): dy_i = -s * sum_j sigma_ij for a positive i, dy_j = +s * sum_i sigma_ij for a negative j, each sum
+ *   over the member's partners in ascending pair index; a pair without a term gets dy = +0.0f.  dy_b goes back through the reducer (LogSumExp, Max,
+ *   TopK + Mean) exactly as the BCE stage's does, and EVERY pair's entries of dS are written -- zeros for a pair without a term, never skipped.  The
+ *   selected probabilities sigmoid(y_b) are stored as before (kprn_read_probs).
+ * No terms.  n_terms == 0: the loss is 0, every gradient is 0, nothing is refused.
+ * Order.  No float atomics: a pair's sums run over its partners in index order, a group's terms are added in index order and scaled once, one plain
+ *   store per group, and the groups' partials are added in group order -- the loss has the same bits run to run.  "deterministic" needs nothing new.
+ *   The sums within a group (up to 1023 addends) are running fp32 sums with Kahan's compensation; the sum over the groups is a plain running sum.
+ * Limits.  KPRN_PAIRWISE_MAX_GROUP pairs per group; a pair's path count keeps the ragged limit of 4096.
+ * Under "loss" "bpr": bce_literal is ignored; a batch without a group table is KPRN_E_ARG; kprn_train_step (host buffers, no groups) is
+ *   KPRN_E_UNSUPPORTED; kprn_config.world > 1 with inv_batch = 0 is KPRN_E_UNSUPPORTED (kprn_train_step_batch passes no inv_batch) -- all decided
+ *   before anything is launched or written.  Scoring, ranking, explaining and recommending calls do not look at the option.
+ *
+ * kprn_batch_set_groups uploads the table into storage the batch owns and counts the terms on the device, in integers; synchronous (one wait).  The table
+ * goes with the batch's contents: any refill or feed of the slot, kprn_batch_slot_reserve and kprn_batch_destroy drop it.  KPRN_E_ARG, with the batch's
+ * previous table left in place: offsets that decrease, go[0] != 0, go[G] != B, a group above the limit, G < 1, or a batch without labels.
+ * kprn_host_pairwise_loss applies the rule on the host cores (no handle, no GPU; the same fp32 formula and partner order): dy [B], *loss, *n_terms from
+ * pooled [B], labels [B] and the table; KPRN_E_ARG for a NULL argument or a bad table.                                                              */
+#define KPRN_PAIRWISE_MAX_GROUP 1024
+int kprn_batch_set_groups(kprn_handle* h, kprn_batch* b, const int32_t* group_offsets /* [G+1] */, int32_t G, int64_t* n_terms /* or NULL */);
+int kprn_host_pairwise_loss(const float* pooled /* [B] */, const float* labels, const int32_t* group_offsets, int32_t G, int32_t B, float inv_batch,
+                            float* dy /* [B] */, float* loss, int64_t* n_terms);
+
 /* ---- dropout on the rnn cell's input (-useDropout / -dropout, OneModel.lua:246-265) ----
  * kprn_set_option(h, "dropout", "p") with 0 < p < 1 makes every TRAINING forward of an rnn_type 1, compute_dtype 0 handle (a forward that saves for the
  * backward: kprn_backward_batch, kprn_train_step, kprn_train_step_batch) apply nn.Dropout(p) to every layer's step input -- x_t for layer 1, h^{l-1}_t
@@ -661,6 +695,9 @@ int kprn_profile_get(kprn_handle* h, kprn_prof_entry* out, int32_t cap, int32_t*
  *                     Not a number or outside [0, 1): KPRN_E_ARG.  A rate > 0 on a handle with rnn_type != 1 (the reference's lstm / gru ignore the flag) or
  *                     compute_dtype != 0 is refused with KPRN_E_UNSUPPORTED when it is set.  With a rate > 0 layer 0's backward leaves the small-table identity
  *                     ("small_tables") for the dx product + table-gradient route.  "0" restores the launches of a handle that never had the option
+ *   "loss"            "bce" (default) | "bpr": what kprn_backward_batch and kprn_train_step_batch train on -- nn.BCECriterion on each pair by itself | the pairwise
+ *                     ranking loss over the batch's group table (see kprn_batch_set_groups, "pairwise loss").  Read at every training call; with "bce" nothing
+ *                     changes.  Any other value: KPRN_E_ARG
  *   "dropout_seed"    decimal or 0x hex uint64 (default: kprn_config.seed + rank, so data-parallel replicas draw different masks): the generator's seed;
  *                     setting it restarts the draw count at 0
  *   (also: "small_tiles", "score_split", "loss_accumulate", "feed_build" / "feed_threads" / "feed_workers", "dp_comm_stream",

@@ -177,6 +177,25 @@ def host_dropout_keep(seed, draw, layer, T, N, Din, p):
     return keep
 
 
+PAIRWISE_MAX_GROUP = 1024   # pairs per group of the pairwise loss (KPRN_PAIRWISE_MAX_GROUP)
+
+
+def host_pairwise_loss(pooled, labels, group_offsets, inv_batch=0.0):
+    """kprn_host_pairwise_loss (no handle, no GPU): the pairwise loss over the groups of consecutive pairs that group_offsets [G+1] cuts (include/kprn.h
+    "pairwise loss") -> (loss, dy [B] = d loss / d pooled, n_terms); inv_batch > 0: the scale, else 1 / n_terms.  Raises KprnError(E_ARG) for a bad table"""
+    y = np.ascontiguousarray(pooled, np.float32).reshape(-1)
+    t = np.ascontiguousarray(labels, np.float32).reshape(-1)
+    go = np.ascontiguousarray(group_offsets, np.int32).reshape(-1)
+    if t.shape != y.shape:
+        raise KprnError(E_ARG, "pooled and labels must both be [B]")
+    dy = np.zeros(y.shape, np.float32)
+    loss, n = C.c_float(), C.c_int64()
+    rc = lib().kprn_host_pairwise_loss(_fp(y), _fp(t), _fp(go), int(go.shape[0]) - 1, int(y.shape[0]), C.c_float(float(inv_batch)), _fp(dy), C.byref(loss), C.byref(n))
+    if rc != 0:
+        raise KprnError(rc, "kprn_host_pairwise_loss: bad group_offsets (go[0] = 0, go[G] = B, non-decreasing, groups of at most %d pairs)" % PAIRWISE_MAX_GROUP)
+    return float(loss.value), dy, int(n.value)
+
+
 FIND_MAX_HOPS, FIND_MAX_PATHS = 3, 4096   # kprn_find_paths: hops per path, kept paths per pair
 FIND_MAX_HOPS_SAMPLED, FIND_MAX_WALKS = 5, 256   # kprn_find_paths_sampled: hops per path, walks per pair and sampled hop count
 
@@ -489,6 +508,14 @@ class Batch:
         self.has_labels = has_labels
         return self
 
+    def set_groups(self, group_offsets):
+        """kprn_batch_set_groups: the group table [G+1] over this batch's consecutive pairs that the pairwise loss (option "loss" = "bpr") trains on -> n_terms,
+        the (positive, negative) pairs within the groups.  The table goes with the contents: a refill drops it.  Raises KprnError(E_ARG) for a bad table"""
+        go = np.ascontiguousarray(group_offsets, np.int32).reshape(-1)
+        n = C.c_int64()
+        self.engine._ck(self.engine.L.kprn_batch_set_groups(self.engine.h, self.ptr, _fp(go), int(go.shape[0]) - 1, C.byref(n)))
+        return int(n.value)
+
     @property
     def n_paths(self):
         return self.N if getattr(self, "counts", None) is not None else self.B * self.P
@@ -602,6 +629,7 @@ class Engine:
         self._batches = weakref.WeakSet()
         self._graphs = weakref.WeakSet()
         self._samplers = weakref.WeakSet()
+        self.options = {}   # what set_option has set on this handle (the library has no getter): key -> last accepted value
         self.cfg = Config(Vt, Ve, Vr, dt, de, dr, F, num_types, H, L, C_, rnn_type, use_relu, rnn_init, compute_dtype, reducer, K, device_id, rank, world,
                           param_init, seed, stream)
         self.h = C.c_void_p()
@@ -1081,3 +1109,4 @@ class Engine:
 
     def set_option(self, key, value):
         self._ck(self.L.kprn_set_option(self.h, key.encode(), value.encode()))
+        self.options[key] = value

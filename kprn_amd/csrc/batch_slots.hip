@@ -56,6 +56,7 @@ void release(kprn_batch* b) {
   if (b->hs) { hipHostFree(b->hs); b->hs = nullptr; }
   if (b->ev_fork) { hipEventDestroy(b->ev_fork); hipEventDestroy(b->ev_fork2); b->ev_fork = b->ev_fork2 = nullptr; }
   free_buffers(b);
+  dfree(b->groups);
   if (b->h_meta) { hipHostFree(b->h_meta); b->h_meta = nullptr; }
   if (b->ev_ready) { hipEventDestroy(b->ev_ready); b->ev_ready = nullptr; }
   delete b;
@@ -381,6 +382,8 @@ static void detach(kprn_handle* h, kprn_batch* b, Why why) {
   // refill only, also when the slot was used: its uploads read the page-locked staging the next fill overwrites (the feed's back-pressure on a host running ahead)
   if (why == Why::refill && b->ev_ready && (b->pending || b->host_built)) HIP_TRY(hipEventSynchronize(b->ev_ready));
   b->pending = false;
+  // 6. the group table of the pairwise loss (kprn_batch_set_groups) names the old contents' pairs: dropped; its storage stays with the slot
+  b->n_groups = 0; b->n_terms = 0;
 }
 
 // body(b, fresh) on the slot's batch, or on a new one that becomes the slot's -- unless body throws: then it is released again and *slot stays as it was
@@ -466,6 +469,31 @@ int kprn_host_ragged_plan(const int32_t* counts, int32_t B, int64_t N, int32_t* 
   summary[0] = sm[0]; summary[1] = sm[1]; summary[2] = sm[2];
   summary[3] = kk::RAGGED_MAX_SEG; summary[4] = kk::RAGGED_THREAD_MAX; summary[5] = kk::RAGGED_WG_PATHS; summary[6] = kk::RAGGED_WG_PAIRS; summary[7] = 0;
   return KPRN_OK;
+}
+
+// The group table of the pairwise loss (include/kprn.h "pairwise loss"): checked on the host, uploaded into storage the batch owns, its terms counted on the
+// device; one wait.  Nothing of the batch changes before the table has passed its checks.
+int kprn_batch_set_groups(kprn_handle* h, kprn_batch* b, const int32_t* group_offsets, int32_t G, int64_t* n_terms) {
+  API_BEGIN(h)
+  KPRN_REQUIRE(b != nullptr, KPRN_E_ARG, "batch is NULL");
+  slots::ready(h, b);
+  KPRN_REQUIRE(b->labels != nullptr, KPRN_E_ARG, "kprn_batch_set_groups: the batch has no labels");
+  if (const char* why = kk::pairwise_groups_why(group_offsets, G, b->B)) throw KprnError{KPRN_E_ARG, std::string("kprn_batch_set_groups: ") + why};
+  const int64_t need = (int64_t)G + 3;
+  if (need > b->groups_cap) {
+    int32_t* grown = dalloc<int32_t>(need * 2);
+    if (b->groups) { HIP_TRY(hipStreamSynchronize(h->stream)); dfree(b->groups); }   // (a loss stage still queued reads the old table)
+    b->groups = grown; b->groups_cap = need * 2;
+  }
+  b->n_groups = 0;
+  HIP_TRY(hipMemcpyAsync(b->groups + 2, group_offsets, (size_t)(G + 1) * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+  kk::count_pair_terms(h->stream, b->labels, b->groups + 2, G, (int64_t*)b->groups);
+  int64_t terms = 0;
+  HIP_TRY(hipMemcpyAsync(&terms, b->groups, sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  b->n_groups = G; b->n_terms = terms;
+  if (n_terms) *n_terms = terms;
+  API_END(h)
 }
 
 int kprn_batch_num_paths(kprn_handle* h, const kprn_batch* b, int64_t* n) {

@@ -168,8 +168,11 @@ void materialize_step_rows(kprn_handle* h) {
   h->rows_view = h->step_rows; h->count_view = h->step_count; h->view_batch = nullptr;
 }
 
+// loss partials a training step over b may write: the BCE stage's workgroups (rectangular / ragged), or one per group of the pairwise stage
+static int64_t batch_partials(const kprn_batch* b) { return std::max<int64_t>(b->n_wg, b->n_groups); }
+
 void ensure_ws_common(kprn_handle* h, int64_t N, int64_t B, int64_t n_wg) {
-  const int64_t np = std::max<int64_t>(kk::loss_partials((int)B), n_wg);   // (n_wg: the loss-stage workgroups of a ragged batch)
+  const int64_t np = std::max<int64_t>(kk::loss_partials((int)B), n_wg);   // (n_wg: the loss-stage workgroups of a ragged batch, the groups of a pairwise loss)
   dev_grow2(h->stream, h->loss_partial, h->loss_partial_cap, np);
   Workspace& w = h->ws;
   const kprn_config& c = h->cfg;
@@ -267,7 +270,7 @@ void forward_impl(kprn_handle* h, const kprn_batch* b, int class_id, bool save_f
   const int64_t N = b->N;
   const int sel = (save_for_backward || !(every_class || all_scores)) ? class_id - 1 : -1;
   catch_up(h, b);
-  ensure_ws_common(h, N, b->B, b->n_wg);
+  ensure_ws_common(h, N, b->B, batch_partials(b));
   if (use_fused(h, b, save_for_backward)) {
     bool dual = false;
     if (save_for_backward && h->score_dual && h->score_rest_batch && h->score_rest_tile0 == 0 && h->ev_score_done) {
@@ -383,9 +386,20 @@ static void det_check(const kprn_handle* h, int T, const kprn_batch* b = nullptr
   if (why) throw KprnError{KPRN_E_UNSUPPORTED, std::string(h->deterministic == 1 ? "deterministic = 1" : "deterministic = 2") + ": training would run on " + why + ", which has no deterministic form; set deterministic = 0"};
 }
 
+// Option "loss" = "bpr": what the pairwise stage cannot serve, refused HERE, before anything is launched or any state is written.  b == null: kprn_train_step,
+// whose host buffers carry no groups.  inv_batch: the caller's scale (kprn_train_step_batch passes none)
+static void loss_check(const kprn_handle* h, const kprn_batch* b, float inv_batch) {
+  if (!h->loss_bpr) return;
+  KPRN_REQUIRE(b != nullptr, KPRN_E_UNSUPPORTED, "loss = bpr: kprn_train_step takes host buffers, which carry no group table; use a batch, kprn_batch_set_groups and kprn_train_step_batch");
+  KPRN_REQUIRE(b->labels != nullptr && b->n_groups > 0, KPRN_E_ARG, "loss = bpr: the batch has no group table (kprn_batch_set_groups; a refill of the slot drops it)");
+  KPRN_REQUIRE(h->cfg.world <= 1 || inv_batch > 0.f, KPRN_E_UNSUPPORTED,
+               "loss = bpr with world > 1: the scale 1 / n_terms would be this rank's alone; pass inv_batch = 1 / (the ranks' terms together) to kprn_backward_batch");
+}
+
 static void backward_impl(kprn_handle* h, const kprn_batch* b, int class_id, int literal, float inv_batch) {
   check_batch(h, b, class_id);
   det_check(h, b->T, b);
+  loss_check(h, b, inv_batch);
   generic::drop_check(h, b);
   KPRN_REQUIRE(b->labels != nullptr && b->has_index, KPRN_E_ARG, "batch has no labels (targets are required, MyOptimizer.lua:179)");
   const kprn_config& c = h->cfg;
@@ -398,9 +412,9 @@ static void backward_impl(kprn_handle* h, const kprn_batch* b, int class_id, int
   if (inv_batch <= 0.f && c.world > 1) invB = 1.0f / ((float)b->B * (float)c.world);
   const bool fusedp = use_fused(h, b, true);
   {
-    // pooling + sigmoid + select + BCE + reducer backward in one launch (the nn.Linear head's weight gradient is formed by the
-    // top layer's backward kernel, fused path, or by the generic pipeline's own head backward)
-    ProfScope ps(h, "loss_stage");
+    // pooling + sigmoid + select + BCE (or the pairwise loss over the batch's groups) + reducer backward in one launch (the nn.Linear head's weight gradient
+    // is formed by the top layer's backward kernel, fused path, or by the generic pipeline's own head backward)
+    ProfScope ps(h, h->loss_bpr ? "loss_stage_pairwise" : "loss_stage");
     kk::TransposeJob tj;  // fused path: the backward's W^T copies, stale after an update, are rebuilt by passenger workgroups
     const bool have_tj = fusedp && fused::transpose_job(h, &tj);
     kk::PoolJob pj{h->S2, 0, 0, 0, h->sel2, nullptr};
@@ -409,6 +423,12 @@ static void backward_impl(kprn_handle* h, const kprn_batch* b, int class_id, int
       pj.B = sb->B; pj.P = sb->P; pj.off = sb->off; pj.wave = sb->seg_wave; pj.cid = h->pool_defer_cid; h->pool_defer_batch = nullptr;
     }
     const kk::Segs g{b->B, b->P, b->off, b->wg, b->n_wg, b->seg_wave};   // (a ragged batch or a ragged passenger: the launcher takes the segmented form)
+    if (h->loss_bpr) {
+      const float scale = inv_batch > 0.f ? inv_batch : (b->n_terms > 0 ? 1.0f / (float)b->n_terms : 0.f);
+      h->loss_pending = kk::loss_stage_pairwise(h->stream, h->score_buf, b->labels, g, b->groups + 2, b->n_groups, c.C, cid, c.reducer, c.K, scale, w.sel, w.dS,
+                                                fusedp ? b->slot_of : nullptr, h->loss_partial, have_tj ? &tj : nullptr,
+                                                h->loss_early_armed ? h->loss_mirror : nullptr, pj.B > 0 ? &pj : nullptr);
+    } else
     h->loss_pending = kk::loss_stage(h->stream, h->score_buf, b->labels, g, c.C, cid, c.reducer, c.K, literal, invB, w.sel, w.dS, fusedp ? b->slot_of : nullptr,
                                      h->loss_partial, have_tj ? &tj : nullptr, h->loss_early_armed ? h->loss_mirror : nullptr, pj.B > 0 ? &pj : nullptr);
     if (h->loss_early_armed) {   // what kprn_train_step_batch waits for instead of the end of the step
@@ -888,13 +908,14 @@ int kprn_train_step_batch(kprn_handle* h, const kprn_batch* b, int32_t class_id,
   opt_check(h, opt);
   check_batch(h, b, class_id);
   det_check(h, b->T, b);
+  loss_check(h, b, 0.f);
   generic::drop_check(h, b);
   catch_up(h, b);
   if (!h->pad_clean) { zero_pad_tokens(h); fused::params_changed(h); bf16p::params_changed(h, false); }  // MyOptimizer.lua:181 (a no-op when the last step left them zero)
   // the loss goes back as soon as the loss stage has run (option "train_step_return" = "loss"); profiling and "drain" wait for the whole step as before
   struct Disarm { kprn_handle* h; ~Disarm() { h->loss_early_armed = false; } } disarm{h};
   if (loss && !h->train_step_drain && !h->prof_on) {
-    const int64_t np = std::max<int64_t>(kk::loss_partials(b->B), b->n_wg);   // (n_wg: the loss-stage workgroups of a ragged batch)
+    const int64_t np = std::max<int64_t>(kk::loss_partials(b->B), batch_partials(b));   // (as ensure_ws_common sizes the device partials)
     grow_pinned(h->loss_mirror, h->loss_mirror_cap, np, (size_t)(2 * np + 64) * sizeof(float), 2 * np + 64, {h->stream});
     if (!h->ev_loss) HIP_TRY(hipEventCreateWithFlags(&h->ev_loss, hipEventDisableTiming));
     h->loss_early_armed = true;
@@ -919,7 +940,7 @@ int kprn_train_step(kprn_handle* h, const int32_t* idx, int32_t B, int32_t P, in
                     const kprn_opt* opt, float* loss) {
   if (!h) return KPRN_E_ARG;
   if (!labels) { h->err = "assert(targets) (MyOptimizer.lua:179)"; return KPRN_E_ARG; }
-  try { opt_check(h, opt); det_check(h, T); } catch (const KprnError& e) { h->err = e.msg; return e.code; }   // (before the feed: a refused call uploads nothing)
+  try { opt_check(h, opt); det_check(h, T); loss_check(h, nullptr, 0.f); } catch (const KprnError& e) { h->err = e.msg; return e.code; }   // (before the feed: a refused call uploads nothing)
   // The minibatch goes through one of two engine-owned feed slots (grow-only capacity, page-locked staging: steady state allocates nothing and
   // frees nothing; alternating, so that the rows the lazy optimiser still names belong to the OTHER slot) instead of a batch created and
   // destroyed per call (two device allocations, a device-side index build with its synchronisations and three stream drains per step:
@@ -1513,6 +1534,12 @@ int kprn_set_option(kprn_handle* h, const char* key, const char* value) {
     // entity and table gradients -- replaced by slabs joined in index order; wherever "1" trains, "2" launches exactly what "1" launches.
     KPRN_REQUIRE(strcmp(value, "0") == 0 || strcmp(value, "1") == 0 || strcmp(value, "2") == 0, KPRN_E_ARG, "deterministic must be 0, 1 or 2");
     h->deterministic = value[0] - '0';
+  } else if (strcmp(key, "loss") == 0) {
+    // what kprn_backward_batch / kprn_train_step_batch train on: nn.BCECriterion per pair ("bce", default) or the pairwise loss over the batch's group table
+    // ("bpr"; include/kprn.h "pairwise loss").  Read at every training call; scoring, ranking, explaining and recommending never look at it.
+    if (strcmp(value, "bce") == 0) h->loss_bpr = 0;
+    else if (strcmp(value, "bpr") == 0) h->loss_bpr = 1;
+    else throw KprnError{KPRN_E_ARG, "loss must be bce or bpr"};
   } else if (strcmp(key, "dropout") == 0) {
     // rate p of nn.Dropout on every rnn layer's step input in training forwards (OneModel.lua:246-265); "0" (default): the kernels launched
     // before this option existed.  Refused HERE where the reference ignores the flag (lstm, gru) or the pipeline has no dropped form (bf16 products).

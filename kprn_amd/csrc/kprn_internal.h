@@ -90,6 +90,12 @@ struct kprn_batch {
   int32_t max_cnt = 0;        // longest segment
   int32_t seg_wave = 0;       // 1: a wave per pair (max_cnt > kk::RAGGED_THREAD_MAX), chosen when the batch is made
   std::vector<int32_t> hrag;  // host: off [B+1] | wg [n_wg+1], the source of their upload
+  // group table of the pairwise loss (kprn_batch_set_groups): an allocation of its own that only grows and goes with the batch; n_groups == 0: no table
+  // (slots::detach drops it with the contents it described)
+  int32_t* groups = nullptr;  // device: n_terms as one int64 (words 0, 1) | group_offsets [n_groups+1] from word 2
+  int64_t groups_cap = 0;     // words
+  int32_t n_groups = 0;
+  int64_t n_terms = 0;        // (positive, negative) pairs within the groups, counted on the device when the table was set
   int32_t* idx = nullptr;     // device [B,P,T,F]  ([N,T,F] when ragged)
   float* labels = nullptr;    // device [B] or null
   int32_t* uniq = nullptr;    // device: distinct entity rows of this batch (0-based); count at uniq[uniq_cap]
@@ -298,6 +304,7 @@ struct kprn_handle {
   // depends on the batch and the launch geometry only; pipelines that cannot do that refuse to train
   // "2" (generic fp32 pipelines too): 1 and 2 launch the same kernels wherever 1 trains; 2 adds the slab forms of the generic backward's joins
   int deterministic = 0;
+  int loss_bpr = 0;            // option "loss": 0 "bce" (nn.BCECriterion per pair) | 1 "bpr" (the pairwise loss over the batch's groups, include/kprn.h "pairwise loss")
   DetScratch det_slab;         // "2": where the generic backward's producers plain-store their partials (one buffer: producer and join are stream-ordered)
   float* det_seg = nullptr; int64_t det_seg_cap = 0;   // "2": bidx::DetEntity::seg_part of the row-major entity gradient [segments][2][de]
   // option "dropout" (rnn cell, fp32): nn.Dropout on every layer's step input in TRAINING forwards.  Masks are regenerated, never stored:
@@ -444,6 +451,13 @@ void pool_sigmoid(hipStream_t s, const float* S, const Segs& g, int C, int reduc
 // (slot_of nullable: dS[slot_of[n]]; partial_host: optional page-locked mirror of the per-workgroup loss partials)
 int loss_stage(hipStream_t s, const float* S, const float* labels, const Segs& g, int C, int cid, int reducer, int K, int literal, float invB, float* sel,
                float* dS, const int32_t* slot_of, float* partial, const TransposeJob* tj = nullptr, float* partial_host = nullptr, const PoolJob* pj = nullptr);
+// the loss stage under option "loss" = "bpr": a workgroup per group of the table go [G+1] (device), the same passengers; returns G, the number of partials
+constexpr int PAIRWISE_MAX_GROUP = 1024;   // pairs per group (KPRN_PAIRWISE_MAX_GROUP)
+int loss_stage_pairwise(hipStream_t s, const float* S, const float* labels, const Segs& g, const int32_t* go, int G, int C, int cid, int reducer, int K, float scale,
+                        float* sel, float* dS, const int32_t* slot_of, float* partial, const TransposeJob* tj = nullptr, float* partial_host = nullptr,
+                        const PoolJob* pj = nullptr);
+void count_pair_terms(hipStream_t s, const float* labels, const int32_t* go, int G, int64_t* out);   // *out (device) = sum over the groups of positives x negatives
+const char* pairwise_groups_why(const int32_t* go, int32_t G, int32_t B);   // what is wrong with a (host) group table over B pairs, or null
 void sum_partials(hipStream_t s, const float* partial, int n, float* out, int accumulate);
 int loss_partials(int B);  // number of per-workgroup loss partials the loss stage writes for B pairs of a rectangular batch (sizes the partial buffer)
 void zero_pad3(hipStream_t s, float* a, int na, float* b, int nb, float* c, int nc);

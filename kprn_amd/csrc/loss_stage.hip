@@ -11,6 +11,8 @@
 //      index order when the loss is asked for (reproducible: no atomics anywhere in this file)
 //   5  two passenger jobs in extra workgroups of the same launch: the fused backward's weight transposes (kk::TransposeJob) and the pooling
 //      stage of a scoring pass that rode in the training forward's launch (kk::PoolJob, "score_dual")
+//   2' the pairwise (BPR) loss over groups of pairs instead of stage 2 (option "loss" = "bpr"; include/kprn.h "pairwise loss"): k_loss_stage_pairwise, a
+//      workgroup per group, with the same stages 1, 3, 4 and 5 around it
 // (The head's weight gradient is NOT formed here: the fused top-layer backward or the generic pipeline's head_bwd does that.)
 //
 //   6  Two forms.  A batch is kk::Segs: B pairs of P paths each, or (off != null, a ragged batch -- an extension, the reference has one path
@@ -84,10 +86,8 @@ struct PairGrad {
   __device__ __forceinline__ float& operator()(int q) const { return slot ? dS[slot[q]] : dpair[q]; }
 };
 
-// Stages 1-3 for one pair by one thread; returns the probability
-__device__ float bce_pair(const float* __restrict__ s, int P, int C, int reducer, int K, int literal, float invB, float t, PairGrad d, float* lossterm) {
-  const float p = sigmoidf_(reduce_col(s, P, C, reducer, K));
-  const float dy = bce(p, t, literal, invB, lossterm);
+// Stage 3 for one pair by one thread: back through the reducer given dy = d loss / d (pooled value)
+__device__ void reducer_bwd(const float* __restrict__ s, int P, int C, int reducer, int K, float dy, PairGrad d) {
   if (reducer == 2) {
     float m = s[0];
     for (int q = 1; q < P; ++q) m = fmaxf(m, s[(int64_t)q * C]);
@@ -112,15 +112,18 @@ __device__ float bce_pair(const float* __restrict__ s, int P, int C, int reducer
       d(bi) = dy / (float)kk; last_v = best; last_i = bi;
     }
   }
+}
+
+// Stages 1-3 for one pair by one thread; returns the probability
+__device__ float bce_pair(const float* __restrict__ s, int P, int C, int reducer, int K, int literal, float invB, float t, PairGrad d, float* lossterm) {
+  const float p = sigmoidf_(reduce_col(s, P, C, reducer, K));
+  reducer_bwd(s, P, C, reducer, K, bce(p, t, literal, invB, lossterm), d);
   return p;
 }
 
-// The same by one wave (cnt > RAGGED_THREAD_MAX).  Path q's gradient is written by lane q % 64 only, so the TopK form's zero-then-set is one
-// thread's program order.
-__device__ float bce_pair_wave(const float* __restrict__ s, int cnt, int C, int reducer, int K, int literal, float invB, float t, PairGrad d, float* lossterm,
-                               int lane) {
-  const float p = sigmoidf_(reduce_col_wave(s, cnt, C, reducer, K, lane));
-  const float dy = bce(p, t, literal, invB, lossterm);
+// Stage 3 by one wave (cnt > RAGGED_THREAD_MAX; the whole wave calls, under wave-uniform control flow).  Path q's gradient is written by lane q % 64 only,
+// so the TopK form's zero-then-set is one thread's program order.
+__device__ void reducer_bwd_wave(const float* __restrict__ s, int cnt, int C, int reducer, int K, float dy, PairGrad d, int lane) {
   if (reducer == 2) {
     float m = -INFINITY;
     for (int q = lane; q < cnt; q += 64) m = fmaxf(m, s[(int64_t)q * C]);
@@ -146,7 +149,27 @@ __device__ float bce_pair_wave(const float* __restrict__ s, int cnt, int C, int 
       last_v = best; last_i = bi;
     }
   }
+}
+
+// Stages 1-3 for one pair by one wave
+__device__ float bce_pair_wave(const float* __restrict__ s, int cnt, int C, int reducer, int K, int literal, float invB, float t, PairGrad d, float* lossterm,
+                               int lane) {
+  const float p = sigmoidf_(reduce_col_wave(s, cnt, C, reducer, K, lane));
+  reducer_bwd_wave(s, cnt, C, reducer, K, bce(p, t, literal, invB, lossterm), d, lane);
   return p;
+}
+
+// ---------------------------------------------------------------------------------------
+// Stage 5, the passengers: workgroup rb of the pooling job (k_pool<SEG, false>'s items of pj's batch) / of the transposes (64 workgroups per 256x64 matrix)
+template <bool SEG>
+__device__ __forceinline__ void pool_passenger(int rb, int tid, int C, int reducer, int K, const kk::PoolJob& pj) {
+  const int b = (SEG && pj.wave) ? rb * 4 + (tid >> 6) : rb * 256 + tid;
+  if (b >= pj.B) return;
+  pool_pair<SEG>(pj.S, pj.off, pj.P, pj.wave, tid & 63, b, pj.cid, C, reducer, K, nullptr, nullptr, 0, pj.cid, pj.sel, pj.sel_host);
+}
+__device__ __forceinline__ void transpose_passenger(int rb, int tid, const kk::TransposeJob& tj) {
+  const int m = rb >> 6, i = (rb & 63) * 256 + tid;  // over the 64*256 outputs of matrix m
+  tj.WT[m][i] = tj.W[m][(i & 255) * 64 + (i >> 8)];
 }
 
 // ---------------------------------------------------------------------------------------
@@ -159,17 +182,12 @@ __global__ __launch_bounds__(256) void k_loss_stage(const float* __restrict__ S,
                                                     const int32_t* __restrict__ slot_of, float* __restrict__ partial, int n_loss_blocks, kk::TransposeJob tj,
                                                     float* __restrict__ partial_host, kk::PoolJob pj) {
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  if ((int)blockIdx.x >= n_loss_blocks + 64 * tj.n) {  // (workgroup-uniform) passenger: the pooling stage of a scoring pass, k_pool<SEG, false>'s items
-    const int rb = (int)blockIdx.x - n_loss_blocks - 64 * tj.n;
-    const int b = (SEG && pj.wave) ? rb * 4 + wv : rb * 256 + tid;
-    if (b >= pj.B) return;
-    pool_pair<SEG>(pj.S, pj.off, pj.P, pj.wave, lane, b, pj.cid, C, reducer, K, nullptr, nullptr, 0, pj.cid, pj.sel, pj.sel_host);
+  if ((int)blockIdx.x >= n_loss_blocks + 64 * tj.n) {  // (workgroup-uniform) passenger: the pooling stage of a scoring pass
+    pool_passenger<SEG>((int)blockIdx.x - n_loss_blocks - 64 * tj.n, tid, C, reducer, K, pj);
     return;
   }
   if ((int)blockIdx.x >= n_loss_blocks) {  // (workgroup-uniform) passenger: 256x64 weight transposes
-    const int rb = blockIdx.x - n_loss_blocks;
-    const int m = rb >> 6, i = (rb & 63) * 256 + tid;  // over the 64*256 outputs of matrix m
-    tj.WT[m][i] = tj.W[m][(i & 255) * 64 + (i >> 8)];
+    transpose_passenger((int)blockIdx.x - n_loss_blocks, tid, tj);
     return;
   }
   __shared__ float lossw[PPW];
@@ -201,6 +219,132 @@ __global__ __launch_bounds__(256) void k_loss_stage(const float* __restrict__ S,
     partial[blockIdx.x] = s;
     if (partial_host) partial_host[blockIdx.x] = s;   // page-locked mirror: the host adds the partials itself (kprn_train_step's early loss)
   }
+}
+
+// ---------------------------------------------------------------------------------------
+// Stage 2': the pairwise loss (include/kprn.h "pairwise loss"), the one statement of its fp32 formula for the kernel and for kprn_host_pairwise_loss.
+__host__ __device__ inline float softplusf_(float x) { return fmaxf(x, 0.f) + log1pf(expf(-fabsf(x))); }
+// A running fp32 sum with Kahan's compensation: a member of a full group adds 1023 addends, and a plain running sum of that many loses a few 1e-7 of the
+// result -- the size of the bar the rule is tested at.  (No product anywhere in add: nothing for the compiler to contract.)
+struct KahanSum {
+  float sum = 0.f, comp = 0.f;
+  __host__ __device__ inline void add(float x) { const float v = x - comp; const float t = sum + v; comp = (t - sum) - v; sum = t; }
+};
+// Member i of a group of n pairs with pooled values y and label bits pos: *dy = d loss / d y[i] over its partners in ascending index, *term = the sum of its
+// loss terms (a positive's; unscaled).  A member without a partner gets +0.0f twice.
+__host__ __device__ inline void pairwise_member(const float* y, const unsigned char* pos, int n, int i, float s, float* dy, float* term) {
+  const float yi = y[i];
+  KahanSum sg, lt;
+  int partners = 0;
+  if (pos[i]) {
+    for (int j = 0; j < n; ++j)
+      if (!pos[j]) { sg.add(1.0f / (1.0f + expf(yi - y[j]))); lt.add(softplusf_(y[j] - yi)); ++partners; }
+    *dy = partners ? -s * sg.sum : 0.f;
+  } else {
+    for (int j = 0; j < n; ++j)
+      if (pos[j]) { sg.add(1.0f / (1.0f + expf(y[j] - yi))); ++partners; }
+    *dy = partners ? s * sg.sum : 0.f;
+  }
+  *term = lt.sum;
+}
+
+constexpr int PW_MAX = kk::PAIRWISE_MAX_GROUP;
+static_assert(PW_MAX == KPRN_PAIRWISE_MAX_GROUP, "the header states the limit");
+
+// The loss stage under option "loss" = "bpr" in one launch: workgroup w < G does stages 1, 2', 3 and 4 for group w = the pairs go[w] .. go[w+1]-1 (at most
+// PW_MAX: kprn_batch_set_groups has checked the table); the workgroups behind them are k_loss_stage's passengers.  A pair takes the reducer form the BCE stage
+// gives it: a thread, or (a ragged batch in wave form, more than RAGGED_THREAD_MAX paths) a wave -- so sel and the pooled values have that stage's bits.
+// Every pair's dS entries are written, zeros where the pair has no term.  s: the scale of the rule (0 when the batch has no term).
+// LDS: y, dy and the members' term sums, 3 x 4 KiB, and the label bits, 1 KiB.
+template <bool SEG>
+__global__ __launch_bounds__(256) void k_loss_stage_pairwise(const float* __restrict__ S, const float* __restrict__ labels, kk::Segs g, const int32_t* __restrict__ go,
+                                                             int G, int C, int cid, int reducer, int K, float s, float* __restrict__ sel, float* __restrict__ dS,
+                                                             const int32_t* __restrict__ slot_of, float* __restrict__ partial, kk::TransposeJob tj,
+                                                             float* __restrict__ partial_host, kk::PoolJob pj) {
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  if ((int)blockIdx.x >= G + 64 * tj.n) {  // (workgroup-uniform)
+    pool_passenger<SEG>((int)blockIdx.x - G - 64 * tj.n, tid, C, reducer, K, pj);
+    return;
+  }
+  if ((int)blockIdx.x >= G) {  // (workgroup-uniform)
+    transpose_passenger((int)blockIdx.x - G, tid, tj);
+    return;
+  }
+  __shared__ float y_s[PW_MAX], dy_s[PW_MAX], term_s[PW_MAX];
+  __shared__ unsigned char pos_s[PW_MAX];
+  const int32_t* off = SEG ? g.off : nullptr;
+  const bool wave = SEG && g.wave;
+  const int b0 = go[blockIdx.x], n = go[blockIdx.x + 1] - b0;
+  // 1: member i belongs to thread i % 256, or (wave form, a long pair) to wave i % 4 (i and the pair's count are wave-uniform there)
+  for (int i = tid; i < n; i += 256) {
+    const int b = b0 + i;
+    const int cnt = seg_count(off, g.P, b);
+    pos_s[i] = labels[b] > 0.5f ? 1 : 0;
+    if (wave && cnt > kk::RAGGED_THREAD_MAX) continue;
+    const float y = reduce_col(S + seg_begin(off, g.P, b) * C + cid, cnt, C, reducer, K);
+    y_s[i] = y;
+    sel[b] = sigmoidf_(y);
+  }
+  if (wave) {
+    for (int i = wv; i < n; i += 4) {
+      const int b = b0 + i;
+      const int cnt = seg_count(off, g.P, b);
+      if (cnt <= kk::RAGGED_THREAD_MAX) continue;
+      const float y = reduce_col_wave(S + seg_begin(off, g.P, b) * C + cid, cnt, C, reducer, K, lane);
+      if (lane == 0) { y_s[i] = y; sel[b] = sigmoidf_(y); }
+    }
+  }
+  __syncthreads();
+  // 2'
+  for (int i = tid; i < n; i += 256) {
+    float dy, lt;
+    pairwise_member(y_s, pos_s, n, i, s, &dy, &lt);
+    dy_s[i] = dy; term_s[i] = lt;
+  }
+  __syncthreads();
+  // 4: the group's terms in index order, scaled once
+  if (tid == 0) {
+    KahanSum acc;
+    for (int i = 0; i < n; ++i) acc.add(term_s[i]);
+    const float a = acc.sum * s;
+    partial[blockIdx.x] = a;
+    if (partial_host) partial_host[blockIdx.x] = a;
+  }
+  // 3: the split of 1
+  for (int i = tid; i < n; i += 256) {
+    const int b = b0 + i;
+    const int cnt = seg_count(off, g.P, b);
+    if (wave && cnt > kk::RAGGED_THREAD_MAX) continue;
+    const int64_t n0 = seg_begin(off, g.P, b);
+    reducer_bwd(S + n0 * C + cid, cnt, C, reducer, K, dy_s[i], PairGrad{dS + n0, dS, slot_of ? slot_of + n0 : nullptr});
+  }
+  if (wave) {
+    for (int i = wv; i < n; i += 4) {
+      const int b = b0 + i;
+      const int cnt = seg_count(off, g.P, b);
+      if (cnt <= kk::RAGGED_THREAD_MAX) continue;
+      const int64_t n0 = seg_begin(off, g.P, b);
+      reducer_bwd_wave(S + n0 * C + cid, cnt, C, reducer, K, dy_s[i], PairGrad{dS + n0, dS, slot_of ? slot_of + n0 : nullptr}, lane);
+    }
+  }
+}
+
+// n_terms of a group table: positives x negatives of every group, in integers (one workgroup; thread t takes the groups t, t + 256, ...)
+__global__ __launch_bounds__(256) void k_count_pair_terms(const float* __restrict__ labels, const int32_t* __restrict__ go, int G, unsigned long long* __restrict__ out) {
+  __shared__ unsigned long long acc[256];
+  unsigned long long a = 0;
+  for (int w = threadIdx.x; w < G; w += 256) {
+    unsigned long long np = 0, nn = 0;
+    for (int b = go[w]; b < go[w + 1]; ++b) { if (labels[b] > 0.5f) ++np; else ++nn; }
+    a += np * nn;
+  }
+  acc[threadIdx.x] = a;
+  __syncthreads();
+  for (int m = 128; m > 0; m >>= 1) {
+    if ((int)threadIdx.x < m) acc[threadIdx.x] += acc[threadIdx.x + m];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) *out = acc[0];
 }
 
 // loss = fixed-order sum of the per-workgroup partials (reproducible)
@@ -257,6 +401,40 @@ int loss_stage(hipStream_t s, const float* S, const float* labels, const Segs& g
   return nlb;
 }
 
+int loss_stage_pairwise(hipStream_t s, const float* S, const float* labels, const Segs& g, const int32_t* go, int G, int C, int cid, int reducer, int K, float scale,
+                        float* sel, float* dS, const int32_t* slot_of, float* partial, const TransposeJob* tj, float* partial_host, const PoolJob* pj) {
+  if (g.B <= 0 || G <= 0) return 0;
+  TransposeJob t;
+  memset(&t, 0, sizeof(t));
+  if (tj) t = *tj;
+  PoolJob pjob;
+  memset(&pjob, 0, sizeof(pjob));
+  if (pj) pjob = *pj;
+  const bool seg = g.off || pjob.off;
+  const int npb = (int)nblocks(pjob.B, seg && pjob.wave ? 4 : 256);
+  hipLaunchKernelGGL(seg ? k_loss_stage_pairwise<true> : k_loss_stage_pairwise<false>, dim3((unsigned)(G + 64 * t.n + npb)), dim3(256), 0, s, S, labels, g, go, G, C,
+                     cid, reducer, K, scale, sel, dS, slot_of, partial, t, partial_host, pjob);
+  CHECK_LAUNCH();
+  return G;
+}
+
+void count_pair_terms(hipStream_t s, const float* labels, const int32_t* go, int G, int64_t* out) {
+  hipLaunchKernelGGL(k_count_pair_terms, dim3(1), dim3(256), 0, s, labels, go, G, (unsigned long long*)out);
+  CHECK_LAUNCH();
+}
+
+// a group table over B consecutive pairs: go[0] = 0, go[G] = B, non-decreasing, no group above PAIRWISE_MAX_GROUP (no device, no handle)
+const char* pairwise_groups_why(const int32_t* go, int32_t G, int32_t B) {
+  if (!go || G < 1 || B < 1) return "group_offsets is NULL, or G or B is below 1";
+  if (go[0] != 0) return "group_offsets[0] must be 0";
+  for (int32_t w = 0; w < G; ++w) {
+    if (go[w + 1] < go[w]) return "group_offsets must not decrease";
+    if (go[w + 1] - go[w] > PAIRWISE_MAX_GROUP) return "a group holds more than 1024 pairs (KPRN_PAIRWISE_MAX_GROUP)";
+  }
+  if (go[G] != B) return "group_offsets[G] must be the batch's number of pairs";
+  return nullptr;
+}
+
 // Offsets, loss-stage workgroup table and the reducer form of a ragged batch (no device, no handle: kprn_host_ragged_plan).  A workgroup takes
 // consecutive pairs while it holds fewer than RAGGED_WG_PAIRS pairs and the next pair keeps it within RAGGED_WG_PATHS paths; a pair longer than that
 // is a workgroup of its own.  Equal counts <= 28 therefore cut as the rectangular loss stage does (RAGGED_WG_PAIRS pairs each).
@@ -288,3 +466,36 @@ void sum_partials(hipStream_t s, const float* partial, int n, float* out, int ac
 }
 
 }  // namespace kk
+
+// The pairwise rule on the host cores (no handle, no GPU): pairwise_member per pair, a group's terms added in index order and scaled once, the groups'
+// partials added in group order -- the kernel's and k_sum_partials' order.
+extern "C" int kprn_host_pairwise_loss(const float* pooled, const float* labels, const int32_t* group_offsets, int32_t G, int32_t B, float inv_batch, float* dy,
+                                       float* loss, int64_t* n_terms) {
+  if (!pooled || !labels || !dy || !loss || !n_terms || kk::pairwise_groups_why(group_offsets, G, B)) return KPRN_E_ARG;
+  try {
+    std::vector<unsigned char> pos((size_t)B);
+    for (int32_t b = 0; b < B; ++b) pos[b] = labels[b] > 0.5f ? 1 : 0;
+    int64_t terms = 0;
+    for (int32_t w = 0; w < G; ++w) {
+      int64_t np = 0;
+      for (int32_t b = group_offsets[w]; b < group_offsets[w + 1]; ++b) np += pos[b];
+      terms += np * (group_offsets[w + 1] - group_offsets[w] - np);
+    }
+    const float s = inv_batch > 0.f ? inv_batch : (terms > 0 ? 1.0f / (float)terms : 0.f);
+    float total = 0.f;
+    for (int32_t w = 0; w < G; ++w) {
+      const int32_t b0 = group_offsets[w], n = group_offsets[w + 1] - b0;
+      KahanSum acc;
+      for (int32_t i = 0; i < n; ++i) {
+        float lt;
+        pairwise_member(pooled + b0, pos.data() + b0, n, i, s, dy + b0 + i, &lt);
+        acc.add(lt);
+      }
+      const float a = acc.sum * s;
+      total += a;
+    }
+    *loss = total;
+    *n_terms = terms;
+  } catch (...) { return KPRN_E_NOMEM; }
+  return KPRN_OK;
+}

@@ -229,12 +229,27 @@ def recommend_users(eng, kg, sampler, users, K, M=0, min_hops=1, max_hops=3, max
         batch.free()
 
 
+def groups_from_counts(counts, n_neg):
+    """The group table of a minibatch that find_training_paths made: rows g (1 + n_neg) .. of its pair list are group g (one positive, then that user's
+    negatives), a row with counts == 0 was dropped from the batch, so group g owns the sum(counts[rows] > 0) consecutive pairs that are left -- none, when
+    all of its rows were dropped.  -> group_offsets [G + 1] int32 for Batch.set_groups"""
+    per = 1 + max(int(n_neg), 0)
+    kept = (np.asarray(counts).reshape(-1) > 0)
+    if kept.shape[0] % per != 0:
+        raise ValueError("counts holds %d rows, not a multiple of 1 + n_neg = %d" % (kept.shape[0], per))
+    sizes = kept.reshape(-1, per).sum(axis=1)
+    return np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
+
+
 def train_from_graph(eng, kg, positives, opt, minibatch, n_neg, num_epochs, seed, sampler=None, max_attempts=16, min_hops=2, max_hops=3, max_paths=28, T=None,
-                     class_id=1, epoch_hooks=(), start_iteration=1, gradient_step_counter=100, out=None, stats=None, walks=0):
+                     class_id=1, epoch_hooks=(), start_iteration=1, gradient_step_counter=100, out=None, stats=None, walks=0, loss="bce"):
     """Training from a knowledge graph alone: every step samples its negatives, finds the paths and trains, all on the device.
     positives [n, 2] = (user, item) entity ids (KnowledgeGraph.interactions); sampler: an _ffi.Sampler (None: the positives' distinct items, uniform).
     Each epoch e shuffles the positives with np.random.RandomState(seed + e) and walks them `minibatch` at a time; a step is
     Engine.find_training_paths (seed, draw = the global step number) -> train_step -> free.  A minibatch in which no pair has a path is skipped and counted.
+    loss = "bpr": the pairwise loss over each positive's group (include/kprn.h "pairwise loss") instead of BCE on each pair: the engine's option "loss" is set
+    for the run and put back afterwards, every step sets the batch's group table (groups_from_counts), and a minibatch without a term -- no group kept both
+    its positive and a negative -- is skipped and counted as well.
     walks > 0: max_hops may be 4 or 5, the hops past 3 sampled by `walks` walks per pair and hop count under the same seed and draw.
     Losses are summed on the device (option "loss_accumulate"); the epoch lines and hooks (OptimizerCallback) are MyOptimizer's.
     -> the epochs' average losses; stats (a dict, optional) receives steps / skipped / pairs."""
@@ -252,9 +267,13 @@ def train_from_graph(eng, kg, positives, opt, minibatch, n_neg, num_epochs, seed
     for hook in epoch_hooks:
         if hook.epochHookFreq == 1:
             hook.hook(0)
+    if loss not in ("bce", "bpr"):
+        raise ValueError("loss must be bce or bpr")
+    loss_before = eng.options.get("loss", "bce")
     eng.set_option("loss_accumulate", "1")
     eng.loss_sum(reset=True)
     try:
+        eng.set_option("loss", loss)
         draw = 0
         prev = time.time()
         for i in range(int(start_iteration), int(num_epochs) + 1):
@@ -269,6 +288,9 @@ def train_from_graph(eng, kg, positives, opt, minibatch, n_neg, num_epochs, seed
                     st["skipped"] += 1
                     continue
                 try:
+                    if loss == "bpr" and batch.set_groups(groups_from_counts(counts, n_neg)) == 0:
+                        st["skipped"] += 1
+                        continue
                     eng.train_step(batch, opt, class_id, want_loss=False)
                 finally:
                     batch.free()
@@ -292,6 +314,7 @@ def train_from_graph(eng, kg, positives, opt, minibatch, n_neg, num_epochs, seed
                     hook.hook(i)
     finally:
         eng.set_option("loss_accumulate", "0")
+        eng.set_option("loss", loss_before)
         if own:
             sampler.free()
     if stats is not None:

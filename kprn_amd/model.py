@@ -55,6 +55,8 @@ def flag_parser():
     a("-negatives", type=int, default=4); a("-neg_alpha", type=float, default=0.0, help="negatives are drawn with weight (item's interactions)^neg_alpha; 0 = uniform")
     a("-neg_attempts", type=int, default=16); a("-min_hops", type=int, default=2); a("-max_hops", type=int, default=3); a("-max_paths", type=int, default=28)
     a("-sampleSeed", type=int, default=1)
+    a("-loss", default="bce", choices=["bce", "bpr"],
+      help="with -kg: bce = nn.BCECriterion on each pair by itself; bpr = the pairwise ranking loss of each positive against its own sampled negatives (the engine's option \"loss\")")
     a("-walks", type=int, default=0, help="walks per pair and hop count that sample the paths of 4 and 5 hops (1..256); needed when -max_hops is above 3")
     return p
 
@@ -75,6 +77,8 @@ def parse_flags(argv=None):
     params = p.parse_args(argv)
     if params.kg and not (params.vocab_dir and params.interaction_rel):
         p.error("-kg needs -vocab_dir DIR (the vocabulary files) and -interaction_rel NAME (the relation of the user-item edges to train on)")
+    if params.loss == "bpr" and not params.kg:
+        p.error("-loss bpr needs -kg: the groups it ranks within (a positive and its sampled negatives) exist only when training from a graph")
     check_walks(params.max_hops, params.walks, p.error)
     return params
 

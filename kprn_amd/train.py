@@ -7,7 +7,8 @@ files), same epoch log lines, checkpoint "<model>-latest" every saveFrequency ep
 With `-kg triples.tsv -vocab_dir DIR -interaction_rel NAME` (an extension) there are no path files: the (user, item) edges of that relation are the
 positives, and every step samples -negatives items per positive (an item's weight is its number of interactions to the power -neg_alpha's value, 0 =
 uniform; at most -neg_attempts draws per negative), finds the pairs' paths of -min_hops .. -max_hops hops (at most -max_paths each; -max_hops 4 or 5 needs -walks N, the walks that sample the paths of more than 3 hops) and trains, all on the device (graph.train_from_graph); -sampleSeed seeds the shuffles
-and the draws.  Same epoch lines, same -model / -saveFrequency.
+and the draws.  Same epoch lines, same -model / -saveFrequency.  -loss bpr trains on the pairwise ranking loss of each positive against its own sampled
+negatives instead of BCE on each pair (include/kprn.h "pairwise loss"); it needs -kg.
 """
 import os
 import sys
@@ -59,7 +60,8 @@ def train_from_kg(params, eng, callbacks):
     print("Training from the graph: %d positives, %d candidate items, %d negatives each" % (len(positives), len(items), params.negatives))
     graph.train_from_graph(eng, kg, positives, model.opt_from_flags(params), params.minibatch, params.negatives, params.numEpochs, params.sampleSeed,
                            sampler=sampler, max_attempts=params.neg_attempts, min_hops=params.min_hops, max_hops=params.max_hops, max_paths=params.max_paths,
-                           epoch_hooks=callbacks, start_iteration=params.startIteration, gradient_step_counter=params.gradientStepCounter, walks=params.walks)
+                           epoch_hooks=callbacks, start_iteration=params.startIteration, gradient_step_counter=params.gradientStepCounter, walks=params.walks,
+                           loss=params.loss)
     return 0
 
 
