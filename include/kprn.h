@@ -638,6 +638,10 @@ int kprn_profile_get(kprn_handle* h, kprn_prof_entry* out, int32_t cap, int32_t*
  *   "persist_layers"  "1" (default): a recurrent layer of the generic fp32 pipeline (FastLSTM / rnn, Din % 4 == 0, Din, H <= 256) runs as ONE
  *                     persistent launch, forward and BPTT, once the batch gives every CU a 64-path tile; "2": at any batch size; "0": one launch
  *                     per step
+ *   "persist_layers_grid" "0" (default): those launches run min(tiles, CUs) workgroups; "n" > 0: at most n, so that a workgroup walks several 64-path tiles at
+ *                     batch sizes a float64 reference handles (tests; same results up to fp32 re-association of the bias and weight gradient sums; the forward
+ *                     is bit-identical).  Per handle, read at every launch.  A value above the CU count (or above the batch's tile count) has no effect.  Negative or not a
+ *                     number: KPRN_E_ARG
  *   "bf16_gemm_pingpong" "0" (default) | "1", "bf16_gemm_regstage" "0" | "1", "bf16_gemm_touch" "0" | chunks ahead, "bf16_t_pad" "64" | 0..512
  *                     (elements, a multiple of 8): measured alternatives of the bf16 split-K dW product (two wave groups one barrier apart; operands
  *                     staged through registers; L2 prefetch by touch; row pitch of its transposed operands) -- none faster than the default,

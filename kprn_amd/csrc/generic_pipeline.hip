@@ -319,7 +319,8 @@ void forward(kprn_handle* h, const kprn_batch* b, bool save) {
       // all T steps of the layer in ONE persistent launch: h (and c) never leave the CU, weights stream L2 -> LDS by DMA (layer_f32_persist.hip).  A scoring
       // pass needs the top layer's last step only; the training forward writes every step
       ProfScope ps(h, cell.layer_fwd);
-      lp32::forward_layer(s, cell.id, in, N, T, Din, H, y.Wi, y.Wo, y.bi, y.bo, y.hs, y.cs, y.act, y.mask, cell.relu, save, /*write_all_h=*/y.has_up, y.Wc, y.Uc, y.bc);
+      lp32::forward_layer(s, cell.id, in, N, T, Din, H, y.Wi, y.Wo, y.bi, y.bo, y.hs, y.cs, y.act, y.mask, cell.relu, save, /*write_all_h=*/y.has_up, y.Wc, y.Uc, y.bc,
+                          h->persist_layers_grid);
     } else if (stepk) {
       // one launch per step: [x_t | h_{t-1}] [W_i2g | W_o2g]^T + b with the cell in the epilogue (gemm_tiled.hip); FastLSTM: gate values are written only
       // when a backward follows; rnn: both biases, the activation and MaskZero
@@ -370,7 +371,7 @@ void backward(kprn_handle* h, const kprn_batch* b, int cid) {
       ProfScope ps(h, cell.layer_bwd);
       float* wot = dev_grow(s, h->lp_wot, h->lp_wot_cap, (int64_t)lp32::bptt_scratch_floats(H, cell.wi_rows));   // W_o2g^T (gru: [c_h2h^T | o2g^T])
       lp32::bptt_layer(s, cell.id, cell.id == 1 ? nullptr : y.act, y.cs, cell.id == 0 ? nullptr : y.hs, y.mask, y.has_up ? w.dIn : w.dH, y.has_up, y.Wo, wot, w.dA, N, T, H,
-                       cell.relu, y.Uc, det ? nullptr : y.gbi, det ? nullptr : y.gb2);
+                       cell.relu, y.Uc, det ? nullptr : y.gbi, det ? nullptr : y.gb2, h->persist_layers_grid);
     } else backward_steps(h, cell, y, T, N, bf);
     if (T > 1) {
       ProfScope ps(h, "gemm_o2g_bwd_dw");

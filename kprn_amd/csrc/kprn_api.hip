@@ -1439,6 +1439,13 @@ int kprn_set_option(kprn_handle* h, const char* key, const char* value) {
     const int v = atoi(value);
     KPRN_REQUIRE(v >= 0 && v <= 2, KPRN_E_ARG, "persist_layers must be 0, 1 or 2");
     h->persist_layers = v;
+  } else if (strcmp(key, "persist_layers_grid") == 0) {
+    // those launches' workgroup count: min(tiles, CUs) ("0", default) or at most this many ("n" > 0: a workgroup then runs several tiles at batch sizes a
+    // float64 reference handles -- tests).  Per handle, read at every launch.
+    char* end = nullptr;
+    const long v = strtol(value, &end, 10);
+    KPRN_REQUIRE(end != value && *end == 0 && v >= 0 && v <= 0x7fffffff, KPRN_E_ARG, "persist_layers_grid must be 0 (one workgroup per CU at most) or a positive workgroup count");
+    h->persist_layers_grid = (int)v;
   } else if (strcmp(key, "small_tables") == 0) {
     // generic fp32 pipelines: layer 0's type / relation gradients from G = dA^T [S_r | S_t] ("1", default) or from the full dx product + the
     // table-gradient launch ("0": the A/B reference)

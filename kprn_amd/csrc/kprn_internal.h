@@ -249,6 +249,7 @@ struct kprn_handle {
   bool score_pending = false;     // a pass is (possibly) still running on score_stream
   int bf16_bptt_dxe = 8;          // option "bf16_bptt_dxe": the persistent BPTT launch also forms dx for the entity slice (weight ring depth 8 | 16; 0: a separate product)
   int persist_layers = 1;     // option "persist_layers": generic fp32 LSTM / rnn layers as one persistent launch per layer where the shape allows (layer_f32_persist.hip)
+  int persist_layers_grid = 0;   // option "persist_layers_grid": > 0 caps the workgroup count of those launches (tests: several tiles per workgroup at small N); 0: min(tiles, CUs)
   bool small_tables_fwd = true;   // option "small_tables_fwd": the fused D = H = 64 forward multiplies [S | x_e] by [Q ; W_i2g[:, e cols]^T] in layer 0 (lstm_fused_fwd.hip fwd_body IDENT)
   bool head_select = true;        // option "head_select": the fused fp32 forward's head forms column classId alone when no reader of the pass needs another (lstm_fused_fwd.hip head_tile_sel)
   bool small_tables = true;       // option "small_tables": generic fp32 pipelines (LSTM / rnn cells) form the layer-0 type / relation gradients from G (generic_pipeline.hip small_tables_route)
@@ -858,14 +859,16 @@ bool supported(int cell /*0 FastLSTM, 1 rnn, 2 gru*/, int64_t N, int Din, int H,
 // [T][N][H] (rnn) in the generic backward's layouts; mask [T][N] (rnn: MaskZero)
 void forward_layer(hipStream_t s, int cell, const float* in, int64_t N, int T, int Din, int H, const float* Wi, const float* Wo, const float* bi, const float* bo,
                    float* hs, float* cs, float* act, const float* mask, int relu, bool save, bool write_all_h, const float* Wc = nullptr /*gru: c_i2h.weight*/,
-                   const float* Uc = nullptr /*gru: c_h2h.weight*/, const float* bc = nullptr /*gru: c_i2h.bias*/);
+                   const float* Uc = nullptr /*gru: c_h2h.weight*/, const float* bc = nullptr /*gru: c_i2h.bias*/,
+                   int grid_cap = 0 /*option "persist_layers_grid": > 0 caps the launch's workgroup count; 0: min(tiles, CUs)*/);
 // (gru: Wi / bi / Wo are i2g.weight [2H][Din] / i2g.bias / o2g.weight [2H][H]; act [T][N][4H] = [r | z | n | r * h'] when save)
 // BPTT through the layer (cell backward of all T steps + dh_{t-1} = dA_t W_o2g) as one persistent launch; dA [T][N][GH] out (GH = 4H FastLSTM, H rnn)
 bool bptt_supported(int cell, int64_t N, int H, bool force);
 size_t bptt_scratch_floats(int H, int GH);
 void bptt_layer(hipStream_t s, int cell, const float* act, const float* cs, const float* hs, const float* mask, const float* dHup, bool up, const float* Wo,
                 float* wot, float* dA, int64_t N, int T, int H, int relu, const float* Uc = nullptr /*gru: c_h2h.weight; Wo = o2g.weight [2H][H], wot of bptt_scratch_floats(H, 3H)*/,
-                float* dbias = nullptr, float* dbias2 = nullptr /*bptt_sums_bias(): the layer's bias gradient(s) += the column sums of dA, formed inside the launch*/);
+                float* dbias = nullptr, float* dbias2 = nullptr /*bptt_sums_bias(): the layer's bias gradient(s) += the column sums of dA, formed inside the launch*/,
+                int grid_cap = 0 /*as forward_layer's*/);
 bool bptt_sums_bias(int cell, int H);
 }  // namespace lp32
 

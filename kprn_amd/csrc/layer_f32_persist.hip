@@ -1110,6 +1110,12 @@ static int num_cus() {
   }
   return n;
 }
+// workgroups of a launch: one per CU at most, every one with a tile; cap > 0 (option "persist_layers_grid"): that many at most
+static int launch_grid(int64_t tiles, int cap) {
+  int64_t g = std::min<int64_t>(tiles, num_cus());
+  if (cap > 0) g = std::min<int64_t>(g, cap);
+  return (int)g;
+}
 static size_t lds_need(int Din, int H, int R) {
   const int KX = (Din + 31) & ~31, KH = (H + 31) & ~31;
   return (size_t)ROWS * (KX + KH + 4) * 4 + (size_t)4 * R * GB + (size_t)BS_FLOATS * 4;
@@ -1125,7 +1131,8 @@ bool supported(int cell, int64_t N, int Din, int H, bool force) {
 }
 
 void forward_layer(hipStream_t s, int cell, const float* in, int64_t N, int T, int Din, int H, const float* Wi, const float* Wo, const float* bi, const float* bo,
-                   float* hs, float* cs, float* act, const float* mask, int relu, bool save, bool write_all_h, const float* Wc, const float* Uc, const float* bc) {
+                   float* hs, float* cs, float* act, const float* mask, int relu, bool save, bool write_all_h, const float* Wc, const float* Uc, const float* bc,
+                   int grid_cap) {
   LArgs a;
   memset(&a, 0, sizeof(a));
   a.in = in; a.N = N; a.T = T; a.Din = Din; a.H = H; a.Wi = Wi; a.Wo = Wo; a.bi = bi; a.bo = bo; a.hs = hs; a.cs = cs; a.act = act; a.mask = mask;
@@ -1135,7 +1142,7 @@ void forward_layer(hipStream_t s, int cell, const float* in, int64_t N, int T, i
   a.KX = (Din + 31) & ~31; a.KH = (H + 31) & ~31; a.PITCH = a.KX + a.KH + 4;
   a.R = lds_need(Din, H, 3) <= (size_t)160 * 1024 ? 3 : 2;
   const size_t lds = lds_need(Din, H, a.R);
-  const int grid = (int)std::min<int64_t>(a.tiles, num_cus());
+  const int grid = launch_grid(a.tiles, grid_cap);
   typedef void (*Kern)(LArgs);
   Kern k = nullptr;
   if (cell == 1) k = save ? (Kern)k_layer<1, 1, true> : (Kern)k_layer<1, 1, false>;
@@ -1170,7 +1177,7 @@ size_t bptt_scratch_floats(int H, int GH) { return (size_t)(H + 8) * GH + 1024; 
 // act / cs / hs / mask: the forward's saves (generic layouts); dHup: the gradient from above ([T][N][H] when up, else the head's [N][H], applied at
 // t = T-1); Wo [GH][H]; wot: scratch of bptt_scratch_floats(); dA out [T][N][GH]
 void bptt_layer(hipStream_t s, int cell, const float* act, const float* cs, const float* hs, const float* mask, const float* dHup, bool up, const float* Wo,
-                float* wot, float* dA, int64_t N, int T, int H, int relu, const float* Uc, float* dbias, float* dbias2) {
+                float* wot, float* dA, int64_t N, int T, int H, int relu, const float* Uc, float* dbias, float* dbias2, int grid_cap) {
   const int GH = cell == 1 ? H : 4 * H;                        // floats per row of dA (gru: the record's four blocks, the last one unused)
   const int WG = cell == 2 ? 3 * H : GH;                       // floats per row of the transposed weights
   HIP_TRY(hipMemsetAsync(wot, 0, bptt_scratch_floats(H, WG) * sizeof(float), s));
@@ -1188,7 +1195,7 @@ void bptt_layer(hipStream_t s, int cell, const float* act, const float* cs, cons
   const int nch = cell == 0 ? (H + 63) / 64 : 1;
   const int nt = cell == 0 ? nch : 4;
   const size_t lds = (size_t)ROWS * BP_LD * 4 + (size_t)4 * BP_R * nt * 1024 + 4096;   // dA chunk tile, the four waves' weight rings, the bias sums' slots
-  const int grid = (int)std::min<int64_t>(a.tiles, num_cus());
+  const int grid = launch_grid(a.tiles, grid_cap);
   typedef void (*Kern)(BPArgs);
   Kern k = nullptr;
 #define KPRN_BK(C_, N_) (up ? (Kern)k_bptt<C_, N_, true> : (Kern)k_bptt<C_, N_, false>)
