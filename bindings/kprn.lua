@@ -110,6 +110,10 @@ int kprn_find_candidates(kprn_handle*, const kprn_graph*, const kprn_sampler*, c
 int kprn_read_candidates(kprn_handle*, int32_t*, int64_t);
 int kprn_find_paths_of_candidates(kprn_handle*, const kprn_graph*, int32_t, int32_t, int32_t, int32_t, int32_t, uint64_t, unsigned int, int32_t*, int64_t*, kprn_batch**);
 int kprn_host_find_candidates(const int32_t*, const int32_t*, const int32_t*, int64_t, int32_t, const int32_t*, int64_t, const int32_t*, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t*, int32_t*);
+/* the N strongest candidates of a user by path count (include/kprn.h "the N strongest candidates of a user") */
+int kprn_find_candidates_top(kprn_handle*, const kprn_graph*, const kprn_sampler*, const int32_t*, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t*, int64_t*);
+int kprn_read_candidate_paths(kprn_handle*, int64_t*, int64_t);
+int kprn_host_find_candidates_top(const int32_t*, const int32_t*, const int32_t*, int64_t, int32_t, const int32_t*, int64_t, const int32_t*, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t*, int32_t*, int64_t*);
 ]]
 
 local C = ffi.load('kprn')

@@ -477,6 +477,35 @@ int kprn_host_find_candidates(const int32_t* src, const int32_t* dst, const int3
                               const int32_t* users, int32_t B, int32_t min_hops, int32_t max_hops, int32_t exclude_adjacent, int32_t threads,
                               int32_t* group_counts, int32_t* cand /* [sum] entity ids, or NULL = counts only */);
 
+/* ---- the N strongest candidates of a user (a retrieval stage in front of the ranker: in three hops a user reaches most of a catalogue) ----
+ * Everything not said here is kprn_find_candidates'.
+ *  - path count of a member: for a user u, 1 <= min_hops <= max_hops <= 3 and a catalogue member c, n_paths(u, c) is the number of paths of min_hops ..
+ *    max_hops hops from u to c in the finder's sense: stored edges, all nodes pairwise distinct, two relations between the same two nodes counted as two
+ *    paths.  An int64.  By definition it equals `found` of kprn_find_paths for the pair (u, c) over the same hops.
+ *  - candidates: exactly kprn_find_candidates': the members with n_paths > 0, less u itself and, with exclude_adjacent, the members u has a stored edge to.
+ *    An excluded member neither appears nor uses up any of the cap.
+ *  - kept: the user's candidates ordered by (n_paths descending, entity id ascending); the first min(cap, number of candidates) are kept,
+ *    1 <= cap <= 2^31 - 1.
+ *  - order of the result: within a user the kept rows lie by entity id ascending, as the list always does, so kprn_find_paths_of_candidates and "the
+ *    batch's pair p is the list's row p" hold unchanged.  With cap >= every user's number of candidates the call leaves exactly the list, group_counts and
+ *    total that kprn_find_candidates leaves.
+ *  - nothing depends on timing: the counts are integer sums (any order of the adds gives the same sum), the cut is found by counting (a radix select
+ *    over histograms), ranks come from prefix sums, and no atomic hands out a slot, a rank or a tie-break.
+ *  - result: the (u, c) rows become the handle's candidate list; beside it lies a device array n_paths [total], row for row, which
+ *    kprn_read_candidate_paths copies back.  A list left by kprn_find_candidates has no counts: the read is KPRN_E_ARG, as is a wrong total.
+ *  - refusals, all decided on the host before anything is allocated or written: kprn_find_candidates' own; cap < 1 and B * M >= 2^28 (the per-user
+ *    counts are 8 bytes each: a block of at most 2 GiB) are KPRN_E_ARG.  A refused call leaves the previous list and its counts as they were.  The fill
+ *    pass is checked as kprn_find_candidates' (KPRN_E_DEVICE, the previous list stays, no write leaves the user's own rows).
+ * Synchronous, with the same two waits: the counts, then the fill pass's verdict.                                                                     */
+int kprn_find_candidates_top(kprn_handle* h, const kprn_graph* g, const kprn_sampler* catalogue, const int32_t* users /* [B] */, int32_t B,
+                             int32_t min_hops, int32_t max_hops, int32_t exclude_adjacent, int32_t cap,
+                             int32_t* group_counts /* [B] */, int64_t* total);
+int kprn_read_candidate_paths(kprn_handle* h, int64_t* n_paths_out /* [total] */, int64_t total);
+/* the same rule on the host cores (no handle, no GPU): kprn_host_find_candidates' arguments and refusals plus the two above; n_paths [sum] or NULL */
+int kprn_host_find_candidates_top(const int32_t* src, const int32_t* dst, const int32_t* rel, int64_t E, int32_t Ve, const int32_t* items, int64_t M,
+                                  const int32_t* users, int32_t B, int32_t min_hops, int32_t max_hops, int32_t exclude_adjacent, int32_t cap, int32_t threads,
+                                  int32_t* group_counts, int32_t* cand /* [sum] entity ids, or NULL = counts only */, int64_t* n_paths /* [sum] or NULL */);
+
 /* ---- training ---------------------------------------------------------------------- */
 /* fEval of MyOptimizer.lua:184-195: zeroGradParameters; forward; BCE; backward.
  * inv_batch = 0 -> 1/B; data-parallel callers pass 1/B_global.  loss may be NULL (async). */

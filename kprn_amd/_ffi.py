@@ -198,6 +198,7 @@ def host_pairwise_loss(pooled, labels, group_offsets, inv_batch=0.0):
 
 FIND_MAX_HOPS, FIND_MAX_PATHS = 3, 4096   # kprn_find_paths: hops per path, kept paths per pair
 FIND_MAX_HOPS_SAMPLED, FIND_MAX_WALKS = 5, 256   # kprn_find_paths_sampled: hops per path, walks per pair and sampled hop count
+CAND_TOP_MAX_BM = 1 << 28   # kprn_find_candidates_top: users * catalogue items of one call must stay below this
 
 
 def _graph_arrays(src, dst, rel, node_types):
@@ -316,6 +317,37 @@ def host_find_candidates(src, dst, rel, Ve, items, users, min_hops, max_hops, ex
     if cand.size:
         call(np.zeros(B, np.int32), cand)
     return cand, gc
+
+
+def host_find_candidates_top(src, dst, rel, Ve, items, users, min_hops, max_hops, cap, exclude_adjacent=True, threads=1):
+    """kprn_host_find_candidates_top (no handle, no GPU): include/kprn.h "the N strongest candidates of a user" -> (cand [sum(group_counts)] entity ids,
+    users in input order and ids ascending; group_counts [B]; n_paths [sum] int64).  Two calls: the counts, then the ids and path counts"""
+    src, dst, rel = (np.ascontiguousarray(a, np.int32).reshape(-1) for a in (src, dst, rel))
+    if not (src.shape == dst.shape == rel.shape):
+        raise KprnError(E_ARG, "a graph is src / dst / rel [E]")
+    it, _ = _sampler_arrays(items, None)
+    us = np.ascontiguousarray(users, np.int32).reshape(-1)
+    B = int(us.shape[0])
+    gc = np.zeros(B, np.int32)
+
+    def call(counts, cand, n_paths):
+        rc = lib().kprn_host_find_candidates_top(_fp(src), _fp(dst), _fp(rel), C.c_int64(int(src.shape[0])), int(Ve), _fp(it), C.c_int64(int(it.shape[0])), _fp(us),
+                                                 B, int(min_hops), int(max_hops), int(bool(exclude_adjacent)), C.c_int32(_as_cap(cap)), int(threads), _fp(counts),
+                                                 _fp(cand), _fp(n_paths))
+        if rc != 0:
+            raise KprnError(rc, "kprn_host_find_candidates_top: bad edges / items / users / hops / cap")
+    call(gc, None, None)
+    total = int(gc.astype(np.int64).sum())
+    cand, n_paths = np.zeros(total, np.int32), np.zeros(total, np.int64)
+    if total:
+        call(np.zeros(B, np.int32), cand, n_paths)
+    return cand, gc, n_paths
+
+
+def _as_cap(cap):
+    """a cap as the int32 the library takes: anything outside int32 becomes a value it refuses (0) rather than one that wraps"""
+    cap = int(cap)
+    return cap if -2**31 <= cap <= 2**31 - 1 else 0
 
 
 def format_score_lines(counter0, probs, labels):
@@ -937,20 +969,34 @@ class Engine:
         return Batch._adopt(self, ptr, counts[counts > 0].copy(), T, self.cfg.F, True), pairs, counts, found
 
     # -- candidates of a user (include/kprn.h "candidates of a user") ---------------------------
-    def find_candidates(self, graph, sampler, users, min_hops, max_hops, exclude_adjacent=True):
+    def find_candidates(self, graph, sampler, users, min_hops, max_hops, exclude_adjacent=True, cap=0):
         """kprn_find_candidates + kprn_read_candidates: the members of the sampler's item list that min_hops .. max_hops (<= 3) hops reach from each of
         `users`, less the user and (exclude_adjacent) the items it has an edge to -> (pairs [total, 2] = (user, item), users in input order and items
-        ascending; group_counts [B]).  The list stays on the device for find_paths_of_candidates"""
+        ascending; group_counts [B]).  The list stays on the device for find_paths_of_candidates.
+        cap > 0: kprn_find_candidates_top, at most `cap` per user, the strongest by path count (include/kprn.h "the N strongest candidates of a user");
+        candidate_path_counts() then returns the counts"""
         us = np.ascontiguousarray(users, np.int32).reshape(-1)
         B = int(us.shape[0])
         gc = np.zeros(B, np.int32)
         total = C.c_int64()
-        self._ck(self.L.kprn_find_candidates(self.h, graph.ptr, sampler.ptr, _fp(us), B, int(min_hops), int(max_hops), int(bool(exclude_adjacent)), _fp(gc),
-                                             C.byref(total)))
+        if cap == 0:
+            self._ck(self.L.kprn_find_candidates(self.h, graph.ptr, sampler.ptr, _fp(us), B, int(min_hops), int(max_hops), int(bool(exclude_adjacent)), _fp(gc),
+                                                 C.byref(total)))
+        else:
+            self._ck(self.L.kprn_find_candidates_top(self.h, graph.ptr, sampler.ptr, _fp(us), B, int(min_hops), int(max_hops), int(bool(exclude_adjacent)),
+                                                     C.c_int32(_as_cap(cap)), _fp(gc), C.byref(total)))
         self._cand_total = int(total.value)
         pairs = np.zeros((int(total.value), 2), np.int32)
         self._ck(self.L.kprn_read_candidates(self.h, _fp(pairs), C.c_int64(int(total.value))))
         return pairs, gc
+
+    def candidate_path_counts(self):
+        """kprn_read_candidate_paths: n_paths [total] int64 of the candidate list a find_candidates(cap > 0) left, row for row (KprnError E_ARG after a
+        plain find_candidates)"""
+        total = getattr(self, "_cand_total", 0)
+        n_paths = np.zeros(total, np.int64)
+        self._ck(self.L.kprn_read_candidate_paths(self.h, _fp(n_paths), C.c_int64(total)))
+        return n_paths
 
     def find_paths_of_candidates(self, graph, total, min_hops, max_hops, max_paths, T, walks=0, seed=0, draw=0):
         """kprn_find_paths_of_candidates: find_paths over the engine's candidate list (`total` rows, as find_candidates returned them), which never visits

@@ -16,6 +16,19 @@
 //   k_fill   the words 256 at a time, ranks by the workgroup's exclusive scan with the running rank carried from chunk to chunk; a thread writes the rows of
 //            its own word while rank < counts[b].  The rows a workgroup placed are summed and compared with counts[b]: a disagreement sets the flag
 //            (KPRN_E_DEVICE), and no write leaves the user's rows either way.
+//
+// The N strongest candidates of a user (include/kprn.h "the N strongest candidates of a user"; kprn_find_candidates_top): the same walk counts its marks, so
+// every member gets n_paths = the finder's `found` for (u, c), and a user keeps its `cap` best by (n_paths descending, id ascending), laid out by id.  A tally
+// of M 64-bit words per user takes the bitmap's place, zeroed by a memset queued before the first kernel:
+//   k_tally   k_mark's spread; an end node that is a member adds 1 to its word (relaxed, agent scope).  Integer adds commute: the sums do not depend on order
+//   k_settle  a thread per entry: the user's own entry and, with exclude_adjacent, the adjacent members' are zeroed with plain stores; the non-zero entries
+//             summed over the workgroup -> ncand [B]
+//   k_select  a user with more than cap candidates: v = its cap-th largest count by a radix select from the most significant non-zero byte of the workgroup's
+//             maximum down, one 256-bin LDS histogram per byte; quota = cap - #(entries > v) of the entries equal to v are kept, lowest ids first.  Otherwise
+//             v = 0: every non-zero entry is kept.  counts [B] = min(cap, ncand) goes to the host
+//   k_fill_top  the entries 256 at a time, one exclusive scan per chunk over (entries > v, entries == v) packed in the halves of an int64, the rank among
+//             kept rows and the rank among ties carried from chunk to chunk; a thread writes its own row and n_paths entry while rank < counts[b]; the rows
+//             placed are checked against counts[b] as k_fill does.
 #include "path_find_dev.h"
 
 namespace cd {
@@ -115,6 +128,138 @@ __global__ __launch_bounds__(TPB) void k_fill(const int32_t* __restrict__ items,
   if (threadIdx.x == 0 && placed != cap) atomicOr(flag, 1);
 }
 
+// ---- the N strongest candidates ----------------------------------------------------------------------------------------------------------------
+typedef unsigned long long u64;
+
+__global__ __launch_bounds__(TPB) void k_tally(Csr g, const int32_t* __restrict__ items, int M, const int32_t* __restrict__ users, int hmask, u64* tally_all) {
+  const int u = users[blockIdx.x];
+  u64* tally = tally_all + (int64_t)blockIdx.x * M;
+  auto mark = [&](int c) {
+    const int j = member(items, M, c);
+    if (j >= 0) __hip_atomic_fetch_add(&tally[j], (u64)1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  };
+  const int beg = g.rowptr[u], end = g.rowptr[u + 1];
+  if (hmask & 1)
+    for (int e0 = beg + threadIdx.x; e0 < end; e0 += TPB) mark(g.col[e0]);
+  if (hmask & 2)   // a thread per first edge
+    for (int e0 = beg + threadIdx.x; e0 < end; e0 += TPB) walk_edge(g, u, e0, true, false, 0, 1, mark);
+  if (hmask & 4) { // a wave per first edge, its lanes over the second edges
+    const int lane = threadIdx.x & 63;
+    for (int e0 = beg + (threadIdx.x >> 6); e0 < end; e0 += TPB / 64) walk_edge(g, u, e0, false, true, lane, 64, mark);
+  }
+}
+
+__global__ __launch_bounds__(TPB) void k_settle(Csr g, const int32_t* __restrict__ items, int M, const int32_t* __restrict__ users, int exclude, u64* tally_all,
+                                                int32_t* __restrict__ ncand) {
+  __shared__ int64_t sh[TPB];
+  const int u = users[blockIdx.x];
+  u64* tally = tally_all + (int64_t)blockIdx.x * M;
+  int64_t n = 0;
+  for (int j = threadIdx.x; j < M; j += TPB) {   // a thread owns its entries: plain loads and stores
+    if (tally[j] == 0) continue;
+    const int c = items[j];
+    bool out = c == u;
+    if (!out && exclude) {
+      int lo, hi;
+      pf::edge_range(g, u, c, lo, hi);
+      out = lo != hi;
+    }
+    if (out) tally[j] = 0; else ++n;
+  }
+  n = pf::block_sum(n, sh);
+  if (threadIdx.x == 0) ncand[blockIdx.x] = (int32_t)n;
+}
+
+// maximum over the workgroup; every thread gets it.  sh [TPB]
+__device__ static inline u64 block_max(u64 v, u64* sh) {
+  __syncthreads();
+  sh[threadIdx.x] = v;
+  __syncthreads();
+  for (int d = TPB / 2; d > 0; d >>= 1) {
+    if ((int)threadIdx.x < d && sh[threadIdx.x + d] > sh[threadIdx.x]) sh[threadIdx.x] = sh[threadIdx.x + d];
+    __syncthreads();
+  }
+  return sh[0];
+}
+
+// counts [b] = min(cap, ncand [b]); cut [b] = v and quota [b]: an entry t is kept iff t > v, or t == v && t > 0 and it is among the first quota such entries
+__global__ __launch_bounds__(TPB) void k_select(int M, int cap, const u64* __restrict__ tally_all, const int32_t* __restrict__ ncand, int32_t* __restrict__ counts,
+                                                u64* __restrict__ cut, int32_t* __restrict__ quota) {
+  __shared__ int64_t sh[TPB];
+  __shared__ int hist[256];
+  static_assert(TPB == 256, "one thread zeroes one bin");
+  const u64* tally = tally_all + (int64_t)blockIdx.x * M;
+  const int n = ncand[blockIdx.x];   // (one address for all lanes: the branches and loop bounds below are workgroup-uniform)
+  if (n <= cap) {
+    if (threadIdx.x == 0) { counts[blockIdx.x] = n; cut[blockIdx.x] = 0; quota[blockIdx.x] = 0; }
+    return;
+  }
+  u64 top = 0;
+  for (int j = threadIdx.x; j < M; j += TPB) top = tally[j] > top ? tally[j] : top;
+  top = block_max(top, (u64*)sh);
+  int d = 7;
+  while (d > 0 && (top >> (8 * d)) == 0) --d;   // the bytes above the maximum's top byte are 0 in every entry
+  u64 v = 0;      // the digits found so far, in place
+  int k = cap;    // v is the k-th largest of the entries that agree with it above digit d (cap < n: there are at least k, and the k-th is not 0)
+  for (; d >= 0; --d) {
+    hist[threadIdx.x] = 0;
+    __syncthreads();
+    for (int j = threadIdx.x; j < M; j += TPB) {
+      const u64 t = tally[j];
+      if (d == 7 || (t >> (8 * (d + 1))) == (v >> (8 * (d + 1)))) atomicAdd(&hist[(int)((t >> (8 * d)) & 255)], 1);   // (integer LDS adds: any order, one sum)
+    }
+    __syncthreads();
+    int bin = 255, above = 0;
+    for (; bin > 0; --bin) {   // every thread reads the same bins: the same digit in all of them
+      const int c = hist[bin];
+      if (above + c >= k) break;
+      above += c;
+    }
+    k -= above;
+    v |= (u64)bin << (8 * d);
+    __syncthreads();   // (hist is zeroed again by the next pass)
+  }
+  int64_t n_gt = 0;
+  for (int j = threadIdx.x; j < M; j += TPB) n_gt += tally[j] > v;
+  n_gt = pf::block_sum(n_gt, sh);
+  if (threadIdx.x == 0) { counts[blockIdx.x] = cap; cut[blockIdx.x] = v; quota[blockIdx.x] = (int32_t)(cap - n_gt); }
+}
+
+// first [b]: the user's first row in list and paths; counts [b]: the rows it was allotted
+__global__ __launch_bounds__(TPB) void k_fill_top(const int32_t* __restrict__ items, int M, const int32_t* __restrict__ users, const u64* __restrict__ tally_all,
+                                                  const int64_t* __restrict__ first, const int32_t* __restrict__ counts, const u64* __restrict__ cut,
+                                                  const int32_t* __restrict__ quota, int32_t* __restrict__ list, int64_t* __restrict__ paths, int32_t* flag) {
+  __shared__ int64_t sh[TPB];
+  const int u = users[blockIdx.x];
+  const u64* tally = tally_all + (int64_t)blockIdx.x * M;
+  const int64_t cap = counts[blockIdx.x], q = quota[blockIdx.x];
+  const u64 v = cut[blockIdx.x];
+  int32_t* out = list + 2 * first[blockIdx.x];
+  int64_t* np = paths + first[blockIdx.x];
+  int64_t run = 0, ties = 0, placed = 0;   // run: the rank of the next chunk's first kept row; ties: the entries == v before the chunk (both workgroup-uniform)
+  for (int base = 0; base < M; base += TPB) {
+    const int j = base + threadIdx.x;
+    const u64 t = j < M ? tally[j] : 0;
+    const bool gt = t > v, tie = t == v && t > 0;
+    int64_t sum;
+    const int64_t ex = pf::block_scan_excl((int64_t)gt | ((int64_t)tie << 32), sh, sum);   // low half: entries > v before mine; high half: ties before mine
+    const int64_t tie_rank = ties + (ex >> 32), kept_ties = ties < q ? ties : q;
+    if (gt || (tie && tie_rank < q)) {
+      const int64_t r = run + (ex & 0xffffffffLL) + ((tie_rank < q ? tie_rank : q) - kept_ties);
+      if (r < cap) {   // (out + 2 r and np + r are formed only for a rank below the cap)
+        out[2 * r] = u;
+        out[2 * r + 1] = items[j];
+        np[r] = (int64_t)t;
+        ++placed;
+      }
+    }
+    ties += sum >> 32;
+    run += (sum & 0xffffffffLL) + ((ties < q ? ties : q) - kept_ties);
+  }
+  placed = pf::block_sum(placed, sh);
+  if (threadIdx.x == 0 && placed != cap) atomicOr(flag, 1);
+}
+
 // ---- host side -------------------------------------------------------------------------------------------------------------------------------
 static int bad(std::string* why, int code, const char* t) { if (why) *why = t; return code; }
 
@@ -126,8 +271,16 @@ static int validate_limits(int64_t M, int32_t B, int32_t min_hops, int32_t max_h
   return KPRN_OK;
 }
 
+// kprn_find_candidates_top's and its twin's, on top of validate_limits
+static int validate_top(int64_t M, int32_t B, int32_t cap, std::string* why) {
+  if (cap < 1) return bad(why, KPRN_E_ARG, "cap < 1");
+  if ((int64_t)B * M >= (1LL << 28)) return bad(why, KPRN_E_ARG, "B * M must stay below 2^28");
+  return KPRN_OK;
+}
+
 void release_all(kprn_handle* h) {
   dfree(h->cand_list);
+  dfree(h->cand_paths);
   h->cand_total = -1;
   if (h->cand_buf) { hipFree(h->cand_buf); h->cand_buf = nullptr; h->cand_buf_bytes = 0; }
 }
@@ -203,9 +356,108 @@ int kprn_find_candidates(kprn_handle* h, const kprn_graph* g, const kprn_sampler
     }
   }
   dfree(h->cand_list);   // (the stream is drained: nothing queued reads the old list)
+  dfree(h->cand_paths);  // (a list of this call has no path counts)
   h->cand_list = list; h->cand_total = n; h->cand_Ve = g->Ve;
   std::copy(cnt.begin(), cnt.end(), group_counts);
   *total = n;
+  API_END(h)
+}
+
+int kprn_find_candidates_top(kprn_handle* h, const kprn_graph* g, const kprn_sampler* catalogue, const int32_t* users, int32_t B, int32_t min_hops, int32_t max_hops,
+                             int32_t exclude_adjacent, int32_t cap, int32_t* group_counts, int64_t* total) {
+  API_BEGIN(h)
+  KPRN_REQUIRE(g && std::find(h->graphs.begin(), h->graphs.end(), g) != h->graphs.end(), KPRN_E_ARG, "g is not a graph of this handle");
+  KPRN_REQUIRE(catalogue && std::find(h->samplers.begin(), h->samplers.end(), catalogue) != h->samplers.end(), KPRN_E_ARG,
+               "catalogue is not a sampler of this handle");
+  KPRN_REQUIRE(group_counts && total, KPRN_E_ARG, "group_counts or total is NULL");
+  const int M = catalogue->M;
+  std::string why;
+  int rc = cd::validate_limits(M, B, min_hops, max_hops, &why);
+  if (rc == KPRN_OK) rc = cd::validate_top(M, B, cap, &why);
+  if (rc == KPRN_OK) rc = ns::validate_users(users, B, g->Ve, &why);
+  if (rc != KPRN_OK) throw KprnError{rc, why};
+  hipStream_t s = h->stream;
+  // device arguments: first [B] (int64) | cut [B] | the tallies [B][M] (uint64), then users [B] | counts [B] | ncand [B] | quota [B] | flag [4] (int32)
+  const size_t n_tally = (size_t)B * M, bytes = ((size_t)2 * B + n_tally) * 8 + ((size_t)4 * B + 4) * 4;
+  grow_call_block(s, h->cand_buf, h->cand_buf_bytes, bytes);
+  int64_t* d_first = (int64_t*)h->cand_buf;
+  cd::u64* d_cut = (cd::u64*)(d_first + B);
+  cd::u64* d_tally = d_cut + B;
+  int32_t* d_users = (int32_t*)(d_tally + n_tally);
+  int32_t* d_counts = d_users + B;
+  int32_t* d_ncand = d_counts + B;
+  int32_t* d_quota = d_ncand + B;
+  int32_t* d_flag = d_quota + B;
+  const pf::Csr csr{g->rowptr, g->col, g->rel};
+  HIP_TRY(hipMemcpyAsync(d_users, users, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemsetAsync(d_tally, 0, n_tally * sizeof(cd::u64), s));   // (the block is grow-only: an earlier call's sums lie in it)
+  {
+    ProfScope ps(h, "candidates_tally");
+    hipLaunchKernelGGL(cd::k_tally, dim3((unsigned)B), dim3(cd::TPB), 0, s, csr, catalogue->items, M, d_users, pf::hop_mask(min_hops, max_hops), d_tally);
+    HIP_TRY(hipGetLastError());
+  }
+  {
+    ProfScope ps(h, "candidates_settle");
+    hipLaunchKernelGGL(cd::k_settle, dim3((unsigned)B), dim3(cd::TPB), 0, s, csr, catalogue->items, M, d_users, exclude_adjacent != 0 ? 1 : 0, d_tally, d_ncand);
+    HIP_TRY(hipGetLastError());
+  }
+  {
+    ProfScope ps(h, "candidates_select");
+    hipLaunchKernelGGL(cd::k_select, dim3((unsigned)B), dim3(cd::TPB), 0, s, M, cap, d_tally, d_ncand, d_counts, d_cut, d_quota);
+    HIP_TRY(hipGetLastError());
+  }
+  std::vector<int32_t> cnt((size_t)B);
+  std::vector<int64_t> first((size_t)B);
+  HIP_TRY(hipMemcpyAsync(cnt.data(), d_counts, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));   // the wait for the list's size
+  int64_t n = 0;
+  for (int32_t b = 0; b < B; ++b) {
+    KPRN_REQUIRE(cnt[b] >= 0 && cnt[b] <= std::min(M, cap), KPRN_E_DEVICE, "find_candidates_top: the selecting pass returned an impossible count");
+    first[b] = n;
+    n += cnt[b];
+  }
+  KPRN_REQUIRE(n <= 0x7fffffffLL, KPRN_E_ARG, "the candidate list must stay below 2^31 rows");
+  int32_t* list = nullptr;
+  int64_t* paths = dalloc<int64_t>(n);   // (never NULL: a list with counts, even an empty one)
+  try {
+    if (n > 0) {
+      list = dalloc<int32_t>(2 * n);
+      HIP_TRY(hipMemcpyAsync(d_first, first.data(), (size_t)B * sizeof(int64_t), hipMemcpyHostToDevice, s));
+      HIP_TRY(hipMemsetAsync(d_flag, 0, sizeof(int32_t), s));
+      {
+        ProfScope ps(h, "candidates_fill_top");
+        hipLaunchKernelGGL(cd::k_fill_top, dim3((unsigned)B), dim3(cd::TPB), 0, s, catalogue->items, M, d_users, d_tally, d_first, d_counts, d_cut, d_quota, list,
+                           paths, d_flag);
+        HIP_TRY(hipGetLastError());
+      }
+      int32_t flag = 0;
+      HIP_TRY(hipMemcpyAsync(&flag, d_flag, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipStreamSynchronize(s));   // (the fill pass's verdict, before the list replaces the handle's)
+      KPRN_REQUIRE(flag == 0, KPRN_E_DEVICE, "find_candidates_top: the fill pass placed a different number of rows than the selecting pass allotted");
+    }
+  } catch (...) {
+    hipStreamSynchronize(s);
+    dfree(list);
+    dfree(paths);
+    throw;
+  }
+  dfree(h->cand_list);   // (the stream is drained: nothing queued reads the old list)
+  dfree(h->cand_paths);
+  h->cand_list = list; h->cand_paths = paths; h->cand_total = n; h->cand_Ve = g->Ve;
+  std::copy(cnt.begin(), cnt.end(), group_counts);
+  *total = n;
+  API_END(h)
+}
+
+int kprn_read_candidate_paths(kprn_handle* h, int64_t* n_paths_out, int64_t total) {
+  API_BEGIN(h)
+  KPRN_REQUIRE(h->cand_total >= 0 && h->cand_paths, KPRN_E_ARG, "the handle's candidate list has no path counts");
+  KPRN_REQUIRE(total == h->cand_total, KPRN_E_ARG, "total is not the candidate list's");
+  if (total > 0) {
+    KPRN_REQUIRE(n_paths_out, KPRN_E_ARG, "n_paths_out is NULL");
+    HIP_TRY(hipMemcpyAsync(n_paths_out, h->cand_paths, (size_t)total * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+  }
   API_END(h)
 }
 
@@ -285,6 +537,63 @@ int kprn_host_find_candidates(const int32_t* src, const int32_t* dst, const int3
     for (int32_t b = 0; b < B; ++b) {
       group_counts[b] = (int32_t)mine[(size_t)b].size();
       if (cand) to = std::copy(mine[(size_t)b].begin(), mine[(size_t)b].end(), to);
+    }
+  } catch (...) { return KPRN_E_NOMEM; }
+  return KPRN_OK;
+}
+
+int kprn_host_find_candidates_top(const int32_t* src, const int32_t* dst, const int32_t* rel, int64_t E, int32_t Ve, const int32_t* items, int64_t M,
+                                  const int32_t* users, int32_t B, int32_t min_hops, int32_t max_hops, int32_t exclude_adjacent, int32_t cap, int32_t threads,
+                                  int32_t* group_counts, int32_t* cand, int64_t* n_paths) {
+  if (E < 0 || E > 0x7fffffffLL || (E > 0 && (!src || !dst || !rel)) || !group_counts) return KPRN_E_ARG;
+  int rc = ns::validate_table(items, nullptr, M, Ve, nullptr);
+  if (rc == KPRN_OK) rc = cd::validate_limits(M, B, min_hops, max_hops, nullptr);
+  if (rc == KPRN_OK) rc = cd::validate_top(M, B, cap, nullptr);
+  if (rc == KPRN_OK) rc = ns::validate_users(users, B, Ve, nullptr);
+  if (rc != KPRN_OK) return rc;
+  for (int64_t e = 0; e < E; ++e)
+    if (src[e] < 1 || src[e] >= Ve || dst[e] < 1 || dst[e] >= Ve) return KPRN_E_INDEX;
+  try {
+    const pf::HostCsr hg = pf::host_csr(src, dst, rel, E, Ve);
+    const pf::Csr g{hg.rowptr.data(), hg.col.data(), hg.rel.data()};
+    const int hmask = pf::hop_mask(min_hops, max_hops);
+    std::vector<std::vector<std::pair<int32_t, int64_t>>> mine((size_t)B);   // per user: (member's position, n_paths), positions ascending
+    pf::parallel_pairs(B, threads, [&](int32_t b) {
+      auto& v = mine[(size_t)b];
+      const int u = users[b];
+      std::vector<int64_t> tally((size_t)M, 0);
+      auto mark = [&](int c) { const int j = cd::member(items, (int)M, c); if (j >= 0) ++tally[(size_t)j]; };
+      for (int e0 = g.rowptr[u]; e0 < g.rowptr[u + 1]; ++e0) {
+        if (hmask & 1) mark(g.col[e0]);
+        if (hmask & 6) cd::walk_edge(g, u, e0, (hmask & 2) != 0, (hmask & 4) != 0, 0, 1, mark);
+      }
+      for (int32_t j = 0; j < (int32_t)M; ++j) {
+        if (tally[(size_t)j] == 0 || items[j] == u) continue;
+        if (exclude_adjacent) {
+          int lo, hi;
+          pf::edge_range(g, u, items[j], lo, hi);
+          if (lo != hi) continue;
+        }
+        v.emplace_back(j, tally[(size_t)j]);
+      }
+      if ((int64_t)v.size() > cap) {   // the cap best by (n_paths descending, id ascending), then back in id order
+        std::nth_element(v.begin(), v.begin() + cap, v.end(),
+                         [](const std::pair<int32_t, int64_t>& x, const std::pair<int32_t, int64_t>& y) { return x.second != y.second ? x.second > y.second : x.first < y.first; });
+        v.resize((size_t)cap);
+        std::sort(v.begin(), v.end());
+      }
+    });
+    int64_t n = 0;
+    for (const auto& v : mine) n += (int64_t)v.size();
+    if (n > 0x7fffffffLL) return KPRN_E_ARG;
+    int64_t at = 0;
+    for (int32_t b = 0; b < B; ++b) {
+      group_counts[b] = (int32_t)mine[(size_t)b].size();
+      for (const auto& p : mine[(size_t)b]) {
+        if (cand) cand[at] = items[p.first];
+        if (n_paths) n_paths[at] = p.second;
+        ++at;
+      }
     }
   } catch (...) { return KPRN_E_NOMEM; }
   return KPRN_OK;

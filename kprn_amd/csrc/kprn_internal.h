@@ -299,7 +299,8 @@ struct kprn_handle {
   void* ns_buf = nullptr; size_t ns_buf_bytes = 0;     // device arguments and results of one sampling call (users or positives, negatives, n_found)
   // candidates.hip: the handle's candidate list = the (user, item) rows of the last successful kprn_find_candidates, [cand_total][2] (cand_total < 0: none yet)
   int32_t* cand_list = nullptr; int64_t cand_total = -1; int32_t cand_Ve = 0;
-  void* cand_buf = nullptr; size_t cand_buf_bytes = 0; // device arguments of one kprn_find_candidates call (first rows, users, counts, flag, the users' bitmaps)
+  int64_t* cand_paths = nullptr;                       // the list's path counts [cand_total], row for row: kprn_find_candidates_top leaves them, kprn_find_candidates none
+  void* cand_buf = nullptr; size_t cand_buf_bytes = 0; // device arguments of one kprn_find_candidates(_top) call (first rows, users, counts, flag, the users' bitmaps or tallies)
 
   // option "deterministic": every float sum of a training step whose addends come from different waves or workgroups of one launch is formed in an order that
   // depends on the batch and the launch geometry only; pipelines that cannot do that refuse to train
@@ -530,7 +531,8 @@ void release_all(kprn_handle* h);   // kprn_destroy: the graphs still alive and 
 namespace ns {
 void release_all(kprn_handle* h);   // kprn_destroy: the samplers still alive and the sampling calls' buffer
 }  // namespace ns
-// ---- candidates of a user (candidates.hip): kprn_find_candidates / kprn_read_candidates / kprn_find_paths_of_candidates / kprn_host_find_candidates ----
+// ---- candidates of a user (candidates.hip): kprn_find_candidates(_top) / kprn_read_candidates / kprn_read_candidate_paths / kprn_find_paths_of_candidates /
+// kprn_host_find_candidates(_top) ----
 namespace cd {
 void release_all(kprn_handle* h);   // kprn_destroy: the handle's candidate list and the call's buffer
 }  // namespace cd

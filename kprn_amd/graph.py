@@ -113,18 +113,22 @@ def read_triples(path):
 
 
 def recommend(eng, kg, user, items, K, M, min_hops=1, max_hops=3, max_paths=28, T=None, class_id=1, mode=_ffi.RANK_PRINTED, walks=0, seed=1, draw=0, sampler=None,
-              exclude_adjacent=True):
+              exclude_adjacent=True, max_candidates=0):
     """Which of `items` for `user` (entity ids), and why: find every pair's paths on the device, score the batch, put the scores on the board, rank the
     one group, explain the K winners and read their paths' ids back.  kg: a KnowledgeGraph, or an _ffi.Graph already on the engine.  The board is
     resized to the candidates that have paths (kprn_board_reserve keeps nothing).  walks > 0: max_hops may be 4 or 5, the hops past 3 sampled by `walks`
     walks per item and hop count under (seed, draw) (include/kprn.h "sampled paths of four and five hops").
     -> the K best items, best first: dict(item, rank, score, n_paths, found, paths = the M strongest as (ids [T,F], weight, score)); items without any
     path are not candidates, so the list may be shorter than K -- empty when no item is reachable.
-    items=None: the candidates are found on the device among the items of `sampler` (an _ffi.Sampler: the catalogue), recommend_users for the one user."""
+    items=None: the candidates are found on the device among the items of `sampler` (an _ffi.Sampler: the catalogue), recommend_users for the one user;
+    max_candidates as there (it has no meaning beside a list of items)."""
     if items is None:
         if sampler is None:
             raise ValueError("recommend needs items, or a sampler whose item list is the catalogue")
-        return recommend_users(eng, kg, sampler, [user], K, M, min_hops, max_hops, max_paths, T, class_id, mode, walks, seed, draw, exclude_adjacent)[0]
+        return recommend_users(eng, kg, sampler, [user], K, M, min_hops, max_hops, max_paths, T, class_id, mode, walks, seed, draw, exclude_adjacent,
+                               max_candidates)[0]
+    if max_candidates:
+        raise ValueError("max_candidates caps the candidates found on the device: it cannot be combined with items")
     graph = kg.on(eng) if isinstance(kg, KnowledgeGraph) else kg
     items = np.asarray(items, np.int32).reshape(-1)
     pairs = np.stack([np.full(items.shape, int(user), np.int32), items], axis=1)
@@ -166,19 +170,31 @@ def _rank_key(scores, mode):
 
 
 def recommend_users(eng, kg, sampler, users, K, M=0, min_hops=1, max_hops=3, max_paths=28, T=None, class_id=1, mode=_ffi.RANK_PRINTED, walks=0, seed=1, draw=0,
-                    exclude_adjacent=True):
+                    exclude_adjacent=True, max_candidates=0):
     """What should each of `users` (entity ids) get, and why, without a candidate list: one chain for all of them.  The candidates -- the items of
     `sampler` (an _ffi.Sampler: the catalogue) that min_hops .. min(max_hops, 3) hops reach from the user, less the user and, with exclude_adjacent, the
     items it already has an edge to -- are found on the device (include/kprn.h "candidates of a user"), the finder reads that list where it lies, the
     batch is scored and put on the board, one rank_groups call ranks every user's group, the winners are explained (M > 0) and their paths read back.
     A group of more than 4096 surviving pairs (kprn_rank_groups' limit) is ranked as consecutive sub-groups of at most 4096 in the same call, whose
     top-K rows are merged here by (key descending, index within the user's group ascending): what a single group would have given.
+    max_candidates = N > 0: only each user's N strongest candidates by path count enter the chain (include/kprn.h "the N strongest candidates of a user"),
+    the users taken in chunks of fewer than 2^28 / M (the catalogue's size) -- a user's result is that of one call; 0: every candidate.
     -> per user, the list of dicts `recommend` returns."""
     graph = kg.on(eng) if isinstance(kg, KnowledgeGraph) else kg
     users = np.asarray(users, np.int32).reshape(-1)
+    max_candidates = int(max_candidates)
+    if max_candidates < 0:
+        raise ValueError("max_candidates must be >= 0")
+    chunk = (_ffi.CAND_TOP_MAX_BM - 1) // max(int(sampler.M), 1)   # the most users of one kprn_find_candidates_top call
+    if max_candidates > 0 and 0 < chunk < len(users):
+        out = []
+        for lo in range(0, len(users), chunk):
+            out += recommend_users(eng, graph, sampler, users[lo:lo + chunk], K, M, min_hops, max_hops, max_paths, T, class_id, mode, walks, seed, draw,
+                                   exclude_adjacent, max_candidates)
+        return out
     T = max_hops + 1 if T is None else int(T)
     out = [[] for _ in users]
-    pairs, gc = eng.find_candidates(graph, sampler, users, min_hops, min(int(max_hops), _ffi.FIND_MAX_HOPS), exclude_adjacent)
+    pairs, gc = eng.find_candidates(graph, sampler, users, min_hops, min(int(max_hops), _ffi.FIND_MAX_HOPS), exclude_adjacent, cap=max_candidates)
     if len(pairs) == 0:
         return out
     batch, counts, found = eng.find_paths_of_candidates(graph, len(pairs), min_hops, max_hops, max_paths, T, walks=walks, seed=seed, draw=draw)

@@ -8,6 +8,7 @@ model flag -K here, because -k is the number of items to return), plus
   -user U  -items FILE the user's entity name; candidate item names, one per line
   -interaction_rel R [-seen 0]   without -items: the catalogue is every item an edge of relation R leads to, and the candidates are those the graph
                        reaches from the user in -min_hops .. min(-max_hops, 3) hops, found on the device; -seen 1 keeps the items the user already has an edge to
+  -max_candidates N    without -items: only the user's N strongest candidates by path count are scored and ranked (0 = all of them)
   -k K                 items to return;  -explain_paths M  strongest paths printed per item
   -min_hops / -max_hops / -max_paths   the finder's limits (1, 3, 28)
   -walks N [-sampleSeed 1]             -max_hops 4 or 5: the paths of more than 3 hops are sampled, N walks (1..256) per item and hop count
@@ -31,8 +32,13 @@ def main(argv=None, out=sys.stdout):
     p.add_argument("-min_hops", type=int, default=1); p.add_argument("-max_hops", type=int, default=3); p.add_argument("-max_paths", type=int, default=28)
     p.add_argument("-walks", type=int, default=0)
     p.add_argument("-interaction_rel", default=""); p.add_argument("-seen", type=int, default=0, choices=(0, 1))
+    p.add_argument("-max_candidates", type=int, default=0)
     args, rest = p.parse_known_args(argv)
     model.check_walks(args.max_hops, args.walks, p.error)
+    if args.max_candidates and args.items:
+        p.error("-max_candidates caps the candidates found in the graph and cannot be combined with -items (a list of candidates)")
+    if not 0 <= args.max_candidates <= 2**31 - 1:
+        p.error("-max_candidates must be in 0 .. 2^31 - 1")
     if not args.items and not args.interaction_rel:
         p.error("-kg needs -vocab_dir DIR (the vocabulary files) and -interaction_rel NAME (the relation of the user-item edges to train on)")   # (train -kg's)
     if not 1 <= args.explain_paths <= 32:
@@ -58,7 +64,8 @@ def main(argv=None, out=sys.stdout):
     try:
         sampler = None if catalogue is None else eng.sampler(catalogue)
         res = graph.recommend(eng, kg, kg.entity_id(args.user), items, args.k, args.explain_paths, args.min_hops, args.max_hops,
-                              args.max_paths, walks=args.walks, seed=params.sampleSeed, sampler=sampler, exclude_adjacent=not args.seen)
+                              args.max_paths, walks=args.walks, seed=params.sampleSeed, sampler=sampler, exclude_adjacent=not args.seen,
+                              max_candidates=args.max_candidates)
     finally:
         eng.close()
     for r in res:
