@@ -80,6 +80,9 @@ int kprn_board_read(kprn_handle*, int64_t, float*, int64_t);
 int kprn_rank_groups(kprn_handle*, const int64_t*, const int64_t*, const int32_t*, int32_t, int32_t, int32_t, int32_t*, int32_t*, float*, int64_t*, int32_t);
 int kprn_recommend_ragged(kprn_handle*, const int32_t*, const int32_t*, int32_t, int64_t, int32_t, int32_t, int32_t, const int32_t*, int32_t, int32_t, int32_t, int32_t*, float*, float*);
 int kprn_host_rank_groups(const float*, int64_t, const int64_t*, const int64_t*, const int32_t*, int32_t, int32_t, int32_t, int32_t*, int32_t*, float*, int64_t*, int32_t);
+/* ranking targets in groups of any size: several targets per group, each placed among the group's non-targets (include/kprn.h) */
+int kprn_rank_targets(kprn_handle*, const int64_t*, const int64_t*, const int64_t*, const int32_t*, int32_t, int32_t, int32_t*, int64_t*, int32_t);
+int kprn_host_rank_targets(const float*, int64_t, const int64_t*, const int64_t*, const int64_t*, const int32_t*, int32_t, int32_t, int32_t*, int64_t*, int32_t);
 /* explanation stage: the M strongest paths behind a pair's pooled score and their weights (include/kprn.h "explaining a recommendation") */
 int kprn_explain_batch(kprn_handle*, const kprn_batch*, int32_t, const int32_t*, int32_t, int32_t, int32_t*, float*, float*, float*, float*);
 int kprn_recommend_explain_ragged(kprn_handle*, const int32_t*, const int32_t*, int32_t, int64_t, int32_t, int32_t, int32_t, const int32_t*, int32_t, int32_t, int32_t, int32_t, int32_t*, float*, int32_t*, float*, float*, float*);

@@ -293,6 +293,35 @@ int kprn_recommend_ragged(kprn_handle* h, const int32_t* idx, const int32_t* cou
 int kprn_host_rank_groups(const float* scores, int64_t n_scores, const int64_t* members, const int64_t* group_offsets, const int32_t* pos, int32_t G,
                           int32_t mode, int32_t K, int32_t* ranks, int32_t* topk_idx, float* topk_score, int64_t* hist, int32_t hist_len);
 
+/* ---- ranking targets in groups of any size (an extension: held-out evaluation against everything a user reaches, not against 100 sampled negatives) ----
+ * kprn_rank_groups stops at 4096 members and one positive; in three hops a user reaches most of a catalogue and has several held-out items.  Here a
+ * group has any size and any number of TARGETS, and only the targets' places and their histogram come back.
+ *  - groups: scores live on the board; group g = members[group_offsets[g] .. group_offsets[g + 1]) as in kprn_rank_groups, members NULL = the
+ *    consecutive board run.  1 <= n < 2^31 members.
+ *  - targets: group g's are targets[target_offsets[g] .. target_offsets[g + 1]), indices WITHIN the group, strictly ascending; a group may have none;
+ *    target_offsets[0] = 0 and NT = target_offsets[G] >= 1.
+ *  - order: key and validity exactly as in "ranking" (modes KPRN_RANK_PRINTED / KPRN_RANK_RAW; NaN invalid in both, anything outside [0, 1] invalid in
+ *    the printed mode; an invalid member sorts below every valid one).  Every member is one integer ((uint64_t)key << 32) | (0xFFFFFFFF - index):
+ *    key descending, first seen first -- the order of "ranking" with the index in 32 bits instead of 12.
+ *  - place: every target is its own sample, ranked against the group's NON-targets (eval_score.py: one positive against that user's negatives):
+ *    place(t) = the number of non-target members of the group whose integer is larger than t's
+ *             = (members with a larger integer) - (targets of the group with a larger integer).
+ *  - zero samples: mode 0, neither t nor any non-target member of its group prints above zero: place KPRN_RANK_ZERO_GROUP (eval_score.py:35, as for
+ *    groups).  A group in which only ANOTHER target prints above zero is a zero sample for t and an ordinary one for that other target.
+ *  - places [NT] (int32), in the order of targets.  hist [hist_len + 4] (int64), hist_len in 1..4096: hist[r] = targets at place r < hist_len,
+ *    [hist_len] = ranked lower, [hist_len + 1] = zero samples, [hist_len + 2] = always 0, [hist_len + 3] = invalid members, each group's counted
+ *    once (groups without targets included).  The layout of kprn_rank_groups' histogram with samples for groups: hit@k and ndcg@k are formed the same way.
+ * Nothing depends on timing: places come from integer counts and a prefix sum, the histogram from integer adds.
+ * kprn_rank_targets waits for every put queued so far; synchronous, one launch and one wait: places and hist are on the host when it returns and hold
+ * this call only.  Everything is checked on the host first and a refused call writes nothing: KPRN_E_ARG for NULL offsets / targets / places / hist, G < 1,
+ * a group outside 1..2^31-1 members, more targets than members, target_offsets[0] != 0, NT = 0, a target outside its group or not above the one before,
+ * hist_len outside 1..4096, an unknown mode, or no board; KPRN_E_INDEX for a member or a run outside the board.                                  */
+int kprn_rank_targets(kprn_handle* h, const int64_t* members, const int64_t* group_offsets, const int64_t* target_offsets, const int32_t* targets,
+                      int32_t G, int32_t mode, int32_t* places, int64_t* hist, int32_t hist_len);
+/* the same rule on the host cores over a host score array (no handle, no GPU): the arguments of kprn_rank_targets with scores [n_scores] as the board */
+int kprn_host_rank_targets(const float* scores, int64_t n_scores, const int64_t* members, const int64_t* group_offsets, const int64_t* target_offsets,
+                           const int32_t* targets, int32_t G, int32_t mode, int32_t* places, int64_t* hist, int32_t hist_len);
+
 /* ---- explaining a recommendation (an extension: the paper's pooling layer read backwards) ----
  * Which paths put a pair where it is: the M strongest paths behind the pair's pooled score in the selected class, each with the share it takes of that
  * score, w_q = d pooled / d s_q (the factor the loss stage multiplies dy by).  For a pair whose cnt paths have the fp32 scores s_0 .. s_{cnt-1}:

@@ -128,6 +128,35 @@ def host_rank_groups(scores, group_offsets, members=None, pos=None, mode=0, K=0,
     return out
 
 
+def _rank_targets_args(group_offsets, target_offsets, targets, members, hist_len):
+    """the arrays of kprn_rank_targets / kprn_host_rank_targets; what the C call reads through an array's length is checked here, the rest there"""
+    goff = np.ascontiguousarray(group_offsets, np.int64)
+    toff = np.ascontiguousarray(target_offsets, np.int64)
+    if goff.ndim != 1 or goff.shape[0] < 2 or toff.shape != goff.shape:
+        raise KprnError(E_ARG, "group_offsets and target_offsets must be [G+1], G >= 1")
+    tg = np.ascontiguousarray(targets, np.int32)
+    if tg.ndim != 1 or toff[0] != 0 or np.any(np.diff(toff) < 0) or toff[-1] != tg.shape[0] or tg.shape[0] < 1:
+        raise KprnError(E_ARG, "target_offsets must run from 0 to len(targets) >= 1 without decreasing")
+    mem = None if members is None else np.ascontiguousarray(members, np.int64)
+    if mem is not None and (mem.ndim != 1 or goff[0] < 0 or goff[-1] > mem.shape[0]):
+        raise KprnError(E_ARG, "group_offsets must lie inside members")
+    out = dict(places=np.full(tg.shape[0], -3, np.int32), hist=np.zeros(int(max(hist_len, 0)) + 4, np.int64))
+    return goff, toff, tg, mem, int(goff.shape[0]) - 1, out
+
+
+def host_rank_targets(scores, group_offsets, target_offsets, targets, members=None, mode=0, hist_len=15, out=None):
+    """kprn_host_rank_targets (no handle, no GPU): the rule of include/kprn.h "ranking targets in groups of any size" over a host score array ->
+    dict(places [NT], hist [hist_len + 4]); out: a dict with those two arrays to write into"""
+    sc = np.ascontiguousarray(scores, np.float32)
+    goff, toff, tg, mem, G, res = _rank_targets_args(group_offsets, target_offsets, targets, members, hist_len)
+    res = res if out is None else out
+    rc = lib().kprn_host_rank_targets(_fp(sc), C.c_int64(int(sc.shape[0])), _fp(mem), _fp(goff), _fp(toff), _fp(tg), G, int(mode), _fp(res["places"]),
+                                      _fp(res["hist"]), int(hist_len))
+    if rc != 0:
+        raise KprnError(rc, "kprn_host_rank_targets: bad groups / members / targets / hist_len / mode")
+    return res
+
+
 EXPLAIN_MAX_M = 32   # strongest paths per explained pair (KPRN_EXPLAIN_MAX_M)
 
 
@@ -892,6 +921,14 @@ class Engine:
         self._ck(self.L.kprn_rank_groups(self.h, _fp(mem), _fp(goff), _fp(p), G, int(mode), int(K) if K > 0 else 1, _fp(out["ranks"]),
                                          _fp(out.get("topk_idx")), _fp(out.get("topk_score")), _fp(out["hist"]), int(hist_len)))
         return out
+
+    def rank_targets(self, group_offsets, target_offsets, targets, members=None, mode=0, hist_len=15, out=None):
+        """kprn_rank_targets over the board: groups of any size, group g's targets = targets[target_offsets[g] : target_offsets[g + 1]] (indices within
+        the group, ascending), each placed among the group's non-targets -> dict(places [NT], hist [hist_len + 4]); out: a dict to write into"""
+        goff, toff, tg, mem, G, res = _rank_targets_args(group_offsets, target_offsets, targets, members, hist_len)
+        res = res if out is None else out
+        self._ck(self.L.kprn_rank_targets(self.h, _fp(mem), _fp(goff), _fp(toff), _fp(tg), G, int(mode), _fp(res["places"]), _fp(res["hist"]), int(hist_len)))
+        return res
 
     def recommend_ragged(self, idx, counts, group_counts, K, class_id=1, mode=0, want_probs=False):
         """kprn_recommend_ragged: idx [N,T,F] / counts [B] as forward_ragged_host; group_counts [G] pairs per group (sum B) ->

@@ -288,7 +288,7 @@ struct kprn_handle {
   // on the stream that produced it; a put queued on the scoring stream leaves ev_put behind it (put_side: not yet waited for by the main stream)
   float* board = nullptr; int64_t board_n = 0;
   hipEvent_t ev_put = nullptr; bool put_side = false;
-  void* rank_buf = nullptr; size_t rank_buf_bytes = 0;   // device arguments and results of one kprn_rank_groups call
+  void* rank_buf = nullptr; size_t rank_buf_bytes = 0;   // device arguments and results of one kprn_rank_groups / kprn_rank_targets call
   int rank_sort_min = 512;   // option "rank_sort_min": counting wins at 257 members, the sort at 512 and above (profiles/rank/README.md, comparison 3)
   void* rank_pin = nullptr; size_t rank_pin_bytes = 0, rank_pin_off[2] = {0, 0};   // page-locked group table and top-K rows of kprn_recommend_ragged
   void* explain_buf = nullptr; size_t explain_buf_bytes = 0;   // device pair list and results of one kprn_explain_batch call
@@ -522,6 +522,16 @@ int validate(int64_t n_scores, const int64_t* members, const int64_t* goff, cons
              int* max_n, std::string* why);
 void launch(hipStream_t s, const Args& a, int max_n);   // hist must be zero; every group is ranked by exactly one of the two kernels
 }  // namespace rk
+
+// ---- ranking targets in groups of any size (rank_targets.hip; the rule, the refusals and the host twin: rank_targets_host.h) ------------------
+namespace rt {
+struct Args {   // device pointers; members may be null; goff indexes members from 0 when it is not
+  const float* scores; const int64_t* members; const int64_t* goff; const int64_t* toff; const int32_t* targets;
+  int G, mode, hist_len;
+  int32_t* places; unsigned long long* hist;
+};
+void launch(hipStream_t s, const Args& a);   // hist must be zero; one workgroup per group
+}  // namespace rt
 
 // ---- path finder (path_find.hip): kprn_graph_* / kprn_find_paths / kprn_host_find_paths ---------------
 namespace pf {

@@ -1,6 +1,6 @@
 // libkprn.so -- the scoring stage: everything that serves a scoring pass and what is done with its result.  Passes beside the main stream
 // (kprn_forward_batch_async and its deferred rest), the synchronous passes (kprn_forward_batch, kprn_forward, kprn_forward_ragged), the score board, the ranking
-// and explanation calls and the one-call routes.  Kernels: lstm_fused_fwd*.hip, rank_groups.hip, explain_paths.hip.  The pass itself and what it shares with
+// and explanation calls and the one-call routes.  Kernels: lstm_fused_fwd*.hip, rank_groups.hip, rank_targets.hip, explain_paths.hip.  The pass itself and what it shares with
 // training (forward_impl, catch_up, pool_stage, dropin_feed) live in kprn_api.hip.
 //
 // Streams.  main = h->stream: training, the synchronous passes, every ranking and explanation launch.  score = h->score_stream (option "score_overlap"; probed
@@ -28,6 +28,7 @@
 #include <algorithm>
 
 #include "kprn_internal.h"
+#include "rank_targets_host.h"
 
 namespace score {
 // while it lives, "the handle's stream and score buffers" are the given side stream and S2 / sel2: what fused::forward and pool_stage launch goes there
@@ -418,6 +419,50 @@ int kprn_rank_groups(kprn_handle* h, const int64_t* members, const int64_t* grou
   join_put(h);
   rank_run(h, h->board, members, group_offsets, pos, G, mode, K, max_n, ranks, topk_idx, topk_score, hist, hist_len);
   HIP_TRY(hipStreamSynchronize(h->stream));
+  prof_drain(h);
+  API_END(h)
+}
+
+// ranking targets in groups of any size (kernel: rank_targets.hip): arguments up, ONE launch, results down, one wait
+int kprn_rank_targets(kprn_handle* h, const int64_t* members, const int64_t* group_offsets, const int64_t* target_offsets, const int32_t* targets, int32_t G,
+                      int32_t mode, int32_t* places, int64_t* hist, int32_t hist_len) {
+  API_BEGIN(h)
+  KPRN_REQUIRE(h->board, KPRN_E_ARG, "no board: call kprn_board_reserve first");
+  KPRN_REQUIRE(places && hist, KPRN_E_ARG, "places and hist are required");
+  const char* why = "";
+  const int rc = rt::validate(h->board_n, members, group_offsets, target_offsets, targets, G, mode, hist_len, &why);
+  if (rc != KPRN_OK) throw KprnError{rc, why};
+  join_put(h);
+  const int64_t m0 = group_offsets[0], M = members ? group_offsets[G] - m0 : 0, NT = target_offsets[G];
+  auto up = [](size_t b) { return (b + 15) & ~(size_t)15; };
+  const size_t o_goff = 0, o_toff = o_goff + up((size_t)(G + 1) * 8), o_mem = o_toff + up((size_t)(G + 1) * 8), o_hist = o_mem + up((size_t)M * 8),
+               o_tg = o_hist + up((size_t)(hist_len + 4) * 8), o_pl = o_tg + up((size_t)NT * 4), total = o_pl + up((size_t)NT * 4);
+  hipStream_t s = h->stream;
+  char* base = (char*)grow_call_block(s, h->rank_buf, h->rank_buf_bytes, total);
+  std::vector<int64_t> rebased;
+  const int64_t* goff_up = group_offsets;
+  if (members && m0 != 0) {   // (the kernel indexes the uploaded slice of members from 0)
+    rebased.assign(group_offsets, group_offsets + G + 1);
+    for (auto& v : rebased) v -= m0;
+    goff_up = rebased.data();
+  }
+  HIP_TRY(hipMemcpyAsync(base + o_goff, goff_up, (size_t)(G + 1) * 8, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(base + o_toff, target_offsets, (size_t)(G + 1) * 8, hipMemcpyHostToDevice, s));
+  if (members) HIP_TRY(hipMemcpyAsync(base + o_mem, members + m0, (size_t)M * 8, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(base + o_tg, targets, (size_t)NT * 4, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemsetAsync(base + o_hist, 0, (size_t)(hist_len + 4) * 8, s));
+  rt::Args a;
+  a.scores = h->board; a.members = members ? (const int64_t*)(base + o_mem) : nullptr;
+  a.goff = (const int64_t*)(base + o_goff); a.toff = (const int64_t*)(base + o_toff); a.targets = (const int32_t*)(base + o_tg);
+  a.G = G; a.mode = mode; a.hist_len = hist_len;
+  a.places = (int32_t*)(base + o_pl); a.hist = (unsigned long long*)(base + o_hist);
+  {
+    ProfScope ps(h, "rank_targets");
+    rt::launch(s, a);
+  }
+  HIP_TRY(hipMemcpyAsync(places, base + o_pl, (size_t)NT * 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(hist, base + o_hist, (size_t)(hist_len + 4) * 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));   // (also covers `rebased`, the source of a pageable copy)
   prof_drain(h);
   API_END(h)
 }

@@ -94,6 +94,28 @@ class KnowledgeGraph:
         deg = np.bincount(self.interactions(relation_name)[:, 1], minlength=self.Ve + 1).astype(np.float64)
         return np.power(deg[np.asarray(items, np.int64)], float(alpha)).astype(np.float32)
 
+    def holdout(self, relation_name, train_fraction=0.8, seed=1):
+        """The reference's split (release/data_prepare/split_train_test.py: a global shuffle, the first int(n * fraction) positives to train) as arrays:
+        pos = interactions(relation), perm = np.random.RandomState(seed).permutation(len(pos)), the first int(len * train_fraction) of pos[perm] stay in
+        train.  A user all of whose pairs were held keeps them all in train instead: a user without an edge cannot be reached (cold start is out of scope).
+        -> (train_kg, held [m, 2] sorted by (user, item)).  train_kg is this graph without EVERY stored edge between a held user and its held item, in
+        either direction and under any relation -- the held pair is not adjacent in the graph the model trains on and is queried through; node types,
+        vocabularies and table sizes are unchanged."""
+        pos = self.interactions(relation_name)
+        if not 0.0 <= float(train_fraction) <= 1.0:
+            raise ValueError("train_fraction must be in 0..1")
+        perm = np.random.RandomState(int(seed) & 0xFFFFFFFF).permutation(len(pos))
+        is_held = np.zeros(len(pos), bool)
+        is_held[perm[int(len(pos) * float(train_fraction)):]] = True
+        kept = np.bincount(pos[~is_held, 0], minlength=self.Ve + 1)   # train pairs per user
+        is_held &= kept[pos[:, 0]] > 0
+        held = pos[is_held]
+        code = lambda a, b: a.astype(np.int64) * (self.Ve + 1) + b.astype(np.int64)
+        gone = code(held[:, 0], held[:, 1])
+        keep = ~(np.isin(code(self.src, self.dst), gone) | np.isin(code(self.dst, self.src), gone))
+        train = KnowledgeGraph(self.src[keep], self.dst[keep], self.rel[keep], self.node_types, self.end_relation, self.Vr, self.Vt, self.vocabs)
+        return train, held
+
     def host_find_paths(self, pairs, min_hops, max_hops, max_paths, T, F=None, threads=1, want_idx=True, walks=0, seed=0, draw=0):
         """walks > 0: the hops past 3 sampled (_ffi.host_find_paths_sampled)"""
         if int(walks) != 0:
@@ -169,6 +191,31 @@ def _rank_key(scores, mode):
     return np.where(np.isnan(s), -np.inf, s.astype(np.float64))
 
 
+def _score_candidates(eng, graph, sampler, users, min_hops, max_hops, max_paths, T, class_id, walks, seed, draw, exclude_adjacent, max_candidates):
+    """The front half of recommend_users and evaluate_from_graph, up to the board put: the users' candidates found on the device (capped at max_candidates by
+    path count when that is > 0), the finder reading that list where it lies, the batch scored, its probabilities put on a board of exactly batch.B lines.
+    -> None when no user has a candidate with a path, else (batch, pairs, cand, uoff, found): pair b of the batch is row cand[b] of the candidate list
+    `pairs` [n, 2] = (user, item), user g's surviving pairs are the batch's pairs uoff[g] .. uoff[g + 1] = those board lines.  The caller frees the batch."""
+    T = max_hops + 1 if T is None else int(T)
+    pairs, gc = eng.find_candidates(graph, sampler, users, min_hops, min(int(max_hops), _ffi.FIND_MAX_HOPS), exclude_adjacent, cap=max_candidates)
+    if len(pairs) == 0:
+        return None
+    batch, counts, found = eng.find_paths_of_candidates(graph, len(pairs), min_hops, max_hops, max_paths, T, walks=walks, seed=seed, draw=draw)
+    if batch is None:
+        return None
+    try:
+        cand = np.nonzero(counts)[0]
+        ends = np.cumsum(gc, dtype=np.int64)
+        uoff = np.searchsorted(cand, np.concatenate([[0], ends]))
+        eng.forward_async(batch, class_id)
+        eng.board_reserve(batch.B)
+        eng.board_put(0, batch.B)
+    except BaseException:
+        batch.free()
+        raise
+    return batch, pairs, cand, uoff, found
+
+
 def recommend_users(eng, kg, sampler, users, K, M=0, min_hops=1, max_hops=3, max_paths=28, T=None, class_id=1, mode=_ffi.RANK_PRINTED, walks=0, seed=1, draw=0,
                     exclude_adjacent=True, max_candidates=0):
     """What should each of `users` (entity ids) get, and why, without a candidate list: one chain for all of them.  The candidates -- the items of
@@ -192,21 +239,12 @@ def recommend_users(eng, kg, sampler, users, K, M=0, min_hops=1, max_hops=3, max
             out += recommend_users(eng, graph, sampler, users[lo:lo + chunk], K, M, min_hops, max_hops, max_paths, T, class_id, mode, walks, seed, draw,
                                    exclude_adjacent, max_candidates)
         return out
-    T = max_hops + 1 if T is None else int(T)
     out = [[] for _ in users]
-    pairs, gc = eng.find_candidates(graph, sampler, users, min_hops, min(int(max_hops), _ffi.FIND_MAX_HOPS), exclude_adjacent, cap=max_candidates)
-    if len(pairs) == 0:
+    scored = _score_candidates(eng, graph, sampler, users, min_hops, max_hops, max_paths, T, class_id, walks, seed, draw, exclude_adjacent, max_candidates)
+    if scored is None:
         return out
-    batch, counts, found = eng.find_paths_of_candidates(graph, len(pairs), min_hops, max_hops, max_paths, T, walks=walks, seed=seed, draw=draw)
-    if batch is None:
-        return out
+    batch, pairs, cand, uoff, found = scored
     try:
-        cand = np.nonzero(counts)[0]            # pair b of the batch is row cand[b] of the candidate list
-        ends = np.cumsum(gc, dtype=np.int64)
-        uoff = np.searchsorted(cand, np.concatenate([[0], ends]))   # user g's surviving pairs = the batch's pairs uoff[g] .. uoff[g + 1]
-        eng.forward_async(batch, class_id)
-        eng.board_reserve(batch.B)
-        eng.board_put(0, batch.B)
         kk = min(int(K), _ffi.RANK_MAX_K)
         goff, owner = [0], []                   # the sub-groups of at most RANK_MAX_GROUP members, and the user each belongs to
         for g in range(len(users)):
@@ -243,6 +281,67 @@ def recommend_users(eng, kg, sampler, users, K, M=0, min_hops=1, max_hops=3, max
         return out
     finally:
         batch.free()
+
+
+PLACE_UNREACHABLE = -3   # evaluate_from_graph's place of a held pair that never reached the ranking stage
+
+
+def evaluate_from_graph(eng, train_kg, held, sampler, users_per_call=64, min_hops=1, max_hops=3, max_paths=28, T=None, class_id=1, mode=_ffi.RANK_PRINTED, walks=0,
+                        seed=1, max_candidates=0, ks=range(1, 16), max_users=0):
+    """Held-out evaluation against everything a user reaches (KnowledgeGraph.holdout made train_kg and held): for the held pairs' distinct users,
+    users_per_call at a time (max_users > 0: the first that many users only), the chain of recommend_users up to the board put on the TRAIN graph with
+    exclude_adjacent -- so a user's train items are no candidates and its held items are -- and then ONE rank_targets call: the groups are the users'
+    surviving pairs, the targets the held items among them, each placed among the user's non-held candidates (include/kprn.h "ranking targets in groups
+    of any size").  A held pair that is not there -- its item outside the sampler's catalogue, not reached, cut by max_candidates, or left without a
+    kept path -- is a miss for every k: it is counted in hist[hist_len] and reported as n_unreachable.
+    -> dict(hits, ndcgs, n (evalrank.metrics_from_hist over the summed histogram), n_unreachable, n_zero, places [m] int32 in the order of `held` (the
+    evaluated rows: place, _ffi.RANK_ZERO_GROUP or PLACE_UNREACHABLE), held [m, 2], hist)."""
+    from . import evalrank
+    graph = train_kg.on(eng) if isinstance(train_kg, KnowledgeGraph) else train_kg
+    held = np.ascontiguousarray(held, np.int32).reshape(-1, 2)
+    held = held[np.lexsort((held[:, 1], held[:, 0]))]
+    users = np.unique(held[:, 0])
+    if int(max_users) > 0:
+        users = users[:int(max_users)]
+        held = held[np.isin(held[:, 0], users)]
+    ks = list(ks)
+    hist_len = max(ks) if ks else 1
+    per = max(int(users_per_call), 1)
+    if int(max_candidates) > 0:
+        per = max(min(per, (_ffi.CAND_TOP_MAX_BM - 1) // max(int(sampler.M), 1)), 1)
+    first = np.searchsorted(held[:, 0], users)             # user u's held rows = held[first[u] : last[u]]
+    last = np.searchsorted(held[:, 0], users, side="right")
+    places = np.full(len(held), PLACE_UNREACHABLE, np.int32)
+    hist = np.zeros(hist_len + 4, np.int64)
+    for lo in range(0, len(users), per):
+        us = users[lo:lo + per]
+        scored = _score_candidates(eng, graph, sampler, us, min_hops, max_hops, max_paths, T, class_id, walks, seed, 0, True, int(max_candidates))
+        if scored is None:
+            continue
+        batch, pairs, cand, uoff, _found = scored
+        try:
+            items = pairs[cand, 1]                          # the item of every board line
+            goff, toff, targets, rows = [int(uoff[0])], [0], [], []
+            for g in range(len(us)):
+                a, b = int(uoff[g]), int(uoff[g + 1])
+                if a == b:
+                    continue                                # nothing of this user survived: every held pair of it is unreachable
+                mine = held[first[lo + g]:last[lo + g], 1]
+                at = np.nonzero(np.isin(items[a:b], mine))[0]                  # ascending within the group
+                targets.append(at.astype(np.int32))
+                rows.append(first[lo + g] + np.searchsorted(mine, items[a:b][at]))   # the held row of each target
+                goff.append(b); toff.append(toff[-1] + len(at))
+            if toff[-1] == 0:
+                continue
+            res = eng.rank_targets(np.array(goff, np.int64), np.array(toff, np.int64), np.concatenate(targets), mode=mode, hist_len=hist_len)
+            places[np.concatenate(rows)] = res["places"]
+            hist += res["hist"]
+        finally:
+            batch.free()
+    n_unreachable = int((places == PLACE_UNREACHABLE).sum())
+    hist[hist_len] += n_unreachable
+    hits, ndcgs, n = evalrank.metrics_from_hist(hist, hist_len, ks)
+    return dict(hits=hits, ndcgs=ndcgs, n=n, n_unreachable=n_unreachable, n_zero=int(hist[hist_len + 1]), places=places, held=held, hist=hist)
 
 
 def groups_from_counts(counts, n_neg):

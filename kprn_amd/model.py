@@ -58,6 +58,12 @@ def flag_parser():
     a("-loss", default="bce", choices=["bce", "bpr"],
       help="with -kg: bce = nn.BCECriterion on each pair by itself; bpr = the pairwise ranking loss of each positive against its own sampled negatives (the engine's option \"loss\")")
     a("-walks", type=int, default=0, help="walks per pair and hop count that sample the paths of 4 and 5 hops (1..256); needed when -max_hops is above 3")
+    # held-out evaluation from the graph (graph.KnowledgeGraph.holdout + graph.evaluate_from_graph; python -m kprn_amd.train / kprn_amd.evaluate)
+    a("-holdout", type=float, default=0.0, help="with -kg: this share of the -interaction_rel pairs is held out (the reference's split_train_test.py with "
+      "train fraction 1 - this), training sees the rest, and every -evaluationFrequency epochs the held pairs are ranked among everything their users reach; 0 = no split")
+    a("-holdout_seed", type=int, default=1, help="seed of the split's shuffle")
+    a("-eval_users", type=int, default=0, help="evaluate the first N held-out users only (0 = all)")
+    a("-max_candidates", type=int, default=0, help="evaluation ranks among each user's N strongest candidates by path count only (0 = all of them)")
     return p
 
 
@@ -80,6 +86,12 @@ def parse_flags(argv=None):
     if params.loss == "bpr" and not params.kg:
         p.error("-loss bpr needs -kg: the groups it ranks within (a positive and its sampled negatives) exist only when training from a graph")
     check_walks(params.max_hops, params.walks, p.error)
+    if not 0.0 <= params.holdout < 1.0:
+        p.error("-holdout must be in 0 .. 1 (the share of the interactions held out)")
+    if params.holdout > 0 and not params.kg:
+        p.error("-holdout needs -kg: it splits the graph's -interaction_rel edges")
+    if not 0 <= params.max_candidates <= 2**31 - 1 or params.eval_users < 0:
+        p.error("-max_candidates must be in 0 .. 2^31 - 1 and -eval_users >= 0")
     return params
 
 

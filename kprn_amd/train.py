@@ -9,6 +9,9 @@ positives, and every step samples -negatives items per positive (an item's weigh
 uniform; at most -neg_attempts draws per negative), finds the pairs' paths of -min_hops .. -max_hops hops (at most -max_paths each; -max_hops 4 or 5 needs -walks N, the walks that sample the paths of more than 3 hops) and trains, all on the device (graph.train_from_graph); -sampleSeed seeds the shuffles
 and the draws.  Same epoch lines, same -model / -saveFrequency.  -loss bpr trains on the pairwise ranking loss of each positive against its own sampled
 negatives instead of BCE on each pair (include/kprn.h "pairwise loss"); it needs -kg.
+-holdout 0.2 [-holdout_seed 1 -eval_users 0 -max_candidates N] (with -kg) holds that share of the interactions out (KnowledgeGraph.holdout), trains on the
+rest -- positives, catalogue, weights and paths are the train graph's -- and every -evaluationFrequency epochs ranks the held pairs among everything
+their users reach (graph.evaluate_from_graph): the evaluation line of -rank_samples, plus the held pairs that never reached the ranking stage.
 """
 import os
 import sys
@@ -48,16 +51,38 @@ def make_evaluator(eng, params, log=None):
     return evaluator
 
 
+def make_graph_evaluator(eng, params, train_kg, held, sampler, log=None):
+    """the epoch hook behind -holdout: the held pairs ranked among everything their users reach in the train graph (graph.evaluate_from_graph); prints
+    make_evaluator's line and the number of held pairs that never reached the ranking stage"""
+    from . import graph
+
+    def evaluator(i):
+        res = graph.evaluate_from_graph(eng, train_kg, held, sampler, min_hops=params.min_hops, max_hops=params.max_hops, max_paths=params.max_paths,
+                                        walks=params.walks, seed=params.sampleSeed, max_candidates=params.max_candidates, max_users=params.eval_users)
+        hits, ndcgs = res["hits"], res["ndcgs"]
+        print("evaluation at epoch %d over %d samples: " % (i, res["n"]) +
+              "  ".join("hit@%d %.5f ndcg@%d %.5f" % (k, hits[k], k, ndcgs[k]) for k in (1, 5, 10, 15)) + "  unreachable %d" % res["n_unreachable"],
+              file=log or sys.stdout)
+        return res
+    return evaluator
+
+
 def train_from_kg(params, eng, callbacks):
     from . import graph
     from .pathformat import Vocabs
     kg = graph.KnowledgeGraph.from_triples(graph.read_triples(params.kg), Vocabs(params.vocab_dir), params.numEntityTypes)
+    held = None
+    if params.holdout > 0:   # everything below -- positives, catalogue, weights, paths -- is the train graph's
+        kg, held = kg.holdout(params.interaction_rel, 1.0 - params.holdout, params.holdout_seed)
     positives = kg.interactions(params.interaction_rel)
     if len(positives) == 0:
         sys.exit("the graph has no edge of relation %s" % params.interaction_rel)
     items = np.unique(positives[:, 1])
     sampler = eng.sampler(items, kg.item_weights(items, params.neg_alpha, params.interaction_rel))
     print("Training from the graph: %d positives, %d candidate items, %d negatives each" % (len(positives), len(items), params.negatives))
+    if held is not None:
+        print("Held out: %d pairs of %d users" % (len(held), len(np.unique(held[:, 0]))))
+        callbacks = callbacks + [OptimizerCallback(params.evaluationFrequency, make_graph_evaluator(eng, params, kg, held, sampler), "evaluation")]
     graph.train_from_graph(eng, kg, positives, model.opt_from_flags(params), params.minibatch, params.negatives, params.numEpochs, params.sampleSeed,
                            sampler=sampler, max_attempts=params.neg_attempts, min_hops=params.min_hops, max_hops=params.max_hops, max_paths=params.max_paths,
                            epoch_hooks=callbacks, start_iteration=params.startIteration, gradient_step_counter=params.gradientStepCounter, walks=params.walks,
