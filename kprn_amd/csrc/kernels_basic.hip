@@ -3,7 +3,7 @@
 // /root/reference/release/songPathRnn/).
 #include <string.h>
 #include "kprn_internal.h"
-#include "adam_rows_dev.h"
+#include "adam_rows_dev.h"   // (the lane rule: pack_rows)
 #include "reduce_dev.h"   // (sigmoidf_: the gate kernels)
 
 namespace {
@@ -14,12 +14,6 @@ inline unsigned nblocks(int64_t n, int per = TPB) { return (unsigned)((n + per -
 __device__ __forceinline__ void lds_atomic_add(float* p, float v) {  // ds_add_f32 (not the flat aperture path)
   typedef __attribute__((address_space(3))) float lds_float;
   __hip_atomic_fetch_add((lds_float*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -427,251 +421,6 @@ __global__ void k_embed_scatter(const int32_t* __restrict__ idx, int64_t N, int 
   }
 }
 
-// ---------------------------------------------------------------------------------------
-__global__ void k_sumsq(const float* __restrict__ x, int64_t n, float* __restrict__ out) {
-  float acc = 0.f;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) acc += x[i] * x[i];
-  acc = wave_sum(acc);
-  if ((threadIdx.x & 63) == 0) unsafeAtomicAdd(out, acc);
-}
-
-__global__ void k_sumsq_rows(const float* __restrict__ G, const int32_t* __restrict__ rows, const int32_t* __restrict__ count, int d,
-                             float* __restrict__ out) {
-  int nrows = *count;
-  float acc = 0.f;
-  int64_t total = (int64_t)nrows * d;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    float v = G[(int64_t)rows[i / d] * d + (i % d)];
-    acc += v * v;
-  }
-  acc = wave_sum(acc);
-  if ((threadIdx.x & 63) == 0) unsafeAtomicAdd(out, acc);
-}
-
-// deterministic mode: workgroups [0, nb) take x, [nb, 2 nb) the listed rows of G (rows == null: they write 0); a thread sums its strided
-// elements in ascending order, the wave adds its lanes by the butterfly of wave_sum, the workgroup's four waves are added as (0 + 1) + (2 + 3); the partial
-// leaves with a plain store and k_sum_partials adds the 2 nb partials in index order
-__global__ __launch_bounds__(256) void k_sumsq_det(const float* __restrict__ x, int64_t n, const float* __restrict__ G, const int32_t* __restrict__ rows,
-                                                   const int32_t* __restrict__ count, int d, int nb, float* __restrict__ partial) {
-  __shared__ float red[4];
-  float acc = 0.f;
-  if ((int)blockIdx.x < nb) {
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)nb * 256) acc += x[i] * x[i];
-  } else if (rows) {
-    const int64_t total = (int64_t)(*count) * d;
-    for (int64_t i = (int64_t)((int)blockIdx.x - nb) * 256 + threadIdx.x; i < total; i += (int64_t)nb * 256) {
-      const float v = G[(int64_t)rows[i / d] * d + (i % d)];
-      acc += v * v;
-    }
-  }
-  acc = wave_sum(acc);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
-}
-
-// ---- optimisers (optim.adam / optim.adagrad, OneModel.lua:347-361; MyOptimizer.lua:196-218) ----
-#pragma clang fp contract(off)
-__device__ __forceinline__ float clip_factor(const float* norm2, float clip) {
-  if (!norm2) return 1.f;
-  float nrm = sqrtf(*norm2);
-  return (nrm > clip) ? clip / nrm : 1.f;
-}
-
-using kk_dev::adam_elem;   // (adam_rows_dev.h: shared with lstm_fused_prefix.hip's catch-up + prefix launch)
-
-// consume != 0: the gradient is zeroed as it is used (zeroGradParameters of the next trainBatch, MyOptimizer.lua:186, done here);
-// [z0,z0+zn0) and [z1,z1+zn1): pad rows of the arena, re-zeroed after the update (zeroPadTokens, MyOptimizer.lua:219);
-// tab_slot: this step's entry of the device step-size table (read by the lazy row replay).
-struct AdamDenseJob {   // the dense arena's share of an optimiser step (k_adam_dense, or extra workgroups of the row update's launch)
-  float *x, *g, *m, *v; int64_t n;
-  float step, b1, b2, eps; const float* norm2; float clip, l2; int reg, consume;
-  int64_t z0; int zn0; int64_t z1; int zn1; float* tab_slot;
-};
-__device__ __forceinline__ void adam_dense_block(const AdamDenseJob& a, int64_t block) {
-  const int64_t i = block * blockDim.x + threadIdx.x;
-  if (i == 0 && a.tab_slot) *a.tab_slot = a.step;
-  if (i >= a.n) return;
-  float gi = a.g[i];
-  float xi = a.x[i];
-  if (a.reg) { gi = gi * clip_factor(a.norm2, a.clip); gi = gi + a.l2 * xi; }
-  float mi = a.m[i], vi = a.v[i];
-  adam_elem(xi, mi, vi, gi, a.step, a.b1, a.b2, a.eps);
-  if ((i >= a.z0 && i < a.z0 + a.zn0) || (i >= a.z1 && i < a.z1 + a.zn1)) xi = 0.f;
-  a.x[i] = xi; a.m[i] = mi; a.v[i] = vi;
-  if (a.consume) a.g[i] = 0.f;
-}
-__global__ void k_adam_dense(AdamDenseJob a) { adam_dense_block(a, blockIdx.x); }
-
-__global__ void k_adagrad_dense(float* __restrict__ x, float* __restrict__ g, float* __restrict__ G, int64_t n, float clr,
-                                const float* __restrict__ norm2, float clip, float l2, int reg, int consume, int64_t z0, int zn0, int64_t z1,
-                                int zn1) {
-  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  float gi = g[i];
-  float xi = x[i];
-  if (reg) { gi = gi * clip_factor(norm2, clip); gi = gi + l2 * xi; }
-  float Gi = G[i] + gi * gi;
-  G[i] = Gi;
-  xi = xi - clr * gi / (sqrtf(Gi) + 1e-10f);
-  if ((i >= z0 && i < z0 + zn0) || (i >= z1 && i < z1 + zn1)) xi = 0.f;
-  x[i] = xi;
-  if (consume) g[i] = 0.f;
-}
-
-// lazy-exact Adam over a list of rows: one wave per row.  Replays the steps the row missed
-// (gradient 0) with the same arithmetic as k_adam_dense, then (apply_step) applies step t_now
-// with the accumulated gradient and clears it.  Result is bit-identical to updating every
-// row at every step, which is what optim.adam does to the flat vector.
-__global__ void k_adam_rows(float* __restrict__ W, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                            int32_t* __restrict__ last, const int32_t* __restrict__ rows, const int32_t* __restrict__ count, int d,
-                            int32_t t_now, int apply_step, const float* __restrict__ step_tab, float b1, float b2, float eps, int64_t pad_row) {
-  const int lane = threadIdx.x & 63;
-  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  if (wave >= *count) return;
-  const int64_t r = rows[wave];
-  const int32_t l = last[r];
-  const int32_t upto = apply_step ? t_now - 1 : t_now;  // replay (l, upto] with g = 0
-  for (int e = lane; e < d; e += 64) {
-    const int64_t o = r * d + e;
-    float x = W[o], mm = m[o], vv = v[o];
-    if (l > 0)
-      for (int32_t k = l + 1; k <= upto; ++k) adam_elem(x, mm, vv, 0.f, step_tab[k], b1, b2, eps);
-    if (apply_step) {
-      adam_elem(x, mm, vv, g[o], step_tab[t_now], b1, b2, eps);
-      g[o] = 0.f;
-    }
-    if (r == pad_row) x = 0.f;  // zeroPadTokens after every step the row lived through (MyOptimizer.lua:219)
-    W[o] = x; m[o] = mm; v[o] = vv;
-  }
-  if (lane == 0) last[r] = t_now;
-}
-
-// the same for rows of d = 4 G floats handled by G = 8 / 16 / 32 lanes with 16-byte accesses (d = 32: eight rows per wave instead of one
-// half-empty wave per row; the per-element arithmetic is adam_elem's, so the result stays bit-identical to the dense sweep)
-// dense (nullable in effect: n_dense_blocks = 0): the dense arena's update rides in the same launch as workgroups [rows_blocks, rows_blocks + n_dense_blocks)
-// -- two latency-bound launches of the step's serial tail become one.  The row update then takes THIS step's size from `step_now` (the dense job writes the
-// table entry for later replays; inside one launch nothing orders that store before a row's read of it); step_now < 0: read it from the table.
-template <int G>
-__global__ void k_adam_rows_v(float* __restrict__ W, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                              int32_t* __restrict__ last, const int32_t* __restrict__ rows, const int32_t* __restrict__ count,
-                              int32_t t_now, int apply_step, const float* __restrict__ step_tab, float b1, float b2, float eps, int64_t pad_row,
-                              int rows_blocks, float step_now, AdamDenseJob dense) {
-  if ((int)blockIdx.x >= rows_blocks) { adam_dense_block(dense, (int64_t)blockIdx.x - rows_blocks); return; }
-  const kk_dev::AdamRowsArgs ra{W, g, m, v, last, rows, count, t_now, apply_step, step_tab, b1, b2, eps, pad_row, step_now};
-  kk_dev::adam_rows_lane_block<G>(ra, (int64_t)blockIdx.x);
-}
-
-// Data-parallel exchange, union + update in ONE launch (lazy-exact Adam, no clip / L2).  `all` = the all-gathered packed buffers
-// [world][stride] of kprn_sparse_grad_pack: {count, -, -, -, ids[cap] ASCENDING (the batch index's run-length-encoded sorted keys, each
-// row once), rows[cap][d]}.  One G-lane group per (rank, entry); lane j finds the row in rank j's list by binary search (world <= G), the
-// positions are shared through the group; the entry of the LOWEST rank that touched the row owns it: it adds the other ranks'
-// contributions in RANK ORDER (the same addition order on every replica, and the order k_add_rank's launches used), replays the row's
-// skipped steps and applies this one.  No flag array over the table, no compaction, no gradient accumulator round trip.
-template <int G>
-__global__ void k_union_adam(const int32_t* __restrict__ all, int world, int cap, int64_t stride, float* __restrict__ W, float* __restrict__ m,
-                             float* __restrict__ v, int32_t* __restrict__ last, int32_t t_now, const float* __restrict__ step_tab, float b1, float b2,
-                             float eps, int64_t pad_row) {
-  typedef float f4 __attribute__((ext_vector_type(4)));
-  const int64_t slot = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / G;
-  const int j = threadIdx.x % G;
-  const int base = (threadIdx.x & 63) & ~(G - 1);
-  const int r = (int)(slot / cap), k = (int)(slot - (int64_t)r * cap);
-  const bool in_range = r < world;
-  const int32_t* mine = all + (int64_t)(in_range ? r : 0) * stride;
-  const bool live = in_range && k < mine[0];
-  const int32_t row = live ? mine[4 + k] : 0;
-  int pos = -1;
-  if (live && j < world && j != r) {
-    const int32_t* o = all + (int64_t)j * stride;
-    const int n = o[0];
-    int lo = 0, hi = n;
-    while (lo < hi) {
-      const int mid = (lo + hi) >> 1;
-      if (o[4 + mid] < row) lo = mid + 1; else hi = mid;
-    }
-    if (lo < n && o[4 + lo] == row) pos = lo;
-  }
-  f4 g4 = f4{0.f, 0.f, 0.f, 0.f};
-  if (live) g4 = *(const f4*)((const float*)(mine + 4 + cap) + (int64_t)k * (4 * G) + 4 * j);
-  bool owner = live;
-  for (int q = 0; q < world; ++q) {   // every lane of the wave takes every shuffle (the groups of one wave may belong to two ranks)
-    const int p = __shfl(pos, base + q, 64);
-    if (p < 0 || !live || q == r) continue;
-    if (q < r) owner = false;
-    else if (owner) g4 = g4 + *(const f4*)((const float*)(all + (int64_t)q * stride + 4 + cap) + (int64_t)p * (4 * G) + 4 * j);
-  }
-  if (!owner) return;
-  const int32_t l = last[row];
-  const int64_t o = (int64_t)row * (4 * G) + 4 * j;
-  const f4 x4 = *(const f4*)(W + o), m4 = *(const f4*)(m + o), v4 = *(const f4*)(v + o);
-  float x[4] = {x4[0], x4[1], x4[2], x4[3]}, mm[4] = {m4[0], m4[1], m4[2], m4[3]}, vv[4] = {v4[0], v4[1], v4[2], v4[3]};
-  if (l > 0)
-    for (int32_t kk = l + 1; kk <= t_now - 1; ++kk) {
-      const float st = step_tab[kk];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) adam_elem(x[q], mm[q], vv[q], 0.f, st, b1, b2, eps);
-    }
-  const float st = step_tab[t_now];
-#pragma unroll
-  for (int q = 0; q < 4; ++q) adam_elem(x[q], mm[q], vv[q], g4[q], st, b1, b2, eps);
-  if (row == pad_row) { x[0] = x[1] = x[2] = x[3] = 0.f; }  // zeroPadTokens (MyOptimizer.lua:219)
-  *(f4*)(W + o) = f4{x[0], x[1], x[2], x[3]}; *(f4*)(m + o) = f4{mm[0], mm[1], mm[2], mm[3]}; *(f4*)(v + o) = f4{vv[0], vv[1], vv[2], vv[3]};
-  if (j == 0) last[row] = t_now;
-}
-
-__global__ void k_adam_flush_all(float* __restrict__ W, float* __restrict__ m, float* __restrict__ v, int32_t* __restrict__ last, int64_t V,
-                                 int d, int32_t t_now, const float* __restrict__ step_tab, float b1, float b2, float eps, int64_t pad_row) {
-  const int lane = threadIdx.x & 63;
-  const int64_t r = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  if (r >= V) return;
-  const int32_t l = last[r];
-  if (l <= 0 || l >= t_now) return;
-  for (int e = lane; e < d; e += 64) {
-    const int64_t o = r * d + e;
-    float x = W[o], mm = m[o], vv = v[o];
-    for (int32_t k = l + 1; k <= t_now; ++k) adam_elem(x, mm, vv, 0.f, step_tab[k], b1, b2, eps);
-    if (r == pad_row) x = 0.f;
-    W[o] = x; m[o] = mm; v[o] = vv;
-  }
-  if (lane == 0) last[r] = t_now;
-}
-
-__global__ void k_adagrad_rows(float* __restrict__ W, float* __restrict__ g, float* __restrict__ G, const int32_t* __restrict__ rows,
-                               const int32_t* __restrict__ count, int d, float clr, int64_t pad_row) {
-  const int lane = threadIdx.x & 63;
-  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  if (wave >= *count) return;
-  const int64_t r = rows[wave];
-  for (int e = lane; e < d; e += 64) {
-    const int64_t o = r * d + e;
-    float gi = g[o];
-    float Gi = G[o] + gi * gi;
-    G[o] = Gi;
-    W[o] = (r == pad_row) ? 0.f : W[o] - clr * gi / (sqrtf(Gi) + 1e-10f);
-    g[o] = 0.f;
-  }
-}
-#pragma clang fp contract(fast)
-
-__global__ void k_zero_row(float* __restrict__ W, int64_t row, int d) {
-  int j = blockIdx.x * blockDim.x + threadIdx.x;
-  if (j < d) W[row * d + j] = 0.f;
-}
-
-// MyOptimizer:zeroPadTokens (MyOptimizer.lua:74-93): the three pad rows in one launch
-__global__ void k_zero_pad3(float* __restrict__ a, int na, float* __restrict__ b, int nb, float* __restrict__ c, int nc) {
-  int j = blockIdx.x * blockDim.x + threadIdx.x;
-  if (j < na) a[j] = 0.f;
-  if (j < nb) b[j] = 0.f;
-  if (j < nc) c[j] = 0.f;
-}
-
-__global__ void k_fill_i32(int32_t* __restrict__ x, int64_t n, int32_t v) {
-  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) x[i] = v;
-}
-
 // data-parallel exchange helpers -------------------------------------------------------------
 __global__ void k_pack_rows(float* __restrict__ G, const int32_t* __restrict__ rows, const int32_t* __restrict__ count, int d,
                             int32_t* __restrict__ ids_out, float* __restrict__ rows_out, int32_t* __restrict__ count_out) {
@@ -711,16 +460,6 @@ __global__ void k_pack_rows_v(float* __restrict__ G, const int32_t* __restrict__
   *src = f4{0.f, 0.f, 0.f, 0.f};
 }
 
-__global__ void k_clear_rows(float* __restrict__ G, const int32_t* __restrict__ rows, const int32_t* __restrict__ count, int d) {
-  const int lane = threadIdx.x & 63;
-  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  if (wave >= *count) return;
-  const int64_t r = rows[wave];
-  for (int e = lane; e < d; e += 64) G[r * d + e] = 0.f;
-}
-
-// per (64-row tile, step): leader[row] = first row of the tile with the same entity id (-1 past N).
-// Used by the fused backward to fold duplicate rows before the embedding-gradient atomics.
 // uniform(-a, a) init (OneModel.lua:306-309); counter-based splitmix64
 __global__ void k_fill_uniform(float* __restrict__ x, int64_t n, float a, uint64_t seed, uint64_t offset) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1307,156 +1046,28 @@ void embed_scatter(hipStream_t s, const int32_t* idx, int64_t N, int T, int F, i
   CHECK_LAUNCH();
 }
 
-void sumsq(hipStream_t s, const float* x, int64_t n, float* out) {
-  if (n <= 0) return;
-  unsigned g = nblocks(n);
-  if (g > 2048) g = 2048;
-  hipLaunchKernelGGL(k_sumsq, dim3(g), dim3(TPB), 0, s, x, n, out);
-  CHECK_LAUNCH();
-}
-
-void sumsq_rows(hipStream_t s, const float* G, const int32_t* rows, const int32_t* count, int d, float* out) {
-  hipLaunchKernelGGL(k_sumsq_rows, dim3(1024), dim3(TPB), 0, s, G, rows, count, d, out);
-  CHECK_LAUNCH();
-}
-
-void sumsq_det(hipStream_t s, const float* x, int64_t n, const float* G, const int32_t* rows, const int32_t* count, int d, float* partial, float* out) {
-  const int nb = SUMSQ_DET_BLOCKS / 2;
-  hipLaunchKernelGGL(k_sumsq_det, dim3(2 * nb), dim3(256), 0, s, x, n, G, rows, count, d, nb, partial);
-  CHECK_LAUNCH();
-  sum_partials(s, partial, 2 * nb, out, 0);
-}
-
-static AdamDenseJob dense_job(float* x, float* g, float* m, float* v, int64_t n, float step, float b1, float b2, float eps,
-                              const float* norm2, float clip, float l2, int consume, int64_t z0, int zn0, int64_t z1, int zn1, float* tab_slot) {
-  AdamDenseJob a;
-  a.x = x; a.g = g; a.m = m; a.v = v; a.n = n; a.step = step; a.b1 = b1; a.b2 = b2; a.eps = eps; a.norm2 = norm2; a.clip = clip; a.l2 = l2;
-  a.reg = (norm2 != nullptr || l2 != 0.f) ? 1 : 0; a.consume = consume; a.z0 = z0; a.zn0 = zn0; a.z1 = z1; a.zn1 = zn1; a.tab_slot = tab_slot;
-  return a;
-}
-void adam_dense(hipStream_t s, float* x, float* g, float* m, float* v, int64_t n, float step, float b1, float b2, float eps,
-                const float* norm2, float clip, float l2, int consume, int64_t z0, int zn0, int64_t z1, int zn1, float* tab_slot) {
-  if (n <= 0) return;
-  hipLaunchKernelGGL(k_adam_dense, dim3(nblocks(n)), dim3(TPB), 0, s, dense_job(x, g, m, v, n, step, b1, b2, eps, norm2, clip, l2, consume, z0, zn0, z1, zn1, tab_slot));
-  CHECK_LAUNCH();
-}
-
-void adagrad_dense(hipStream_t s, float* x, float* g, float* G, int64_t n, float clr, const float* norm2, float clip, float l2, int consume,
-                   int64_t z0, int zn0, int64_t z1, int zn1) {
-  if (n <= 0) return;
-  int reg = (norm2 != nullptr || l2 != 0.f) ? 1 : 0;
-  hipLaunchKernelGGL(k_adagrad_dense, dim3(nblocks(n)), dim3(TPB), 0, s, x, g, G, n, clr, norm2, clip, l2, reg, consume, z0, zn0, z1, zn1);
-  CHECK_LAUNCH();
-}
-
-void adam_rows(hipStream_t s, float* W, float* g, float* m, float* v, int32_t* last, const int32_t* rows, const int32_t* count, int64_t max_rows,
-               int d, int32_t t_now, int apply_step, const float* step_tab, float b1, float b2, float eps, int64_t pad_row) {
-  if (max_rows <= 0) return;
-  const bool al = !(((uintptr_t)W | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15);
-  AdamDenseJob none;
-  memset(&none, 0, sizeof(none));
-  if (al && d == 32) { const int nb = (int)nblocks(max_rows * 8); hipLaunchKernelGGL(k_adam_rows_v<8>, dim3(nb), dim3(TPB), 0, s, W, g, m, v, last, rows, count, t_now, apply_step, step_tab, b1, b2, eps, pad_row, nb, -1.f, none); }
-  else if (al && d == 64) { const int nb = (int)nblocks(max_rows * 16); hipLaunchKernelGGL(k_adam_rows_v<16>, dim3(nb), dim3(TPB), 0, s, W, g, m, v, last, rows, count, t_now, apply_step, step_tab, b1, b2, eps, pad_row, nb, -1.f, none); }
-  else if (al && d == 128) { const int nb = (int)nblocks(max_rows * 32); hipLaunchKernelGGL(k_adam_rows_v<32>, dim3(nb), dim3(TPB), 0, s, W, g, m, v, last, rows, count, t_now, apply_step, step_tab, b1, b2, eps, pad_row, nb, -1.f, none); }
-  else hipLaunchKernelGGL(k_adam_rows, dim3(nblocks(max_rows * 64)), dim3(TPB), 0, s, W, g, m, v, last, rows, count, d, t_now, apply_step, step_tab, b1,
-                          b2, eps, pad_row);
-  CHECK_LAUNCH();
-}
-
-// the optimiser step of the lazy-exact row update AND of the dense arena as ONE launch (rows of 32 / 64 / 128 floats, 16-byte aligned tables); false: the
-// caller launches the two separately.  Same per-element arithmetic as the separate kernels (adam_elem): bit-identical results.
-bool adam_step_merged(hipStream_t s, float* W, float* g, float* m, float* v, int32_t* last, const int32_t* rows, const int32_t* count, int64_t max_rows, int d,
-                      int32_t t_now, const float* step_tab, int64_t pad_row, float* dx, float* dg, float* dm, float* dv, int64_t dn, float step, float b1,
-                      float b2, float eps, const float* norm2, float clip, float l2, int64_t z0, int zn0, int64_t z1, int zn1, float* tab_slot) {
-  const bool al = !(((uintptr_t)W | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15);
-  if (max_rows <= 0 || dn <= 0 || !al || !(d == 32 || d == 64 || d == 128)) return false;
-  const AdamDenseJob dj = dense_job(dx, dg, dm, dv, dn, step, b1, b2, eps, norm2, clip, l2, /*consume=*/1, z0, zn0, z1, zn1, tab_slot);
-  const int nd = (int)nblocks(dn);
-  if (d == 32) { const int nb = (int)nblocks(max_rows * 8); hipLaunchKernelGGL(k_adam_rows_v<8>, dim3(nb + nd), dim3(TPB), 0, s, W, g, m, v, last, rows, count, t_now, 1, step_tab, b1, b2, eps, pad_row, nb, step, dj); }
-  else if (d == 64) { const int nb = (int)nblocks(max_rows * 16); hipLaunchKernelGGL(k_adam_rows_v<16>, dim3(nb + nd), dim3(TPB), 0, s, W, g, m, v, last, rows, count, t_now, 1, step_tab, b1, b2, eps, pad_row, nb, step, dj); }
-  else { const int nb = (int)nblocks(max_rows * 32); hipLaunchKernelGGL(k_adam_rows_v<32>, dim3(nb + nd), dim3(TPB), 0, s, W, g, m, v, last, rows, count, t_now, 1, step_tab, b1, b2, eps, pad_row, nb, step, dj); }
-  CHECK_LAUNCH();
-  return true;
-}
-
-void adam_flush_all(hipStream_t s, float* W, float* m, float* v, int32_t* last, int64_t V, int d, int32_t t_now, const float* step_tab, float b1,
-                    float b2, float eps, int64_t pad_row) {
-  hipLaunchKernelGGL(k_adam_flush_all, dim3(nblocks(V * 64)), dim3(TPB), 0, s, W, m, v, last, V, d, t_now, step_tab, b1, b2, eps, pad_row);
-  CHECK_LAUNCH();
-}
-
-void adagrad_rows(hipStream_t s, float* W, float* g, float* G, const int32_t* rows, const int32_t* count, int64_t max_rows, int d, float clr,
-                  int64_t pad_row) {
-  if (max_rows <= 0) return;
-  hipLaunchKernelGGL(k_adagrad_rows, dim3(nblocks(max_rows * 64)), dim3(TPB), 0, s, W, g, G, rows, count, d, clr, pad_row);
-  CHECK_LAUNCH();
-}
-
-void zero_pad3(hipStream_t s, float* a, int na, float* b, int nb, float* c, int nc) {
-  const int n = na > nb ? (na > nc ? na : nc) : (nb > nc ? nb : nc);
-  hipLaunchKernelGGL(k_zero_pad3, dim3(nblocks(n)), dim3(TPB), 0, s, a, na, b, nb, c, nc);
-  CHECK_LAUNCH();
-}
-
-void zero_rows(hipStream_t s, float* W, int64_t row, int d) {
-  hipLaunchKernelGGL(k_zero_row, dim3(nblocks(d)), dim3(TPB), 0, s, W, row, d);
-  CHECK_LAUNCH();
-}
-
 void pack_rows(hipStream_t s, float* G, const int32_t* rows, const int32_t* count, int64_t max_rows, int d, int32_t* ids_out, float* rows_out,
                int32_t* count_out, const float* tail_src, int64_t n_tail, float* tail_dst) {
   int64_t waves = max_rows > 0 ? max_rows : 1;
-  const bool al = !(((uintptr_t)G | (uintptr_t)rows_out | (uintptr_t)tail_dst) & 15);
-  const int tail_blocks = n_tail > 0 ? (int)std::min<int64_t>((n_tail + 255) / 256, 256) : 0;
-#define KPRN_PACK_V(LG)                                                                                                                      \
-  {                                                                                                                                          \
-    const int rb = (int)nblocks(waves * LG);                                                                                                 \
-    hipLaunchKernelGGL(k_pack_rows_v<LG>, dim3((unsigned)(rb + tail_blocks)), dim3(TPB), 0, s, G, rows, count, ids_out, rows_out, count_out, rb, \
-                       tail_src, n_tail, tail_dst);                                                                                          \
-  }
-  if (al && d == 32) KPRN_PACK_V(8)
-  else if (al && d == 64) KPRN_PACK_V(16)
-  else if (al && d == 128) KPRN_PACK_V(32)
-  else {
+  const int lanes = kk_dev::row_lanes(d, kk_dev::addr_or(G, rows_out, tail_dst));
+  if (lanes) {
+    const int tail_blocks = n_tail > 0 ? (int)std::min<int64_t>((n_tail + 255) / 256, 256) : 0;
+    kk_dev::with_lanes(lanes, [&](auto lg) {
+      constexpr int LG = decltype(lg)::value;
+      const int rb = (int)nblocks(waves * LG);
+      hipLaunchKernelGGL(k_pack_rows_v<LG>, dim3((unsigned)(rb + tail_blocks)), dim3(TPB), 0, s, G, rows, count, ids_out, rows_out, count_out, rb, tail_src,
+                         n_tail, tail_dst);
+    });
+  } else {
     hipLaunchKernelGGL(k_pack_rows, dim3(nblocks(waves * 64)), dim3(TPB), 0, s, G, rows, count, d, ids_out, rows_out, count_out);
     if (n_tail > 0) HIP_TRY(hipMemcpyAsync(tail_dst, tail_src, (size_t)n_tail * sizeof(float), hipMemcpyDeviceToDevice, s));
   }
-#undef KPRN_PACK_V
   CHECK_LAUNCH();
 }
-
-// union of all ranks' packed rows + the lazy-exact Adam step on it (k_union_adam); false = shape not covered (the caller materialises
-// the union with bidx::merge_rows and takes the ordinary row update)
-bool union_adam(hipStream_t s, const void* all, int world, int cap, int64_t stride, int d, float* W, float* m, float* v, int32_t* last, int32_t t_now,
-                const float* step_tab, float b1, float b2, float eps, int64_t pad_row) {
-  const bool al = !(((uintptr_t)W | (uintptr_t)m | (uintptr_t)v | (uintptr_t)all) & 15) && (stride & 3) == 0 && (cap & 3) == 0;
-  const int lg = d >> 2;
-  if (!al || !(d == 32 || d == 64 || d == 128) || world > lg || world <= 0 || cap <= 0) return false;
-  const int64_t n = (int64_t)world * cap;
-  if (d == 32) hipLaunchKernelGGL(k_union_adam<8>, dim3(nblocks(n * 8)), dim3(TPB), 0, s, (const int32_t*)all, world, cap, stride, W, m, v, last, t_now, step_tab, b1, b2, eps, pad_row);
-  else if (d == 64) hipLaunchKernelGGL(k_union_adam<16>, dim3(nblocks(n * 16)), dim3(TPB), 0, s, (const int32_t*)all, world, cap, stride, W, m, v, last, t_now, step_tab, b1, b2, eps, pad_row);
-  else hipLaunchKernelGGL(k_union_adam<32>, dim3(nblocks(n * 32)), dim3(TPB), 0, s, (const int32_t*)all, world, cap, stride, W, m, v, last, t_now, step_tab, b1, b2, eps, pad_row);
-  CHECK_LAUNCH();
-  return true;
-}
-
 
 void fill_uniform(hipStream_t s, float* x, int64_t n, float a, uint64_t seed, uint64_t offset) {
   if (n <= 0) return;
   hipLaunchKernelGGL(k_fill_uniform, dim3(nblocks(n)), dim3(TPB), 0, s, x, n, a, seed, offset);
-  CHECK_LAUNCH();
-}
-
-void clear_rows(hipStream_t s, float* G, const int32_t* rows, const int32_t* count, int64_t max_rows, int d) {
-  if (max_rows <= 0) return;
-  hipLaunchKernelGGL(k_clear_rows, dim3(nblocks(max_rows * 64)), dim3(TPB), 0, s, G, rows, count, d);
-  CHECK_LAUNCH();
-}
-
-
-void fill_i32(hipStream_t s, int32_t* x, int64_t n, int32_t v) {
-  if (n <= 0) return;
-  hipLaunchKernelGGL(k_fill_i32, dim3(nblocks(n)), dim3(TPB), 0, s, x, n, v);
   CHECK_LAUNCH();
 }
 

@@ -104,43 +104,6 @@ static const ParamInfo* find_param(kprn_handle* h, const char* name) {
   return nullptr;
 }
 
-static void step_tab_reserve(kprn_handle* h, int64_t need) {
-  if (need < h->step_tab_cap) return;
-  int64_t cap = std::max<int64_t>(4096, h->step_tab_cap * 2);
-  while (cap <= need) cap *= 2;
-  float* nd = dalloc<float>(cap);
-  float* nh = nullptr;
-  HIP_TRY(hipHostMalloc((void**)&nh, (size_t)cap * sizeof(float)));
-  memset(nh, 0, (size_t)cap * sizeof(float));
-  if (h->step_tab) {
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    memcpy(nh, h->step_tab_host, (size_t)h->step_tab_cap * sizeof(float));
-    HIP_TRY(hipMemcpy(nd, nh, (size_t)h->step_tab_cap * sizeof(float), hipMemcpyHostToDevice));
-    hipFree(h->step_tab);
-    hipHostFree(h->step_tab_host);
-  }
-  h->step_tab = nd; h->step_tab_host = nh; h->step_tab_cap = cap;
-}
-
-// bring every entity row up to opt_step (needed before anything reads the whole table)
-static void flush_lazy(kprn_handle* h) {
-  join_score(h);
-  if (!h->lazy_pending) return;
-  ProfScope ps(h, "adam_flush_all");
-  kk::adam_flush_all(h->stream, h->We, h->s1_We, h->s2_We, h->We_last, h->cfg.Ve, h->cfg.de, (int32_t)h->opt_step, h->step_tab,
-                     h->last_b1, h->last_b2, h->last_eps, (int64_t)h->cfg.Ve - 1);
-  h->lazy_pending = false;
-  bf16p::params_changed(h, false);   // the replay rewrote rows no row list names: the bf16 shadow of the whole table is stale
-}
-
-static void zero_pad_tokens(kprn_handle* h) {
-  const kprn_config& c = h->cfg;
-  join_score(h);
-  kk::zero_pad3(h->stream, h->dense + h->off_Wt + (int64_t)(c.Vt - 1) * c.dt, c.dt, h->dense + h->off_Wr + (int64_t)(c.Vr - 1) * c.dr, c.dr,
-                h->We + (int64_t)(c.Ve - 1) * c.de, c.de);
-  h->pad_clean = true;
-}
-
 // parameters were written from outside the optimiser: every steady-state shortcut is off
 static void params_touched(kprn_handle* h) {
   join_score(h);
@@ -217,24 +180,6 @@ void ensure_ws_generic(kprn_handle* h, int64_t N, int T) {
   }
 }
 
-// rows of this batch that are behind opt_step are replayed before the forward reads them
-void catch_up(kprn_handle* h, const kprn_batch* b) {
-  if (h->lazy_pending && !b->has_index) { flush_lazy(h); return; }   // (no row list: bring the whole table up to date instead)
-  if (!h->lazy_pending || b->n_uniq == 0) return;
-  if (h->caught_serial == b->serial && h->caught_step == h->opt_step) return;  // this batch's rows are already current
-  join_score(h);
-  ProfScope ps(h, "adam_rows_catchup");
-  // (fused path, a batch with an identical-prefix plan: its prefix table is one more workgroup of this launch -- fused::catch_up_with_prefix)
-  const bool with_prefix = h->cfg.compute_dtype == 0 && use_fused(h, b, false) &&
-                           fused::catch_up_with_prefix(h, b, h->We, h->g_We, h->s1_We, h->s2_We, h->We_last, (int32_t)h->opt_step, h->step_tab, h->last_b1, h->last_b2, h->last_eps);
-  // count lives at the tail of the list buffer
-  if (!with_prefix)
-  kk::adam_rows(h->stream, h->We, h->g_We, h->s1_We, h->s2_We, h->We_last, b->uniq, b->uniq + b->uniq_cap, b->n_uniq, h->cfg.de,
-                (int32_t)h->opt_step, 0, h->step_tab, h->last_b1, h->last_b2, h->last_eps, (int64_t)h->cfg.Ve - 1);
-  bf16p::rows_updated(h, b->uniq, b->uniq + b->uniq_cap, b->n_uniq);
-  h->caught_serial = b->serial; h->caught_step = h->opt_step;
-}
-
 // every_class: also pooled / probs of all C classes (what kprn_forward_batch can hand out); else the selected class only
 void pool_stage(kprn_handle* h, const kprn_batch* b, int cid, bool every_class) {
   const kprn_config& c = h->cfg;
@@ -269,7 +214,7 @@ void forward_impl(kprn_handle* h, const kprn_batch* b, int class_id, bool save_f
   check_batch(h, b, class_id);
   const int64_t N = b->N;
   const int sel = (save_for_backward || !(every_class || all_scores)) ? class_id - 1 : -1;
-  catch_up(h, b);
+  optim::catch_up(h, b);
   ensure_ws_common(h, N, b->B, batch_partials(b));
   if (use_fused(h, b, save_for_backward)) {
     bool dual = false;
@@ -305,11 +250,11 @@ void forward_impl(kprn_handle* h, const kprn_batch* b, int class_id, bool save_f
 static void dp_release(kprn_handle* h);
 // words of the dense gradient arena riding behind the packed rows (padded so that every rank's slice of the gathered buffer keeps
 // 16-byte alignment)
-static inline int64_t dp_tail_words(const kprn_handle* h) { return h->dp_dense_in_pack ? ((h->n_dense + 3) & ~(int64_t)3) : 0; }
+int64_t dp_tail_words(const kprn_handle* h) { return h->dp_dense_in_pack ? ((h->n_dense + 3) & ~(int64_t)3) : 0; }
 
 // a union recorded by kprn_sparse_grad_merge (dp_fused_update) -> the summed rows in g_We + the sorted union list, as the unfused merge
 // leaves them
-static void materialize_union(kprn_handle* h) {
+void materialize_union(kprn_handle* h) {
   if (!h->dp_union_pending) return;
   h->dp_union_pending = false;
   const int64_t n = (int64_t)h->dp_world * h->dp_cap;
@@ -448,134 +393,6 @@ static void backward_impl(kprn_handle* h, const kprn_batch* b, int class_id, int
   h->grads_serial = b->serial;
 }
 
-// What a kprn_opt may not ask of this handle, checked before a step launches or writes anything.  The method stays what the handle's first step used: optimiser
-// slot 0 holds Adam's first moments or Adagrad's sums of squares, one or the other -- Adagrad's square root over Adam's negative moments is NaN, Adam would
-// read the sums as momentum -- and an Adagrad step leaves no step size for a lagging row's replay.
-static void opt_check(const kprn_handle* h, const kprn_opt* o) {
-  KPRN_REQUIRE(o != nullptr, KPRN_E_ARG, "opt is NULL");
-  KPRN_REQUIRE(o->method == 0 || o->method == 1, KPRN_E_ARG, "opt.method must be 0 (adagrad) or 1 (adam)");
-  KPRN_REQUIRE(h->opt_method < 0 || o->method == h->opt_method, KPRN_E_ARG,
-               std::string("opt.method changed from ") + (h->opt_method == 1 ? "adam to adagrad" : "adagrad to adam") +
-                   " on a handle that has taken steps: the two methods keep different state in optimiser slot 0 (first moments / sums of squares); use a new handle");
-}
-
-static void apply_update_impl(kprn_handle* h, const kprn_opt* o) {
-  opt_check(h, o);
-  const kprn_config& c = h->cfg;
-  join_score(h);
-  hipStream_t s = h->stream;
-  const bool reg = (o->regularize == 1);
-  const bool dense_ent = reg || o->entity_update == 1;
-  // the exchange's union: walked in place by the row update (lazy-exact Adam, fp32 table only) or materialised first
-  bool fuse_union = h->dp_union_pending && o->method == 1 && !dense_ent && !h->bf16_state && h->dp_world <= (c.de >> 2) &&
-                    (c.de == 32 || c.de == 64 || c.de == 128) && (h->dp_cap & 3) == 0;
-  if (h->dp_union_pending && !fuse_union) materialize_union(h);
-  if (!h->view_batch) { h->rows_view = h->step_rows; h->count_view = h->step_count; }  // (the exchange may have re-allocated the list)
-  const int32_t* rows = h->rows_view;
-  const int32_t* rcount = h->count_view;   // (re-read below if a union is materialised late)
-  const float* norm2 = nullptr;
-  if (reg && o->use_grad_clip) {
-    ProfScope ps(h, "grad_norm");
-    if (h->deterministic) {   // one plain-stored partial per workgroup, added in index order (kk::sumsq_det)
-      if (!h->det_norm_part) h->det_norm_part = dalloc<float>(kk::SUMSQ_DET_BLOCKS);
-      kk::sumsq_det(s, h->g_dense, h->n_dense, h->g_We, h->step_rows_ub > 0 ? rows : nullptr, rcount, c.de, h->det_norm_part, h->d_norm2);
-    } else {
-      HIP_TRY(hipMemsetAsync(h->d_norm2, 0, sizeof(float), s));
-      kk::sumsq(s, h->g_dense, h->n_dense, h->d_norm2);
-      if (h->step_rows_ub > 0) kk::sumsq_rows(s, h->g_We, rows, rcount, c.de, h->d_norm2);
-    }
-    norm2 = h->d_norm2;
-  }
-  const float l2 = reg ? o->l2 : 0.f;
-  // pad rows of the dense arena: re-zeroed by the dense kernels right after the update (zeroPadTokens, MyOptimizer.lua:219)
-  const int64_t z0 = h->off_Wt + (int64_t)(c.Vt - 1) * c.dt, z1 = h->off_Wr + (int64_t)(c.Vr - 1) * c.dr;
-  const int64_t pad_row = (int64_t)c.Ve - 1;
-  bool pad_done = false;
-  if (o->method == 1) {
-    // rows that lag replay their skipped steps with the constants those steps ran with: new ones are adopted only once the table is current
-    if (h->lazy_pending && (o->beta1 != h->last_b1 || o->beta2 != h->last_b2 || o->eps != h->last_eps)) flush_lazy(h);
-    h->last_b1 = o->beta1; h->last_b2 = o->beta2; h->last_eps = o->eps;
-    if (dense_ent && !h->ent_dense_mode) { flush_lazy(h); h->ent_dense_mode = true; }
-    if (!dense_ent && h->ent_dense_mode) {
-      kk::fill_i32(s, h->We_last, c.Ve, (int32_t)h->opt_step);
-      h->ent_dense_mode = false;
-    }
-    h->opt_step += 1;
-    const int64_t t = h->opt_step;
-    step_tab_reserve(h, t + 1);
-    const double bc1 = 1.0 - pow((double)o->beta1, (double)t), bc2 = 1.0 - pow((double)o->beta2, (double)t);
-    const float step = (float)((double)o->lr * sqrt(bc2) / bc1);
-    h->step_tab_host[t] = step;  // host mirror (table growth); the device entry is written by the dense kernel
-    // the row update and the dense arena's update as ONE launch where the shapes allow (two latency-bound launches of the serial tail less; option
-    // "adam_merged" = "0": separately): the same arithmetic per element either way
-    bool merged = false;
-    if (h->adam_merged && !dense_ent && !fuse_union && h->step_rows_ub > 0) {
-      ProfScope ps(h, "adam_step");
-      merged = kk::adam_step_merged(s, h->We, h->g_We, h->s1_We, h->s2_We, h->We_last, rows, rcount, h->step_rows_ub, c.de, (int32_t)t, h->step_tab, pad_row,
-                                    h->dense, h->g_dense, h->s1_dense, h->s2_dense, h->n_dense, step, o->beta1, o->beta2, o->eps, norm2, o->grad_clip_norm,
-                                    l2, z0, c.dt, z1, c.dr, h->step_tab + t);
-    }
-    if (!merged) {
-      ProfScope ps(h, "adam_dense");
-      kk::adam_dense(s, h->dense, h->g_dense, h->s1_dense, h->s2_dense, h->n_dense, step, o->beta1, o->beta2, o->eps, norm2, o->grad_clip_norm, l2,
-                     /*consume=*/1, z0, c.dt, z1, c.dr, h->step_tab + t);
-    }
-    if (merged) {
-      h->lazy_pending = true;
-      pad_done = h->pad_clean;
-    } else if (dense_ent) {
-      ProfScope ps(h, "adam_entity_dense");
-      kk::adam_dense(s, h->We, h->g_We, h->s1_We, h->s2_We, h->n_ent, step, o->beta1, o->beta2, o->eps, norm2, o->grad_clip_norm, l2,
-                     /*consume=*/0, pad_row * c.de, c.de, 0, 0, nullptr);
-      if (h->step_rows_ub > 0) kk::clear_rows(s, h->g_We, rows, rcount, h->step_rows_ub, c.de);
-      pad_done = true;
-    } else {
-      ProfScope ps(h, "adam_entity_rows");
-      if (fuse_union) {
-        const int64_t stride = 4 + (int64_t)h->dp_cap * (1 + c.de) + dp_tail_words(h);
-        const bool ok = kk::union_adam(s, h->dp_all, h->dp_world, h->dp_cap, stride, c.de, h->We, h->s1_We, h->s2_We, h->We_last, (int32_t)t, h->step_tab,
-                                       o->beta1, o->beta2, o->eps, pad_row);
-        if (ok) { h->dp_union_pending = false; h->step_rows_ub = 0; h->rows_view = h->step_rows; h->count_view = h->step_count; h->view_batch = nullptr; }
-        else { fuse_union = false; materialize_union(h); rows = h->rows_view; rcount = h->count_view; }
-      }
-      if (!fuse_union)
-        kk::adam_rows(s, h->We, h->g_We, h->s1_We, h->s2_We, h->We_last, rows, rcount, h->step_rows_ub, c.de, (int32_t)t, 1,
-                      h->step_tab, o->beta1, o->beta2, o->eps, pad_row);
-      h->lazy_pending = true;
-      pad_done = h->pad_clean;  // the pad row is re-zeroed whenever the row update touches it; untouched it stays what it was
-    }
-  } else {
-    const float clr = (float)((double)o->lr / (1.0 + (double)h->opt_step * (double)o->lr_decay));
-    {
-      ProfScope ps(h, "adagrad_dense");
-      kk::adagrad_dense(s, h->dense, h->g_dense, h->s1_dense, h->n_dense, clr, norm2, o->grad_clip_norm, l2, /*consume=*/1, z0, c.dt, z1, c.dr);
-    }
-    if (reg) {
-      ProfScope ps(h, "adagrad_entity_dense");
-      kk::adagrad_dense(s, h->We, h->g_We, h->s1_We, h->n_ent, clr, norm2, o->grad_clip_norm, l2, /*consume=*/0, pad_row * c.de, c.de, 0, 0);
-      if (h->step_rows_ub > 0) kk::clear_rows(s, h->g_We, rows, rcount, h->step_rows_ub, c.de);
-      pad_done = true;
-    } else {
-      ProfScope ps(h, "adagrad_entity_rows");
-      kk::adagrad_rows(s, h->We, h->g_We, h->s1_We, rows, rcount, h->step_rows_ub, c.de, clr, pad_row);
-      pad_done = h->pad_clean;
-    }
-    h->opt_step += 1;
-  }
-  h->ent_grads_dirty = false;
-  h->dense_grads_clean = true;
-  h->opt_method = o->method;
-  if (pad_done) h->pad_clean = true;
-  else zero_pad_tokens(h);   // MyOptimizer.lua:219
-  // the rows this step updated are current; if they were one batch's rows, a forward over that batch needs no catch-up
-  h->caught_serial = h->grads_serial; h->caught_step = h->opt_step;
-  fused::params_changed(h);
-  // bf16 shadows: the dense arena always; the entity table row by row unless the whole table moved (dense sweep)
-  const bool whole_table = (o->method == 1) ? dense_ent : reg;
-  bf16p::params_changed(h, !whole_table);
-  if (!whole_table && h->step_rows_ub > 0) bf16p::rows_updated(h, rows, rcount, h->step_rows_ub);
-}
-
 // ---------------------------------------------------------------------------------------
 extern "C" {
 
@@ -653,7 +470,7 @@ int kprn_create(const kprn_config* cfg, kprn_handle** out) {
         HIP_TRY(hipStreamSynchronize(s));
       }
     }
-    step_tab_reserve(h, 1);
+    optim::step_tab_reserve(h, 1);
     HIP_TRY(hipStreamSynchronize(s));
     *out = h;
     return KPRN_OK;
@@ -728,7 +545,7 @@ static int copy_named(kprn_handle* h, const char* name, float* dst, const float*
   KPRN_REQUIRE(n == p->rows * p->cols, KPRN_E_ARG, "element count does not match the tensor");
   if (n == 0) return KPRN_OK;   // (a table that is not part of the model: -includeEntity 0 / -includeEntityTypes 0)
   KPRN_REQUIRE(dst || src, KPRN_E_ARG, "NULL buffer");
-  if (p->where == 1 && which == 0) flush_lazy(h);
+  if (p->where == 1 && which == 0) optim::flush_lazy(h);
   if (which == 1) materialize_union(h);
   float* base;
   if (which == 0) base = (p->where == 1 ? h->We : h->dense);
@@ -776,7 +593,7 @@ static int copy_rows(kprn_handle* h, const char* name, const int64_t* rows, int6
   KPRN_REQUIRE(n_rows >= 0 && (rows || n_rows == 0) && (dst || src || n_rows == 0), KPRN_E_ARG, "NULL buffer");
   if (n_rows == 0 || p->rows * p->cols == 0) return KPRN_OK;
   for (int64_t i = 0; i < n_rows; ++i) KPRN_REQUIRE(rows[i] >= 0 && rows[i] < p->rows, KPRN_E_INDEX, "row index outside the tensor");
-  if (p->where == 1) flush_lazy(h);
+  if (p->where == 1) optim::flush_lazy(h);
   if (src) params_touched(h);   // (BEFORE the write is queued: it makes the main stream wait for a scoring pass that may still read these rows)
   float* base = (p->where == 1 ? h->We : h->dense) + p->dev_off;
   int64_t* d_rows = nullptr;
@@ -805,7 +622,7 @@ static int copy_flat(kprn_handle* h, float* dst, const float* src, int64_t n, in
   API_BEGIN(h)
   KPRN_REQUIRE(n == h->n_params, KPRN_E_ARG, "n must equal kprn_num_params");
   KPRN_REQUIRE(dst || src, KPRN_E_ARG, "NULL buffer");
-  if (which != 1) flush_lazy(h);
+  if (which != 1) optim::flush_lazy(h);
   else materialize_union(h);
   for (auto& p : h->params) {
     float* base;
@@ -838,7 +655,7 @@ int kprn_zero_pad_tokens(kprn_handle* h) {
   // data-parallel step calls this before every backward, and zeroing again made the main stream wait for the scoring pass on the side
   // stream and invalidated the fused kernels' derived weight copies -- 0.3 ms of a 1.5 ms step
   if (h->pad_clean) return KPRN_OK;
-  zero_pad_tokens(h);
+  optim::zero_pad_tokens(h);
   fused::params_changed(h);
   bf16p::params_changed(h, false);
   API_END(h)
@@ -873,7 +690,7 @@ int kprn_embed(kprn_handle* h, const int32_t* idx, int64_t N, int32_t T, int32_t
   }
   float* dx = nullptr;
   try {
-    catch_up(h, b);
+    optim::catch_up(h, b);
     const kprn_config& c = h->cfg;
     dx = dalloc<float>(N * T * h->D);
     kk::embed_gather(h->stream, b->idx, N, T, F, c.num_types, h->dense + h->off_Wt, h->We, h->dense + h->off_Wr, c.dt, c.de, c.dr, dx, false);
@@ -899,19 +716,19 @@ int kprn_backward_batch(kprn_handle* h, const kprn_batch* b, int32_t class_id, i
 
 int kprn_apply_update(kprn_handle* h, const kprn_opt* opt) {
   API_BEGIN(h)
-  apply_update_impl(h, opt);
+  optim::apply_update(h, opt);
   API_END(h)
 }
 
 int kprn_train_step_batch(kprn_handle* h, const kprn_batch* b, int32_t class_id, const kprn_opt* opt, float* loss) {
   API_BEGIN(h)
-  opt_check(h, opt);
+  optim::opt_check(h, opt);
   check_batch(h, b, class_id);
   det_check(h, b->T, b);
   loss_check(h, b, 0.f);
   generic::drop_check(h, b);
-  catch_up(h, b);
-  if (!h->pad_clean) { zero_pad_tokens(h); fused::params_changed(h); bf16p::params_changed(h, false); }  // MyOptimizer.lua:181 (a no-op when the last step left them zero)
+  optim::catch_up(h, b);
+  if (!h->pad_clean) { optim::zero_pad_tokens(h); fused::params_changed(h); bf16p::params_changed(h, false); }  // MyOptimizer.lua:181 (a no-op when the last step left them zero)
   // the loss goes back as soon as the loss stage has run (option "train_step_return" = "loss"); profiling and "drain" wait for the whole step as before
   struct Disarm { kprn_handle* h; ~Disarm() { h->loss_early_armed = false; } } disarm{h};
   if (loss && !h->train_step_drain && !h->prof_on) {
@@ -921,7 +738,7 @@ int kprn_train_step_batch(kprn_handle* h, const kprn_batch* b, int32_t class_id,
     h->loss_early_armed = true;
   }
   backward_impl(h, b, class_id, opt->bce_literal, 0.f);
-  apply_update_impl(h, opt);
+  optim::apply_update(h, opt);
   if (loss && h->loss_early_armed) {
     HIP_TRY(hipEventSynchronize(h->ev_loss));
     float s = 0.f;   // k_sum_partials' order: one running fp32 sum over the partials in index order
@@ -940,7 +757,7 @@ int kprn_train_step(kprn_handle* h, const int32_t* idx, int32_t B, int32_t P, in
                     const kprn_opt* opt, float* loss) {
   if (!h) return KPRN_E_ARG;
   if (!labels) { h->err = "assert(targets) (MyOptimizer.lua:179)"; return KPRN_E_ARG; }
-  try { opt_check(h, opt); det_check(h, T); loss_check(h, nullptr, 0.f); } catch (const KprnError& e) { h->err = e.msg; return e.code; }   // (before the feed: a refused call uploads nothing)
+  try { optim::opt_check(h, opt); det_check(h, T); loss_check(h, nullptr, 0.f); } catch (const KprnError& e) { h->err = e.msg; return e.code; }   // (before the feed: a refused call uploads nothing)
   // The minibatch goes through one of two engine-owned feed slots (grow-only capacity, page-locked staging: steady state allocates nothing and
   // frees nothing; alternating, so that the rows the lazy optimiser still names belong to the OTHER slot) instead of a batch created and
   // destroyed per call (two device allocations, a device-side index build with its synchronisations and three stream drains per step:
@@ -1254,7 +1071,7 @@ int kprn_dp_exchange_finish(kprn_handle* h, const kprn_opt* opt) {
   h->dp_begun = false;
   if (h->dp_comm_stream_on && h->dp_comm_stream) HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_dp_gathered, 0));
   merge_impl(h, h->dp_gather, h->dp_nranks, (int32_t)h->pack_cap);
-  apply_update_impl(h, opt);
+  optim::apply_update(h, opt);
   API_END(h)
 }
 

@@ -194,7 +194,7 @@ struct kprn_handle {
   // packing buffers for the data-parallel exchange
   int32_t* dp_mark = nullptr;   // [Ve] flags of the exchange's union (all zero between steps)
   // union + update fused (option "dp_fused_update"): kprn_sparse_grad_merge only records the gathered buffer; the update walks it directly
-  // (kk::union_adam) or, where that does not apply (clip / L2, Adagrad, dense entity sweeps, bf16 shadows), materialises the union first
+  // (optim_step.hip k_union_adam) or, where that does not apply (clip / L2, Adagrad, dense entity sweeps, bf16 shadows), materialises the union first
   bool dp_fused_update = false, dp_union_pending = false;
   const void* dp_all = nullptr; int dp_world = 0, dp_cap = 0;
   // the exchange issued by the engine itself (kprn_dp_init / kprn_dp_exchange_begin / _finish): RCCL communicator (ncclComm_t), the
@@ -315,7 +315,7 @@ struct kprn_handle {
   uint64_t dropout_seed = 0;   // default cfg.seed + cfg.rank (kprn_create)
   uint32_t drop_draw = 0, drop_draw_cur = 0;
   bool drop_live = false;      // the state saved by the last generic training forward was dropped (what generic::backward must undo)
-  float* det_norm_part = nullptr;   // [kk::SUMSQ_DET_BLOCKS] per-workgroup partials of the gradient norm
+  float* det_norm_part = nullptr;   // [SUMSQ_DET_BLOCKS of optim_step.hip] per-workgroup partials of the gradient norm
 
   bool prof_on = false;
 
@@ -374,12 +374,23 @@ inline hipStream_t make_priority_stream(bool high) {
 bool use_fused(kprn_handle* h, const kprn_batch* b, bool save_for_backward);   // this pass over b runs on the fused D = H = 64 path
 void materialize_step_rows(kprn_handle* h);  // the optimiser's row list stops being a view of a batch: copied to the handle's own storage
 void check_batch(kprn_handle* h, const kprn_batch* b, int class_id);   // a fed slot is ready, class_id in 1..C
-void catch_up(kprn_handle* h, const kprn_batch* b);                    // the batch's entity rows that are behind opt_step are replayed
 void ensure_ws_common(kprn_handle* h, int64_t N, int64_t B, int64_t n_wg = 0);
 void pool_stage(kprn_handle* h, const kprn_batch* b, int cid, bool every_class);   // reducer + sigmoid + select on h->stream over ws.S into ws.sel (and the mirror, if armed)
 void forward_impl(kprn_handle* h, const kprn_batch* b, int class_id, bool save_for_backward, bool do_pool = true, bool every_class = true, bool all_scores = false);
 int dropin_feed(kprn_handle* h, bool score, const int32_t* idx, const float* labels, int32_t B, int32_t P, int32_t T, int32_t F, const int32_t* counts = nullptr,
                 int64_t n_ragged = 0);   // the host-buffer entry points' minibatch -> the feed slot h->dropin_slot[h->dropin_last]; a status, its text in h->err
+void materialize_union(kprn_handle* h);      // a gathered gradient still pending -> the summed rows in g_We + the sorted union list (no-op when there is none)
+int64_t dp_tail_words(const kprn_handle* h); // words of the dense gradient arena riding behind the packed rows of the data-parallel exchange
+// ---- the optimiser step (optim_step.hip): gradient norm, dense sweep, lazy-exact row update of the entity table, zeroPadTokens ----------------
+namespace kk_dev { struct AdamRowsArgs; }    // adam_rows_dev.h
+namespace optim {
+void opt_check(const kprn_handle* h, const kprn_opt* o);    // what a kprn_opt may not ask of this handle; throws before a step launches or writes anything
+void apply_update(kprn_handle* h, const kprn_opt* o);       // one optimiser step on the gradients the handle holds
+void catch_up(kprn_handle* h, const kprn_batch* b);         // the batch's entity rows that are behind opt_step are replayed
+void flush_lazy(kprn_handle* h);                            // every entity row is brought up to opt_step (before anything reads the whole table)
+void zero_pad_tokens(kprn_handle* h);                       // MyOptimizer:zeroPadTokens: the three pad rows = 0
+void step_tab_reserve(kprn_handle* h, int64_t need);        // the step-size table holds entry `need`
+}  // namespace optim
 // ---- the scoring stage (score_stages.hip): passes beside the main stream, the score board, ranking and explanation calls ----------------
 void launch_score_rest(kprn_handle* h);      // the deferred part of a split scoring pass goes out now (no-op when there is none)
 namespace score {
@@ -462,7 +473,6 @@ void count_pair_terms(hipStream_t s, const float* labels, const int32_t* go, int
 const char* pairwise_groups_why(const int32_t* go, int32_t G, int32_t B);   // what is wrong with a (host) group table over B pairs, or null
 void sum_partials(hipStream_t s, const float* partial, int n, float* out, int accumulate);
 int loss_partials(int B);  // number of per-workgroup loss partials the loss stage writes for B pairs of a rectangular batch (sizes the partial buffer)
-void zero_pad3(hipStream_t s, float* a, int na, float* b, int nb, float* c, int nc);
 void head_bwd(hipStream_t s, const float* dS, const float* hT, const float* Wout, int64_t N, int H, int cid, float* dH, float* gWout, float* gbout,
               DetScratch* det = nullptr);
 // det: the one-hot product route only (embed_scatter_det_ok) with skip_entity; anything else throws KPRN_E_UNSUPPORTED
@@ -479,34 +489,10 @@ void onehot_cols(hipStream_t s, const int32_t* idx, int64_t N, int T, int F, int
 // (ct_has_entity = false: Ct = G [GH][ns], the entity columns of gWi are formed elsewhere -- the fused path)
 void small_tables_finish(hipStream_t s, const float* Ct, int ns, int GH, int Din, int dt, int de, int dr, int Vt, int Vr, const float* Wt, const float* Wr,
                          const float* Wi, float* gWi, float* gWt, float* gWr, bool ct_has_entity = true);
-void sumsq(hipStream_t s, const float* x, int64_t n, float* out);
-void sumsq_rows(hipStream_t s, const float* G, const int32_t* rows, const int32_t* count, int d, float* out);
-// deterministic mode: *out = |x|^2 + |listed rows of G|^2 (rows == null: the first term only) from one plain-stored partial per workgroup (a grid that depends on
-// nothing but n), summed in index order by kk::sum_partials' kernel -- no atomics
-constexpr int SUMSQ_DET_BLOCKS = 512;   // 256 for x, 256 for the rows
-void sumsq_det(hipStream_t s, const float* x, int64_t n, const float* G, const int32_t* rows, const int32_t* count, int d, float* partial, float* out);
-// dense optimiser over a contiguous span; scale_src: device float norm2 -> clip factor computed in-kernel
-// consume: zero the gradient as it is used; [z0,z0+zn0), [z1,z1+zn1): pad rows re-zeroed after the update; tab_slot: device step table entry
-void adam_dense(hipStream_t s, float* x, float* g, float* m, float* v, int64_t n, float step, float b1, float b2, float eps,
-                const float* norm2, float clip, float l2, int consume, int64_t z0, int zn0, int64_t z1, int zn1, float* tab_slot);
-void adagrad_dense(hipStream_t s, float* x, float* g, float* G, int64_t n, float clr, const float* norm2, float clip, float l2, int consume,
-                   int64_t z0, int zn0, int64_t z1, int zn1);
-// lazy-exact row update of the entity table
-void adam_rows(hipStream_t s, float* W, float* g, float* m, float* v, int32_t* last, const int32_t* rows, const int32_t* count, int64_t max_rows,
-               int d, int32_t t_now, int apply_step, const float* step_tab, float b1, float b2, float eps, int64_t pad_row);
-bool adam_step_merged(hipStream_t s, float* W, float* g, float* m, float* v, int32_t* last, const int32_t* rows, const int32_t* count, int64_t max_rows, int d,
-                      int32_t t_now, const float* step_tab, int64_t pad_row, float* dx, float* dg, float* dm, float* dv, int64_t dn, float step, float b1,
-                      float b2, float eps, const float* norm2, float clip, float l2, int64_t z0, int zn0, int64_t z1, int zn1, float* tab_slot);
-void adam_flush_all(hipStream_t s, float* W, float* m, float* v, int32_t* last, int64_t V, int d, int32_t t_now, const float* step_tab, float b1, float b2, float eps, int64_t pad_row);
-void adagrad_rows(hipStream_t s, float* W, float* g, float* G, const int32_t* rows, const int32_t* count, int64_t max_rows, int d, float clr, int64_t pad_row);
-void zero_rows(hipStream_t s, float* W, int64_t row, int d);
 void pack_rows(hipStream_t s, float* G, const int32_t* rows, const int32_t* count, int64_t max_rows, int d, int32_t* ids_out, float* rows_out, int32_t* count_out,
                const float* tail_src = nullptr, int64_t n_tail = 0, float* tail_dst = nullptr);
-bool union_adam(hipStream_t s, const void* all, int world, int cap, int64_t stride, int d, float* W, float* m, float* v, int32_t* last, int32_t t_now,
-                const float* step_tab, float b1, float b2, float eps, int64_t pad_row);
 void fill_uniform(hipStream_t s, float* x, int64_t n, float a, uint64_t seed, uint64_t offset);
-void fill_i32(hipStream_t s, int32_t* x, int64_t n, int32_t v);
-void clear_rows(hipStream_t s, float* G, const int32_t* rows, const int32_t* count, int64_t max_rows, int d);
+void clear_rows(hipStream_t s, float* G, const int32_t* rows, const int32_t* count, int64_t max_rows, int d);   // (optim_step.hip) the listed rows of G = 0
 }  // namespace kk
 
 // ---- ranking stage (rank_groups.hip) -------------------------------------------------------------
@@ -743,8 +729,7 @@ void params_changed(kprn_handle* h);
 bool transpose_job(kprn_handle* h, kk::TransposeJob* tj);
 void prefix_forward(kprn_handle* h, const kprn_batch* b);
 bool forward_dual(kprn_handle* h, const kprn_batch* bt, const kprn_batch* bs, float* S_score, int sel_train, int sel_score);
-bool catch_up_with_prefix(kprn_handle* h, const kprn_batch* b, float* W, float* g, float* m, float* v, int32_t* last, int32_t t_now, const float* step_tab,
-                          float b1, float b2, float eps);
+bool catch_up_with_prefix(kprn_handle* h, const kprn_batch* b, const kk_dev::AdamRowsArgs& rows);   // (optim::catch_up: b's rows and b's prefix table in one launch)
 void mc_prepare(kprn_handle* h);
 void forward_mc(kprn_handle* h, const kprn_batch* b, bool save);                     // (between the fused files)
 bool prefix_backward(kprn_handle* h, const kprn_batch* b, int64_t n_tiles);         // (between the fused files)

@@ -143,7 +143,7 @@ __device__ __forceinline__ void prefix_fwd_block(const PrefFwdArgs& a) {
 template <int L>
 __global__ __launch_bounds__(256) void k_prefix_fwd(PrefFwdArgs a) { prefix_fwd_block<L>(a); }
 
-// The catch-up of a batch's entity rows (lazy-exact Adam, kernels_basic.hip) and this batch's prefix table in ONE launch: both sit in the serial stretch
+// The catch-up of a batch's entity rows (lazy-exact Adam, optim_step.hip) and this batch's prefix table in ONE launch: both sit in the serial stretch
 // between the optimiser step and the next forward, the table is one workgroup's latency chain (12-16 us) and the catch-up is a chain of dependent loads whose
 // time does not depend on its occupancy (measured with 72 KB of LDS per workgroup: 13.0 against 12.8 us).  Workgroup 0 = the table, the others = the rows.
 // Host side: only when the reference step's entity IS the pad row -- the one row both jobs touch, zero before and after (zeroPadTokens) whichever comes first.
@@ -284,25 +284,23 @@ static void prefix_fwd_args(kprn_handle* h, const kprn_batch* b, State* s, PrefF
 
 // the catch-up of b's rows AND b's prefix table as one launch (k_catchup_prefix); false: not applicable, the caller launches the catch-up by itself and
 // prefix_forward follows where it always did.  The caller has joined the scoring stream.
-bool catch_up_with_prefix(kprn_handle* h, const kprn_batch* b, float* W, float* g, float* m, float* v, int32_t* last, int32_t t_now, const float* step_tab,
-                          float b1, float b2, float eps) {
+bool catch_up_with_prefix(kprn_handle* h, const kprn_batch* b, const kk_dev::AdamRowsArgs& ra) {
   State* s = st(h);
   const kprn_config& c = h->cfg;
   if (!h->catchup_prefix || !b->tile_k || b->h_kmax == 0 || b->n_uniq <= 0) return false;
-  if (!(c.de == 32 || c.de == 64 || c.de == 128) || (((uintptr_t)W | (uintptr_t)m | (uintptr_t)v) & 15)) return false;
+  const int lanes = kk_dev::row_lanes(c.de, kk_dev::addr_or(ra.W, ra.m, ra.v));
+  if (!lanes) return false;
   if (b->h_ref[b->F - 2] != c.Ve) return false;   // (1-based id of the pad row: the last one)
   ensure_prefix_buffers(s, h->stream);
   if (s->pf_batch == b->serial) return false;
   PrefFwdArgs pa;
   prefix_fwd_args(h, b, s, pa);
-  kk_dev::AdamRowsArgs ra{W, g, m, v, last, b->uniq, b->uniq + b->uniq_cap, t_now, 0, step_tab, b1, b2, eps, (int64_t)c.Ve - 1, -1.f};
-  const int G = c.de / 4;
-  const unsigned nb = (unsigned)(((int64_t)b->n_uniq * G + 255) / 256) + 1;
-#define KPRN_CP(G_) \
-  { if (c.L == 1) hipLaunchKernelGGL((k_catchup_prefix<G_, 1>), dim3(nb), dim3(256), 0, h->stream, ra, pa); \
-    else hipLaunchKernelGGL((k_catchup_prefix<G_, 2>), dim3(nb), dim3(256), 0, h->stream, ra, pa); }
-  if (G == 8) KPRN_CP(8) else if (G == 16) KPRN_CP(16) else KPRN_CP(32)
-#undef KPRN_CP
+  const unsigned nb = (unsigned)(((int64_t)b->n_uniq * lanes + 255) / 256) + 1;
+  kk_dev::with_lanes(lanes, [&](auto lg) {
+    constexpr int G = decltype(lg)::value;
+    if (c.L == 1) hipLaunchKernelGGL((k_catchup_prefix<G, 1>), dim3(nb), dim3(256), 0, h->stream, ra, pa);
+    else hipLaunchKernelGGL((k_catchup_prefix<G, 2>), dim3(nb), dim3(256), 0, h->stream, ra, pa);
+  });
   HIP_TRY(hipGetLastError());
   s->pf_batch = b->serial;
   return true;

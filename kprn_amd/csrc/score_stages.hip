@@ -1,7 +1,7 @@
 // libkprn.so -- the scoring stage: everything that serves a scoring pass and what is done with its result.  Passes beside the main stream
 // (kprn_forward_batch_async and its deferred rest), the synchronous passes (kprn_forward_batch, kprn_forward, kprn_forward_ragged), the score board, the ranking
 // and explanation calls and the one-call routes.  Kernels: lstm_fused_fwd*.hip, rank_groups.hip, rank_targets.hip, explain_paths.hip.  The pass itself and what it shares with
-// training (forward_impl, catch_up, pool_stage, dropin_feed) live in kprn_api.hip.
+// training (forward_impl, pool_stage, dropin_feed) live in kprn_api.hip, the catch-up of a batch's rows in optim_step.hip.
 //
 // Streams.  main = h->stream: training, the synchronous passes, every ranking and explanation launch.  score = h->score_stream (option "score_overlap"; probed
 // to run beside main): an asynchronous pass, or the first part of a split one; the copies of kprn_read_probs and kprn_board_put out of sel2.  rest =
@@ -143,7 +143,7 @@ int kprn_forward_batch_async(kprn_handle* h, const kprn_batch* b, int32_t class_
     // the pass goes to the side stream with its own output buffers; everything it reads is final on the main stream first
     check_batch(h, b, class_id);
     const int64_t N = b->N;
-    catch_up(h, b);
+    optim::catch_up(h, b);
     ensure_ws_common(h, N, b->B);
     if (!h->score_stream) {
       h->score_stream = make_concurrent_stream(h);
