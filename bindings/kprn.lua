@@ -108,6 +108,9 @@ int kprn_find_training_paths(kprn_handle*, const kprn_graph*, const kprn_sampler
 int kprn_find_paths_sampled(kprn_handle*, const kprn_graph*, const int32_t*, const float*, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, uint64_t, unsigned int, int32_t*, int64_t*, kprn_batch**);
 int kprn_host_find_paths_sampled(const int32_t*, const int32_t*, const int32_t*, int64_t, const int32_t*, int32_t, int32_t, int32_t, int32_t, int32_t, const int32_t*, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, uint64_t, unsigned int, int32_t, int32_t*, int64_t*, int32_t*);
 int kprn_find_training_paths_sampled(kprn_handle*, const kprn_graph*, const kprn_sampler*, const int32_t*, int32_t, int32_t, int32_t, uint64_t, unsigned int, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t*, int32_t*, int64_t*, kprn_batch**);
+/* the cap mode of option "path_cap" on the host: 0 = the first paths, 1 = a spread of the pair's sequence (include/kprn.h "finding a pair's paths", cap mode) */
+int kprn_host_find_paths_cap(const int32_t*, const int32_t*, const int32_t*, int64_t, const int32_t*, int32_t, int32_t, int32_t, int32_t, int32_t, const int32_t*, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, uint64_t, unsigned int, int32_t, int32_t, int32_t*, int64_t*, int32_t*);
+int kprn_host_cap_select(int64_t, int32_t, int32_t, uint64_t, unsigned int, int64_t*);
 /* candidates of a user: the catalogue items the graph reaches, found on the device (include/kprn.h "candidates of a user") */
 int kprn_find_candidates(kprn_handle*, const kprn_graph*, const kprn_sampler*, const int32_t*, int32_t, int32_t, int32_t, int32_t, int32_t*, int64_t*);
 int kprn_read_candidates(kprn_handle*, int32_t*, int64_t);

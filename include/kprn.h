@@ -368,6 +368,22 @@ int kprn_host_explain(const float* path_scores, const int32_t* offsets /* [B+1] 
  *  - order within a pair (canonical): hops ascending, then the integer sequence (n1, r0, n2, r1, ..., r_{h-1}) ascending lexicographically.
  *  - cap: found[b] = the number of paths that exist; the kept ones are the first counts[b] = min(found[b], max_paths) in that order, 1 <= max_paths <= 4096.
  *    Nothing depends on timing: ranks come from a counting pass and prefix sums, never from an atomic counter.
+ *  - cap mode (kprn_set_option "path_cap" = "first" (default) | "spread"; any other value is KPRN_E_ARG).  "first" is the rule above.  "spread" keeps a
+ *    stratified random subset of the pair's whole sequence -- hops 1, 2, 3 in canonical order, then the sampled hops 4 and 5 in walk order -- instead of its
+ *    beginning, which holds only the paths through the user's lowest-id first edges.  It is read by every device find call that carries (seed, draw):
+ *    kprn_find_paths_sampled, kprn_find_training_paths, kprn_find_training_paths_sampled, kprn_find_paths_of_candidates.  kprn_find_paths has no seed: it always
+ *    keeps the first paths.  For the pair in row b of the call's pair list, F = found[b], K = max_paths:
+ *      F <= K: every path is kept, exactly as under "first".
+ *      F > K:  the ranks [0, F) are cut into K strata, lo_j = floor(j F / K), j = 0 .. K: stratum j = [lo_j, lo_{j+1}) is never empty and the sizes differ by
+ *              at most one; the stratum of rank r is floor(((r + 1) K - 1) / F).  One rank is kept in each: r_j = lo_j + mulhi64(x_j, lo_{j+1} - lo_j) (the high
+ *              half of the 128-bit product), x_j = (w[2 (j % 2)] << 32) | w[2 (j % 2) + 1], w = Philox4x32-10(counter = (j / 2, 131072, b, draw), key =
+ *              (seed & 0xffffffff, seed >> 32)).  131072 keeps these counters apart from the negative sampler's (a / 4, n <= 255, b, draw) and the walks'
+ *              (w, 65536 + h, b, draw) under the same seed and draw.  The counter holds the ROW b, not the ids: the same pair in two rows draws two subsets.
+ *      Kept row j of the pair is the path of rank r_j, so the kept rows stay in the sequence's order.  counts[b] = min(F, K) and found[b] are what they are
+ *      under "first"; the ragged plan, the labels and the compaction do not change.  A path in a stratum of size s is kept with probability 1 / s, s in
+ *      {floor(F / K), ceil(F / K)}: hop counts and first edges are represented in proportion to their share of the sequence.  Nothing depends on timing, and no
+ *      atomic hands out a slot or a rank.  All products stay in 64 bits while F < 2^51; a pair beyond that under "spread" is refused on the host after the
+ *      counting pass (KPRN_E_ARG).
  *  - row of a kept path, [T][F], T >= max_hops + 1, as pathformat.py lays it out: T - (h + 1) steps of left padding (Vt x num_types, Ve, Vr), then step k < h =
  *    (node_types[n_k], n_k, r_k) and the last step (node_types[i], i, end_relation).  Where F > num_types + 2 the leading columns, which no kernel reads and
  *    the id validation does not look at, are written as Vt.
@@ -411,8 +427,8 @@ int kprn_host_find_paths(const int32_t* src, const int32_t* dst, const int32_t* 
  *    the order above.  Walk order, not lexicographic order: the cap keeps an unbiased prefix of the sample, not the lowest ids.
  *  - found[b] = (the paths of hops <= 3 that exist) + (the distinct sampled paths of hops 4 and 5): for h > 3 found counts what was SAMPLED, not what
  *    exists.  counts[b] = min(found[b], max_paths).
- *  - limits: walks in 1..256 when max_hops > 3 (else KPRN_E_ARG); when max_hops <= 3, walks / seed / draw are ignored (walks may be 0) and the call returns
- *    exactly what the unsampled call returns.  T >= max_hops + 1.  Everything else -- row layout, padding, leading columns, compaction of the pairs without
+ *  - limits: walks in 1..256 when max_hops > 3 (else KPRN_E_ARG); when max_hops <= 3, walks is ignored (it may be 0), and under "path_cap" "first" so are seed
+ *    and draw: the call returns exactly what the unsampled call returns.  Under "spread" seed and draw address the cap's draws at every hop count.  T >= max_hops + 1.  Everything else -- row layout, padding, leading columns, compaction of the pairs without
  *    paths, labels, refusals, the KPRN_E_DEVICE check of the fill pass -- is kprn_find_paths'.  Nothing depends on timing: no atomic hands out a slot or a rank. */
 int kprn_find_paths_sampled(kprn_handle* h, const kprn_graph* g, const int32_t* pairs /* [B][2] = (u, i) */, const float* labels /* [B] or NULL */, int32_t B,
                             int32_t min_hops, int32_t max_hops, int32_t max_paths, int32_t T, int32_t walks, uint64_t seed, unsigned int draw /* uint32 */,
@@ -422,6 +438,14 @@ int kprn_host_find_paths_sampled(const int32_t* src, const int32_t* dst, const i
                                  int32_t Vt, int32_t num_types, int32_t end_relation, const int32_t* pairs, int32_t B, int32_t min_hops, int32_t max_hops,
                                  int32_t max_paths, int32_t T, int32_t F, int32_t walks, uint64_t seed, unsigned int draw, int32_t threads, int32_t* counts,
                                  int64_t* found, int32_t* idx);
+/* kprn_host_find_paths_sampled with the cap mode: cap_mode 0 = "first" (exactly kprn_host_find_paths_sampled), 1 = "spread"; anything else is KPRN_E_ARG */
+int kprn_host_find_paths_cap(const int32_t* src, const int32_t* dst, const int32_t* rel, int64_t E, const int32_t* node_types, int32_t Ve, int32_t Vr, int32_t Vt,
+                             int32_t num_types, int32_t end_relation, const int32_t* pairs, int32_t B, int32_t min_hops, int32_t max_hops, int32_t max_paths,
+                             int32_t T, int32_t F, int32_t walks, uint64_t seed, unsigned int draw, int32_t cap_mode, int32_t threads, int32_t* counts,
+                             int64_t* found, int32_t* idx);
+/* the ranks "spread" keeps of a pair in row b with `found` paths, ascending: ranks [min(found, max_paths)] (found <= max_paths: 0, 1, ..).  Host-only; it exists
+ * so that a selection can be rebuilt anywhere.  found outside 0 .. 2^51 - 1, max_paths outside 1..4096 or b < 0 is KPRN_E_ARG.                              */
+int kprn_host_cap_select(int64_t found, int32_t max_paths, int32_t b, uint64_t seed, unsigned int draw, int64_t* ranks /* [min(found, max_paths)] */);
 
 /* ---- sampling negatives (an extension: the reference draws them offline, data_prepare/sample.py:18-26,101-117 -- distinct non-interacted items, uniform at
  * alpha = 0, else weighted by frequency^alpha; its draws, numpy.random.multinomial and Python's random, cannot be reproduced and are not restated) ----
@@ -455,7 +479,8 @@ int kprn_host_sample_negatives(const int32_t* src, const int32_t* dst, const int
  * paths are dropped and the labels compacted exactly as kprn_find_paths does.  pairs_out (host [B * (1 + n_neg)][2], or NULL), counts and found
  * [B * (1 + n_neg)] (or NULL) and the batch -- ids, counts, labels -- equal those of kprn_sample_negatives followed by kprn_find_paths on the same pair list
  * and labels, the rows of item 0 left out of that call and counted as 0 paths.  A node of pos outside 1 .. Ve-1 is KPRN_E_INDEX; the limits are the two
- * calls'; B * (1 + n_neg) must stay below 2^31.  No pair has a path: *out = NULL with KPRN_OK.                                                          */
+ * calls'; B * (1 + n_neg) must stay below 2^31.  No pair has a path: *out = NULL with KPRN_OK.  Under "path_cap" "spread" the seed and draw address the
+ * cap's draws too, and the equality holds with kprn_find_paths_sampled (walks 0) in kprn_find_paths' place.                                             */
 int kprn_find_training_paths(kprn_handle* h, const kprn_graph* g, const kprn_sampler* s, const int32_t* pos /* [B][2] = (u, i) */, int32_t B, int32_t n_neg,
                              int32_t max_attempts, uint64_t seed, unsigned int draw /* uint32 */, int32_t min_hops, int32_t max_hops, int32_t max_paths,
                              int32_t T, int32_t* pairs_out, int32_t* counts, int64_t* found, kprn_batch** out);
@@ -496,7 +521,8 @@ int kprn_read_candidates(kprn_handle* h, int32_t* pairs_out /* [total][2] */, in
  * kprn_find_paths_sampled's (max_hops up to 5).  By definition the outputs equal those of kprn_find_paths (kprn_find_paths_sampled) on the pair list
  * kprn_read_candidates returns.  No list yet: KPRN_E_ARG.  An empty list: *out = NULL with KPRN_OK.  A graph whose Ve differs from that of the graph the list
  * was made on: KPRN_E_INDEX.  When the call asks for the same exhaustive hops that produced the list, every pair has found > 0, no pair is dropped, and
- * the batch's pair p is the list's row p.                                                                                                           */
+ * the batch's pair p is the list's row p.  Under "path_cap" "spread" seed and draw are read at walks == 0 too, and the outputs equal
+ * kprn_find_paths_sampled's on that list.                                                                                                           */
 int kprn_find_paths_of_candidates(kprn_handle* h, const kprn_graph* g, int32_t min_hops, int32_t max_hops, int32_t max_paths, int32_t T, int32_t walks,
                                   uint64_t seed, unsigned int draw /* uint32 */, int32_t* counts /* [total] */, int64_t* found /* [total] */, kprn_batch** out);
 /* the same rule on the host cores over the graph's raw edge arrays and the item list (no handle, no GPU), on `threads` threads; rel is not looked at.
@@ -760,6 +786,9 @@ int kprn_profile_get(kprn_handle* h, kprn_prof_entry* out, int32_t cap, int32_t*
  *   "loss"            "bce" (default) | "bpr": what kprn_backward_batch and kprn_train_step_batch train on -- nn.BCECriterion on each pair by itself | the pairwise
  *                     ranking loss over the batch's group table (see kprn_batch_set_groups, "pairwise loss").  Read at every training call; with "bce" nothing
  *                     changes.  Any other value: KPRN_E_ARG
+ *   "path_cap"        "first" (default) | "spread": which of a pair's paths a find call keeps when more exist than max_paths -- the first ones in the pair's
+ *                     order | one drawn in each of max_paths strata of that order ("finding a pair's paths", cap mode).  Read by every find call that has a
+ *                     seed and a draw; kprn_find_paths has none and always keeps the first.  With "first" nothing changes.  Any other value: KPRN_E_ARG
  *   "dropout_seed"    decimal or 0x hex uint64 (default: kprn_config.seed + rank, so data-parallel replicas draw different masks): the generator's seed;
  *                     setting it restarts the draw count at 0
  *   (also: "small_tiles", "score_split", "loss_accumulate", "feed_build" / "feed_threads" / "feed_workers", "dp_comm_stream",

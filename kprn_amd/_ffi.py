@@ -296,6 +296,35 @@ def host_find_paths_sampled(src, dst, rel, node_types, Vr, Vt, end_relation, pai
     return _host_find(call, "kprn_host_find_paths_sampled", src, dst, rel, node_types, pairs, T, F, want_idx)
 
 
+PATH_CAPS = {"first": 0, "spread": 1}   # option "path_cap" / the cap_mode of kprn_host_find_paths_cap (include/kprn.h "finding a pair's paths", cap mode)
+
+
+def host_find_paths_cap(src, dst, rel, node_types, Vr, Vt, end_relation, pairs, min_hops, max_hops, max_paths, T, walks, seed, draw, cap="first", F=None,
+                        threads=1, want_idx=True):
+    """kprn_host_find_paths_cap (no handle, no GPU): host_find_paths_sampled with the cap mode -- "first" (exactly host_find_paths_sampled) or "spread", one
+    path drawn in each of max_paths strata of a pair's sequence under (seed, draw) -> (idx, counts, found)"""
+    if cap not in PATH_CAPS:
+        raise KprnError(E_ARG, "cap must be first or spread")
+    sd, dr = _seed_draw(seed, draw)
+
+    def call(src, dst, rel, nt, pr, B, F, counts, found, idx):
+        return lib().kprn_host_find_paths_cap(_fp(src), _fp(dst), _fp(rel), C.c_int64(int(src.shape[0])), _fp(nt), int(nt.shape[0]), int(Vr), int(Vt),
+                                              int(nt.shape[1]), int(end_relation), _fp(pr), B, int(min_hops), int(max_hops), int(max_paths), int(T), F,
+                                              int(walks), sd, dr, PATH_CAPS[cap], int(threads), _fp(counts), _fp(found), _fp(idx))
+    return _host_find(call, "kprn_host_find_paths_cap", src, dst, rel, node_types, pairs, T, F, want_idx)
+
+
+def host_cap_select(found, max_paths, b, seed, draw):
+    """kprn_host_cap_select: the ranks "spread" keeps of the pair in row b of a pair list that has `found` paths -> ranks [min(found, max_paths)] int64, ascending"""
+    n = max(min(int(found), int(max_paths)), 0)
+    ranks = np.zeros(n, np.int64)
+    sd, dr = _seed_draw(seed, draw)
+    rc = lib().kprn_host_cap_select(C.c_int64(int(found)), int(max_paths), int(b), sd, dr, _fp(ranks))
+    if rc != 0:
+        raise KprnError(rc, "kprn_host_cap_select: found must be in 0 .. 2^51 - 1, max_paths in 1..4096, b >= 0")
+    return ranks
+
+
 SAMPLE_MAX_NEG, SAMPLE_MAX_ATTEMPTS = 256, 64   # kprn_sample_negatives: negatives per user slot, attempts per negative
 
 
@@ -954,12 +983,13 @@ class Engine:
     def find_paths(self, graph, pairs, min_hops, max_hops, max_paths, T, labels=None, walks=0, seed=0, draw=0):
         """kprn_find_paths: every path of min_hops .. max_hops (<= 3) hops between the pairs [B,2] = (user, item), the first max_paths per pair in the
         canonical order -> (ragged Batch of the pairs that have paths, or None when none has; counts [B]; found [B]).  walks > 0:
-        kprn_find_paths_sampled, max_hops up to 5 with the hops past 3 sampled by `walks` walks per pair and hop count under (seed, draw)"""
+        kprn_find_paths_sampled, max_hops up to 5 with the hops past 3 sampled by `walks` walks per pair and hop count under (seed, draw).  An engine whose
+        option "path_cap" is "spread" takes the seeded call at walks == 0 too (kprn_find_paths has no seed and always keeps the first paths)"""
         pr, lab = _pairs_array(pairs, labels)
         B = int(pr.shape[0])
         counts, found = np.zeros(B, np.int32), np.zeros(B, np.int64)
         ptr = C.c_void_p()
-        if int(walks) != 0:
+        if int(walks) != 0 or self.options.get("path_cap", "first") == "spread":
             sd, dr = _seed_draw(seed, draw)
             self._ck(self.L.kprn_find_paths_sampled(self.h, graph.ptr, _fp(pr), _fp(lab), B, int(min_hops), int(max_hops), int(max_paths), int(T), int(walks), sd, dr,
                                                     _fp(counts), _fp(found), C.byref(ptr)))

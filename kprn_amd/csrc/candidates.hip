@@ -492,7 +492,8 @@ int kprn_find_paths_of_candidates(kprn_handle* h, const kprn_graph* g, int32_t m
     const pf::StagePairs stage = [&](int32_t* d_pairs, hipStream_t s) {
       HIP_TRY(hipMemcpyAsync(d_pairs, list, (size_t)2 * B * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
     };
-    pf::find_staged(h, g, stage, nullptr, B, min_hops, max_hops, max_paths, T, sm, nullptr, counts, found, out);
+    pf::Sampling spread;
+    pf::find_staged(h, g, stage, nullptr, B, min_hops, max_hops, max_paths, T, pf::with_cap(h, sm, seed, draw, spread), nullptr, counts, found, out);
   }
   API_END(h)
 }

@@ -1364,6 +1364,13 @@ int kprn_set_option(kprn_handle* h, const char* key, const char* value) {
     if (strcmp(value, "bce") == 0) h->loss_bpr = 0;
     else if (strcmp(value, "bpr") == 0) h->loss_bpr = 1;
     else throw KprnError{KPRN_E_ARG, "loss must be bce or bpr"};
+  } else if (strcmp(key, "path_cap") == 0) {
+    // which of a pair's paths a find call keeps when more exist than max_paths (include/kprn.h "finding a pair's paths", cap): the first ones in the pair's
+    // order ("first", default: the kernels' results before this option existed, bit for bit) or one drawn in each of max_paths strata of that order ("spread").
+    // Read by every find call that has a seed and a draw; kprn_find_paths has none and always keeps the first.
+    if (strcmp(value, "first") == 0) h->path_cap = 0;
+    else if (strcmp(value, "spread") == 0) h->path_cap = 1;
+    else throw KprnError{KPRN_E_ARG, "path_cap must be first or spread"};
   } else if (strcmp(key, "dropout") == 0) {
     // rate p of nn.Dropout on every rnn layer's step input in training forwards (OneModel.lua:246-265); "0" (default): the kernels launched
     // before this option existed.  Refused HERE where the reference ignores the flag (lstm, gru) or the pipeline has no dropped form (bf16 products).

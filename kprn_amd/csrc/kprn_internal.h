@@ -295,6 +295,8 @@ struct kprn_handle {
   void* explain_pin = nullptr; size_t explain_pin_bytes = 0;   // page-locked explanation rows of kprn_recommend_explain_ragged
   std::vector<kprn_graph*> graphs;                     // path_find.hip: the knowledge graphs alive on this handle (kprn_destroy frees what is left)
   void* pf_buf = nullptr; size_t pf_buf_bytes = 0;     // device arguments of one kprn_find_paths call (pairs, totals, first rows, counts, flag; per-walk counts)
+  void* pf_keep = nullptr; size_t pf_keep_bytes = 0;   // option "path_cap" = "spread": the kept ranks of one find call, [rows of the batch] int64 beside the pairs' rows
+  int path_cap = 0;                                    // option "path_cap": 0 "first" | 1 "spread" (path_find_dev.h CAP_*), read by every find call that has a seed
   std::vector<kprn_sampler*> samplers;                 // neg_sample.hip: the negative samplers alive on this handle (kprn_destroy frees what is left)
   void* ns_buf = nullptr; size_t ns_buf_bytes = 0;     // device arguments and results of one sampling call (users or positives, negatives, n_found)
   // candidates.hip: the handle's candidate list = the (user, item) rows of the last successful kprn_find_candidates, [cand_total][2] (cand_total < 0: none yet)

@@ -261,7 +261,8 @@ static int find_training_paths(kprn_handle* h, const kprn_graph* g, const kprn_s
     HIP_TRY(hipMemcpyAsync(d_pos, pos, (size_t)2 * B * sizeof(int32_t), hipMemcpyHostToDevice, st));
     ns::launch(h, g, s, rng, d_pos, 2, B, n_neg, max_attempts, nullptr, nullptr, d_pairs, st);
   };
-  pf::find_staged(h, g, stage, labels.data(), n_pairs, min_hops, max_hops, max_paths, T, sm, pairs_out, counts, found, out);
+  pf::Sampling spread;   // (option "path_cap": the seed and draw of the negatives serve the cap too; their counters differ)
+  pf::find_staged(h, g, stage, labels.data(), n_pairs, min_hops, max_hops, max_paths, T, pf::with_cap(h, sm, seed, draw, spread), pairs_out, counts, found, out);
   API_END(h)
 }
 

@@ -14,11 +14,12 @@
 //             lanes over the second edges.  The host turns them into counts = min(found, max_paths), compacts the pairs that have paths and scans the
 //             counts into each pair's first row
 //   k_fill    ranks by prefix sums in the workgroup (Hillis-Steele in LDS, int64): 2 hops over 256 first edges at a time; 3 hops first edge by first edge,
-//             256 second edges at a time, a running rank carried from chunk to chunk.  A thread writes the rows of its own first / second edge at their ranks
-//             while rank < counts[b] -- the range the pair was allotted -- and a hop's chunks stop once the running rank reaches it (with a cap of 28 the fill
-//             pass touches a few chunks, whatever found is).  The rows a workgroup placed are summed and compared with counts[b] (with the pair's exhaustive total
-//             where sampled rows follow, which path_walk.hip places and checks the same way): a disagreement between
-//             the passes sets the flag (KPRN_E_DEVICE), and no write leaves the pair's range either way.
+//             256 second edges at a time, a running rank carried from chunk to chunk.  Which ranks are kept is path_find_dev.h's Keep: the first counts[b]
+//             (a thread writes the rows of its own first / second edge at their ranks while rank < counts[b], and a hop's chunks stop once the running rank
+//             reaches it: with a cap of 28 the fill pass touches a few chunks, whatever found is), or, under option "path_cap" = "spread", the ranks k_cap_ranks
+//             drew (a path of rank r goes to kept row j iff r is the pair's j-th kept rank; the chunks run on to the last kept rank).  The rows a workgroup
+//             placed are summed and compared with the kept ranks below the pair's exhaustive total (the rest, where sampled rows follow, path_walk.hip places
+//             and checks the same way): a disagreement between the passes sets the flag (KPRN_E_DEVICE), and no write leaves the pair's range either way.
 // The host twin walks the same primitives (edge_range, mid_range, write_row) pair by pair on its threads.  The graph, the CSR view and edge_range are in
 // path_find_dev.h, shared with neg_sample.hip; find_staged runs the two passes over a pair list that is staged into HBM by its caller.
 #include "path_find_dev.h"
@@ -50,47 +51,49 @@ __host__ __device__ static inline void subtree_count(const Csr& g, int u, int i,
   for (int e1 = g.rowptr[n1]; e1 < end; ++e1) c3 += mid_range(g, u, i, n1, e1, lo);
 }
 
-// the first room1 paths of 1 hop among the edges lo + first, lo + first + step, ... of [lo, hi), each at its rank; returns the rows written
-__host__ __device__ static inline int hop1_fill(const Csr& g, const Fmt& f, int u, int i, int lo, int hi, int first, int step, int64_t room1, int32_t* out) {
+// the kept paths of 1 hop (ranks 0 .. hi - lo - 1 = the edges [lo, hi)) among the pair's rows first, first + step, ..; out = the pair's rows; returns the rows written
+__host__ __device__ static inline int hop1_fill(const Csr& g, const Fmt& f, int u, int i, int lo, int hi, int first, int step, const Keep& keep, int32_t* out) {
   int placed = 0;
   const int64_t row = (int64_t)f.T * f.F;
-  for (int64_t j = first; j < hi - lo && j < room1; j += step) {
-    const int nodes[2] = {u, i}, rels[1] = {g.rel[lo + j]};
+  for (int64_t j = first; j < keep.cap && keep_rank(keep, j) < hi - lo; j += step) {
+    const int nodes[2] = {u, i}, rels[1] = {g.rel[lo + keep_rank(keep, j)]};
     write_row(f, out + j * row, 1, nodes, rels);
     ++placed;
   }
   return placed;
 }
 
-// the rows of first edge e0 in order: at most room2 paths of 2 hops from out2 on, at most room3 of 3 hops from out3 on; returns the rows written
-__host__ __device__ static inline int subtree_fill(const Csr& g, const Fmt& f, int u, int i, int e0, int64_t room2, int64_t room3, int32_t* out2, int32_t* out3) {
+// the kept rows of first edge e0: its paths of 2 hops have the ranks from r2 on, those of 3 hops from r3 on (< 0: that hop is not looked at); out = the pair's
+// rows; returns the rows written
+__host__ __device__ static inline int subtree_fill(const Csr& g, const Fmt& f, int u, int i, int e0, const Keep& keep, int64_t r2, int64_t r3, int32_t* out) {
   const int n1 = g.col[e0];
   if (n1 == u || n1 == i) return 0;
   const int64_t row = (int64_t)f.T * f.F;
   int placed = 0, lo, hi;
-  if (room2 > 0) {
+  int64_t j = r2 >= 0 ? keep_lower(keep, r2) : keep.cap;
+  if (j < keep.cap) {
     edge_range(g, n1, i, lo, hi);
-    for (int e = lo; e < hi && room2 > 0; ++e, --room2) {
-      const int nodes[3] = {u, n1, i}, rels[2] = {g.rel[e0], g.rel[e]};
-      write_row(f, out2, 2, nodes, rels);
-      out2 += row; ++placed;
+    for (; j < keep.cap && keep_rank(keep, j) - r2 < hi - lo; ++j) {
+      const int nodes[3] = {u, n1, i}, rels[2] = {g.rel[e0], g.rel[lo + (keep_rank(keep, j) - r2)]};
+      write_row(f, out + j * row, 2, nodes, rels);
+      ++placed;
     }
   }
-  if (room3 > 0) {
+  if (r3 >= 0) {
     const int end = g.rowptr[n1 + 1];
-    for (int e1 = g.rowptr[n1]; e1 < end && room3 > 0; ++e1) {
-      hi = mid_range(g, u, i, n1, e1, lo) + lo;
-      for (int e = lo; e < hi && room3 > 0; ++e, --room3) {
-        const int nodes[4] = {u, n1, g.col[e1], i}, rels[3] = {g.rel[e0], g.rel[e1], g.rel[e]};
-        write_row(f, out3, 3, nodes, rels);
-        out3 += row; ++placed;
+    j = keep_lower(keep, r3);
+    for (int e1 = g.rowptr[n1]; e1 < end && j < keep.cap; ++e1) {
+      const int c = mid_range(g, u, i, n1, e1, lo);
+      for (; j < keep.cap && keep_rank(keep, j) - r3 < c; ++j) {
+        const int nodes[4] = {u, n1, g.col[e1], i}, rels[3] = {g.rel[e0], g.rel[e1], g.rel[lo + (keep_rank(keep, j) - r3)]};
+        write_row(f, out + j * row, 3, nodes, rels);
+        ++placed;
       }
+      r3 += c;
     }
   }
   return placed;
 }
-
-__host__ __device__ static inline int64_t room(int64_t cap, int64_t rank) { return rank < cap ? cap - rank : 0; }
 
 // ---- kernels ---------------------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(TPB) void k_count(Csr g, const int32_t* __restrict__ pairs, int hmask, int64_t* __restrict__ tot) {
@@ -123,62 +126,82 @@ __global__ __launch_bounds__(TPB) void k_count(Csr g, const int32_t* __restrict_
   if (threadIdx.x == 0) { tot[4 * (int64_t)b] = c1; tot[4 * (int64_t)b + 1] = c2; tot[4 * (int64_t)b + 2] = c3; tot[4 * (int64_t)b + 3] = c1 + c2 + c3; }
 }
 
-// first [b]: the pair's first row in idx (-1: the pair has no paths and owns nothing); cnt [b]: the rows it was allotted
+// the kept ranks of every pair under CAP_SPREAD, a thread per kept row (64-thread workgroups: a cap of 28 is one wave): ranks [first[b] + j] = cap_rank of
+// the pair's found = its exhaustive total + its sampled sums (wsum == NULL: no sampled hops).  Plain stores; rebuilt by every call, read by the fill kernels
+__global__ __launch_bounds__(64) void k_cap_ranks(const int64_t* __restrict__ tot, const int64_t* __restrict__ wsum, const int64_t* __restrict__ first,
+                                                  const int32_t* __restrict__ cnt, int max_paths, Sampling sm, int64_t* __restrict__ ranks) {
+  const int b = blockIdx.x;
+  const int64_t off = first[b];
+  if (off < 0) return;
+  const int64_t found = tot[4 * (int64_t)b + 3] + (wsum ? wsum[2 * (int64_t)b] + wsum[2 * (int64_t)b + 1] : 0);
+  for (int j = threadIdx.x; j < cnt[b]; j += 64) ranks[off + j] = cap_rank(found, max_paths, j, b, sm.k0, sm.k1, sm.draw);
+}
+
+// first [b]: the pair's first row in idx (-1: the pair has no paths and owns nothing); cnt [b]: the rows it was allotted; ranks (or NULL = the first cnt[b]):
+// k_cap_ranks' array.  nxt = the first kept row whose rank is not behind the running rank: a hop's chunks stop once it reaches cnt[b], a chunk without a kept
+// rank writes nothing, and a thread looks its own ranks up from nxt on (all three workgroup-uniform: every thread reads the same ranks).  SPREAD = false: ranks
+// is not looked at, and the rank lookups fold into the comparisons with cnt[b] that the kernel made before there was a cap mode
+template <bool SPREAD>
 __global__ __launch_bounds__(TPB) void k_fill(Csr g, Fmt f, const int32_t* __restrict__ pairs, int hmask, const int64_t* __restrict__ tot,
-                                              const int64_t* __restrict__ first, const int32_t* __restrict__ cnt, int32_t* __restrict__ idx, int32_t* flag) {
+                                              const int64_t* __restrict__ first, const int32_t* __restrict__ cnt, const int64_t* __restrict__ ranks,
+                                              int32_t* __restrict__ idx, int32_t* flag) {
   __shared__ int64_t sh[TPB];
   const int b = blockIdx.x;
   const int64_t off = first[b];
   if (off < 0) return;   // (workgroup-uniform)
   const int u = pairs[2 * b], i = pairs[2 * b + 1];
   const int64_t cap = cnt[b], row = (int64_t)f.T * f.F;
+  const Keep keep{SPREAD ? ranks + off : nullptr, cap};
   const int64_t base2 = tot[4 * (int64_t)b], base3 = base2 + tot[4 * (int64_t)b + 1];
   int32_t* out = idx + off * row;
   int64_t placed = 0;
   if (hmask & 1) {
     int lo, hi;
     edge_range(g, u, i, lo, hi);
-    placed += hop1_fill(g, f, u, i, lo, hi, threadIdx.x, TPB, cap, out);
+    placed += hop1_fill(g, f, u, i, lo, hi, threadIdx.x, TPB, keep, out);
   }
   const int end = g.rowptr[u + 1];
-  // 2 hops: a thread per first edge, 256 first edges at a time; done2 = the paths under earlier chunks (workgroup-uniform, like every loop bound below)
-  if ((hmask & 2) && base2 < cap) {
-    int64_t done2 = 0;
-    for (int e_base = g.rowptr[u]; e_base < end && base2 + done2 < cap; e_base += TPB) {
+  // 2 hops: a thread per first edge, 256 first edges at a time; run2 = rank of the next chunk's first path (workgroup-uniform, like every loop bound below)
+  if (hmask & 2) {
+    int64_t run2 = base2, nxt = keep_lower(keep, run2);
+    for (int e_base = g.rowptr[u]; e_base < end && nxt < cap; e_base += TPB) {
       const int e0 = e_base + threadIdx.x;
       int64_t c2 = 0, c3, sum2;
       if (e0 < end) subtree_count(g, u, i, e0, true, false, c2, c3);
-      const int64_t r2 = base2 + done2 + block_scan_excl(c2, sh, sum2);
-      // (a rank at or past the cap has no room; out + rank * row is formed only for a rank below it)
-      if (c2 && r2 < cap) placed += subtree_fill(g, f, u, i, e0, cap - r2, 0, out + r2 * row, out);
-      done2 += sum2;
+      const int64_t r2 = run2 + block_scan_excl(c2, sh, sum2);
+      // (every row written is a kept row j < cap: out + j * row stays inside the pair's range)
+      if (c2 && keep_rank(keep, nxt) < run2 + sum2) placed += subtree_fill(g, f, u, i, e0, keep, r2, -1, out);
+      run2 += sum2;
+      nxt = keep_lower(keep, run2, nxt);
     }
   }
-  // 3 hops: the first edges in order, the workgroup's threads over the second edges 256 at a time; a thread writes the paths through its second edge
-  if ((hmask & 4) && base3 < cap) {
-    int64_t run3 = base3;   // rank of the next chunk's first path
-    for (int e0 = g.rowptr[u]; e0 < end && run3 < cap; ++e0) {
+  // 3 hops: the first edges in order, the workgroup's threads over the second edges 256 at a time; a thread writes the kept paths through its second edge
+  if (hmask & 4) {
+    int64_t run3 = base3, nxt = keep_lower(keep, run3);   // rank of the next chunk's first path
+    for (int e0 = g.rowptr[u]; e0 < end && nxt < cap; ++e0) {
       const int n1 = g.col[e0];
       if (n1 == u || n1 == i) continue;
       const int end1 = g.rowptr[n1 + 1];
-      for (int e1_base = g.rowptr[n1]; e1_base < end1 && run3 < cap; e1_base += TPB) {
+      for (int e1_base = g.rowptr[n1]; e1_base < end1 && nxt < cap; e1_base += TPB) {
         const int e1 = e1_base + threadIdx.x;
         int lo = 0;
         const int64_t c = e1 < end1 ? mid_range(g, u, i, n1, e1, lo) : 0;
         int64_t sum3;
         const int64_t r3 = run3 + block_scan_excl(c, sh, sum3);
-        for (int64_t k = 0; k < c && r3 + k < cap; ++k) {
-          const int nodes[4] = {u, n1, g.col[e1], i}, rels[3] = {g.rel[e0], g.rel[e1], g.rel[lo + k]};
-          write_row(f, out + (r3 + k) * row, 3, nodes, rels);
-          ++placed;
-        }
+        if (c && keep_rank(keep, nxt) < run3 + sum3)
+          for (int64_t j = keep_lower(keep, r3, nxt); j < cap && keep_rank(keep, j) - r3 < c; ++j) {
+            const int nodes[4] = {u, n1, g.col[e1], i}, rels[3] = {g.rel[e0], g.rel[e1], g.rel[lo + (keep_rank(keep, j) - r3)]};
+            write_row(f, out + j * row, 3, nodes, rels);
+            ++placed;
+          }
         run3 += sum3;
+        nxt = keep_lower(keep, run3, nxt);
       }
     }
   }
   placed = block_sum(placed, sh);
-  // (cap > the exhaustive total only where sampled paths follow: those rows are path_walk.hip's)
-  if (threadIdx.x == 0 && placed != min(cap, tot[4 * (int64_t)b + 3])) atomicOr(flag, 1);
+  // the kept ranks below the exhaustive total are this kernel's (the rest, where sampled paths follow, are path_walk.hip's)
+  if (threadIdx.x == 0 && placed != keep_lower(keep, tot[4 * (int64_t)b + 3])) atomicOr(flag, 1);
 }
 
 // ---- graph build -----------------------------------------------------------------------------------------------------------------------------
@@ -334,6 +357,7 @@ void release_all(kprn_handle* h) {
   for (kprn_graph* g : h->graphs) free_graph(g);
   h->graphs.clear();
   if (h->pf_buf) { hipFree(h->pf_buf); h->pf_buf = nullptr; h->pf_buf_bytes = 0; }
+  if (h->pf_keep) { hipFree(h->pf_keep); h->pf_keep = nullptr; h->pf_keep_bytes = 0; }
 }
 
 // ---- host twin: the same rule over the host CSR (path_find_dev.h) ---------------------------------------------------------------------------
@@ -352,19 +376,17 @@ static void host_pair_totals(const Csr& g, int u, int i, int hmask, int64_t* t4)
   t4[0] = c1; t4[1] = c2; t4[2] = c3; t4[3] = c1 + c2 + c3;
 }
 
-static int64_t host_pair_fill(const Csr& g, const Fmt& f, int u, int i, int hmask, const int64_t* t4, int64_t cap, int32_t* out) {
-  const int64_t row = (int64_t)f.T * f.F, base2 = t4[0], base3 = t4[0] + t4[1];
+static int64_t host_pair_fill(const Csr& g, const Fmt& f, int u, int i, int hmask, const int64_t* t4, const Keep& keep, int32_t* out) {
+  const int64_t base2 = t4[0], base3 = t4[0] + t4[1];
   int64_t placed = 0, done2 = 0, done3 = 0;
   int lo, hi;
-  if (hmask & 1) { edge_range(g, u, i, lo, hi); placed += hop1_fill(g, f, u, i, lo, hi, 0, 1, cap, out); }
+  if (hmask & 1) { edge_range(g, u, i, lo, hi); placed += hop1_fill(g, f, u, i, lo, hi, 0, 1, keep, out); }
   for (int e0 = g.rowptr[u]; e0 < g.rowptr[u + 1]; ++e0) {
-    const bool go2 = (hmask & 2) && base2 + done2 < cap, go3 = (hmask & 4) && base3 + done3 < cap;
+    const bool go2 = (hmask & 2) && keep_lower(keep, base2 + done2) < keep.cap, go3 = (hmask & 4) && keep_lower(keep, base3 + done3) < keep.cap;
     if (!go2 && !go3) break;
     int64_t c2, c3;
     subtree_count(g, u, i, e0, go2, go3, c2, c3);
-    const int64_t r2 = base2 + done2, r3 = base3 + done3;
-    const int64_t room2 = c2 ? room(cap, r2) : 0, room3 = c3 ? room(cap, r3) : 0;
-    placed += subtree_fill(g, f, u, i, e0, room2, room3, room2 ? out + r2 * row : out, room3 ? out + r3 * row : out);
+    placed += subtree_fill(g, f, u, i, e0, keep, c2 ? base2 + done2 : -1, c3 ? base3 + done3 : -1, out);
     done2 += c2; done3 += c3;
   }
   return placed;
@@ -377,6 +399,7 @@ void find_staged(kprn_handle* h, const kprn_graph* g, const StagePairs& stage, c
   hipStream_t s = h->stream;
   const int hmask = hop_mask(min_hops, max_hops);
   const bool sampled = (hmask & HOPS_SAMPLED) != 0;   // (validated: sm is there)
+  const bool spread = sm && sm->cap_mode == CAP_SPREAD;
   const size_t n_wc = sampled ? (size_t)2 * B * sm->walks : 0;
   // device arguments of the two passes: pairs [2B] | cnt [B] | flag [4] (int32), then tot [4B] | first [B] (int64); sampled hops add wsum [2B] | wc [B][2][walks]
   const size_t w32 = ((size_t)3 * B + 4 + 1) & ~(size_t)1, total = w32 * 4 + ((size_t)(sampled ? 7 : 5) * B + n_wc) * 8;
@@ -413,6 +436,7 @@ void find_staged(kprn_handle* h, const kprn_graph* g, const StagePairs& stage, c
     const int64_t fx = tot[4 * (size_t)b + 3], fs = sampled ? wsum[2 * (size_t)b] + wsum[2 * (size_t)b + 1] : 0, f = fx + fs;
     KPRN_REQUIRE(fx >= 0 && fs >= 0 && (!sampled || (wsum[2 * (size_t)b] >= 0 && wsum[2 * (size_t)b + 1] >= 0)), KPRN_E_DEVICE,
                  "find_paths: the counting pass returned a negative count");
+    KPRN_REQUIRE(!spread || f < CAP_MAX_FOUND, KPRN_E_ARG, "find_paths: path_cap = spread takes pairs of fewer than 2^51 paths");
     fnd[b] = f;
     cnt[b] = (int32_t)std::min<int64_t>(f, max_paths);
     first[b] = cnt[b] > 0 ? N : -1;
@@ -424,15 +448,22 @@ void find_staged(kprn_handle* h, const kprn_graph* g, const StagePairs& stage, c
     HIP_TRY(hipMemcpyAsync(d_first, first.data(), (size_t)B * sizeof(int64_t), hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemsetAsync(d_flag, 0, sizeof(int32_t), s));
     const Fmt fmt{g->types, g->nT, g->Vt, g->Ve, g->Vr, T, c.F, g->end_rel};
+    // spread: every pair's kept ranks, one int64 per row of the batch, at the pair's first row (a block of its own: its size is known only now)
+    int64_t* d_keep = spread ? (int64_t*)grow_call_block(s, h->pf_keep, h->pf_keep_bytes, (size_t)N * sizeof(int64_t)) : nullptr;
     const slots::DeviceFill fill = [&](int32_t* idx_dev, hipStream_t st) {
+      if (spread) {
+        ProfScope pr(h, "find_paths_cap_ranks", st);
+        hipLaunchKernelGGL(k_cap_ranks, dim3((unsigned)B), dim3(64), 0, st, d_tot, sampled ? d_wsum : nullptr, d_first, d_cnt, max_paths, *sm, d_keep);
+        HIP_TRY(hipGetLastError());
+      }
       {
         ProfScope ps(h, "find_paths_fill", st);
-        hipLaunchKernelGGL(k_fill, dim3((unsigned)B), dim3(TPB), 0, st, csr, fmt, d_pairs, hmask, d_tot, d_first, d_cnt, idx_dev, d_flag);
+        hipLaunchKernelGGL(spread ? k_fill<true> : k_fill<false>, dim3((unsigned)B), dim3(TPB), 0, st, csr, fmt, d_pairs, hmask, d_tot, d_first, d_cnt, d_keep, idx_dev, d_flag);
         HIP_TRY(hipGetLastError());
       }
       if (sampled) {
         ProfScope pw(h, "find_paths_walk_fill", st);
-        walk_fill_launch(csr, fmt, d_pairs, B, *sm, d_tot, d_wc, d_first, d_cnt, idx_dev, d_flag, st);
+        walk_fill_launch(csr, fmt, d_pairs, B, *sm, d_tot, d_wc, d_first, d_cnt, d_keep, idx_dev, d_flag, st);
       }
     };
     kprn_batch* nb = nullptr;
@@ -466,8 +497,9 @@ int host_find(const int32_t* src, const int32_t* dst, const int32_t* rel, int64_
     const pf::Fmt f{node_types, num_types, Vt, Ve, Vr, T, F, end_relation};
     const int hmask = pf::hop_mask(min_hops, max_hops);
     const bool sampled = (hmask & HOPS_SAMPLED) != 0;
+    const bool spread = sm && sm->cap_mode == CAP_SPREAD;
     const size_t per = sampled ? (size_t)2 * sm->walks : 0;   // a pair's per-walk counts
-    std::vector<int64_t> tot((size_t)4 * B), first((size_t)B), wc(per * B), wsum(sampled ? (size_t)2 * B : 0);
+    std::vector<int64_t> tot((size_t)4 * B), first((size_t)B), fnd((size_t)B), wc(per * B), wsum(sampled ? (size_t)2 * B : 0);
     pf::parallel_pairs(B, threads, [&](int32_t b) {
       pf::host_pair_totals(g, pairs[2 * b], pairs[2 * b + 1], hmask, &tot[4 * (size_t)b]);
       if (sampled) host_walk_counts(g, pairs[2 * b], pairs[2 * b + 1], b, hmask, *sm, &wc[per * b], &wsum[2 * (size_t)b]);
@@ -475,7 +507,9 @@ int host_find(const int32_t* src, const int32_t* dst, const int32_t* rel, int64_
     int64_t N = 0;
     for (int32_t b = 0; b < B; ++b) {
       const int64_t f = tot[4 * (size_t)b + 3] + (sampled ? wsum[2 * (size_t)b] + wsum[2 * (size_t)b + 1] : 0);
+      if (spread && f >= CAP_MAX_FOUND) return KPRN_E_ARG;
       counts[b] = (int32_t)std::min<int64_t>(f, max_paths);
+      fnd[(size_t)b] = f;
       if (found) found[b] = f;
       first[b] = N;
       N += counts[b];
@@ -485,8 +519,14 @@ int host_find(const int32_t* src, const int32_t* dst, const int32_t* rel, int64_
     pf::parallel_pairs(B, threads, [&](int32_t b) {
       if (counts[b] == 0) return;
       int32_t* rows = idx + first[b] * T * F;
-      int64_t placed = pf::host_pair_fill(g, f, pairs[2 * b], pairs[2 * b + 1], hmask, &tot[4 * (size_t)b], counts[b], rows);
-      if (sampled) placed += host_walk_fill(g, f, pairs[2 * b], pairs[2 * b + 1], b, *sm, &wc[per * b], tot[4 * (size_t)b + 3], counts[b], rows);
+      std::vector<int64_t> ranks;   // (spread, a pair over the cap: its kept ranks; every other pair keeps the first counts[b])
+      if (spread && fnd[(size_t)b] > max_paths) {
+        ranks.resize((size_t)counts[b]);
+        for (int32_t j = 0; j < counts[b]; ++j) ranks[(size_t)j] = cap_rank(fnd[(size_t)b], max_paths, j, b, sm->k0, sm->k1, sm->draw);
+      }
+      const Keep keep{ranks.empty() ? nullptr : ranks.data(), counts[b]};
+      int64_t placed = pf::host_pair_fill(g, f, pairs[2 * b], pairs[2 * b + 1], hmask, &tot[4 * (size_t)b], keep, rows);
+      if (sampled) placed += host_walk_fill(g, f, pairs[2 * b], pairs[2 * b + 1], b, *sm, &wc[per * b], tot[4 * (size_t)b + 3], keep, rows);
       if (placed != counts[b]) wrong = 1;
     });
     if (wrong) return KPRN_E_DEVICE;
@@ -531,9 +571,9 @@ int kprn_graph_num_edges(kprn_handle* h, const kprn_graph* g, int64_t* n) {
 
 }  // extern "C"
 
-// kprn_find_paths (sm == NULL) and kprn_find_paths_sampled
+// kprn_find_paths (sm == NULL: no seed, the first paths are kept whatever option "path_cap" says) and kprn_find_paths_sampled
 static int find_paths(kprn_handle* h, const kprn_graph* g, const int32_t* pairs, const float* labels, int32_t B, int32_t min_hops, int32_t max_hops,
-                      int32_t max_paths, int32_t T, const pf::Sampling* sm, int32_t* counts, int64_t* found, kprn_batch** out) {
+                      int32_t max_paths, int32_t T, const pf::Sampling* sm, uint64_t seed, uint32_t draw, int32_t* counts, int64_t* found, kprn_batch** out) {
   API_BEGIN(h)
   KPRN_REQUIRE(out, KPRN_E_ARG, "out is NULL");
   *out = nullptr;
@@ -544,7 +584,8 @@ static int find_paths(kprn_handle* h, const kprn_graph* g, const int32_t* pairs,
   const pf::StagePairs stage = [&](int32_t* d_pairs, hipStream_t s) {
     HIP_TRY(hipMemcpyAsync(d_pairs, pairs, (size_t)2 * B * sizeof(int32_t), hipMemcpyHostToDevice, s));
   };
-  pf::find_staged(h, g, stage, labels, B, min_hops, max_hops, max_paths, T, sm, nullptr, counts, found, out);
+  pf::Sampling spread;
+  pf::find_staged(h, g, stage, labels, B, min_hops, max_hops, max_paths, T, sm ? pf::with_cap(h, sm, seed, draw, spread) : nullptr, nullptr, counts, found, out);
   API_END(h)
 }
 
@@ -552,13 +593,13 @@ extern "C" {
 
 int kprn_find_paths(kprn_handle* h, const kprn_graph* g, const int32_t* pairs, const float* labels, int32_t B, int32_t min_hops, int32_t max_hops,
                     int32_t max_paths, int32_t T, int32_t* counts, int64_t* found, kprn_batch** out) {
-  return find_paths(h, g, pairs, labels, B, min_hops, max_hops, max_paths, T, nullptr, counts, found, out);
+  return find_paths(h, g, pairs, labels, B, min_hops, max_hops, max_paths, T, nullptr, 0, 0, counts, found, out);
 }
 
 int kprn_find_paths_sampled(kprn_handle* h, const kprn_graph* g, const int32_t* pairs, const float* labels, int32_t B, int32_t min_hops, int32_t max_hops,
                             int32_t max_paths, int32_t T, int32_t walks, uint64_t seed, unsigned int draw, int32_t* counts, int64_t* found, kprn_batch** out) {
   const pf::Sampling sm = pf::sampling_of(walks, seed, draw);
-  return find_paths(h, g, pairs, labels, B, min_hops, max_hops, max_paths, T, &sm, counts, found, out);
+  return find_paths(h, g, pairs, labels, B, min_hops, max_hops, max_paths, T, &sm, seed, draw, counts, found, out);
 }
 
 int kprn_host_find_paths(const int32_t* src, const int32_t* dst, const int32_t* rel, int64_t E, const int32_t* node_types, int32_t Ve, int32_t Vr, int32_t Vt,
@@ -572,9 +613,26 @@ int kprn_host_find_paths_sampled(const int32_t* src, const int32_t* dst, const i
                                  int32_t Vt, int32_t num_types, int32_t end_relation, const int32_t* pairs, int32_t B, int32_t min_hops, int32_t max_hops,
                                  int32_t max_paths, int32_t T, int32_t F, int32_t walks, uint64_t seed, unsigned int draw, int32_t threads, int32_t* counts,
                                  int64_t* found, int32_t* idx) {
-  const pf::Sampling sm = pf::sampling_of(walks, seed, draw);
+  return kprn_host_find_paths_cap(src, dst, rel, E, node_types, Ve, Vr, Vt, num_types, end_relation, pairs, B, min_hops, max_hops, max_paths, T, F, walks, seed, draw,
+                                  pf::CAP_FIRST, threads, counts, found, idx);
+}
+
+int kprn_host_find_paths_cap(const int32_t* src, const int32_t* dst, const int32_t* rel, int64_t E, const int32_t* node_types, int32_t Ve, int32_t Vr, int32_t Vt,
+                             int32_t num_types, int32_t end_relation, const int32_t* pairs, int32_t B, int32_t min_hops, int32_t max_hops, int32_t max_paths,
+                             int32_t T, int32_t F, int32_t walks, uint64_t seed, unsigned int draw, int32_t cap_mode, int32_t threads, int32_t* counts,
+                             int64_t* found, int32_t* idx) {
+  if (cap_mode != pf::CAP_FIRST && cap_mode != pf::CAP_SPREAD) return KPRN_E_ARG;
+  const pf::Sampling sm = pf::sampling_of(walks, seed, draw, cap_mode);
   return pf::host_find(src, dst, rel, E, node_types, Ve, Vr, Vt, num_types, end_relation, pairs, B, min_hops, max_hops, max_paths, T, F, &sm, threads, counts, found,
                        idx);
+}
+
+int kprn_host_cap_select(int64_t found, int32_t max_paths, int32_t b, uint64_t seed, unsigned int draw, int64_t* ranks) {
+  if (found < 0 || found >= pf::CAP_MAX_FOUND || max_paths < 1 || max_paths > kk::RAGGED_MAX_SEG || b < 0 || (found > 0 && !ranks)) return KPRN_E_ARG;
+  const pf::Sampling sm = pf::sampling_of(0, seed, draw, pf::CAP_SPREAD);
+  const int64_t n = std::min<int64_t>(found, max_paths);
+  for (int64_t j = 0; j < n; ++j) ranks[j] = pf::cap_rank(found, max_paths, j, b, sm.k0, sm.k1, sm.draw);
+  return KPRN_OK;
 }
 
 }  // extern "C"

@@ -91,6 +91,43 @@ __device__ static inline int64_t block_scan_excl(int64_t v, int64_t* sh, int64_t
   return sh[threadIdx.x] - v;
 }
 
+// ---- the cap (include/kprn.h "finding a pair's paths", cap) ----------------------------------------------------------------------------------
+// Which min(found, max_paths) ranks of a pair's path sequence are kept.  CAP_FIRST: the first ones.  CAP_SPREAD: one rank drawn in each of max_paths strata
+// of [0, found), addressed by the pair-list row and the stratum, so any selection can be rebuilt anywhere.  One definition serves the rank kernel
+// (path_find.hip k_cap_ranks), the fill kernels and the host twin.
+constexpr int CAP_FIRST = 0, CAP_SPREAD = 1;
+constexpr uint32_t CAP_COUNTER = 131072u;              // second counter word: apart from the negative sampler's n <= 255 and the walks' 65536 + h
+constexpr int64_t CAP_MAX_FOUND = (int64_t)1 << 51;    // j * found stays below 2^63 for j <= 4096
+
+KPRN_HD uint64_t mulhi64(uint64_t a, uint64_t b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __umul64hi(a, b);
+#else
+  return (uint64_t)(((unsigned __int128)a * b) >> 64);
+#endif
+}
+
+// the rank kept row j holds, of a pair in row b with F paths under a cap of K: j itself while everything fits, else the draw of stratum j
+KPRN_HD int64_t cap_rank(int64_t F, int64_t K, int64_t j, int b, uint32_t k0, uint32_t k1, uint32_t draw) {
+  if (F <= K) return j;
+  const int64_t lo = j * F / K, hi = (j + 1) * F / K;
+  uint32_t w[4];
+  philox::philox4x32_10((uint32_t)(j >> 1), CAP_COUNTER, (uint32_t)b, draw, k0, k1, w);
+  const uint64_t x = ((uint64_t)w[2 * (j & 1)] << 32) | w[2 * (j & 1) + 1];
+  return lo + (int64_t)mulhi64(x, (uint64_t)(hi - lo));
+}
+
+// a pair's kept ranks as the fill passes see them: ranks [cap] strictly ascending, kept row j = the path of rank ranks[j]; ranks == NULL: row j = rank j
+struct Keep { const int64_t* ranks; int64_t cap; };
+KPRN_HD int64_t keep_rank(const Keep& k, int64_t j) { return k.ranks ? k.ranks[j] : j; }
+// the first kept row at or after row `from` whose rank is >= r; cap: none.  A run of c paths from rank r on owns the rows from there while keep_rank < r + c
+KPRN_HD int64_t keep_lower(const Keep& k, int64_t r, int64_t from = 0) {
+  if (!k.ranks) return r < k.cap ? (r > from ? r : from) : k.cap;
+  int64_t l = from, h = k.cap;
+  while (l < h) { const int64_t m = l + ((h - l) >> 1); if (k.ranks[m] < r) l = m + 1; else h = m; }
+  return l;
+}
+
 // ---- host twins: the same rule over a CSR built by std::sort --------------------------------------------------------------------------------
 struct HostCsr { std::vector<int32_t> rowptr, col, rel; };
 static inline HostCsr host_csr(const int32_t* src, const int32_t* dst, const int32_t* rel, int64_t E, int32_t Ve) {
@@ -121,10 +158,14 @@ static void parallel_pairs(int32_t B, int threads, Fn&& fn) {
 // The finder's two passes over B pairs whose list stage(d_pairs, s) queues into HBM on the handle's stream -- a copy from the host (kprn_find_paths) or the
 // kernels that form it there (kprn_find_training_paths); a pair's item may be 0 = no item (the pair counts no paths), its user is a node.  pairs_out
 // (or NULL): the list back on the host, [B][2].  Everything else as kprn_find_paths.
-// sm (or NULL = hops 1..3 only): the sampled hops 4 and 5 (path_walk.hip) follow the exhaustive ones in every pair's rows.
+// sm (or NULL = hops 1..3 only, the first paths kept): the sampled hops 4 and 5 (path_walk.hip) follow the exhaustive ones in every pair's rows where the
+// hops ask for them, and sm->cap_mode says which paths the cap keeps.
 typedef std::function<void(int32_t* d_pairs, hipStream_t s)> StagePairs;
-struct Sampling { int32_t walks; uint32_t k0, k1, draw; };   // walks per pair and hop count; Philox key = the seed's halves
-static inline Sampling sampling_of(int32_t walks, uint64_t seed, uint32_t draw) { return Sampling{walks, (uint32_t)(seed & 0xffffffffu), (uint32_t)(seed >> 32), draw}; }
+// walks per pair and hop count; Philox key = the seed's halves; cap_mode: which of a pair's paths the cap keeps (CAP_FIRST | CAP_SPREAD, below)
+struct Sampling { int32_t walks; uint32_t k0, k1, draw; int32_t cap_mode; };
+static inline Sampling sampling_of(int32_t walks, uint64_t seed, uint32_t draw, int32_t cap_mode = 0) {
+  return Sampling{walks, (uint32_t)(seed & 0xffffffffu), (uint32_t)(seed >> 32), draw, cap_mode};
+}
 constexpr int MAX_WALKS = 256, HOPS_SAMPLED = 8 | 16;   // (bits of the hop mask: bit h - 1 = paths of h hops are asked for)
 static inline int hop_mask(int min_hops, int max_hops) { int m = 0; for (int h = min_hops; h <= max_hops; ++h) m |= 1 << (h - 1); return m; }
 void find_staged(kprn_handle* h, const kprn_graph* g, const StagePairs& stage, const float* labels, int32_t B, int32_t min_hops, int32_t max_hops,
@@ -136,15 +177,23 @@ int validate_find(const int32_t* pairs, int32_t B, int32_t Ve, int32_t min_hops,
 int host_find(const int32_t* src, const int32_t* dst, const int32_t* rel, int64_t E, const int32_t* node_types, int32_t Ve, int32_t Vr, int32_t Vt, int32_t num_types,
               int32_t end_relation, const int32_t* pairs, int32_t B, int32_t min_hops, int32_t max_hops, int32_t max_paths, int32_t T, int32_t F, const Sampling* sm,
               int32_t threads, int32_t* counts, int64_t* found, int32_t* idx);
+// what a device find call hands find_staged: the caller's sampling (or NULL) where the handle keeps the first paths, else `spread` = the same walks, seed and
+// draw with the cap mode of option "path_cap"
+static inline const Sampling* with_cap(const kprn_handle* h, const Sampling* sm, uint64_t seed, uint32_t draw, Sampling& spread) {
+  if (h->path_cap == CAP_FIRST) return sm;
+  spread = sampling_of(sm ? sm->walks : 0, seed, draw, h->path_cap);
+  return &spread;
+}
 
 // ---- the sampled hops (path_walk.hip; include/kprn.h "sampled paths of four and five hops") ----
 // per-walk path counts wc [B][2][walks] (slot 0 = 4 hops, 1 = 5 hops; 0 for a dead or dropped walk or a hop count hmask leaves out) and their sums wsum [B][2]
 void walk_count_launch(const Csr& g, const int32_t* d_pairs, int32_t B, int hmask, const Sampling& sm, int64_t* d_wc, int64_t* d_wsum, hipStream_t s);
-// the sampled rows of every pair, from rank tot[4 b + 3] (the pair's exhaustive paths) up to cnt[b]; flag as k_fill's
+// the kept sampled rows of every pair, ranks from tot[4 b + 3] (the pair's exhaustive paths) on; d_keep (or NULL = the first cnt[b] ranks): every pair's kept
+// ranks at its first row; flag as k_fill's
 void walk_fill_launch(const Csr& g, const Fmt& f, const int32_t* d_pairs, int32_t B, const Sampling& sm, const int64_t* d_tot, const int64_t* d_wc,
-                      const int64_t* d_first, const int32_t* d_cnt, int32_t* idx, int32_t* d_flag, hipStream_t s);
-// the same on the host for row b: wc [2][walks] -> the two sums in s2; the rows from rank base up to cap -> the rows written
+                      const int64_t* d_first, const int32_t* d_cnt, const int64_t* d_keep, int32_t* idx, int32_t* d_flag, hipStream_t s);
+// the same on the host for row b: wc [2][walks] -> the two sums in s2; the kept rows of rank base and above -> the rows written
 void host_walk_counts(const Csr& g, int u, int i, int b, int hmask, const Sampling& sm, int64_t* wc, int64_t* s2);
-int64_t host_walk_fill(const Csr& g, const Fmt& f, int u, int i, int b, const Sampling& sm, const int64_t* wc, int64_t base, int64_t cap, int32_t* out);
+int64_t host_walk_fill(const Csr& g, const Fmt& f, int u, int i, int b, const Sampling& sm, const int64_t* wc, int64_t base, const Keep& keep, int32_t* out);
 
 }  // namespace pf

@@ -14,9 +14,11 @@
 //                 last node's adjacency, one closing search (edge_range m -> i) per lane: a popular node is 64 searches wide.  Per-walk counts -> wc
 //                 [B][2][walks], their sums -> wsum [B][2]; the host adds them to found and caps
 //   k_walk_fill   one workgroup scan over the pair's 2 * walks stored counts gives every walk its first rank.  A wave per walk whose first rank is below
-//                 the pair's allotment regenerates the prefix from its Philox words (a dropped walk has count 0 and is never looked at) and walks the
-//                 closing adjacency 64 edges at a time, a wave prefix sum (shuffles) per chunk and the running rank carried along; no workgroup barrier in
-//                 that loop.  Rows are written while rank < counts[b]; the rows placed are summed and compared with the allotment (the finder's flag)
+//                 the pair's allotment and whose rank range holds a kept rank (path_find_dev.h Keep: the first counts[b] ranks, or the drawn ones of option
+//                 "path_cap" = "spread") regenerates the prefix from its Philox words (a dropped walk has count 0 and is never looked at) and walks the
+//                 closing adjacency 64 edges at a time, a wave prefix sum (shuffles) per chunk and the running rank carried along, until the walk's last kept
+//                 rank is behind it; no workgroup barrier in that loop.  A path goes to kept row j iff its rank is the pair's j-th kept rank; the rows placed
+//                 are summed and compared with the kept ranks at or above the exhaustive total (the finder's flag)
 // Control flow around every shuffle and barrier is wave- / workgroup-uniform: the loop bounds and branch conditions there are kernel arguments, values
 // every lane reads from the same address, or results of the cross-lane operations themselves.
 #include "path_find_dev.h"
@@ -118,17 +120,21 @@ __global__ __launch_bounds__(TPB) void k_walk_count(Csr g, const int32_t* __rest
   if (tid == 0) { wsum[2 * (int64_t)b] = s4; wsum[2 * (int64_t)b + 1] = s5; }
 }
 
-// tot [b][3]: the pair's exhaustive paths = the rank of its first sampled path; first / cnt / flag as k_fill's
+// tot [b][3]: the pair's exhaustive paths = the rank of its first sampled path; first / cnt / ranks / flag as k_fill's.  nxt = the first kept row whose rank
+// is not behind the running rank (wave-uniform: every lane reads the same ranks); SPREAD as k_fill's
+template <bool SPREAD>
 __global__ __launch_bounds__(TPB) void k_walk_fill(Csr g, Fmt f, const int32_t* __restrict__ pairs, Sampling sm, const int64_t* __restrict__ tot,
                                                    const int64_t* __restrict__ wc, const int64_t* __restrict__ first, const int32_t* __restrict__ cnt,
-                                                   int32_t* __restrict__ idx, int32_t* flag) {
+                                                   const int64_t* __restrict__ ranks, int32_t* __restrict__ idx, int32_t* flag) {
   __shared__ int64_t sh[TPB];
   __shared__ int64_t wbase[2 * MAX_WALKS];   // rank of a walk's first path
   const int b = blockIdx.x;
   const int64_t off = first[b];
   if (off < 0) return;   // (workgroup-uniform)
   const int64_t cap = cnt[b], base = tot[4 * (int64_t)b + 3], row = (int64_t)f.T * f.F;
-  if (base >= cap) return;   // the exhaustive paths fill the allotment
+  const Keep keep{SPREAD ? ranks + off : nullptr, cap};
+  const int64_t row0 = keep_lower(keep, base);   // the kept rows before it are the exhaustive paths'
+  if (row0 >= cap) return;   // the exhaustive paths fill the allotment
   const int u = pairs[2 * b], i = pairs[2 * b + 1];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int nw = 2 * sm.walks;   // the pair's walks in rank order: 4 hops' then 5 hops'
@@ -142,13 +148,15 @@ __global__ __launch_bounds__(TPB) void k_walk_fill(Csr g, Fmt f, const int32_t* 
   int64_t placed = 0;
   for (int fl = wave; fl < nw; fl += WAVES) {   // (what decides the branches below is read by every lane from one address)
     int64_t run = wbase[fl];   // rank of the next chunk's first path
-    if (run >= cap) break;     // (the ranks ascend)
-    if (mine[fl] == 0) continue;
+    const int64_t wend = run + mine[fl];
+    int64_t nxt = keep_lower(keep, run, row0);
+    if (nxt >= cap) break;     // (the ranks ascend)
+    if (keep_rank(keep, nxt) >= wend) continue;   // no kept rank in the walk (an empty walk among them): its prefix is not regenerated
     const int s = fl >= sm.walks ? 1 : 0, w = fl - s * sm.walks, h = 4 + s;
     int e[3], n[4], r[3];
     if (!walk_prefix(g, sm, u, i, b, w, h, e, n, r)) continue;   // (never: a dead walk's count is 0; the sum below would tell)
     const int last = n[h - 2], end = g.rowptr[last + 1];
-    for (int e_base = g.rowptr[last]; e_base < end && run < cap; e_base += 64) {
+    for (int e_base = g.rowptr[last]; e_base < end && nxt < cap && keep_rank(keep, nxt) < wend; e_base += 64) {
       const int e1 = e_base + lane;
       int lo = 0;
       const int c = e1 < end ? close_range(g, n, h, i, e1, lo) : 0;
@@ -156,12 +164,17 @@ __global__ __launch_bounds__(TPB) void k_walk_fill(Csr g, Fmt f, const int32_t* 
       for (int d = 1; d < 64; d <<= 1) { const int t = __shfl_up(incl, d); if (lane >= d) incl += t; }
       const int chunk = __shfl(incl, 63);
       const int64_t r0 = run + incl - c;
-      for (int k = 0; k < c && r0 + k < cap; ++k) { walk_row(g, f, out + (r0 + k) * row, n, r, h, i, e1, lo + k); ++placed; }
+      if (c && keep_rank(keep, nxt) < run + chunk)
+        for (int64_t j = keep_lower(keep, r0, nxt); j < cap && keep_rank(keep, j) - r0 < c; ++j) {
+          walk_row(g, f, out + j * row, n, r, h, i, e1, lo + (int)(keep_rank(keep, j) - r0));
+          ++placed;
+        }
       run += chunk;
+      nxt = keep_lower(keep, run, nxt);
     }
   }
   placed = block_sum(placed, sh);
-  if (tid == 0 && placed != cap - base) atomicOr(flag, 1);
+  if (tid == 0 && placed != cap - row0) atomicOr(flag, 1);
 }
 
 void walk_count_launch(const Csr& g, const int32_t* d_pairs, int32_t B, int hmask, const Sampling& sm, int64_t* d_wc, int64_t* d_wsum, hipStream_t s) {
@@ -170,8 +183,8 @@ void walk_count_launch(const Csr& g, const int32_t* d_pairs, int32_t B, int hmas
 }
 
 void walk_fill_launch(const Csr& g, const Fmt& f, const int32_t* d_pairs, int32_t B, const Sampling& sm, const int64_t* d_tot, const int64_t* d_wc,
-                      const int64_t* d_first, const int32_t* d_cnt, int32_t* idx, int32_t* d_flag, hipStream_t s) {
-  hipLaunchKernelGGL(k_walk_fill, dim3((unsigned)B), dim3(TPB), 0, s, g, f, d_pairs, sm, d_tot, d_wc, d_first, d_cnt, idx, d_flag);
+                      const int64_t* d_first, const int32_t* d_cnt, const int64_t* d_keep, int32_t* idx, int32_t* d_flag, hipStream_t s) {
+  hipLaunchKernelGGL(d_keep ? k_walk_fill<true> : k_walk_fill<false>, dim3((unsigned)B), dim3(TPB), 0, s, g, f, d_pairs, sm, d_tot, d_wc, d_first, d_cnt, d_keep, idx, d_flag);
   HIP_TRY(hipGetLastError());
 }
 
@@ -199,19 +212,21 @@ void host_walk_counts(const Csr& g, int u, int i, int b, int hmask, const Sampli
   }
 }
 
-int64_t host_walk_fill(const Csr& g, const Fmt& f, int u, int i, int b, const Sampling& sm, const int64_t* wc, int64_t base, int64_t cap, int32_t* out) {
-  const int64_t row = (int64_t)f.T * f.F;
-  int64_t run = base, placed = 0;
-  for (int fl = 0; fl < 2 * sm.walks && run < cap; ++fl) {
-    if (wc[fl] == 0) continue;
+int64_t host_walk_fill(const Csr& g, const Fmt& f, int u, int i, int b, const Sampling& sm, const int64_t* wc, int64_t base, const Keep& keep, int32_t* out) {
+  const int64_t row = (int64_t)f.T * f.F, cap = keep.cap;
+  int64_t run = base, placed = 0, j = keep_lower(keep, base);   // j: the next kept row
+  for (int fl = 0; fl < 2 * sm.walks && j < cap; run += wc[fl], ++fl) {
+    if (keep_rank(keep, j) >= run + wc[fl]) continue;
     const int s = fl >= sm.walks ? 1 : 0, w = fl - s * sm.walks, h = 4 + s;
     int e[3], n[4], r[3];
     if (!walk_prefix(g, sm, u, i, b, w, h, e, n, r)) continue;
     const int last = n[h - 2];
-    for (int e1 = g.rowptr[last]; e1 < g.rowptr[last + 1] && run < cap; ++e1) {
+    int64_t r0 = run;
+    for (int e1 = g.rowptr[last]; e1 < g.rowptr[last + 1] && j < cap; ++e1) {
       int lo;
       const int c = close_range(g, n, h, i, e1, lo);
-      for (int k = 0; k < c && run < cap; ++k, ++run) { walk_row(g, f, out + run * row, n, r, h, i, e1, lo + k); ++placed; }
+      for (; j < cap && keep_rank(keep, j) - r0 < c; ++j) { walk_row(g, f, out + j * row, n, r, h, i, e1, lo + (int)(keep_rank(keep, j) - r0)); ++placed; }
+      r0 += c;
     }
   }
   return placed;

@@ -116,8 +116,12 @@ class KnowledgeGraph:
         train = KnowledgeGraph(self.src[keep], self.dst[keep], self.rel[keep], self.node_types, self.end_relation, self.Vr, self.Vt, self.vocabs)
         return train, held
 
-    def host_find_paths(self, pairs, min_hops, max_hops, max_paths, T, F=None, threads=1, want_idx=True, walks=0, seed=0, draw=0):
-        """walks > 0: the hops past 3 sampled (_ffi.host_find_paths_sampled)"""
+    def host_find_paths(self, pairs, min_hops, max_hops, max_paths, T, F=None, threads=1, want_idx=True, walks=0, seed=0, draw=0, cap="first"):
+        """walks > 0: the hops past 3 sampled (_ffi.host_find_paths_sampled); cap = "spread": the cap keeps a spread of a pair's paths under (seed, draw)
+        (_ffi.host_find_paths_cap)"""
+        if cap != "first":
+            return _ffi.host_find_paths_cap(self.src, self.dst, self.rel, self.node_types, self.Vr, self.Vt, self.end_relation, pairs, min_hops, max_hops,
+                                            max_paths, T, walks, seed, draw, cap=cap, F=F, threads=threads, want_idx=want_idx)
         if int(walks) != 0:
             return _ffi.host_find_paths_sampled(self.src, self.dst, self.rel, self.node_types, self.Vr, self.Vt, self.end_relation, pairs, min_hops, max_hops,
                                                 max_paths, T, walks, seed, draw, F=F, threads=threads, want_idx=want_idx)
@@ -134,8 +138,24 @@ def read_triples(path):
                 yield parts[0], parts[1], parts[2]
 
 
+class path_cap:
+    """`with path_cap(eng, cap):` the engine's option "path_cap" is `cap` ("first" | "spread") inside and what it was afterwards; cap=None changes nothing"""
+
+    def __init__(self, eng, cap):
+        self.eng, self.cap = eng, cap
+
+    def __enter__(self):
+        self.before = self.eng.options.get("path_cap", "first")
+        if self.cap is not None:
+            self.eng.set_option("path_cap", self.cap)
+
+    def __exit__(self, *exc):
+        if self.cap is not None:
+            self.eng.set_option("path_cap", self.before)
+
+
 def recommend(eng, kg, user, items, K, M, min_hops=1, max_hops=3, max_paths=28, T=None, class_id=1, mode=_ffi.RANK_PRINTED, walks=0, seed=1, draw=0, sampler=None,
-              exclude_adjacent=True, max_candidates=0):
+              exclude_adjacent=True, max_candidates=0, cap=None):
     """Which of `items` for `user` (entity ids), and why: find every pair's paths on the device, score the batch, put the scores on the board, rank the
     one group, explain the K winners and read their paths' ids back.  kg: a KnowledgeGraph, or an _ffi.Graph already on the engine.  The board is
     resized to the candidates that have paths (kprn_board_reserve keeps nothing).  walks > 0: max_hops may be 4 or 5, the hops past 3 sampled by `walks`
@@ -143,7 +163,13 @@ def recommend(eng, kg, user, items, K, M, min_hops=1, max_hops=3, max_paths=28, 
     -> the K best items, best first: dict(item, rank, score, n_paths, found, paths = the M strongest as (ids [T,F], weight, score)); items without any
     path are not candidates, so the list may be shorter than K -- empty when no item is reachable.
     items=None: the candidates are found on the device among the items of `sampler` (an _ffi.Sampler: the catalogue), recommend_users for the one user;
-    max_candidates as there (it has no meaning beside a list of items)."""
+    max_candidates as there (it has no meaning beside a list of items).
+    cap = "first" | "spread": the engine's option "path_cap" for this call (None: as the engine stands) -- "spread" keeps one path in each of max_paths strata
+    of a pair's sequence under (seed, draw) instead of its first max_paths; the same (seed, draw) gives the same answer every time."""
+    if cap is not None:
+        with path_cap(eng, cap):
+            return recommend(eng, kg, user, items, K, M, min_hops, max_hops, max_paths, T, class_id, mode, walks, seed, draw, sampler, exclude_adjacent,
+                             max_candidates)
     if items is None:
         if sampler is None:
             raise ValueError("recommend needs items, or a sampler whose item list is the catalogue")
@@ -357,7 +383,7 @@ def groups_from_counts(counts, n_neg):
 
 
 def train_from_graph(eng, kg, positives, opt, minibatch, n_neg, num_epochs, seed, sampler=None, max_attempts=16, min_hops=2, max_hops=3, max_paths=28, T=None,
-                     class_id=1, epoch_hooks=(), start_iteration=1, gradient_step_counter=100, out=None, stats=None, walks=0, loss="bce"):
+                     class_id=1, epoch_hooks=(), start_iteration=1, gradient_step_counter=100, out=None, stats=None, walks=0, loss="bce", cap=None):
     """Training from a knowledge graph alone: every step samples its negatives, finds the paths and trains, all on the device.
     positives [n, 2] = (user, item) entity ids (KnowledgeGraph.interactions); sampler: an _ffi.Sampler (None: the positives' distinct items, uniform).
     Each epoch e shuffles the positives with np.random.RandomState(seed + e) and walks them `minibatch` at a time; a step is
@@ -366,6 +392,8 @@ def train_from_graph(eng, kg, positives, opt, minibatch, n_neg, num_epochs, seed
     for the run and put back afterwards, every step sets the batch's group table (groups_from_counts), and a minibatch without a term -- no group kept both
     its positive and a negative -- is skipped and counted as well.
     walks > 0: max_hops may be 4 or 5, the hops past 3 sampled by `walks` walks per pair and hop count under the same seed and draw.
+    cap = "first" | "spread": the engine's option "path_cap" for the run, put back afterwards (None: as the engine stands).  Under "spread" the draw -- the
+    global step -- addresses the cap's draws too, so every epoch trains on another subset of a busy pair's paths.
     Losses are summed on the device (option "loss_accumulate"); the epoch lines and hooks (OptimizerCallback) are MyOptimizer's.
     -> the epochs' average losses; stats (a dict, optional) receives steps / skipped / pairs."""
     out = sys.stdout if out is None else out
@@ -384,11 +412,15 @@ def train_from_graph(eng, kg, positives, opt, minibatch, n_neg, num_epochs, seed
             hook.hook(0)
     if loss not in ("bce", "bpr"):
         raise ValueError("loss must be bce or bpr")
-    loss_before = eng.options.get("loss", "bce")
+    if cap not in (None,) + tuple(_ffi.PATH_CAPS):
+        raise ValueError("cap must be first or spread")
+    loss_before, cap_before = eng.options.get("loss", "bce"), eng.options.get("path_cap", "first")
     eng.set_option("loss_accumulate", "1")
     eng.loss_sum(reset=True)
     try:
         eng.set_option("loss", loss)
+        if cap is not None:
+            eng.set_option("path_cap", cap)
         draw = 0
         prev = time.time()
         for i in range(int(start_iteration), int(num_epochs) + 1):
@@ -430,6 +462,8 @@ def train_from_graph(eng, kg, positives, opt, minibatch, n_neg, num_epochs, seed
     finally:
         eng.set_option("loss_accumulate", "0")
         eng.set_option("loss", loss_before)
+        if cap is not None:
+            eng.set_option("path_cap", cap_before)
         if own:
             sampler.free()
     if stats is not None:

@@ -58,6 +58,8 @@ def flag_parser():
     a("-loss", default="bce", choices=["bce", "bpr"],
       help="with -kg: bce = nn.BCECriterion on each pair by itself; bpr = the pairwise ranking loss of each positive against its own sampled negatives (the engine's option \"loss\")")
     a("-walks", type=int, default=0, help="walks per pair and hop count that sample the paths of 4 and 5 hops (1..256); needed when -max_hops is above 3")
+    a("-path_cap", default="first", help="which of a pair's paths are kept when more than -max_paths exist: first = the first ones in the finder's order; "
+      "spread = one drawn in each of -max_paths strata of that order under -sampleSeed (the engine's option \"path_cap\"): training draws anew every step")
     # held-out evaluation from the graph (graph.KnowledgeGraph.holdout + graph.evaluate_from_graph; python -m kprn_amd.train / kprn_amd.evaluate)
     a("-holdout", type=float, default=0.0, help="with -kg: this share of the -interaction_rel pairs is held out (the reference's split_train_test.py with "
       "train fraction 1 - this), training sees the rest, and every -evaluationFrequency epochs the held pairs are ranked among everything their users reach; 0 = no split")
@@ -86,6 +88,8 @@ def parse_flags(argv=None):
     if params.loss == "bpr" and not params.kg:
         p.error("-loss bpr needs -kg: the groups it ranks within (a positive and its sampled negatives) exist only when training from a graph")
     check_walks(params.max_hops, params.walks, p.error)
+    if params.path_cap not in _ffi.PATH_CAPS:
+        p.error("-path_cap must be first or spread, got %s" % params.path_cap)
     if not 0.0 <= params.holdout < 1.0:
         p.error("-holdout must be in 0 .. 1 (the share of the interactions held out)")
     if params.holdout > 0 and not params.kg:
@@ -174,6 +178,8 @@ def build_engine(params, rank=0, world=1, device_id=None, stream=None):
         if getattr(params, "dropoutSeed", None) is not None:
             # like the default seed (-seed + rank), the given one is offset by the rank: data-parallel replicas do not share masks
             eng.set_option("dropout_seed", str((int(params.dropoutSeed) + rank) & 0xFFFFFFFFFFFFFFFF))
+        if getattr(params, "path_cap", "first") != "first":
+            eng.set_option("path_cap", params.path_cap)   # (read by every find call that has a seed: training, recommending, evaluating from a graph)
         if getattr(params, "deterministic", 0):
             eng.set_option("deterministic", str(int(params.deterministic)))   # (a training call on a pipeline without fixed-order sums then raises KprnError(E_UNSUPPORTED))
         if params.initModel:

@@ -4,7 +4,9 @@ sampled by --walks walks per pair and hop count, a cap per pair, T = 6 -- and, b
   python scripts/gpu_path_walk_bench.py [--users 80000 --items 20000 --ratings 1000000 --pairs 4096 --cap 28 --walks 64 --threads 16 --reps 5]
 
 Prints one JSON line: per configuration (hops5 / hops3) the synchronous call (median of --reps calls after one warm-up), the finder's kernels from the engine's
-profiler and whether the device equals the twin; the twin's time on --threads host threads; the pairs and paths found at 4 and at 5 hops."""
+profiler and whether the device equals the twin; the twin's time on --threads host threads; the pairs and paths found at 4 and at 5 hops.
+Then, under "cap_modes" (DESIGN.md 3.20), the hops5 call with option "path_cap" "first" and "spread" in turn in the same process: per mode the synchronous
+call, the kernels, and whether the device equals the twin kprn_host_find_paths_cap."""
 import argparse
 import json
 import os
@@ -17,6 +19,36 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from kprn_amd import _ffi  # noqa: E402
 
 T = 6
+
+
+def alternate(eng, call, reps):
+    """option "path_cap" "first" and "spread" in turn in one process, reps + 1 rounds (a warm-up first), then one profiled call each -> per mode: the batch's ids and
+    counts of the warm-up, the median and all times of the synchronous call, the finder's kernels from the engine's profiler"""
+    res = {m: dict(ts=[]) for m in ("first", "spread")}
+    for rep in range(reps + 1):
+        for m in res:
+            eng.set_option("path_cap", m)
+            t0 = time.perf_counter()
+            b, c, f = call()
+            res[m]["ts"].append(time.perf_counter() - t0)
+            if rep == 0:
+                res[m]["got"] = (b.read_idx(), c, f)
+            b.free()
+    for m in res:
+        eng.set_option("path_cap", m)
+        eng.sync()
+        eng.profile_reset()
+        eng.profile(True)
+        call()[0].free()
+        eng.sync()
+        eng.profile(False)
+        res[m]["kernels_ms"] = {k: round(v[0], 4) for k, v in eng.profile_get().items() if k.startswith("find_paths")}
+    eng.set_option("path_cap", "first")
+    return res
+
+
+def report(r):
+    return dict(find_paths_s=float(np.median(r["ts"][1:])), find_paths_all_s=[round(t, 5) for t in r["ts"]], kernels_ms=r["kernels_ms"])
 
 
 def main():
@@ -68,6 +100,13 @@ def main():
             out[name]["find_paths_all_s"] = [round(t, 5) for t in ts]
             eng.sync()
             out[name]["kernels_ms"] = {k: round(v[0], 4) for k, v in eng.profile_get().items() if k.startswith("find_paths")}
+        eng.profile(False)
+        res = alternate(eng, lambda: eng.find_paths(gr, pairs, 1, 5, a.cap, T, walks=a.walks, seed=1, draw=0), a.reps)
+        spread = _ffi.host_find_paths_cap(src, dst, rel, nt, Vr, Vt, end_rel, pairs, 1, 5, a.cap, T, a.walks, 1, 0, cap="spread", threads=a.threads)
+        out["cap_modes"] = {m: report(res[m]) for m in res}
+        out["cap_modes"]["first"]["equal_to_twin"] = bool(all(np.array_equal(x, y) for x, y in zip(res["first"]["got"], want["hops5"])))
+        out["cap_modes"]["spread"]["equal_to_twin"] = bool(all(np.array_equal(x, y) for x, y in zip(res["spread"]["got"], spread)))
+        out["cap_modes"]["spread"]["rows_that_differ_from_first"] = int((res["spread"]["got"][0] != res["first"]["got"][0]).any(axis=(1, 2)).sum())
         eng.close()
     print(json.dumps(out))
 
