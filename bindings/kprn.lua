@@ -91,6 +91,10 @@ int kprn_host_dropout_keep(uint64_t, unsigned int, int32_t, int32_t, int64_t, in
 /* pairwise loss: a batch's group table and the rule on the host cores (include/kprn.h "pairwise loss"; kprn_set_option "loss" "bpr") */
 int kprn_batch_set_groups(kprn_handle*, kprn_batch*, const int32_t*, int32_t, int64_t*);
 int kprn_host_pairwise_loss(const float*, const float*, const int32_t*, int32_t, int32_t, float, float*, float*, int64_t*);
+/* hard negatives: a keep mask over board groups (the positive and the n_keep highest-scoring others), a batch of the kept pairs of a batch (include/kprn.h "hard negatives") */
+int kprn_select_hardest(kprn_handle*, const int64_t*, const int64_t*, const int32_t*, int32_t, int32_t, unsigned char*, int64_t*);
+int kprn_host_select_hardest(const float*, int64_t, const int64_t*, const int64_t*, const int32_t*, int32_t, int32_t, unsigned char*, int64_t*);
+int kprn_batch_subset(kprn_handle*, const kprn_batch*, const unsigned char*, kprn_batch**);
 /* path finder: a knowledge graph in HBM, a pair's paths as a ragged batch, the batch's ids back (include/kprn.h "finding a pair's paths") */
 int kprn_graph_create(kprn_handle*, const int32_t*, const int32_t*, const int32_t*, int64_t, const int32_t*, int32_t, kprn_graph**);
 void kprn_graph_destroy(kprn_handle*, kprn_graph*);

@@ -623,6 +623,43 @@ int kprn_batch_set_groups(kprn_handle* h, kprn_batch* b, const int32_t* group_of
 int kprn_host_pairwise_loss(const float* pooled /* [B] */, const float* labels, const int32_t* group_offsets, int32_t G, int32_t B, float inv_batch,
                             float* dy /* [B] */, float* loss, int64_t* n_terms);
 
+/* ---- hard negatives (an extension: dynamic negative sampling -- draw a pool of negatives per positive, score it, train on the ones that score highest;
+ * the reference trains on the negatives its offline sampler drew) ----
+ * Two calls.  kprn_select_hardest says which members of board groups to keep; kprn_batch_subset makes a batch of the kept pairs of a batch out of the rows that
+ * were scored.  Each is useful on its own (a subset by any keep mask; a keep mask over any board groups).
+ * Selection.  Groups over the score board, addressed exactly as in kprn_rank_groups: group g = members[group_offsets[g] .. group_offsets[g + 1]) (a line may
+ *   appear more than once), members NULL = the consecutive board run; 1 <= n <= KPRN_RANK_MAX_GROUP members; pos[g] in -1 .. n-1 = the group's positive, -1 =
+ *   none; pos NULL = -1 everywhere (NOT kprn_rank_groups' 0).
+ *  - order: the RAW order of "ranking" and nothing else.  Member i's integer is c_i = (key << 12) | (4095 - i), key = 0 for NaN (invalid: a board entry nothing
+ *    wrote), else the fp32 value mapped to 1 .. in fp32 order, -0 and +0 one value, -inf and +inf ordinary values.  An invalid member sorts below every valid
+ *    one; equal scores go to the lower index.  There is no printed mode: the "%.5f" key ties most of a saturated pool.
+ *  - rule: member i is kept iff i == pos[g], or fewer than n_keep members j != pos[g] have c_j > c_i.  1 <= n_keep <= KPRN_SELECT_MAX_KEEP.  A group with n_keep
+ *    or fewer non-positive members keeps them all (invalid ones included).  The positive is excluded from the counting -- it is not counted and subtracted
+ *    afterwards -- and is kept wherever its own score lies.
+ *  - keep (uint8, host): keep[m] = 1 / 0 for the member at m, group_offsets[0] <= m < group_offsets[G] (member order; a line that appears twice has two
+ *    entries); nothing below group_offsets[0] is touched.  n_invalid (int64, or NULL): the invalid non-positive members seen, each entry counted once.
+ *  - kprn_select_hardest waits for every put queued so far; synchronous, ONE launch and one wait.  Places come from integer counts; the only atomic is the
+ *    integer add of the invalid count: nothing depends on timing.  Everything is checked on the host first and a refused call writes nothing: the refusals
+ *    are kprn_rank_groups' -- KPRN_E_ARG for NULL offsets, G < 1, a group outside 1..4096 members, pos outside -1..n-1, no board; KPRN_E_INDEX for a member or a
+ *    run outside the board -- plus KPRN_E_ARG for n_keep outside 1..256 or a NULL keep.
+ *  - kprn_host_select_hardest: the same rule on the host cores over a host score array scores [n_scores] in the board's place (no handle, no GPU); the same
+ *    arguments otherwise, the same refusals.
+ * Subset.  kprn_batch_subset(h, src, keep, out): keep [src's pair count] (uint8, host).  src: any batch, ragged or rectangular (P <= 4096, the ragged limit of
+ *   a pair).  *out = a RAGGED batch of the pairs b with keep[b] != 0, in order; each keeps its paths' rows [cnt][T][F] unchanged and in order (copied on the
+ *   device from src's ids in the caller's order) and its label; a src without labels gives an out without.  The result is a batch like any other: validation,
+ *   occurrence index, identical-prefix plan and ragged plan are derived for it.  src's group table is not inherited; src itself is left as it was and stays
+ *   usable.  Nothing kept: *out = NULL with KPRN_OK.  A fed src nobody used yet is waited for first; a src whose contents hold an id out of range is
+ *   KPRN_E_INDEX; a src that does not hold its ids in the caller's order (a label-less fed batch with an identical-prefix plan) is KPRN_E_ARG.  Synchronous (the
+ *   one wait of kprn_batch_create_ragged).
+ * Why a subset and not a second find call: the sampled walks and the draws of "path_cap" "spread" are addressed by the pair-list ROW b; a kept pair that moves
+ *   to another row of a second call's pair list gets other paths than the ones that were scored.                                                        */
+#define KPRN_SELECT_MAX_KEEP 256
+int kprn_select_hardest(kprn_handle* h, const int64_t* members, const int64_t* group_offsets, const int32_t* pos, int32_t G, int32_t n_keep,
+                        unsigned char* keep /* uint8 [group_offsets[G]] */, int64_t* n_invalid /* or NULL */);
+int kprn_host_select_hardest(const float* scores, int64_t n_scores, const int64_t* members, const int64_t* group_offsets, const int32_t* pos, int32_t G,
+                             int32_t n_keep, unsigned char* keep, int64_t* n_invalid);
+int kprn_batch_subset(kprn_handle* h, const kprn_batch* src, const unsigned char* keep /* uint8 [src's pairs] */, kprn_batch** out);
+
 /* ---- dropout on the rnn cell's input (-useDropout / -dropout, OneModel.lua:246-265) ----
  * kprn_set_option(h, "dropout", "p") with 0 < p < 1 makes every TRAINING forward of an rnn_type 1, compute_dtype 0 handle (a forward that saves for the
  * backward: kprn_backward_batch, kprn_train_step, kprn_train_step_batch) apply nn.Dropout(p) to every layer's step input -- x_t for layer 1, h^{l-1}_t

@@ -128,6 +128,41 @@ def host_rank_groups(scores, group_offsets, members=None, pos=None, mode=0, K=0,
     return out
 
 
+SELECT_MAX_KEEP = 256   # kprn_select_hardest's n_keep limit (KPRN_SELECT_MAX_KEEP)
+
+
+def _select_args(group_offsets, members, pos, keep):
+    """the arrays of kprn_select_hardest / kprn_host_select_hardest; what the C call reads through an array's length is checked here, the rest there.
+    keep: a uint8 array of at least group_offsets[G] entries to write into (None: a new one of zeros)"""
+    goff = np.ascontiguousarray(group_offsets, np.int64)
+    if goff.ndim != 1 or goff.shape[0] < 2:
+        raise KprnError(E_ARG, "group_offsets must be [G+1], G >= 1")
+    G = int(goff.shape[0]) - 1
+    mem = None if members is None else np.ascontiguousarray(members, np.int64)
+    if mem is not None and (mem.ndim != 1 or goff[0] < 0 or goff[-1] > mem.shape[0]):
+        raise KprnError(E_ARG, "group_offsets must lie inside members")
+    p = None if pos is None else np.ascontiguousarray(pos, np.int32)
+    if p is not None and p.shape != (G,):
+        raise KprnError(E_ARG, "pos must be [G]")
+    if keep is None:
+        keep = np.zeros(max(int(goff[-1]), 0), np.uint8)
+    elif keep.dtype != np.uint8 or keep.ndim != 1 or not keep.flags.c_contiguous or keep.shape[0] < goff[-1]:
+        raise KprnError(E_ARG, "keep must be a contiguous uint8 array of at least group_offsets[G] entries")
+    return goff, G, mem, p, keep
+
+
+def host_select_hardest(scores, group_offsets, n_keep, members=None, pos=None, keep=None):
+    """kprn_host_select_hardest (no handle, no GPU): the rule of include/kprn.h "hard negatives" over a host score array -> (keep uint8 [group_offsets[G]] in
+    member order: the group's positive pos[g] (-1 / None: none) and its n_keep highest-scoring other members, n_invalid)"""
+    sc = np.ascontiguousarray(scores, np.float32)
+    goff, G, mem, p, keep = _select_args(group_offsets, members, pos, keep)
+    ninv = C.c_int64(0)
+    rc = lib().kprn_host_select_hardest(_fp(sc), C.c_int64(int(sc.shape[0])), _fp(mem), _fp(goff), _fp(p), G, int(n_keep), _fp(keep), C.byref(ninv))
+    if rc != 0:
+        raise KprnError(rc, "kprn_host_select_hardest: bad groups / members / pos / n_keep")
+    return keep, int(ninv.value)
+
+
 def _rank_targets_args(group_offsets, target_offsets, targets, members, hist_len):
     """the arrays of kprn_rank_targets / kprn_host_rank_targets; what the C call reads through an array's length is checked here, the rest there"""
     goff = np.ascontiguousarray(group_offsets, np.int64)
@@ -958,6 +993,29 @@ class Engine:
         res = res if out is None else out
         self._ck(self.L.kprn_rank_targets(self.h, _fp(mem), _fp(goff), _fp(toff), _fp(tg), G, int(mode), _fp(res["places"]), _fp(res["hist"]), int(hist_len)))
         return res
+
+    # -- hard negatives (include/kprn.h "hard negatives") ---------------------------------------
+    def select_hardest(self, group_offsets, n_keep, members=None, pos=None, keep=None):
+        """kprn_select_hardest over the board: per group its positive pos[g] (-1 / None: none) and the n_keep other members that score highest (raw fp32 order,
+        NaN last, ties to the lower index) -> (keep uint8 [group_offsets[G]] in member order, n_invalid); keep: an array to write into"""
+        goff, G, mem, p, keep = _select_args(group_offsets, members, pos, keep)
+        ninv = C.c_int64(0)
+        self._ck(self.L.kprn_select_hardest(self.h, _fp(mem), _fp(goff), _fp(p), G, int(n_keep), _fp(keep), C.byref(ninv)))
+        return keep, int(ninv.value)
+
+    def batch_subset(self, batch, keep):
+        """kprn_batch_subset: a ragged Batch of the pairs of `batch` (ragged or rectangular) with keep[b] != 0, in order, their rows taken from the batch where
+        they lie in HBM and their labels with them -> the Batch, or None when nothing is kept.  `batch` stays as it was"""
+        kp = np.ascontiguousarray(keep).reshape(-1)
+        if kp.shape[0] != batch.B:
+            raise KprnError(E_ARG, "keep must have one entry per pair of the batch")
+        kp = np.ascontiguousarray(kp != 0, np.uint8)
+        ptr = C.c_void_p()
+        self._ck(self.L.kprn_batch_subset(self.h, batch.ptr, _fp(kp), C.byref(ptr)))
+        if not ptr:
+            return None
+        src_counts = batch.counts if getattr(batch, "counts", None) is not None else np.full(batch.B, batch.P, np.int32)
+        return Batch._adopt(self, ptr, np.ascontiguousarray(src_counts[kp != 0], np.int32), batch.T, batch.F, batch.has_labels)
 
     def recommend_ragged(self, idx, counts, group_counts, K, class_id=1, mode=0, want_probs=False):
         """kprn_recommend_ragged: idx [N,T,F] / counts [B] as forward_ragged_host; group_counts [G] pairs per group (sum B) ->

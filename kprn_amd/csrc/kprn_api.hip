@@ -495,6 +495,7 @@ void kprn_destroy(kprn_handle* h) {
   if (h->ev_put) hipEventDestroy(h->ev_put);
   dfree(h->board);
   if (h->rank_buf) { hipFree(h->rank_buf); h->rank_buf = nullptr; }
+  if (h->sub_buf) { hipFree(h->sub_buf); h->sub_buf = nullptr; }
   if (h->rank_pin) { hipHostFree(h->rank_pin); h->rank_pin = nullptr; }
   if (h->explain_buf) { hipFree(h->explain_buf); h->explain_buf = nullptr; }
   if (h->explain_pin) { hipHostFree(h->explain_pin); h->explain_pin = nullptr; }

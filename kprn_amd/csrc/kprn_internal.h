@@ -289,6 +289,7 @@ struct kprn_handle {
   float* board = nullptr; int64_t board_n = 0;
   hipEvent_t ev_put = nullptr; bool put_side = false;
   void* rank_buf = nullptr; size_t rank_buf_bytes = 0;   // device arguments and results of one kprn_rank_groups / kprn_rank_targets call
+  void* sub_buf = nullptr; size_t sub_buf_bytes = 0;     // device arguments of one kprn_batch_subset call (the kept pairs' offsets, first source rows, pair numbers)
   int rank_sort_min = 512;   // option "rank_sort_min": counting wins at 257 members, the sort at 512 and above (profiles/rank/README.md, comparison 3)
   void* rank_pin = nullptr; size_t rank_pin_bytes = 0, rank_pin_off[2] = {0, 0};   // page-locked group table and top-K rows of kprn_recommend_ragged
   void* explain_buf = nullptr; size_t explain_buf_bytes = 0;   // device pair list and results of one kprn_explain_batch call

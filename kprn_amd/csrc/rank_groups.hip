@@ -12,30 +12,13 @@
 // Both are launched over all groups and leave the groups of the other size class alone.  Histogram counters are int64 in global memory, bumped with one
 // integer atomicAdd per group: the sums do not depend on the order of arrival.
 #include "kprn_internal.h"
+#include "rank_key.h"   // rk::key_of / composite / printed_positive: the order, shared with select_hardest.hip
 
 #include <algorithm>
 #include <cmath>
 #include <cstring>
 
 namespace rk {
-
-// mode 0: the integer "%.5f" prints, times 1e5: the product of a 24-bit and a 17-bit significand is exact in double, rint rounds half to even as printf does
-__host__ __device__ static inline uint32_t key_of(float p, int mode) {
-  if (mode == 0) {
-    if (!(p >= 0.f && p <= 1.f)) return 0u;   // (NaN included)
-    return 1u + (uint32_t)(int32_t)rint((double)p * 1e5);
-  }
-  if (p != p) return 0u;
-  if (p == 0.f) p = 0.f;   // (-0 and +0 are one value)
-  uint32_t u;
-  memcpy(&u, &p, 4);
-  u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);   // fp32 order -> unsigned order; -inf -> 0x007fffff, never 0
-  return u;
-}
-__host__ __device__ static inline uint64_t composite(float p, int i, int mode) { return ((uint64_t)key_of(p, mode) << 12) | (uint64_t)(4095 - i); }
-// mode 0: a member whose printed score is above zero (key >= 2)
-__host__ __device__ static inline bool printed_positive(uint64_t c) { return (c >> 12) >= 2u; }
-
 
 __device__ static inline int64_t line_of(const Args& a, int64_t o, int i) { return a.members ? a.members[o + i] : o + i; }
 
@@ -186,20 +169,9 @@ int validate(int64_t n_scores, const int64_t* members, const int64_t* goff, cons
   if (mode != KPRN_RANK_PRINTED && mode != KPRN_RANK_RAW) return bad(KPRN_E_ARG, "mode must be KPRN_RANK_PRINTED or KPRN_RANK_RAW");
   if (K < 1 || K > KPRN_RANK_MAX_K) return bad(KPRN_E_ARG, "K must be in 1..64");
   if (hist_len < 1 || hist_len > KPRN_RANK_MAX_GROUP) return bad(KPRN_E_ARG, "hist_len must be in 1..4096");
-  if (goff[0] < 0) return bad(KPRN_E_ARG, "group_offsets[0] < 0");
-  int mx = 0;
-  for (int32_t g = 0; g < G; ++g) {
-    const int64_t n = goff[g + 1] - goff[g];
-    if (n < 1 || n > KPRN_RANK_MAX_GROUP) return bad(KPRN_E_ARG, "a group must have 1..4096 members");
-    if (pos && (pos[g] < -1 || pos[g] >= n)) return bad(KPRN_E_ARG, "pos must be in -1..n-1");
-    mx = std::max(mx, (int)n);
-  }
-  if (members) {
-    for (int64_t m = goff[0]; m < goff[G]; ++m)
-      if (members[m] < 0 || members[m] >= n_scores) return bad(KPRN_E_INDEX, "a member is outside the scores");
-  } else if (goff[G] > n_scores) return bad(KPRN_E_INDEX, "a group runs past the end of the scores");
-  if (max_n) *max_n = mx;
-  return KPRN_OK;
+  const char* text = "";
+  const int rc = validate_groups(n_scores, members, goff, pos, G, max_n, &text);   // (rank_key.h: the groups, pos and the members)
+  return rc == KPRN_OK ? rc : bad(rc, text);
 }
 
 void launch(hipStream_t s, const Args& a, int max_n) {

@@ -3,8 +3,8 @@
 //
 // The order is rank_groups.hip's -- key descending, first seen first -- with the member index in 32 bits instead of 12:
 //   (key << 32) | (0xFFFFFFFF - index)      key = rk::key_of's: 0 for an invalid member, else 1 + the "%.5f" integer (mode 0) or 1.. from the fp32 order (mode 1)
-// key_of is restated here because rank_groups.hip keeps its own as a file-local; tests/test_rank_targets_host.py holds the two equal through every score
-// class (the single-target cases must give kprn_host_rank_groups' ranks).
+// key_of is restated here (rk::key_of lives in rank_key.h; this file keeps its own copy, written when rank_groups.hip held rk's as a file-local);
+// tests/test_rank_targets_host.py holds the two equal through every score class (the single-target cases must give kprn_host_rank_groups' ranks).
 #pragma once
 
 #include <algorithm>

@@ -382,8 +382,28 @@ def groups_from_counts(counts, n_neg):
     return np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
 
 
+def _keep_hardest(eng, pool_batch, counts, pool, n_keep, class_id):
+    """One step's selection (train_from_graph, neg_pool): the pool batch that find_training_paths(n_neg=pool) made is scored, its probabilities put on the
+    board from line 0, every group's positive and n_keep highest-scoring negatives kept, and the kept pairs' rows taken from the pool batch, which is freed.
+    -> (the kept pairs' batch or None, its group table [G + 1] int32 over ALL the step's groups, the pool batch's pair count)"""
+    try:
+        eng.forward_async(pool_batch, class_id)
+        eng.board_put(0, pool_batch.B)
+        goff = groups_from_counts(counts, pool).astype(np.int64)
+        has_pos = np.asarray(counts).reshape(-1, 1 + pool)[:, 0] > 0
+        full = np.diff(goff) > 0                         # (kprn_select_hardest takes no empty group: those are left out of the call)
+        sel_off = np.concatenate([[0], np.cumsum(np.diff(goff)[full])]).astype(np.int64)
+        keep, _ = eng.select_hardest(sel_off, n_keep, pos=np.where(has_pos[full], 0, -1).astype(np.int32))
+        keep = keep[:pool_batch.B]
+        sub = eng.batch_subset(pool_batch, keep)
+        upto = np.concatenate([[0], np.cumsum(keep, dtype=np.int64)])
+        return sub, upto[goff].astype(np.int32), pool_batch.B
+    finally:
+        pool_batch.free()
+
+
 def train_from_graph(eng, kg, positives, opt, minibatch, n_neg, num_epochs, seed, sampler=None, max_attempts=16, min_hops=2, max_hops=3, max_paths=28, T=None,
-                     class_id=1, epoch_hooks=(), start_iteration=1, gradient_step_counter=100, out=None, stats=None, walks=0, loss="bce", cap=None):
+                     class_id=1, epoch_hooks=(), start_iteration=1, gradient_step_counter=100, out=None, stats=None, walks=0, loss="bce", cap=None, neg_pool=0):
     """Training from a knowledge graph alone: every step samples its negatives, finds the paths and trains, all on the device.
     positives [n, 2] = (user, item) entity ids (KnowledgeGraph.interactions); sampler: an _ffi.Sampler (None: the positives' distinct items, uniform).
     Each epoch e shuffles the positives with np.random.RandomState(seed + e) and walks them `minibatch` at a time; a step is
@@ -394,8 +414,14 @@ def train_from_graph(eng, kg, positives, opt, minibatch, n_neg, num_epochs, seed
     walks > 0: max_hops may be 4 or 5, the hops past 3 sampled by `walks` walks per pair and hop count under the same seed and draw.
     cap = "first" | "spread": the engine's option "path_cap" for the run, put back afterwards (None: as the engine stands).  Under "spread" the draw -- the
     global step -- addresses the cap's draws too, so every epoch trains on another subset of a busy pair's paths.
+    neg_pool = P > n_neg (at most 256): hard negatives (include/kprn.h "hard negatives").  A step draws P negatives per positive instead of n_neg, scores that
+    pool batch with the current model (forward_async -> board_put, on a board of minibatch * (1 + P) lines reserved once per run: the engine's previous board
+    is gone), keeps each group's positive and its n_neg highest-scoring negatives (Engine.select_hardest; pos = -1 where the positive's row kept no path),
+    and trains on Engine.batch_subset of the pool batch -- the rows that were scored, not the rows a second find call would draw.  Under bpr the group table
+    comes from the kept sizes.  The skip rules are unchanged.  0 or n_neg: today's step, not one call differs.
     Losses are summed on the device (option "loss_accumulate"); the epoch lines and hooks (OptimizerCallback) are MyOptimizer's.
-    -> the epochs' average losses; stats (a dict, optional) receives steps / skipped / pairs."""
+    -> the epochs' average losses; stats (a dict, optional) receives steps / skipped / pairs, and with a pool pool_pairs / kept_pairs (the pairs scored and
+    the pairs kept, summed over the steps that made a selection)."""
     out = sys.stdout if out is None else out
     graph = kg.on(eng) if isinstance(kg, KnowledgeGraph) else kg
     pos = np.ascontiguousarray(positives, np.int32).reshape(-1, 2)
@@ -414,6 +440,13 @@ def train_from_graph(eng, kg, positives, opt, minibatch, n_neg, num_epochs, seed
         raise ValueError("loss must be bce or bpr")
     if cap not in (None,) + tuple(_ffi.PATH_CAPS):
         raise ValueError("cap must be first or spread")
+    pool = int(neg_pool)
+    if pool != 0 and not int(n_neg) <= pool <= _ffi.SELECT_MAX_KEEP:
+        raise ValueError("neg_pool must be 0 or in n_neg .. %d" % _ffi.SELECT_MAX_KEEP)
+    hard = pool > int(n_neg)
+    if hard:
+        st.update(pool_pairs=0, kept_pairs=0)
+    board_ready = False
     loss_before, cap_before = eng.options.get("loss", "bce"), eng.options.get("path_cap", "first")
     eng.set_option("loss_accumulate", "1")
     eng.loss_sum(reset=True)
@@ -428,14 +461,25 @@ def train_from_graph(eng, kg, positives, opt, minibatch, n_neg, num_epochs, seed
             total, batches, processed, since = 0.0, 0, 0, 0
             for k in range(0, len(pos), int(minibatch)):
                 mb = pos[order[k:k + int(minibatch)]]
-                batch, _, counts, _ = eng.find_training_paths(graph, sampler, mb, n_neg, seed, draw, min_hops, max_hops, max_paths, T, max_attempts=max_attempts,
-                                                              walks=walks)
+                batch, _, counts, _ = eng.find_training_paths(graph, sampler, mb, pool if hard else n_neg, seed, draw, min_hops, max_hops, max_paths, T,
+                                                              max_attempts=max_attempts, walks=walks)
                 draw += 1
                 if batch is None:
                     st["skipped"] += 1
                     continue
+                groups = None
+                if hard:
+                    if not board_ready:
+                        eng.board_reserve(int(minibatch) * (1 + pool))
+                        board_ready = True
+                    batch, groups, n_pool = _keep_hardest(eng, batch, counts, pool, n_neg, class_id)   # (frees the pool batch)
+                    if batch is None:
+                        st["skipped"] += 1
+                        continue
+                    st["pool_pairs"] += n_pool
+                    st["kept_pairs"] += batch.B
                 try:
-                    if loss == "bpr" and batch.set_groups(groups_from_counts(counts, n_neg)) == 0:
+                    if loss == "bpr" and batch.set_groups(groups_from_counts(counts, n_neg) if groups is None else groups) == 0:
                         st["skipped"] += 1
                         continue
                     eng.train_step(batch, opt, class_id, want_loss=False)

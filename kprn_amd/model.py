@@ -60,6 +60,8 @@ def flag_parser():
     a("-walks", type=int, default=0, help="walks per pair and hop count that sample the paths of 4 and 5 hops (1..256); needed when -max_hops is above 3")
     a("-path_cap", default="first", help="which of a pair's paths are kept when more than -max_paths exist: first = the first ones in the finder's order; "
       "spread = one drawn in each of -max_paths strata of that order under -sampleSeed (the engine's option \"path_cap\"): training draws anew every step")
+    a("-neg_pool", type=int, default=0, help="with -kg: hard negatives -- every step draws this many negatives per positive, scores them with the current model and "
+      "trains on the -negatives that score highest (graph.train_from_graph neg_pool); 0 or -negatives = the sampled negatives as they are; at most 256")
     # held-out evaluation from the graph (graph.KnowledgeGraph.holdout + graph.evaluate_from_graph; python -m kprn_amd.train / kprn_amd.evaluate)
     a("-holdout", type=float, default=0.0, help="with -kg: this share of the -interaction_rel pairs is held out (the reference's split_train_test.py with "
       "train fraction 1 - this), training sees the rest, and every -evaluationFrequency epochs the held pairs are ranked among everything their users reach; 0 = no split")
@@ -90,6 +92,10 @@ def parse_flags(argv=None):
     check_walks(params.max_hops, params.walks, p.error)
     if params.path_cap not in _ffi.PATH_CAPS:
         p.error("-path_cap must be first or spread, got %s" % params.path_cap)
+    if params.neg_pool != 0 and not params.kg:
+        p.error("-neg_pool needs -kg: the pool it selects from (a positive's sampled negatives) exists only when training from a graph")
+    if params.neg_pool != 0 and not params.negatives <= params.neg_pool <= _ffi.SELECT_MAX_KEEP:
+        p.error("-neg_pool must be 0 or in -negatives .. %d (the pool holds at least the negatives kept), got %d" % (_ffi.SELECT_MAX_KEEP, params.neg_pool))
     if not 0.0 <= params.holdout < 1.0:
         p.error("-holdout must be in 0 .. 1 (the share of the interactions held out)")
     if params.holdout > 0 and not params.kg:

@@ -9,6 +9,8 @@ positives, and every step samples -negatives items per positive (an item's weigh
 uniform; at most -neg_attempts draws per negative), finds the pairs' paths of -min_hops .. -max_hops hops (at most -max_paths each; -max_hops 4 or 5 needs -walks N, the walks that sample the paths of more than 3 hops) and trains, all on the device (graph.train_from_graph); -sampleSeed seeds the shuffles
 and the draws.  Same epoch lines, same -model / -saveFrequency.  -loss bpr trains on the pairwise ranking loss of each positive against its own sampled
 negatives instead of BCE on each pair (include/kprn.h "pairwise loss"); it needs -kg.
+-neg_pool P (with -kg; 0 or -negatives .. 256) trains on hard negatives: every step draws P negatives per positive, scores that pool with the current model
+and keeps the -negatives that score highest, their rows taken from the scored batch (include/kprn.h "hard negatives").
 -holdout 0.2 [-holdout_seed 1 -eval_users 0 -max_candidates N] (with -kg) holds that share of the interactions out (KnowledgeGraph.holdout), trains on the
 rest -- positives, catalogue, weights and paths are the train graph's -- and every -evaluationFrequency epochs ranks the held pairs among everything
 their users reach (graph.evaluate_from_graph): the evaluation line of -rank_samples, plus the held pairs that never reached the ranking stage.
@@ -79,14 +81,15 @@ def train_from_kg(params, eng, callbacks):
         sys.exit("the graph has no edge of relation %s" % params.interaction_rel)
     items = np.unique(positives[:, 1])
     sampler = eng.sampler(items, kg.item_weights(items, params.neg_alpha, params.interaction_rel))
-    print("Training from the graph: %d positives, %d candidate items, %d negatives each" % (len(positives), len(items), params.negatives))
+    pool = ", the highest-scoring of a pool of %d" % params.neg_pool if params.neg_pool > params.negatives else ""
+    print("Training from the graph: %d positives, %d candidate items, %d negatives each%s" % (len(positives), len(items), params.negatives, pool))
     if held is not None:
         print("Held out: %d pairs of %d users" % (len(held), len(np.unique(held[:, 0]))))
         callbacks = callbacks + [OptimizerCallback(params.evaluationFrequency, make_graph_evaluator(eng, params, kg, held, sampler), "evaluation")]
     graph.train_from_graph(eng, kg, positives, model.opt_from_flags(params), params.minibatch, params.negatives, params.numEpochs, params.sampleSeed,
                            sampler=sampler, max_attempts=params.neg_attempts, min_hops=params.min_hops, max_hops=params.max_hops, max_paths=params.max_paths,
                            epoch_hooks=callbacks, start_iteration=params.startIteration, gradient_step_counter=params.gradientStepCounter, walks=params.walks,
-                           loss=params.loss)
+                           loss=params.loss, neg_pool=params.neg_pool)
     return 0
 
 
