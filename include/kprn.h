@@ -447,6 +447,50 @@ int kprn_host_find_paths_cap(const int32_t* src, const int32_t* dst, const int32
  * so that a selection can be rebuilt anywhere.  found outside 0 .. 2^51 - 1, max_paths outside 1..4096 or b < 0 is KPRN_E_ARG.                              */
 int kprn_host_cap_select(int64_t found, int32_t max_paths, int32_t b, uint64_t seed, unsigned int draw, int64_t* ranks /* [min(found, max_paths)] */);
 
+/* ---- meta-paths (the reference's miners extend a path only along named schemas -- item-person-item, item-type-item, item-user-item, each with a budget
+ * where 0 switches it off, data_prepare/path_find_depth_3.py and path_find_depth_5.py; here: keep only the paths whose relation sequence matches a pattern) ----
+ * A graph may carry a pattern set of n patterns, 0 <= n <= KPRN_PATTERN_MAX.
+ *  - pattern p has hops[p] in 1..5 positions; position k is a set of relation ids S[p][k], a subset of 1 .. Vr; an empty set means "any relation".
+ *  - a path with relations (r_0 .. r_{h-1}) MATCHES iff some p has hops[p] == h and r_k in S[p][k] (or S[p][k] empty) for every k.  A path that matches several
+ *    patterns is still one path.
+ *  - n == 0 is the default and means no filter: every call then behaves exactly as described elsewhere in this header, in its results and in the kernels it
+ *    launches.
+ *  - n >= 1: every device call that takes the graph works on the FILTERED SEQUENCE of a pair = the pair's sequence as defined above (hops 1, 2, 3 in
+ *    canonical order, then the sampled hops 4 and 5 in walk order) with the non-matching paths removed and the order kept.  found[b] is its length, counts[b] =
+ *    min(found[b], max_paths), "first" keeps its first rows, "spread" draws its strata over F = the filtered found with the same Philox counters.  Ranks, row
+ *    layout, compaction of the pairs without paths, labels and the KPRN_E_DEVICE check of the fill passes stay as they are.  An asked hop count that no
+ *    pattern has yields no paths; a pattern whose hop count the call does not ask for is inert.
+ *  - sampled hops: the walks are drawn exactly as without patterns -- words, the dead rule, the duplicate rule, no retries; whether a walk is live does not
+ *    depend on the patterns.  The paths of a live walk are those of its (e, c) closes that match; the per-walk counts count matching paths only.  (A walk
+ *    whose prefix no pattern admits has no matching close; an implementation may skip it.)
+ *  - candidates: membership and n_paths count matching paths only, so "the candidates are exactly the members for which the finder would report found > 0"
+ *    and "n_paths equals found" hold with a pattern set.  exclude_adjacent, the user's own entry and the negative sampler's adjacency test keep looking at
+ *    stored edges of any relation.
+ *  - kprn_find_paths_of_candidates, kprn_find_training_paths and kprn_find_training_paths_sampled inherit all of this through the finder's two passes.
+ *    Changing the patterns between making a candidate list and finding its paths is allowed; pairs that end up with 0 paths are dropped, as everywhere.
+ * The set is given with its positions numbered consecutively over the patterns: S = sum(hops); position s allows set_rels[set_offsets[s] ..
+ * set_offsets[s + 1]) (empty = any relation).  n == 0 (the arrays may be NULL) clears the set.  Repeated relations in a set and repeated patterns are fine.
+ * Refusals are decided on the host before anything is written, and a refused call leaves the previous set in place: n outside 0..32, a hop count outside
+ * 1..5, offsets not ascending from 0, NULL arrays with n > 0: KPRN_E_ARG; a relation outside 1 .. Vr: KPRN_E_INDEX.  The table the kernels read -- bit p of
+ * word [k][r] = position k of pattern p admits r, 5 (Vr + 1) words in HBM, owned by the graph -- is uploaded on the handle's stream; the call is synchronous. */
+#define KPRN_PATTERN_MAX 32
+int kprn_graph_set_patterns(kprn_handle* h, kprn_graph* g, const int32_t* hops /* [n] */, const int64_t* set_offsets /* [S + 1] */, const int32_t* set_rels,
+                            int32_t n);
+int kprn_graph_num_patterns(kprn_handle* h, const kprn_graph* g, int32_t* n);
+/* the host twins (no handle, no GPU).  kprn_host_find_paths_patterns: the arguments of kprn_host_find_paths_cap, then the four pattern arguments.
+ * kprn_host_find_candidates_patterns: the arguments of kprn_host_find_candidates_top (below), then the same four; a cap of 2^31 - 1 gives the plain candidates.
+ * With n == 0 each returns exactly what the older twin returns.  The refusals of a set are those above; the candidates twin, which takes no Vr, refuses a
+ * relation below 1 (KPRN_E_INDEX) and lets the table reach the largest relation the edges or the sets name.                                           */
+int kprn_host_find_paths_patterns(const int32_t* src, const int32_t* dst, const int32_t* rel, int64_t E, const int32_t* node_types, int32_t Ve, int32_t Vr,
+                                  int32_t Vt, int32_t num_types, int32_t end_relation, const int32_t* pairs, int32_t B, int32_t min_hops, int32_t max_hops,
+                                  int32_t max_paths, int32_t T, int32_t F, int32_t walks, uint64_t seed, unsigned int draw, int32_t cap_mode, int32_t threads,
+                                  int32_t* counts, int64_t* found, int32_t* idx, const int32_t* hops, const int64_t* set_offsets, const int32_t* set_rels,
+                                  int32_t n);
+int kprn_host_find_candidates_patterns(const int32_t* src, const int32_t* dst, const int32_t* rel, int64_t E, int32_t Ve, const int32_t* items, int64_t M,
+                                       const int32_t* users, int32_t B, int32_t min_hops, int32_t max_hops, int32_t exclude_adjacent, int32_t cap,
+                                       int32_t threads, int32_t* group_counts, int32_t* cand, int64_t* n_paths, const int32_t* hops,
+                                       const int64_t* set_offsets, const int32_t* set_rels, int32_t n);
+
 /* ---- sampling negatives (an extension: the reference draws them offline, data_prepare/sample.py:18-26,101-117 -- distinct non-interacted items, uniform at
  * alpha = 0, else weighted by frequency^alpha; its draws, numpy.random.multinomial and Python's random, cannot be reproduced and are not restated) ----
  * For B user slots, n_neg items per slot from a weighted candidate list, on the device and fully specified, so that any id can be rebuilt anywhere:

@@ -349,6 +349,41 @@ def host_find_paths_cap(src, dst, rel, node_types, Vr, Vt, end_relation, pairs, 
     return _host_find(call, "kprn_host_find_paths_cap", src, dst, rel, node_types, pairs, T, F, want_idx)
 
 
+PATTERN_MAX, PATTERN_MAX_HOPS = 32, 5   # KPRN_PATTERN_MAX; a pattern's positions (include/kprn.h "meta-paths")
+
+
+def _pattern_arrays(patterns):
+    """patterns: a list of patterns, each a list of positions, each an iterable of relation ids or None / empty for any -> the four pattern arguments of
+    kprn_graph_set_patterns: (hops [n] int32, set_offsets [S + 1] int64, set_rels int32, n); None or an empty list: (None, None, None, 0)"""
+    if not patterns:
+        return None, None, None, 0
+    hops, offs, rels = [], [0], []
+    for pat in patterns:
+        pat = list(pat)
+        hops.append(len(pat))
+        for pos in pat:
+            rels += [] if pos is None else [int(r) for r in pos]
+            offs.append(len(rels))
+    return np.array(hops, np.int32), np.array(offs, np.int64), np.array(rels if rels else [0], np.int32), len(hops)
+
+
+def host_find_paths_patterns(src, dst, rel, node_types, Vr, Vt, end_relation, pairs, min_hops, max_hops, max_paths, T, walks=0, seed=0, draw=0, cap="first",
+                             patterns=None, F=None, threads=1, want_idx=True):
+    """kprn_host_find_paths_patterns (no handle, no GPU): host_find_paths_cap over the pairs' filtered sequences -- only the paths whose relation sequence
+    matches one of `patterns` (include/kprn.h "meta-paths"; the form of Graph.set_patterns); no patterns: exactly host_find_paths_cap -> (idx, counts, found)"""
+    if cap not in PATH_CAPS:
+        raise KprnError(E_ARG, "cap must be first or spread")
+    sd, dr = _seed_draw(seed, draw)
+    ph, po, prl, n = _pattern_arrays(patterns)
+
+    def call(src, dst, rel, nt, pr, B, F, counts, found, idx):
+        return lib().kprn_host_find_paths_patterns(_fp(src), _fp(dst), _fp(rel), C.c_int64(int(src.shape[0])), _fp(nt), int(nt.shape[0]), int(Vr), int(Vt),
+                                                   int(nt.shape[1]), int(end_relation), _fp(pr), B, int(min_hops), int(max_hops), int(max_paths), int(T), F,
+                                                   int(walks), sd, dr, PATH_CAPS[cap], int(threads), _fp(counts), _fp(found), _fp(idx), _fp(ph), _fp(po),
+                                                   _fp(prl), n)
+    return _host_find(call, "kprn_host_find_paths_patterns", src, dst, rel, node_types, pairs, T, F, want_idx)
+
+
 def host_cap_select(found, max_paths, b, seed, draw):
     """kprn_host_cap_select: the ranks "spread" keeps of the pair in row b of a pair list that has `found` paths -> ranks [min(found, max_paths)] int64, ascending"""
     n = max(min(int(found), int(max_paths)), 0)
@@ -429,6 +464,32 @@ def host_find_candidates_top(src, dst, rel, Ve, items, users, min_hops, max_hops
                                                  _fp(cand), _fp(n_paths))
         if rc != 0:
             raise KprnError(rc, "kprn_host_find_candidates_top: bad edges / items / users / hops / cap")
+    call(gc, None, None)
+    total = int(gc.astype(np.int64).sum())
+    cand, n_paths = np.zeros(total, np.int32), np.zeros(total, np.int64)
+    if total:
+        call(np.zeros(B, np.int32), cand, n_paths)
+    return cand, gc, n_paths
+
+
+def host_find_candidates_patterns(src, dst, rel, Ve, items, users, min_hops, max_hops, cap=2**31 - 1, exclude_adjacent=True, patterns=None, threads=1):
+    """kprn_host_find_candidates_patterns (no handle, no GPU): host_find_candidates_top where only the paths that match one of `patterns` count (include/kprn.h
+    "meta-paths"); cap = 2^31 - 1: the plain candidates; no patterns: exactly host_find_candidates_top -> (cand, group_counts, n_paths)"""
+    src, dst, rel = (np.ascontiguousarray(a, np.int32).reshape(-1) for a in (src, dst, rel))
+    if not (src.shape == dst.shape == rel.shape):
+        raise KprnError(E_ARG, "a graph is src / dst / rel [E]")
+    it, _ = _sampler_arrays(items, None)
+    us = np.ascontiguousarray(users, np.int32).reshape(-1)
+    B = int(us.shape[0])
+    gc = np.zeros(B, np.int32)
+    ph, po, prl, n = _pattern_arrays(patterns)
+
+    def call(counts, cand, n_paths):
+        rc = lib().kprn_host_find_candidates_patterns(_fp(src), _fp(dst), _fp(rel), C.c_int64(int(src.shape[0])), int(Ve), _fp(it), C.c_int64(int(it.shape[0])),
+                                                      _fp(us), B, int(min_hops), int(max_hops), int(bool(exclude_adjacent)), C.c_int32(_as_cap(cap)), int(threads),
+                                                      _fp(counts), _fp(cand), _fp(n_paths), _fp(ph), _fp(po), _fp(prl), n)
+        if rc != 0:
+            raise KprnError(rc, "kprn_host_find_candidates_patterns: bad edges / items / users / hops / cap / patterns")
     call(gc, None, None)
     total = int(gc.astype(np.int64).sum())
     cand, n_paths = np.zeros(total, np.int32), np.zeros(total, np.int64)
@@ -702,6 +763,18 @@ class Graph:
         """edges stored: the input's less duplicates and self-loops"""
         n = C.c_int64()
         self.engine._ck(self.engine.L.kprn_graph_num_edges(self.engine.h, self.ptr, C.byref(n)))
+        return int(n.value)
+
+    def set_patterns(self, patterns):
+        """kprn_graph_set_patterns (include/kprn.h "meta-paths"): from the next call on, every device call that takes this graph sees only the paths whose
+        relation sequence matches a pattern.  patterns: a list of patterns; a pattern: a list of 1..5 positions; a position: an iterable of relation ids, or
+        None / empty for any relation.  None or an empty list clears the set.  A refused call leaves the previous set in place"""
+        ph, po, prl, n = _pattern_arrays(patterns)
+        self.engine._ck(self.engine.L.kprn_graph_set_patterns(self.engine.h, self.ptr, _fp(ph), _fp(po), _fp(prl), n))
+
+    def num_patterns(self):
+        n = C.c_int32()
+        self.engine._ck(self.engine.L.kprn_graph_num_patterns(self.engine.h, self.ptr, C.byref(n)))
         return int(n.value)
 
     def free(self):

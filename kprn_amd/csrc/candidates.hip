@@ -29,6 +29,7 @@
 //   k_fill_top  the entries 256 at a time, one exclusive scan per chunk over (entries > v, entries == v) packed in the halves of an int64, the rank among
 //             kept rows and the rank among ties carried from chunk to chunk; a thread writes its own row and n_paths entry while rank < counts[b]; the rows
 //             placed are checked against counts[b] as k_fill does.
+// Meta-paths (PAT = true; path_pattern_dev.h): k_mark and k_tally mark only the ends of walks whose relation sequence matches a pattern of the graph's set.
 #include "path_find_dev.h"
 
 namespace cd {
@@ -42,23 +43,46 @@ __host__ __device__ static inline int member(const int32_t* items, int M, int c)
   return (l < M && items[l] == c) ? l : -1;
 }
 
-// the end nodes of the 2-hop walks through first edge e0 (want2) and of the 3-hop walks through its second edges e1_first, e1_first + e1_step, ... (want3)
-template <class Mark>
-__host__ __device__ static inline void walk_edge(const Csr& g, int u, int e0, bool want2, bool want3, int e1_first, int e1_step, Mark&& mark) {
+// the end nodes of the 2-hop walks through first edge e0 (want2) and of the 3-hop walks through its second edges e1_first, e1_first + e1_step, ... (want3).
+// PAT (include/kprn.h "meta-paths"): the walk carries the patterns its edges left alive, leaves an edge none of them admits -- a first edge with its whole fan --
+// and marks only the ends of matching walks; PAT = false never reads pt
+template <bool PAT, class Mark>
+__host__ __device__ static inline void walk_edge(const Csr& g, const pat::Table& pt, int u, int e0, bool want2, bool want3, int e1_first, int e1_step, Mark&& mark) {
   const int a = g.col[e0];   // (a != u: no self-loops)
+  uint32_t a2 = 0, a3 = 0;
+  if (PAT) {
+    a2 = pat::step(pt, pt.len[2], 0, g.rel[e0]); a3 = pat::step(pt, pt.len[3], 0, g.rel[e0]);
+    want2 = want2 && a2; want3 = want3 && a3;
+    if (!want2 && !want3) return;
+  }
   const int end1 = g.rowptr[a + 1];
   if (want2 && e1_first == 0)
-    for (int e1 = g.rowptr[a]; e1 < end1; ++e1) { const int c = g.col[e1]; if (c != u) mark(c); }
+    for (int e1 = g.rowptr[a]; e1 < end1; ++e1) { const int c = g.col[e1]; if (c != u && (!PAT || pat::step(pt, a2, 1, g.rel[e1]))) mark(c); }
   if (!want3) return;
   for (int e1 = g.rowptr[a] + e1_first; e1 < end1; e1 += e1_step) {
     const int b = g.col[e1];
     if (b == u) continue;
+    uint32_t al = 0;
+    if (PAT) { al = pat::step(pt, a3, 1, g.rel[e1]); if (!al) continue; }
     const int end2 = g.rowptr[b + 1];
-    for (int e2 = g.rowptr[b]; e2 < end2; ++e2) { const int c = g.col[e2]; if (c != u && c != a) mark(c); }
+    for (int e2 = g.rowptr[b]; e2 < end2; ++e2) { const int c = g.col[e2]; if (c != u && c != a && (!PAT || pat::step(pt, al, 2, g.rel[e2]))) mark(c); }
+  }
+}
+// the 1-hop walk over first edge e0 marks its end
+template <bool PAT>
+__host__ __device__ static inline bool hop1_ok(const Csr& g, const pat::Table& pt, int e0) { return !PAT || pat::step(pt, pt.len[1], 0, g.rel[e0]) != 0; }
+
+// the walk of one user on the host: every first edge in order
+template <bool PAT, class Mark>
+static inline void host_walk(const Csr& g, const pat::Table& pt, int u, int hmask, Mark&& mark) {
+  for (int e0 = g.rowptr[u]; e0 < g.rowptr[u + 1]; ++e0) {
+    if ((hmask & 1) && hop1_ok<PAT>(g, pt, e0)) mark(g.col[e0]);
+    if (hmask & 6) walk_edge<PAT>(g, pt, u, e0, (hmask & 2) != 0, (hmask & 4) != 0, 0, 1, mark);
   }
 }
 
-__global__ __launch_bounds__(TPB) void k_mark(Csr g, const int32_t* __restrict__ items, int M, int W, const int32_t* __restrict__ users, int hmask,
+template <bool PAT>
+__global__ __launch_bounds__(TPB) void k_mark(Csr g, pat::Table pt, const int32_t* __restrict__ items, int M, int W, const int32_t* __restrict__ users, int hmask,
                                               uint32_t* bits_all) {
   const int u = users[blockIdx.x];
   uint32_t* bits = bits_all + (int64_t)blockIdx.x * W;
@@ -70,12 +94,12 @@ __global__ __launch_bounds__(TPB) void k_mark(Csr g, const int32_t* __restrict__
   };
   const int beg = g.rowptr[u], end = g.rowptr[u + 1];
   if (hmask & 1)
-    for (int e0 = beg + threadIdx.x; e0 < end; e0 += TPB) mark(g.col[e0]);
+    for (int e0 = beg + threadIdx.x; e0 < end; e0 += TPB) if (hop1_ok<PAT>(g, pt, e0)) mark(g.col[e0]);
   if (hmask & 2)   // a thread per first edge
-    for (int e0 = beg + threadIdx.x; e0 < end; e0 += TPB) walk_edge(g, u, e0, true, false, 0, 1, mark);
+    for (int e0 = beg + threadIdx.x; e0 < end; e0 += TPB) walk_edge<PAT>(g, pt, u, e0, true, false, 0, 1, mark);
   if (hmask & 4) { // a wave per first edge, its lanes over the second edges
     const int lane = threadIdx.x & 63;
-    for (int e0 = beg + (threadIdx.x >> 6); e0 < end; e0 += TPB / 64) walk_edge(g, u, e0, false, true, lane, 64, mark);
+    for (int e0 = beg + (threadIdx.x >> 6); e0 < end; e0 += TPB / 64) walk_edge<PAT>(g, pt, u, e0, false, true, lane, 64, mark);
   }
 }
 
@@ -131,7 +155,8 @@ __global__ __launch_bounds__(TPB) void k_fill(const int32_t* __restrict__ items,
 // ---- the N strongest candidates ----------------------------------------------------------------------------------------------------------------
 typedef unsigned long long u64;
 
-__global__ __launch_bounds__(TPB) void k_tally(Csr g, const int32_t* __restrict__ items, int M, const int32_t* __restrict__ users, int hmask, u64* tally_all) {
+template <bool PAT>
+__global__ __launch_bounds__(TPB) void k_tally(Csr g, pat::Table pt, const int32_t* __restrict__ items, int M, const int32_t* __restrict__ users, int hmask, u64* tally_all) {
   const int u = users[blockIdx.x];
   u64* tally = tally_all + (int64_t)blockIdx.x * M;
   auto mark = [&](int c) {
@@ -140,12 +165,12 @@ __global__ __launch_bounds__(TPB) void k_tally(Csr g, const int32_t* __restrict_
   };
   const int beg = g.rowptr[u], end = g.rowptr[u + 1];
   if (hmask & 1)
-    for (int e0 = beg + threadIdx.x; e0 < end; e0 += TPB) mark(g.col[e0]);
+    for (int e0 = beg + threadIdx.x; e0 < end; e0 += TPB) if (hop1_ok<PAT>(g, pt, e0)) mark(g.col[e0]);
   if (hmask & 2)   // a thread per first edge
-    for (int e0 = beg + threadIdx.x; e0 < end; e0 += TPB) walk_edge(g, u, e0, true, false, 0, 1, mark);
+    for (int e0 = beg + threadIdx.x; e0 < end; e0 += TPB) walk_edge<PAT>(g, pt, u, e0, true, false, 0, 1, mark);
   if (hmask & 4) { // a wave per first edge, its lanes over the second edges
     const int lane = threadIdx.x & 63;
-    for (int e0 = beg + (threadIdx.x >> 6); e0 < end; e0 += TPB / 64) walk_edge(g, u, e0, false, true, lane, 64, mark);
+    for (int e0 = beg + (threadIdx.x >> 6); e0 < end; e0 += TPB / 64) walk_edge<PAT>(g, pt, u, e0, false, true, lane, 64, mark);
   }
 }
 
@@ -311,11 +336,15 @@ int kprn_find_candidates(kprn_handle* h, const kprn_graph* g, const kprn_sampler
   int32_t* d_flag = d_counts + B;
   uint32_t* d_bits = (uint32_t*)(d_flag + 4);
   const pf::Csr csr{g->rowptr, g->col, g->rel};
+  // with a pattern set, an asked hop count that no pattern has reaches nobody
+  const bool pat_on = g->n_pat > 0;
+  const pat::Table pt = pf::table_of(g);
+  const int hmask = pf::hop_mask(min_hops, max_hops) & (pat_on ? pat::hops_mask(pt) : ~0);
   HIP_TRY(hipMemcpyAsync(d_users, users, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, s));
   HIP_TRY(hipMemsetAsync(d_bits, 0, n_bits * sizeof(uint32_t), s));
   {
     ProfScope ps(h, "candidates_mark");
-    hipLaunchKernelGGL(cd::k_mark, dim3((unsigned)B), dim3(cd::TPB), 0, s, csr, catalogue->items, M, W, d_users, pf::hop_mask(min_hops, max_hops), d_bits);
+    hipLaunchKernelGGL(pat_on ? cd::k_mark<true> : cd::k_mark<false>, dim3((unsigned)B), dim3(cd::TPB), 0, s, csr, pt, catalogue->items, M, W, d_users, hmask, d_bits);
     HIP_TRY(hipGetLastError());
   }
   {
@@ -389,11 +418,15 @@ int kprn_find_candidates_top(kprn_handle* h, const kprn_graph* g, const kprn_sam
   int32_t* d_quota = d_ncand + B;
   int32_t* d_flag = d_quota + B;
   const pf::Csr csr{g->rowptr, g->col, g->rel};
+  // with a pattern set, an asked hop count that no pattern has reaches nobody
+  const bool pat_on = g->n_pat > 0;
+  const pat::Table pt = pf::table_of(g);
+  const int hmask = pf::hop_mask(min_hops, max_hops) & (pat_on ? pat::hops_mask(pt) : ~0);
   HIP_TRY(hipMemcpyAsync(d_users, users, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, s));
   HIP_TRY(hipMemsetAsync(d_tally, 0, n_tally * sizeof(cd::u64), s));   // (the block is grow-only: an earlier call's sums lie in it)
   {
     ProfScope ps(h, "candidates_tally");
-    hipLaunchKernelGGL(cd::k_tally, dim3((unsigned)B), dim3(cd::TPB), 0, s, csr, catalogue->items, M, d_users, pf::hop_mask(min_hops, max_hops), d_tally);
+    hipLaunchKernelGGL(pat_on ? cd::k_tally<true> : cd::k_tally<false>, dim3((unsigned)B), dim3(cd::TPB), 0, s, csr, pt, catalogue->items, M, d_users, hmask, d_tally);
     HIP_TRY(hipGetLastError());
   }
   {
@@ -498,9 +531,11 @@ int kprn_find_paths_of_candidates(kprn_handle* h, const kprn_graph* g, int32_t m
   API_END(h)
 }
 
-int kprn_host_find_candidates(const int32_t* src, const int32_t* dst, const int32_t* rel, int64_t E, int32_t Ve, const int32_t* items, int64_t M,
+}  // extern "C"
+
+static int host_candidates(const int32_t* src, const int32_t* dst, const int32_t* rel, int64_t E, int32_t Ve, const int32_t* items, int64_t M,
                               const int32_t* users, int32_t B, int32_t min_hops, int32_t max_hops, int32_t exclude_adjacent, int32_t threads,
-                              int32_t* group_counts, int32_t* cand) {
+                              int32_t* group_counts, int32_t* cand, const pat::Table* ptp) {
   if (E < 0 || E > 0x7fffffffLL || (E > 0 && (!src || !dst || !rel)) || !group_counts) return KPRN_E_ARG;
   int rc = ns::validate_table(items, nullptr, M, Ve, nullptr);
   if (rc == KPRN_OK) rc = cd::validate_limits(M, B, min_hops, max_hops, nullptr);
@@ -511,16 +546,15 @@ int kprn_host_find_candidates(const int32_t* src, const int32_t* dst, const int3
   try {
     const pf::HostCsr hg = pf::host_csr(src, dst, rel, E, Ve);
     const pf::Csr g{hg.rowptr.data(), hg.col.data(), hg.rel.data()};
-    const int hmask = pf::hop_mask(min_hops, max_hops);
+    const pat::Table none{nullptr, 0, {0, 0, 0, 0, 0, 0}};
+    const pat::Table& pt = ptp ? *ptp : none;
+    const int hmask = pf::hop_mask(min_hops, max_hops) & (ptp ? pat::hops_mask(pt) : ~0);
     std::vector<std::vector<int32_t>> mine((size_t)B);
     pf::parallel_pairs(B, threads, [&](int32_t b) {
       std::vector<int32_t>& v = mine[(size_t)b];
       const int u = users[b];
       auto mark = [&](int c) { if (cd::member(items, (int)M, c) >= 0) v.push_back(c); };
-      for (int e0 = g.rowptr[u]; e0 < g.rowptr[u + 1]; ++e0) {
-        if (hmask & 1) mark(g.col[e0]);
-        if (hmask & 6) cd::walk_edge(g, u, e0, (hmask & 2) != 0, (hmask & 4) != 0, 0, 1, mark);
-      }
+      if (ptp) cd::host_walk<true>(g, pt, u, hmask, mark); else cd::host_walk<false>(g, pt, u, hmask, mark);
       std::sort(v.begin(), v.end());
       v.erase(std::unique(v.begin(), v.end()), v.end());
       v.erase(std::remove_if(v.begin(), v.end(), [&](int32_t c) {
@@ -543,9 +577,9 @@ int kprn_host_find_candidates(const int32_t* src, const int32_t* dst, const int3
   return KPRN_OK;
 }
 
-int kprn_host_find_candidates_top(const int32_t* src, const int32_t* dst, const int32_t* rel, int64_t E, int32_t Ve, const int32_t* items, int64_t M,
+static int host_candidates_top(const int32_t* src, const int32_t* dst, const int32_t* rel, int64_t E, int32_t Ve, const int32_t* items, int64_t M,
                                   const int32_t* users, int32_t B, int32_t min_hops, int32_t max_hops, int32_t exclude_adjacent, int32_t cap, int32_t threads,
-                                  int32_t* group_counts, int32_t* cand, int64_t* n_paths) {
+                                  int32_t* group_counts, int32_t* cand, int64_t* n_paths, const pat::Table* ptp) {
   if (E < 0 || E > 0x7fffffffLL || (E > 0 && (!src || !dst || !rel)) || !group_counts) return KPRN_E_ARG;
   int rc = ns::validate_table(items, nullptr, M, Ve, nullptr);
   if (rc == KPRN_OK) rc = cd::validate_limits(M, B, min_hops, max_hops, nullptr);
@@ -557,17 +591,16 @@ int kprn_host_find_candidates_top(const int32_t* src, const int32_t* dst, const 
   try {
     const pf::HostCsr hg = pf::host_csr(src, dst, rel, E, Ve);
     const pf::Csr g{hg.rowptr.data(), hg.col.data(), hg.rel.data()};
-    const int hmask = pf::hop_mask(min_hops, max_hops);
+    const pat::Table none{nullptr, 0, {0, 0, 0, 0, 0, 0}};
+    const pat::Table& pt = ptp ? *ptp : none;
+    const int hmask = pf::hop_mask(min_hops, max_hops) & (ptp ? pat::hops_mask(pt) : ~0);
     std::vector<std::vector<std::pair<int32_t, int64_t>>> mine((size_t)B);   // per user: (member's position, n_paths), positions ascending
     pf::parallel_pairs(B, threads, [&](int32_t b) {
       auto& v = mine[(size_t)b];
       const int u = users[b];
       std::vector<int64_t> tally((size_t)M, 0);
       auto mark = [&](int c) { const int j = cd::member(items, (int)M, c); if (j >= 0) ++tally[(size_t)j]; };
-      for (int e0 = g.rowptr[u]; e0 < g.rowptr[u + 1]; ++e0) {
-        if (hmask & 1) mark(g.col[e0]);
-        if (hmask & 6) cd::walk_edge(g, u, e0, (hmask & 2) != 0, (hmask & 4) != 0, 0, 1, mark);
-      }
+      if (ptp) cd::host_walk<true>(g, pt, u, hmask, mark); else cd::host_walk<false>(g, pt, u, hmask, mark);
       for (int32_t j = 0; j < (int32_t)M; ++j) {
         if (tally[(size_t)j] == 0 || items[j] == u) continue;
         if (exclude_adjacent) {
@@ -598,6 +631,43 @@ int kprn_host_find_candidates_top(const int32_t* src, const int32_t* dst, const 
     }
   } catch (...) { return KPRN_E_NOMEM; }
   return KPRN_OK;
+}
+
+extern "C" {
+
+int kprn_host_find_candidates(const int32_t* src, const int32_t* dst, const int32_t* rel, int64_t E, int32_t Ve, const int32_t* items, int64_t M,
+                              const int32_t* users, int32_t B, int32_t min_hops, int32_t max_hops, int32_t exclude_adjacent, int32_t threads,
+                              int32_t* group_counts, int32_t* cand) {
+  return host_candidates(src, dst, rel, E, Ve, items, M, users, B, min_hops, max_hops, exclude_adjacent, threads, group_counts, cand, nullptr);
+}
+
+int kprn_host_find_candidates_top(const int32_t* src, const int32_t* dst, const int32_t* rel, int64_t E, int32_t Ve, const int32_t* items, int64_t M,
+                                  const int32_t* users, int32_t B, int32_t min_hops, int32_t max_hops, int32_t exclude_adjacent, int32_t cap, int32_t threads,
+                                  int32_t* group_counts, int32_t* cand, int64_t* n_paths) {
+  return host_candidates_top(src, dst, rel, E, Ve, items, M, users, B, min_hops, max_hops, exclude_adjacent, cap, threads, group_counts, cand, n_paths, nullptr);
+}
+
+// The candidates twins take no Vr: the table's columns reach the largest relation the edges or the sets name, and a relation below 1 is KPRN_E_INDEX
+int kprn_host_find_candidates_patterns(const int32_t* src, const int32_t* dst, const int32_t* rel, int64_t E, int32_t Ve, const int32_t* items, int64_t M,
+                                       const int32_t* users, int32_t B, int32_t min_hops, int32_t max_hops, int32_t exclude_adjacent, int32_t cap, int32_t threads,
+                                       int32_t* group_counts, int32_t* cand, int64_t* n_paths, const int32_t* hops, const int64_t* set_offsets,
+                                       const int32_t* set_rels, int32_t n_pat) {
+  if (n_pat == 0) return host_candidates_top(src, dst, rel, E, Ve, items, M, users, B, min_hops, max_hops, exclude_adjacent, cap, threads, group_counts, cand, n_paths, nullptr);
+  if (E < 0 || E > 0x7fffffffLL || (E > 0 && (!src || !dst || !rel))) return KPRN_E_ARG;
+  try {
+    int rc = pat::validate(hops, set_offsets, set_rels, n_pat, 0x7fffffff, nullptr);   // (the shape, and no relation below 1)
+    if (rc != KPRN_OK) return rc;
+    int32_t Vr = 1;
+    for (int64_t e = 0; e < E; ++e) { if (rel[e] < 1) return KPRN_E_INDEX; Vr = std::max(Vr, rel[e]); }
+    int64_t S = 0;
+    for (int32_t p = 0; p < n_pat; ++p) S += hops[p];
+    for (int64_t k = 0; k < set_offsets[S]; ++k) Vr = std::max(Vr, set_rels[k]);
+    if (Vr > (1 << 24)) return KPRN_E_INDEX;   // (a table of 5 (Vr + 1) words)
+    pf::HostPat hp;
+    rc = hp.set(hops, set_offsets, set_rels, n_pat, Vr);
+    if (rc != KPRN_OK) return rc;
+    return host_candidates_top(src, dst, rel, E, Ve, items, M, users, B, min_hops, max_hops, exclude_adjacent, cap, threads, group_counts, cand, n_paths, &hp.t);
+  } catch (...) { return KPRN_E_NOMEM; }
 }
 
 }  // extern "C"

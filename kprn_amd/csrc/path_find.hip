@@ -20,6 +20,8 @@
 //             drew (a path of rank r goes to kept row j iff r is the pair's j-th kept rank; the chunks run on to the last kept rank).  The rows a workgroup
 //             placed are summed and compared with the kept ranks below the pair's exhaustive total (the rest, where sampled rows follow, path_walk.hip places
 //             and checks the same way): a disagreement between the passes sets the flag (KPRN_E_DEVICE), and no write leaves the pair's range either way.
+// Meta-paths (include/kprn.h "meta-paths"; path_pattern_dev.h): a graph with a pattern set launches the PAT = true instantiations, which count and place only
+// the paths whose relation sequence matches a pattern (close_count / close_edge over the closing multi-edge); PAT = false is the rule above, unchanged.
 // The host twin walks the same primitives (edge_range, mid_range, write_row) pair by pair on its threads.  The graph, the CSR view and edge_range are in
 // path_find_dev.h, shared with neg_sample.hip; find_staged runs the two passes over a pair list that is staged into HBM by its caller.
 #include "path_find_dev.h"
@@ -29,34 +31,49 @@
 
 namespace pf {
 
-// the closing edges of the 3-hop paths u -> n1 -> col[e1] -> i: their number, the first one in lo; none when the middle node repeats u, i or n1
-__host__ __device__ static inline int mid_range(const Csr& g, int u, int i, int n1, int e1, int& lo) {
+// the closing edges of the 3-hop paths u -> n1 -> col[e1] -> i: their number, the range in [lo, hi); none when the middle node repeats u, i or n1.  PAT: a0 =
+// the patterns of 3 hops that admit the first edge; alive = those that also admit e1 -- none: no search is made -- and the number counts the admitted closes
+template <bool PAT>
+__host__ __device__ static inline int mid_range(const Csr& g, const pat::Table& pt, uint32_t a0, int u, int i, int n1, int e1, int& lo, int& hi, uint32_t& alive) {
   const int n2 = g.col[e1];
-  lo = 0;
+  lo = 0; hi = 0; alive = a0;
   if (n2 == u || n2 == i || n2 == n1) return 0;
-  int hi;
+  if (PAT) { alive = pat::step(pt, a0, 1, g.rel[e1]); if (!alive) return 0; }
   edge_range(g, n2, i, lo, hi);
-  return hi - lo;
+  return close_count<PAT>(g, pt, alive, 2, lo, hi);
 }
 
 // paths of 2 / 3 hops whose first edge is e0 (want2 / want3: the hop is asked for)
-__host__ __device__ static inline void subtree_count(const Csr& g, int u, int i, int e0, bool want2, bool want3, int64_t& c2, int64_t& c3) {
+template <bool PAT>
+__host__ __device__ static inline void subtree_count(const Csr& g, const pat::Table& pt, int u, int i, int e0, bool want2, bool want3, int64_t& c2, int64_t& c3) {
   c2 = 0; c3 = 0;
   const int n1 = g.col[e0];
   if (n1 == u || n1 == i) return;
+  uint32_t a2 = 0, a3 = 0, a;
+  if (PAT) {   // a first edge no pattern of that length admits: its whole fan of second edges is left alone
+    a2 = pat::step(pt, pt.len[2], 0, g.rel[e0]); a3 = pat::step(pt, pt.len[3], 0, g.rel[e0]);
+    want2 = want2 && a2; want3 = want3 && a3;
+  }
   int lo, hi;
-  if (want2) { edge_range(g, n1, i, lo, hi); c2 = hi - lo; }
+  if (want2) { edge_range(g, n1, i, lo, hi); c2 = close_count<PAT>(g, pt, a2, 1, lo, hi); }
   if (!want3) return;
   const int end = g.rowptr[n1 + 1];
-  for (int e1 = g.rowptr[n1]; e1 < end; ++e1) c3 += mid_range(g, u, i, n1, e1, lo);
+  for (int e1 = g.rowptr[n1]; e1 < end; ++e1) c3 += mid_range<PAT>(g, pt, a3, u, i, n1, e1, lo, hi, a);
 }
 
-// the kept paths of 1 hop (ranks 0 .. hi - lo - 1 = the edges [lo, hi)) among the pair's rows first, first + step, ..; out = the pair's rows; returns the rows written
-__host__ __device__ static inline int hop1_fill(const Csr& g, const Fmt& f, int u, int i, int lo, int hi, int first, int step, const Keep& keep, int32_t* out) {
+// the paths of 1 hop: the admitted edges of [lo, hi)
+template <bool PAT>
+__host__ __device__ static inline int hop1_count(const Csr& g, const pat::Table& pt, int lo, int hi) { return close_count<PAT>(g, pt, pt.len[1], 0, lo, hi); }
+
+// the kept paths of 1 hop (ranks 0 .. n - 1 = the admitted edges of [lo, hi), n of them) among the pair's rows first, first + step, ..; out = the pair's rows;
+// returns the rows written
+template <bool PAT>
+__host__ __device__ static inline int hop1_fill(const Csr& g, const pat::Table& pt, const Fmt& f, int u, int i, int lo, int hi, int n, int first, int step,
+                                                const Keep& keep, int32_t* out) {
   int placed = 0;
   const int64_t row = (int64_t)f.T * f.F;
-  for (int64_t j = first; j < keep.cap && keep_rank(keep, j) < hi - lo; j += step) {
-    const int nodes[2] = {u, i}, rels[1] = {g.rel[lo + keep_rank(keep, j)]};
+  for (int64_t j = first; j < keep.cap && keep_rank(keep, j) < n; j += step) {
+    const int nodes[2] = {u, i}, rels[1] = {g.rel[close_edge<PAT>(g, pt, pt.len[1], 0, lo, hi, keep_rank(keep, j))]};
     write_row(f, out + j * row, 1, nodes, rels);
     ++placed;
   }
@@ -65,16 +82,21 @@ __host__ __device__ static inline int hop1_fill(const Csr& g, const Fmt& f, int 
 
 // the kept rows of first edge e0: its paths of 2 hops have the ranks from r2 on, those of 3 hops from r3 on (< 0: that hop is not looked at); out = the pair's
 // rows; returns the rows written
-__host__ __device__ static inline int subtree_fill(const Csr& g, const Fmt& f, int u, int i, int e0, const Keep& keep, int64_t r2, int64_t r3, int32_t* out) {
+template <bool PAT>
+__host__ __device__ static inline int subtree_fill(const Csr& g, const pat::Table& pt, const Fmt& f, int u, int i, int e0, const Keep& keep, int64_t r2, int64_t r3,
+                                                   int32_t* out) {
   const int n1 = g.col[e0];
   if (n1 == u || n1 == i) return 0;
   const int64_t row = (int64_t)f.T * f.F;
   int placed = 0, lo, hi;
+  uint32_t a2 = 0, a3 = 0, a;
+  if (PAT) { a2 = pat::step(pt, pt.len[2], 0, g.rel[e0]); a3 = pat::step(pt, pt.len[3], 0, g.rel[e0]); }
   int64_t j = r2 >= 0 ? keep_lower(keep, r2) : keep.cap;
   if (j < keep.cap) {
     edge_range(g, n1, i, lo, hi);
-    for (; j < keep.cap && keep_rank(keep, j) - r2 < hi - lo; ++j) {
-      const int nodes[3] = {u, n1, i}, rels[2] = {g.rel[e0], g.rel[lo + (keep_rank(keep, j) - r2)]};
+    const int c = close_count<PAT>(g, pt, a2, 1, lo, hi);
+    for (; j < keep.cap && keep_rank(keep, j) - r2 < c; ++j) {
+      const int nodes[3] = {u, n1, i}, rels[2] = {g.rel[e0], g.rel[close_edge<PAT>(g, pt, a2, 1, lo, hi, keep_rank(keep, j) - r2)]};
       write_row(f, out + j * row, 2, nodes, rels);
       ++placed;
     }
@@ -83,9 +105,9 @@ __host__ __device__ static inline int subtree_fill(const Csr& g, const Fmt& f, i
     const int end = g.rowptr[n1 + 1];
     j = keep_lower(keep, r3);
     for (int e1 = g.rowptr[n1]; e1 < end && j < keep.cap; ++e1) {
-      const int c = mid_range(g, u, i, n1, e1, lo);
+      const int c = mid_range<PAT>(g, pt, a3, u, i, n1, e1, lo, hi, a);
       for (; j < keep.cap && keep_rank(keep, j) - r3 < c; ++j) {
-        const int nodes[4] = {u, n1, g.col[e1], i}, rels[3] = {g.rel[e0], g.rel[e1], g.rel[lo + (keep_rank(keep, j) - r3)]};
+        const int nodes[4] = {u, n1, g.col[e1], i}, rels[3] = {g.rel[e0], g.rel[e1], g.rel[close_edge<PAT>(g, pt, a, 2, lo, hi, keep_rank(keep, j) - r3)]};
         write_row(f, out + j * row, 3, nodes, rels);
         ++placed;
       }
@@ -96,18 +118,21 @@ __host__ __device__ static inline int subtree_fill(const Csr& g, const Fmt& f, i
 }
 
 // ---- kernels ---------------------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(TPB) void k_count(Csr g, const int32_t* __restrict__ pairs, int hmask, int64_t* __restrict__ tot) {
+// PAT (every kernel below that walks edges): the graph has a pattern set and pt is its table; PAT = false never reads pt, and the match folds out of the code.
+// The match sits inside a lane's own count; what surrounds a barrier or a workgroup sum stays workgroup-uniform (hmask, the first edge's relation)
+template <bool PAT>
+__global__ __launch_bounds__(TPB) void k_count(Csr g, pat::Table pt, const int32_t* __restrict__ pairs, int hmask, int64_t* __restrict__ tot) {
   __shared__ int64_t sh[TPB];
   const int b = blockIdx.x, u = pairs[2 * b], i = pairs[2 * b + 1];
   int64_t c1 = 0, c2 = 0, c3 = 0;
   if (u != i) {   // (workgroup-uniform)
     int lo, hi;
-    if (hmask & 1) { edge_range(g, u, i, lo, hi); c1 = hi - lo; }
+    if (hmask & 1) { edge_range(g, u, i, lo, hi); c1 = hop1_count<PAT>(g, pt, lo, hi); }
     const int end = g.rowptr[u + 1];
     if (hmask & 2) {   // a thread per first edge: one search each
       for (int e0 = g.rowptr[u] + threadIdx.x; e0 < end; e0 += TPB) {
         int64_t a2, a3;
-        subtree_count(g, u, i, e0, true, false, a2, a3);
+        subtree_count<PAT>(g, pt, u, i, e0, true, false, a2, a3);
         c2 += a2;
       }
       c2 = block_sum(c2, sh);
@@ -117,8 +142,10 @@ __global__ __launch_bounds__(TPB) void k_count(Csr g, const int32_t* __restrict_
       for (int e0 = g.rowptr[u] + (threadIdx.x >> 6); e0 < end; e0 += TPB / 64) {
         const int n1 = g.col[e0];
         if (n1 == u || n1 == i) continue;   // (wave-uniform)
+        uint32_t a3 = 0, a;
+        if (PAT) { a3 = pat::step(pt, pt.len[3], 0, g.rel[e0]); if (!a3) continue; }   // (wave-uniform: the fan of a first edge no pattern admits is skipped)
         const int end1 = g.rowptr[n1 + 1];
-        for (int e1 = g.rowptr[n1] + lane; e1 < end1; e1 += 64) { int lo; c3 += mid_range(g, u, i, n1, e1, lo); }
+        for (int e1 = g.rowptr[n1] + lane; e1 < end1; e1 += 64) { int lo, hi; c3 += mid_range<PAT>(g, pt, a3, u, i, n1, e1, lo, hi, a); }
       }
       c3 = block_sum(c3, sh);
     }
@@ -141,8 +168,8 @@ __global__ __launch_bounds__(64) void k_cap_ranks(const int64_t* __restrict__ to
 // k_cap_ranks' array.  nxt = the first kept row whose rank is not behind the running rank: a hop's chunks stop once it reaches cnt[b], a chunk without a kept
 // rank writes nothing, and a thread looks its own ranks up from nxt on (all three workgroup-uniform: every thread reads the same ranks).  SPREAD = false: ranks
 // is not looked at, and the rank lookups fold into the comparisons with cnt[b] that the kernel made before there was a cap mode
-template <bool SPREAD>
-__global__ __launch_bounds__(TPB) void k_fill(Csr g, Fmt f, const int32_t* __restrict__ pairs, int hmask, const int64_t* __restrict__ tot,
+template <bool SPREAD, bool PAT>
+__global__ __launch_bounds__(TPB) void k_fill(Csr g, pat::Table pt, Fmt f, const int32_t* __restrict__ pairs, int hmask, const int64_t* __restrict__ tot,
                                               const int64_t* __restrict__ first, const int32_t* __restrict__ cnt, const int64_t* __restrict__ ranks,
                                               int32_t* __restrict__ idx, int32_t* flag) {
   __shared__ int64_t sh[TPB];
@@ -158,7 +185,7 @@ __global__ __launch_bounds__(TPB) void k_fill(Csr g, Fmt f, const int32_t* __res
   if (hmask & 1) {
     int lo, hi;
     edge_range(g, u, i, lo, hi);
-    placed += hop1_fill(g, f, u, i, lo, hi, threadIdx.x, TPB, keep, out);
+    placed += hop1_fill<PAT>(g, pt, f, u, i, lo, hi, PAT ? (int)base2 : hi - lo, threadIdx.x, TPB, keep, out);   // (tot[0] = the hop's count)
   }
   const int end = g.rowptr[u + 1];
   // 2 hops: a thread per first edge, 256 first edges at a time; run2 = rank of the next chunk's first path (workgroup-uniform, like every loop bound below)
@@ -167,10 +194,10 @@ __global__ __launch_bounds__(TPB) void k_fill(Csr g, Fmt f, const int32_t* __res
     for (int e_base = g.rowptr[u]; e_base < end && nxt < cap; e_base += TPB) {
       const int e0 = e_base + threadIdx.x;
       int64_t c2 = 0, c3, sum2;
-      if (e0 < end) subtree_count(g, u, i, e0, true, false, c2, c3);
+      if (e0 < end) subtree_count<PAT>(g, pt, u, i, e0, true, false, c2, c3);
       const int64_t r2 = run2 + block_scan_excl(c2, sh, sum2);
       // (every row written is a kept row j < cap: out + j * row stays inside the pair's range)
-      if (c2 && keep_rank(keep, nxt) < run2 + sum2) placed += subtree_fill(g, f, u, i, e0, keep, r2, -1, out);
+      if (c2 && keep_rank(keep, nxt) < run2 + sum2) placed += subtree_fill<PAT>(g, pt, f, u, i, e0, keep, r2, -1, out);
       run2 += sum2;
       nxt = keep_lower(keep, run2, nxt);
     }
@@ -181,16 +208,18 @@ __global__ __launch_bounds__(TPB) void k_fill(Csr g, Fmt f, const int32_t* __res
     for (int e0 = g.rowptr[u]; e0 < end && nxt < cap; ++e0) {
       const int n1 = g.col[e0];
       if (n1 == u || n1 == i) continue;
+      uint32_t a3 = 0, a = 0;
+      if (PAT) { a3 = pat::step(pt, pt.len[3], 0, g.rel[e0]); if (!a3) continue; }   // (workgroup-uniform)
       const int end1 = g.rowptr[n1 + 1];
       for (int e1_base = g.rowptr[n1]; e1_base < end1 && nxt < cap; e1_base += TPB) {
         const int e1 = e1_base + threadIdx.x;
-        int lo = 0;
-        const int64_t c = e1 < end1 ? mid_range(g, u, i, n1, e1, lo) : 0;
+        int lo = 0, hi = 0;
+        const int64_t c = e1 < end1 ? mid_range<PAT>(g, pt, a3, u, i, n1, e1, lo, hi, a) : 0;
         int64_t sum3;
         const int64_t r3 = run3 + block_scan_excl(c, sh, sum3);
         if (c && keep_rank(keep, nxt) < run3 + sum3)
           for (int64_t j = keep_lower(keep, r3, nxt); j < cap && keep_rank(keep, j) - r3 < c; ++j) {
-            const int nodes[4] = {u, n1, g.col[e1], i}, rels[3] = {g.rel[e0], g.rel[e1], g.rel[lo + (keep_rank(keep, j) - r3)]};
+            const int nodes[4] = {u, n1, g.col[e1], i}, rels[3] = {g.rel[e0], g.rel[e1], g.rel[close_edge<PAT>(g, pt, a, 2, lo, hi, keep_rank(keep, j) - r3)]};
             write_row(f, out + j * row, 3, nodes, rels);
             ++placed;
           }
@@ -349,7 +378,7 @@ static kprn_graph* build_graph(kprn_handle* h, const int32_t* src, const int32_t
 }
 
 static void free_graph(kprn_graph* g) {
-  dfree(g->rowptr); dfree(g->col); dfree(g->rel); dfree(g->types);
+  dfree(g->rowptr); dfree(g->col); dfree(g->rel); dfree(g->types); dfree(g->pat_match);
   delete g;
 }
 
@@ -361,32 +390,34 @@ void release_all(kprn_handle* h) {
 }
 
 // ---- host twin: the same rule over the host CSR (path_find_dev.h) ---------------------------------------------------------------------------
-static void host_pair_totals(const Csr& g, int u, int i, int hmask, int64_t* t4) {
+template <bool PAT>
+static void host_pair_totals(const Csr& g, const pat::Table& pt, int u, int i, int hmask, int64_t* t4) {
   int64_t c1 = 0, c2 = 0, c3 = 0;
   if (u != i) {
     int lo, hi;
-    if (hmask & 1) { edge_range(g, u, i, lo, hi); c1 = hi - lo; }
+    if (hmask & 1) { edge_range(g, u, i, lo, hi); c1 = hop1_count<PAT>(g, pt, lo, hi); }
     if (hmask & 6)
       for (int e0 = g.rowptr[u]; e0 < g.rowptr[u + 1]; ++e0) {
         int64_t a2, a3;
-        subtree_count(g, u, i, e0, (hmask & 2) != 0, (hmask & 4) != 0, a2, a3);
+        subtree_count<PAT>(g, pt, u, i, e0, (hmask & 2) != 0, (hmask & 4) != 0, a2, a3);
         c2 += a2; c3 += a3;
       }
   }
   t4[0] = c1; t4[1] = c2; t4[2] = c3; t4[3] = c1 + c2 + c3;
 }
 
-static int64_t host_pair_fill(const Csr& g, const Fmt& f, int u, int i, int hmask, const int64_t* t4, const Keep& keep, int32_t* out) {
+template <bool PAT>
+static int64_t host_pair_fill(const Csr& g, const pat::Table& pt, const Fmt& f, int u, int i, int hmask, const int64_t* t4, const Keep& keep, int32_t* out) {
   const int64_t base2 = t4[0], base3 = t4[0] + t4[1];
   int64_t placed = 0, done2 = 0, done3 = 0;
   int lo, hi;
-  if (hmask & 1) { edge_range(g, u, i, lo, hi); placed += hop1_fill(g, f, u, i, lo, hi, 0, 1, keep, out); }
+  if (hmask & 1) { edge_range(g, u, i, lo, hi); placed += hop1_fill<PAT>(g, pt, f, u, i, lo, hi, (int)t4[0], 0, 1, keep, out); }
   for (int e0 = g.rowptr[u]; e0 < g.rowptr[u + 1]; ++e0) {
     const bool go2 = (hmask & 2) && keep_lower(keep, base2 + done2) < keep.cap, go3 = (hmask & 4) && keep_lower(keep, base3 + done3) < keep.cap;
     if (!go2 && !go3) break;
     int64_t c2, c3;
-    subtree_count(g, u, i, e0, go2, go3, c2, c3);
-    placed += subtree_fill(g, f, u, i, e0, keep, c2 ? base2 + done2 : -1, c3 ? base3 + done3 : -1, out);
+    subtree_count<PAT>(g, pt, u, i, e0, go2, go3, c2, c3);
+    placed += subtree_fill<PAT>(g, pt, f, u, i, e0, keep, c2 ? base2 + done2 : -1, c3 ? base3 + done3 : -1, out);
     done2 += c2; done3 += c3;
   }
   return placed;
@@ -397,7 +428,10 @@ void find_staged(kprn_handle* h, const kprn_graph* g, const StagePairs& stage, c
   const kprn_config& c = h->cfg;
   KPRN_REQUIRE(c.F >= c.num_types + 2, KPRN_E_ARG, "F must hold num_types + 2 columns");
   hipStream_t s = h->stream;
-  const int hmask = hop_mask(min_hops, max_hops);
+  // with a pattern set, an asked hop count that no pattern has yields no paths: it leaves the mask here, and its kernels' work with it
+  const bool pat_on = g->n_pat > 0;
+  const pat::Table pt = table_of(g);
+  const int hmask = hop_mask(min_hops, max_hops) & (pat_on ? pat::hops_mask(pt) : ~0);
   const bool sampled = (hmask & HOPS_SAMPLED) != 0;   // (validated: sm is there)
   const bool spread = sm && sm->cap_mode == CAP_SPREAD;
   const size_t n_wc = sampled ? (size_t)2 * B * sm->walks : 0;
@@ -415,13 +449,13 @@ void find_staged(kprn_handle* h, const kprn_graph* g, const StagePairs& stage, c
   stage(d_pairs, s);
   {
     ProfScope ps(h, "find_paths_count");
-    hipLaunchKernelGGL(k_count, dim3((unsigned)B), dim3(TPB), 0, s, csr, d_pairs, hmask, d_tot);
+    hipLaunchKernelGGL(pat_on ? k_count<true> : k_count<false>, dim3((unsigned)B), dim3(TPB), 0, s, csr, pt, d_pairs, hmask, d_tot);
     HIP_TRY(hipGetLastError());
   }
   std::vector<int64_t> tot((size_t)4 * B), first((size_t)B), wsum(sampled ? (size_t)2 * B : 0);
   if (sampled) {
     ProfScope ps(h, "find_paths_walk_count");
-    walk_count_launch(csr, d_pairs, B, hmask, *sm, d_wc, d_wsum, s);
+    walk_count_launch(csr, d_pairs, B, hmask, *sm, d_wc, d_wsum, s, pat_on ? &pt : nullptr);
     HIP_TRY(hipMemcpyAsync(wsum.data(), d_wsum, wsum.size() * sizeof(int64_t), hipMemcpyDeviceToHost, s));
   }
   HIP_TRY(hipMemcpyAsync(tot.data(), d_tot, tot.size() * sizeof(int64_t), hipMemcpyDeviceToHost, s));
@@ -458,12 +492,13 @@ void find_staged(kprn_handle* h, const kprn_graph* g, const StagePairs& stage, c
       }
       {
         ProfScope ps(h, "find_paths_fill", st);
-        hipLaunchKernelGGL(spread ? k_fill<true> : k_fill<false>, dim3((unsigned)B), dim3(TPB), 0, st, csr, fmt, d_pairs, hmask, d_tot, d_first, d_cnt, d_keep, idx_dev, d_flag);
+        const auto kern = pat_on ? (spread ? k_fill<true, true> : k_fill<false, true>) : (spread ? k_fill<true, false> : k_fill<false, false>);
+        hipLaunchKernelGGL(kern, dim3((unsigned)B), dim3(TPB), 0, st, csr, pt, fmt, d_pairs, hmask, d_tot, d_first, d_cnt, d_keep, idx_dev, d_flag);
         HIP_TRY(hipGetLastError());
       }
       if (sampled) {
         ProfScope pw(h, "find_paths_walk_fill", st);
-        walk_fill_launch(csr, fmt, d_pairs, B, *sm, d_tot, d_wc, d_first, d_cnt, d_keep, idx_dev, d_flag, st);
+        walk_fill_launch(csr, fmt, d_pairs, B, *sm, d_tot, d_wc, d_first, d_cnt, d_keep, idx_dev, d_flag, st, pat_on ? &pt : nullptr);
       }
     };
     kprn_batch* nb = nullptr;
@@ -485,7 +520,7 @@ void find_staged(kprn_handle* h, const kprn_graph* g, const StagePairs& stage, c
 
 int host_find(const int32_t* src, const int32_t* dst, const int32_t* rel, int64_t E, const int32_t* node_types, int32_t Ve, int32_t Vr, int32_t Vt, int32_t num_types,
               int32_t end_relation, const int32_t* pairs, int32_t B, int32_t min_hops, int32_t max_hops, int32_t max_paths, int32_t T, int32_t F, const Sampling* sm,
-              int32_t threads, int32_t* counts, int64_t* found, int32_t* idx) {
+              int32_t threads, int32_t* counts, int64_t* found, int32_t* idx, const pat::Table* ptp) {
   int rc = pf::validate_graph(src, dst, rel, E, node_types, Ve, Vr, Vt, num_types, end_relation, nullptr);
   if (rc != KPRN_OK) return rc;
   rc = pf::validate_find(pairs, B, Ve, min_hops, max_hops, max_paths, T, sm, nullptr);
@@ -495,14 +530,17 @@ int host_find(const int32_t* src, const int32_t* dst, const int32_t* rel, int64_
     const pf::HostCsr hg = pf::host_csr(src, dst, rel, E, Ve);
     const pf::Csr g{hg.rowptr.data(), hg.col.data(), hg.rel.data()};
     const pf::Fmt f{node_types, num_types, Vt, Ve, Vr, T, F, end_relation};
-    const int hmask = pf::hop_mask(min_hops, max_hops);
+    const pat::Table none{nullptr, 0, {0, 0, 0, 0, 0, 0}};
+    const pat::Table& pt = ptp ? *ptp : none;
+    const int hmask = pf::hop_mask(min_hops, max_hops) & (ptp ? pat::hops_mask(pt) : ~0);
     const bool sampled = (hmask & HOPS_SAMPLED) != 0;
     const bool spread = sm && sm->cap_mode == CAP_SPREAD;
     const size_t per = sampled ? (size_t)2 * sm->walks : 0;   // a pair's per-walk counts
     std::vector<int64_t> tot((size_t)4 * B), first((size_t)B), fnd((size_t)B), wc(per * B), wsum(sampled ? (size_t)2 * B : 0);
     pf::parallel_pairs(B, threads, [&](int32_t b) {
-      pf::host_pair_totals(g, pairs[2 * b], pairs[2 * b + 1], hmask, &tot[4 * (size_t)b]);
-      if (sampled) host_walk_counts(g, pairs[2 * b], pairs[2 * b + 1], b, hmask, *sm, &wc[per * b], &wsum[2 * (size_t)b]);
+      if (ptp) pf::host_pair_totals<true>(g, pt, pairs[2 * b], pairs[2 * b + 1], hmask, &tot[4 * (size_t)b]);
+      else pf::host_pair_totals<false>(g, pt, pairs[2 * b], pairs[2 * b + 1], hmask, &tot[4 * (size_t)b]);
+      if (sampled) host_walk_counts(g, pairs[2 * b], pairs[2 * b + 1], b, hmask, *sm, &wc[per * b], &wsum[2 * (size_t)b], ptp);
     });
     int64_t N = 0;
     for (int32_t b = 0; b < B; ++b) {
@@ -525,8 +563,9 @@ int host_find(const int32_t* src, const int32_t* dst, const int32_t* rel, int64_
         for (int32_t j = 0; j < counts[b]; ++j) ranks[(size_t)j] = cap_rank(fnd[(size_t)b], max_paths, j, b, sm->k0, sm->k1, sm->draw);
       }
       const Keep keep{ranks.empty() ? nullptr : ranks.data(), counts[b]};
-      int64_t placed = pf::host_pair_fill(g, f, pairs[2 * b], pairs[2 * b + 1], hmask, &tot[4 * (size_t)b], keep, rows);
-      if (sampled) placed += host_walk_fill(g, f, pairs[2 * b], pairs[2 * b + 1], b, *sm, &wc[per * b], tot[4 * (size_t)b + 3], keep, rows);
+      int64_t placed = ptp ? pf::host_pair_fill<true>(g, pt, f, pairs[2 * b], pairs[2 * b + 1], hmask, &tot[4 * (size_t)b], keep, rows)
+                           : pf::host_pair_fill<false>(g, pt, f, pairs[2 * b], pairs[2 * b + 1], hmask, &tot[4 * (size_t)b], keep, rows);
+      if (sampled) placed += host_walk_fill(g, f, pairs[2 * b], pairs[2 * b + 1], b, *sm, &wc[per * b], tot[4 * (size_t)b + 3], keep, rows, ptp);
       if (placed != counts[b]) wrong = 1;
     });
     if (wrong) return KPRN_E_DEVICE;
@@ -566,6 +605,33 @@ int kprn_graph_num_edges(kprn_handle* h, const kprn_graph* g, int64_t* n) {
   API_BEGIN(h)
   KPRN_REQUIRE(g && n, KPRN_E_ARG, "NULL argument");
   *n = g->E;
+  API_END(h)
+}
+
+int kprn_graph_set_patterns(kprn_handle* h, kprn_graph* g, const int32_t* hops, const int64_t* set_offsets, const int32_t* set_rels, int32_t n) {
+  API_BEGIN(h)
+  KPRN_REQUIRE(g && std::find(h->graphs.begin(), h->graphs.end(), g) != h->graphs.end(), KPRN_E_ARG, "g is not a graph of this handle");
+  const char* why = "";
+  const int rc = pat::validate(hops, set_offsets, set_rels, n, g->Vr, &why);   // (every refusal, before anything is written)
+  if (rc != KPRN_OK) throw KprnError{rc, why};
+  if (n > 0) {
+    std::vector<uint32_t> match((size_t)pat::table_words(g->Vr));
+    uint32_t len[pat::MAX_HOPS + 1];
+    pat::build(hops, set_offsets, set_rels, n, g->Vr, match.data(), len);
+    if (!g->pat_match) g->pat_match = dalloc<uint32_t>(pat::table_words(g->Vr));
+    HIP_TRY(hipStreamSynchronize(h->stream));   // (a launch still queued reads the old table)
+    HIP_TRY(hipMemcpyAsync(g->pat_match, match.data(), match.size() * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));   // (match leaves scope)
+    std::copy(len, len + pat::MAX_HOPS + 1, g->pat_len);
+  }
+  g->n_pat = n;
+  API_END(h)
+}
+
+int kprn_graph_num_patterns(kprn_handle* h, const kprn_graph* g, int32_t* n) {
+  API_BEGIN(h)
+  KPRN_REQUIRE(g && n, KPRN_E_ARG, "NULL argument");
+  *n = g->n_pat;
   API_END(h)
 }
 
@@ -625,6 +691,22 @@ int kprn_host_find_paths_cap(const int32_t* src, const int32_t* dst, const int32
   const pf::Sampling sm = pf::sampling_of(walks, seed, draw, cap_mode);
   return pf::host_find(src, dst, rel, E, node_types, Ve, Vr, Vt, num_types, end_relation, pairs, B, min_hops, max_hops, max_paths, T, F, &sm, threads, counts, found,
                        idx);
+}
+
+int kprn_host_find_paths_patterns(const int32_t* src, const int32_t* dst, const int32_t* rel, int64_t E, const int32_t* node_types, int32_t Ve, int32_t Vr, int32_t Vt,
+                                  int32_t num_types, int32_t end_relation, const int32_t* pairs, int32_t B, int32_t min_hops, int32_t max_hops, int32_t max_paths,
+                                  int32_t T, int32_t F, int32_t walks, uint64_t seed, unsigned int draw, int32_t cap_mode, int32_t threads, int32_t* counts,
+                                  int64_t* found, int32_t* idx, const int32_t* hops, const int64_t* set_offsets, const int32_t* set_rels, int32_t n_pat) {
+  if (cap_mode != pf::CAP_FIRST && cap_mode != pf::CAP_SPREAD) return KPRN_E_ARG;
+  if (Vr < 1) return KPRN_E_ARG;
+  const pf::Sampling sm = pf::sampling_of(walks, seed, draw, cap_mode);
+  try {
+    pf::HostPat hp;
+    const int rc = hp.set(hops, set_offsets, set_rels, n_pat, Vr);
+    if (rc != KPRN_OK) return rc;
+    return pf::host_find(src, dst, rel, E, node_types, Ve, Vr, Vt, num_types, end_relation, pairs, B, min_hops, max_hops, max_paths, T, F, &sm, threads, counts, found,
+                         idx, hp.on ? &hp.t : nullptr);
+  } catch (...) { return KPRN_E_NOMEM; }
 }
 
 int kprn_host_cap_select(int64_t found, int32_t max_paths, int32_t b, uint64_t seed, unsigned int draw, int64_t* ranks) {

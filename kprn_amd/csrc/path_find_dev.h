@@ -1,8 +1,10 @@
 // What the path finder (path_find.hip), its sampled hops (path_walk.hip), the negative sampler (neg_sample.hip) and the candidates (candidates.hip) share: the graph in HBM, the CSR view they
-// walk and a path's row (namespace pf, __host__ __device__), the workgroup's sums, the host CSR of the twins and their thread loop.
+// walk and a path's row (namespace pf, __host__ __device__), the closing multi-edge under a pattern set (close_count / close_edge; path_pattern_dev.h), the
+// workgroup's sums, the host CSR of the twins and their thread loop.
 #pragma once
 #include "kprn_internal.h"
 #include "philox_dev.h"
+#include "path_pattern_dev.h"
 
 #include <algorithm>
 #include <atomic>
@@ -16,6 +18,10 @@ struct kprn_graph {
   int32_t* col = nullptr;        // device [E] destination
   int32_t* rel = nullptr;        // device [E] relation
   int32_t* types = nullptr;      // device [Ve][nT]: row e - 1 = the type slots of entity e
+  // the pattern set (include/kprn.h "meta-paths"; path_pattern_dev.h): n_pat == 0 = no filter.  The table's block is made by the first set and kept
+  int32_t n_pat = 0;
+  uint32_t* pat_match = nullptr; // device [5][Vr + 1]
+  uint32_t pat_len[pat::MAX_HOPS + 1] = {0, 0, 0, 0, 0, 0};
 };
 
 struct kprn_sampler {
@@ -43,6 +49,45 @@ __host__ __device__ static inline void edge_range(const Csr& g, int n, int targe
   while (l < r) { const int m = l + ((r - l) >> 1); if (g.col[m] <= target) l = m + 1; else r = m; }
   hi = l;
 }
+
+// ---- meta-paths: the closing multi-edge [lo, hi) under a pattern set.  PAT = false is the unfiltered rule: every edge of the range, the j-th one at lo + j ----
+// alive: the patterns the path's earlier edges left; k: the closing edge's position
+template <bool PAT>
+__host__ __device__ static inline int close_count(const Csr& g, const pat::Table& pt, uint32_t alive, int k, int lo, int hi) {
+  if (!PAT) return hi - lo;
+  int c = 0;
+  for (int e = lo; e < hi; ++e) c += pat::step(pt, alive, k, g.rel[e]) != 0;
+  return c;
+}
+// the j-th admitted edge of the range, j < close_count (hi - 1 otherwise: never past the range)
+template <bool PAT>
+__host__ __device__ static inline int close_edge(const Csr& g, const pat::Table& pt, uint32_t alive, int k, int lo, int hi, int64_t j) {
+  if (!PAT) return lo + (int)j;
+  int e = lo;
+  for (; e < hi - 1; ++e)
+    if (pat::step(pt, alive, k, g.rel[e]) != 0 && j-- == 0) break;
+  return e;
+}
+// a graph's table as the kernels take it, and the hop mask of a call on it: with patterns, an asked hop count that no pattern has yields no paths
+static inline pat::Table table_of(const kprn_graph* g) {
+  pat::Table t{g->pat_match, g->Vr + 1, {0, 0, 0, 0, 0, 0}};
+  for (int h = 0; h <= pat::MAX_HOPS; ++h) t.len[h] = g->n_pat > 0 ? g->pat_len[h] : 0u;
+  return t;
+}
+// a pattern set on the host (the twins): the table built from the four pattern arguments; n == 0: none
+struct HostPat {
+  std::vector<uint32_t> match;
+  pat::Table t{nullptr, 0, {0, 0, 0, 0, 0, 0}};
+  bool on = false;
+  int set(const int32_t* hops, const int64_t* set_offsets, const int32_t* set_rels, int32_t n, int32_t Vr) {
+    const int rc = pat::validate(hops, set_offsets, set_rels, n, Vr, nullptr);
+    if (rc != KPRN_OK || n == 0) return rc;
+    match.resize((size_t)pat::table_words(Vr));
+    pat::build(hops, set_offsets, set_rels, n, Vr, match.data(), t.len);
+    t.match = match.data(); t.stride = Vr + 1; on = true;
+    return KPRN_OK;
+  }
+};
 
 struct Fmt { const int32_t* types; int nT, Vt, Ve, Vr, T, F, end_rel; };
 constexpr int TPB = 256;
@@ -176,7 +221,7 @@ int validate_find(const int32_t* pairs, int32_t B, int32_t Ve, int32_t min_hops,
 // the host twin's body (kprn_host_find_paths and kprn_host_find_paths_sampled)
 int host_find(const int32_t* src, const int32_t* dst, const int32_t* rel, int64_t E, const int32_t* node_types, int32_t Ve, int32_t Vr, int32_t Vt, int32_t num_types,
               int32_t end_relation, const int32_t* pairs, int32_t B, int32_t min_hops, int32_t max_hops, int32_t max_paths, int32_t T, int32_t F, const Sampling* sm,
-              int32_t threads, int32_t* counts, int64_t* found, int32_t* idx);
+              int32_t threads, int32_t* counts, int64_t* found, int32_t* idx, const pat::Table* pt = nullptr);
 // what a device find call hands find_staged: the caller's sampling (or NULL) where the handle keeps the first paths, else `spread` = the same walks, seed and
 // draw with the cap mode of option "path_cap"
 static inline const Sampling* with_cap(const kprn_handle* h, const Sampling* sm, uint64_t seed, uint32_t draw, Sampling& spread) {
@@ -186,14 +231,17 @@ static inline const Sampling* with_cap(const kprn_handle* h, const Sampling* sm,
 }
 
 // ---- the sampled hops (path_walk.hip; include/kprn.h "sampled paths of four and five hops") ----
+// pt (or NULL = no patterns): the graph's table; a walk's paths are then those of its closes that match
 // per-walk path counts wc [B][2][walks] (slot 0 = 4 hops, 1 = 5 hops; 0 for a dead or dropped walk or a hop count hmask leaves out) and their sums wsum [B][2]
-void walk_count_launch(const Csr& g, const int32_t* d_pairs, int32_t B, int hmask, const Sampling& sm, int64_t* d_wc, int64_t* d_wsum, hipStream_t s);
+void walk_count_launch(const Csr& g, const int32_t* d_pairs, int32_t B, int hmask, const Sampling& sm, int64_t* d_wc, int64_t* d_wsum, hipStream_t s,
+                       const pat::Table* pt);
 // the kept sampled rows of every pair, ranks from tot[4 b + 3] (the pair's exhaustive paths) on; d_keep (or NULL = the first cnt[b] ranks): every pair's kept
 // ranks at its first row; flag as k_fill's
 void walk_fill_launch(const Csr& g, const Fmt& f, const int32_t* d_pairs, int32_t B, const Sampling& sm, const int64_t* d_tot, const int64_t* d_wc,
-                      const int64_t* d_first, const int32_t* d_cnt, const int64_t* d_keep, int32_t* idx, int32_t* d_flag, hipStream_t s);
+                      const int64_t* d_first, const int32_t* d_cnt, const int64_t* d_keep, int32_t* idx, int32_t* d_flag, hipStream_t s, const pat::Table* pt);
 // the same on the host for row b: wc [2][walks] -> the two sums in s2; the kept rows of rank base and above -> the rows written
-void host_walk_counts(const Csr& g, int u, int i, int b, int hmask, const Sampling& sm, int64_t* wc, int64_t* s2);
-int64_t host_walk_fill(const Csr& g, const Fmt& f, int u, int i, int b, const Sampling& sm, const int64_t* wc, int64_t base, const Keep& keep, int32_t* out);
+void host_walk_counts(const Csr& g, int u, int i, int b, int hmask, const Sampling& sm, int64_t* wc, int64_t* s2, const pat::Table* pt);
+int64_t host_walk_fill(const Csr& g, const Fmt& f, int u, int i, int b, const Sampling& sm, const int64_t* wc, int64_t base, const Keep& keep, int32_t* out,
+                       const pat::Table* pt);
 
 }  // namespace pf

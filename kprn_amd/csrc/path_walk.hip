@@ -19,6 +19,8 @@
 //                 closing adjacency 64 edges at a time, a wave prefix sum (shuffles) per chunk and the running rank carried along, until the walk's last kept
 //                 rank is behind it; no workgroup barrier in that loop.  A path goes to kept row j iff its rank is the pair's j-th kept rank; the rows placed
 //                 are summed and compared with the kept ranks at or above the exhaustive total (the finder's flag)
+// Meta-paths (PAT = true; path_pattern_dev.h): the walks are drawn as above, a walk's paths are its closes whose whole relation sequence matches a pattern, and
+// a live walk whose prefix no pattern admits counts 0 without walking its closes.
 // Control flow around every shuffle and barrier is wave- / workgroup-uniform: the loop bounds and branch conditions there are kernel arguments, values
 // every lane reads from the same address, or results of the cross-lane operations themselves.
 #include "path_find_dev.h"
@@ -49,15 +51,25 @@ __host__ __device__ static inline bool walk_prefix(const Csr& g, const Sampling&
   return true;
 }
 
-// the closing edges of the paths through edge e of the prefix's last node: their number, the first one in lo; none when col[e] is i or on the prefix
-__host__ __device__ static inline int close_range(const Csr& g, const int* n, int h, int i, int e, int& lo) {
+// the patterns of h hops that admit a walk's prefix relations r [h - 2]
+__host__ __device__ static inline uint32_t prefix_alive(const pat::Table& pt, const int* r, int h) {
+  uint32_t a = pt.len[h];
+  for (int k = 0; k <= h - 3; ++k) a = pat::step(pt, a, k, r[k]);
+  return a;
+}
+
+// the closing edges of the paths through edge e of the prefix's last node: their number, the range in [lo, hi); none when col[e] is i or on the prefix.
+// PAT: a0 = prefix_alive; alive = the patterns that also admit e -- none: no search is made -- and the number counts the admitted closes
+template <bool PAT>
+__host__ __device__ static inline int close_range(const Csr& g, const pat::Table& pt, uint32_t a0, const int* n, int h, int i, int e, int& lo, int& hi,
+                                                  uint32_t& alive) {
   const int m = g.col[e];
-  lo = 0;
+  lo = 0; hi = 0; alive = a0;
   if (m == i) return 0;
   for (int j = 0; j <= h - 2; ++j) if (m == n[j]) return 0;
-  int hi;
+  if (PAT) { alive = pat::step(pt, a0, h - 2, g.rel[e]); if (!alive) return 0; }
   edge_range(g, m, i, lo, hi);
-  return hi - lo;
+  return close_count<PAT>(g, pt, alive, h - 1, lo, hi);
 }
 
 // the row of the path prefix -> col[e] -> i over edges e and c
@@ -76,7 +88,8 @@ __device__ static inline int64_t wave_sum(int64_t v) {
   return v;
 }
 
-__global__ __launch_bounds__(TPB) void k_walk_count(Csr g, const int32_t* __restrict__ pairs, int hmask, Sampling sm, int64_t* __restrict__ wc,
+template <bool PAT>
+__global__ __launch_bounds__(TPB) void k_walk_count(Csr g, pat::Table pt, const int32_t* __restrict__ pairs, int hmask, Sampling sm, int64_t* __restrict__ wc,
                                                     int64_t* __restrict__ wsum) {
   __shared__ int32_t seq[2][MAX_WALKS][3];   // a walk's edges; [0] = -1: dead or dropped
   __shared__ int64_t sh[TPB];
@@ -106,11 +119,13 @@ __global__ __launch_bounds__(TPB) void k_walk_count(Csr g, const int32_t* __rest
     for (int w = wave; w < sm.walks; w += WAVES) {
       int64_t c = 0;
       if (asked && seq[s][w][0] >= 0) {   // (wave-uniform: one LDS word)
-        int n[4];
+        int n[4], r[3];
         n[0] = u;
-        for (int k = 0; k <= h - 3; ++k) n[k + 1] = g.col[seq[s][w][k]];
-        const int last = n[h - 2], end = g.rowptr[last + 1];
-        for (int e = g.rowptr[last] + lane; e < end; e += 64) { int lo; c += close_range(g, n, h, i, e, lo); }
+        for (int k = 0; k <= h - 3; ++k) { n[k + 1] = g.col[seq[s][w][k]]; if (PAT) r[k] = g.rel[seq[s][w][k]]; }
+        const uint32_t a0 = PAT ? prefix_alive(pt, r, h) : 0u;   // (wave-uniform: LDS words every lane reads)
+        uint32_t a;
+        const int last = n[h - 2], end = !PAT || a0 ? g.rowptr[last + 1] : 0;   // a prefix no pattern admits: its closes are not walked, the sum is 0
+        for (int e = g.rowptr[last] + lane; e < end; e += 64) { int lo, hi; c += close_range<PAT>(g, pt, a0, n, h, i, e, lo, hi, a); }
         c = wave_sum(c);
       }
       if (lane == 0) { wc[((int64_t)b * 2 + s) * sm.walks + w] = c; sum[s] += c; }
@@ -122,8 +137,8 @@ __global__ __launch_bounds__(TPB) void k_walk_count(Csr g, const int32_t* __rest
 
 // tot [b][3]: the pair's exhaustive paths = the rank of its first sampled path; first / cnt / ranks / flag as k_fill's.  nxt = the first kept row whose rank
 // is not behind the running rank (wave-uniform: every lane reads the same ranks); SPREAD as k_fill's
-template <bool SPREAD>
-__global__ __launch_bounds__(TPB) void k_walk_fill(Csr g, Fmt f, const int32_t* __restrict__ pairs, Sampling sm, const int64_t* __restrict__ tot,
+template <bool SPREAD, bool PAT>
+__global__ __launch_bounds__(TPB) void k_walk_fill(Csr g, pat::Table pt, Fmt f, const int32_t* __restrict__ pairs, Sampling sm, const int64_t* __restrict__ tot,
                                                    const int64_t* __restrict__ wc, const int64_t* __restrict__ first, const int32_t* __restrict__ cnt,
                                                    const int64_t* __restrict__ ranks, int32_t* __restrict__ idx, int32_t* flag) {
   __shared__ int64_t sh[TPB];
@@ -155,18 +170,20 @@ __global__ __launch_bounds__(TPB) void k_walk_fill(Csr g, Fmt f, const int32_t* 
     const int s = fl >= sm.walks ? 1 : 0, w = fl - s * sm.walks, h = 4 + s;
     int e[3], n[4], r[3];
     if (!walk_prefix(g, sm, u, i, b, w, h, e, n, r)) continue;   // (never: a dead walk's count is 0; the sum below would tell)
+    const uint32_t a0 = PAT ? prefix_alive(pt, r, h) : 0u;
+    uint32_t a = 0;
     const int last = n[h - 2], end = g.rowptr[last + 1];
     for (int e_base = g.rowptr[last]; e_base < end && nxt < cap && keep_rank(keep, nxt) < wend; e_base += 64) {
       const int e1 = e_base + lane;
-      int lo = 0;
-      const int c = e1 < end ? close_range(g, n, h, i, e1, lo) : 0;
+      int lo = 0, hi = 0;
+      const int c = e1 < end ? close_range<PAT>(g, pt, a0, n, h, i, e1, lo, hi, a) : 0;
       int incl = c;
       for (int d = 1; d < 64; d <<= 1) { const int t = __shfl_up(incl, d); if (lane >= d) incl += t; }
       const int chunk = __shfl(incl, 63);
       const int64_t r0 = run + incl - c;
       if (c && keep_rank(keep, nxt) < run + chunk)
         for (int64_t j = keep_lower(keep, r0, nxt); j < cap && keep_rank(keep, j) - r0 < c; ++j) {
-          walk_row(g, f, out + j * row, n, r, h, i, e1, lo + (int)(keep_rank(keep, j) - r0));
+          walk_row(g, f, out + j * row, n, r, h, i, e1, close_edge<PAT>(g, pt, a, h - 1, lo, hi, keep_rank(keep, j) - r0));
           ++placed;
         }
       run += chunk;
@@ -177,19 +194,24 @@ __global__ __launch_bounds__(TPB) void k_walk_fill(Csr g, Fmt f, const int32_t* 
   if (tid == 0 && placed != cap - row0) atomicOr(flag, 1);
 }
 
-void walk_count_launch(const Csr& g, const int32_t* d_pairs, int32_t B, int hmask, const Sampling& sm, int64_t* d_wc, int64_t* d_wsum, hipStream_t s) {
-  hipLaunchKernelGGL(k_walk_count, dim3((unsigned)B), dim3(TPB), 0, s, g, d_pairs, hmask, sm, d_wc, d_wsum);
+void walk_count_launch(const Csr& g, const int32_t* d_pairs, int32_t B, int hmask, const Sampling& sm, int64_t* d_wc, int64_t* d_wsum, hipStream_t s,
+                       const pat::Table* pt) {
+  const pat::Table none{nullptr, 0, {0, 0, 0, 0, 0, 0}};
+  hipLaunchKernelGGL(pt ? k_walk_count<true> : k_walk_count<false>, dim3((unsigned)B), dim3(TPB), 0, s, g, pt ? *pt : none, d_pairs, hmask, sm, d_wc, d_wsum);
   HIP_TRY(hipGetLastError());
 }
 
 void walk_fill_launch(const Csr& g, const Fmt& f, const int32_t* d_pairs, int32_t B, const Sampling& sm, const int64_t* d_tot, const int64_t* d_wc,
-                      const int64_t* d_first, const int32_t* d_cnt, const int64_t* d_keep, int32_t* idx, int32_t* d_flag, hipStream_t s) {
-  hipLaunchKernelGGL(d_keep ? k_walk_fill<true> : k_walk_fill<false>, dim3((unsigned)B), dim3(TPB), 0, s, g, f, d_pairs, sm, d_tot, d_wc, d_first, d_cnt, d_keep, idx, d_flag);
+                      const int64_t* d_first, const int32_t* d_cnt, const int64_t* d_keep, int32_t* idx, int32_t* d_flag, hipStream_t s, const pat::Table* pt) {
+  const pat::Table none{nullptr, 0, {0, 0, 0, 0, 0, 0}};
+  const auto kern = pt ? (d_keep ? k_walk_fill<true, true> : k_walk_fill<false, true>) : (d_keep ? k_walk_fill<true, false> : k_walk_fill<false, false>);
+  hipLaunchKernelGGL(kern, dim3((unsigned)B), dim3(TPB), 0, s, g, pt ? *pt : none, f, d_pairs, sm, d_tot, d_wc, d_first, d_cnt, d_keep, idx, d_flag);
   HIP_TRY(hipGetLastError());
 }
 
 // ---- host twin -------------------------------------------------------------------------------------------------------------------------------
-void host_walk_counts(const Csr& g, int u, int i, int b, int hmask, const Sampling& sm, int64_t* wc, int64_t* s2) {
+template <bool PAT>
+static void host_walk_counts_t(const Csr& g, const pat::Table& pt, int u, int i, int b, int hmask, const Sampling& sm, int64_t* wc, int64_t* s2) {
   std::vector<int> seq((size_t)3 * sm.walks);
   for (int s = 0; s < 2; ++s) {
     const int h = 4 + s;
@@ -206,13 +228,22 @@ void host_walk_counts(const Csr& g, int u, int i, int b, int hmask, const Sampli
       for (int v = 0; v < w && !dup; ++v) dup = std::equal(e, e + 3, &seq[(size_t)3 * v]);   // (a dropped walk equals a kept one before it)
       if (dup) continue;
       const int last = n[h - 2];
-      for (int e1 = g.rowptr[last]; e1 < g.rowptr[last + 1]; ++e1) { int lo; mine[w] += close_range(g, n, h, i, e1, lo); }
+      const uint32_t a0 = PAT ? prefix_alive(pt, r, h) : 0u;
+      uint32_t a;
+      for (int e1 = g.rowptr[last]; e1 < g.rowptr[last + 1]; ++e1) { int lo, hi; mine[w] += close_range<PAT>(g, pt, a0, n, h, i, e1, lo, hi, a); }
       s2[s] += mine[w];
     }
   }
 }
+void host_walk_counts(const Csr& g, int u, int i, int b, int hmask, const Sampling& sm, int64_t* wc, int64_t* s2, const pat::Table* pt) {
+  const pat::Table none{nullptr, 0, {0, 0, 0, 0, 0, 0}};
+  if (pt) host_walk_counts_t<true>(g, *pt, u, i, b, hmask, sm, wc, s2);
+  else host_walk_counts_t<false>(g, none, u, i, b, hmask, sm, wc, s2);
+}
 
-int64_t host_walk_fill(const Csr& g, const Fmt& f, int u, int i, int b, const Sampling& sm, const int64_t* wc, int64_t base, const Keep& keep, int32_t* out) {
+template <bool PAT>
+static int64_t host_walk_fill_t(const Csr& g, const pat::Table& pt, const Fmt& f, int u, int i, int b, const Sampling& sm, const int64_t* wc, int64_t base,
+                                const Keep& keep, int32_t* out) {
   const int64_t row = (int64_t)f.T * f.F, cap = keep.cap;
   int64_t run = base, placed = 0, j = keep_lower(keep, base);   // j: the next kept row
   for (int fl = 0; fl < 2 * sm.walks && j < cap; run += wc[fl], ++fl) {
@@ -221,15 +252,25 @@ int64_t host_walk_fill(const Csr& g, const Fmt& f, int u, int i, int b, const Sa
     int e[3], n[4], r[3];
     if (!walk_prefix(g, sm, u, i, b, w, h, e, n, r)) continue;
     const int last = n[h - 2];
+    const uint32_t a0 = PAT ? prefix_alive(pt, r, h) : 0u;
+    uint32_t a;
     int64_t r0 = run;
     for (int e1 = g.rowptr[last]; e1 < g.rowptr[last + 1] && j < cap; ++e1) {
-      int lo;
-      const int c = close_range(g, n, h, i, e1, lo);
-      for (; j < cap && keep_rank(keep, j) - r0 < c; ++j) { walk_row(g, f, out + j * row, n, r, h, i, e1, lo + (int)(keep_rank(keep, j) - r0)); ++placed; }
+      int lo, hi;
+      const int c = close_range<PAT>(g, pt, a0, n, h, i, e1, lo, hi, a);
+      for (; j < cap && keep_rank(keep, j) - r0 < c; ++j) {
+        walk_row(g, f, out + j * row, n, r, h, i, e1, close_edge<PAT>(g, pt, a, h - 1, lo, hi, keep_rank(keep, j) - r0));
+        ++placed;
+      }
       r0 += c;
     }
   }
   return placed;
+}
+int64_t host_walk_fill(const Csr& g, const Fmt& f, int u, int i, int b, const Sampling& sm, const int64_t* wc, int64_t base, const Keep& keep, int32_t* out,
+                       const pat::Table* pt) {
+  const pat::Table none{nullptr, 0, {0, 0, 0, 0, 0, 0}};
+  return pt ? host_walk_fill_t<true>(g, *pt, f, u, i, b, sm, wc, base, keep, out) : host_walk_fill_t<false>(g, none, f, u, i, b, sm, wc, base, keep, out);
 }
 
 }  // namespace pf

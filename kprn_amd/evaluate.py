@@ -8,6 +8,7 @@ Flags: those of `python -m kprn_amd.score` that shape and load the model (-model
   -holdout 0.2 [-holdout_seed 1]                        the share held out and the shuffle's seed: give what training was given
   -eval_users N  -max_candidates N                      the first N held-out users only; only each user's N strongest candidates by path count
   -min_hops / -max_hops / -max_paths / -walks / -sampleSeed   the finder's limits (1, 3, 28), as for python -m kprn_amd.recommend
+  -meta_paths FILE                                      only the paths whose relation sequence matches a pattern of FILE (graph.parse_meta_paths)
 Output: the two lines of eval_score.py (`hit scores`, `ndcg scores`, k = 1..15), then `samples \\t unreachable \\t zero`: the held pairs evaluated, those
 that never reached the ranking stage (misses), and the zero samples (misses)."""
 import argparse
@@ -32,6 +33,9 @@ def main(argv=None, out=sys.stdout):
     if (kg.Vt, kg.Ve, kg.Vr) != (params.entityTypeVocabSize, params.entityVocabSize, params.relationVocabSize):
         sys.exit("the vocabularies hold %d types, %d entities, %d relations; the model flags say %d, %d, %d"
                  % (kg.Vt, kg.Ve, kg.Vr, params.entityTypeVocabSize, params.entityVocabSize, params.relationVocabSize))
+    if params.meta_paths:
+        with open(params.meta_paths) as f:
+            kg.patterns = graph.parse_meta_paths(f, kg)
     train_kg, held = kg.holdout(params.interaction_rel, 1.0 - params.holdout, params.holdout_seed)
     if len(held) == 0:
         sys.exit("nothing was held out: relation %s has too few edges for -holdout %g" % (params.interaction_rel, params.holdout))

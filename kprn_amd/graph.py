@@ -20,12 +20,13 @@ from .pathformat import PathFormatter
 class KnowledgeGraph:
     """src / dst / rel [E] (1-based ids), node_types [Ve, num_types] (row e - 1 = entity e), end_relation, the table sizes Ve / Vr / Vt."""
 
-    def __init__(self, src, dst, rel, node_types, end_relation, Vr, Vt, vocabs=None):
+    def __init__(self, src, dst, rel, node_types, end_relation, Vr, Vt, vocabs=None, patterns=None):
         self.src, self.dst, self.rel = (np.ascontiguousarray(a, np.int32) for a in (src, dst, rel))
         self.node_types = np.ascontiguousarray(node_types, np.int32)
         self.Ve, self.num_types = (int(x) for x in self.node_types.shape)
         self.Vr, self.Vt, self.end_relation = int(Vr), int(Vt), int(end_relation)
         self.vocabs = vocabs
+        self.patterns = patterns   # meta-paths (include/kprn.h "meta-paths"): the form of _ffi.Graph.set_patterns; None = every path; set it before .on(eng)
         self._names = None
         self._device = {}   # id(engine) -> _ffi.Graph
 
@@ -75,6 +76,10 @@ class KnowledgeGraph:
         g = self._device.get(id(eng))
         if g is None or not g.ptr:
             g = self._device[id(eng)] = eng.graph(self.src, self.dst, self.rel, self.node_types, self.end_relation)
+            g._patterns = None
+        if g._patterns is not self.patterns:   # (the attribute was set or replaced since: the device graph follows)
+            g.set_patterns(self.patterns)
+            g._patterns = self.patterns
         return g
 
     def relation_id(self, relation_name):
@@ -113,12 +118,16 @@ class KnowledgeGraph:
         code = lambda a, b: a.astype(np.int64) * (self.Ve + 1) + b.astype(np.int64)
         gone = code(held[:, 0], held[:, 1])
         keep = ~(np.isin(code(self.src, self.dst), gone) | np.isin(code(self.dst, self.src), gone))
-        train = KnowledgeGraph(self.src[keep], self.dst[keep], self.rel[keep], self.node_types, self.end_relation, self.Vr, self.Vt, self.vocabs)
+        train = KnowledgeGraph(self.src[keep], self.dst[keep], self.rel[keep], self.node_types, self.end_relation, self.Vr, self.Vt, self.vocabs,
+                               self.patterns)
         return train, held
 
     def host_find_paths(self, pairs, min_hops, max_hops, max_paths, T, F=None, threads=1, want_idx=True, walks=0, seed=0, draw=0, cap="first"):
         """walks > 0: the hops past 3 sampled (_ffi.host_find_paths_sampled); cap = "spread": the cap keeps a spread of a pair's paths under (seed, draw)
-        (_ffi.host_find_paths_cap)"""
+        (_ffi.host_find_paths_cap); with `patterns` set, only the matching paths (_ffi.host_find_paths_patterns)"""
+        if self.patterns:
+            return _ffi.host_find_paths_patterns(self.src, self.dst, self.rel, self.node_types, self.Vr, self.Vt, self.end_relation, pairs, min_hops, max_hops,
+                                                 max_paths, T, walks, seed, draw, cap=cap, patterns=self.patterns, F=F, threads=threads, want_idx=want_idx)
         if cap != "first":
             return _ffi.host_find_paths_cap(self.src, self.dst, self.rel, self.node_types, self.Vr, self.Vt, self.end_relation, pairs, min_hops, max_hops,
                                             max_paths, T, walks, seed, draw, cap=cap, F=F, threads=threads, want_idx=want_idx)
@@ -127,6 +136,38 @@ class KnowledgeGraph:
                                                 max_paths, T, walks, seed, draw, F=F, threads=threads, want_idx=want_idx)
         return _ffi.host_find_paths(self.src, self.dst, self.rel, self.node_types, self.Vr, self.Vt, self.end_relation, pairs, min_hops, max_hops, max_paths,
                                     T, F=F, threads=threads, want_idx=want_idx)
+
+
+def parse_meta_paths(lines, kg):
+    """The text form of a pattern set (include/kprn.h "meta-paths") -> the list KnowledgeGraph.patterns takes.  One pattern per line; positions separated by
+    whitespace; a position is `*` (any relation) or relation names joined by `|`, as spelt in kg's relation vocabulary; `#` starts a comment, blank lines are
+    skipped.  An unknown relation name, a line of more than 5 positions or more than 32 patterns raises ValueError naming the line."""
+    patterns = []
+    for no, line in enumerate(lines, 1):
+        words = line.split("#", 1)[0].split()
+        if not words:
+            continue
+        if len(words) > _ffi.PATTERN_MAX_HOPS:
+            raise ValueError("meta-paths line %d: %d positions, at most %d" % (no, len(words), _ffi.PATTERN_MAX_HOPS))
+        if len(patterns) == _ffi.PATTERN_MAX:
+            raise ValueError("meta-paths line %d: more than %d patterns" % (no, _ffi.PATTERN_MAX))
+        pat = []
+        for w in words:
+            if w == "*":
+                pat.append(None)
+                continue
+            try:
+                pat.append(sorted({kg.relation_id(name) for name in w.split("|")}))
+            except ValueError as e:
+                raise ValueError("meta-paths line %d: %s" % (no, e)) from None
+        patterns.append(pat)
+    return patterns
+
+
+def format_meta_paths(patterns, kg):
+    """parse_meta_paths backwards: the lines of a pattern set"""
+    names = {int(i) + 1: n for n, i in kg.vocabs.relation.items()}
+    return [" ".join("*" if not pos else "|".join(names[int(r)] for r in pos) for pos in pat) for pat in patterns]
 
 
 def read_triples(path):

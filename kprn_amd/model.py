@@ -68,6 +68,8 @@ def flag_parser():
     a("-holdout_seed", type=int, default=1, help="seed of the split's shuffle")
     a("-eval_users", type=int, default=0, help="evaluate the first N held-out users only (0 = all)")
     a("-max_candidates", type=int, default=0, help="evaluation ranks among each user's N strongest candidates by path count only (0 = all of them)")
+    a("-meta_paths", default="", help="with -kg: a file of relation-sequence patterns, one per line (graph.parse_meta_paths: positions separated by blanks, "
+      "a position `*` or relation names joined by `|`); only the paths that match one are found, as candidates, for training and for evaluation")
     return p
 
 
@@ -96,6 +98,8 @@ def parse_flags(argv=None):
         p.error("-neg_pool needs -kg: the pool it selects from (a positive's sampled negatives) exists only when training from a graph")
     if params.neg_pool != 0 and not params.negatives <= params.neg_pool <= _ffi.SELECT_MAX_KEEP:
         p.error("-neg_pool must be 0 or in -negatives .. %d (the pool holds at least the negatives kept), got %d" % (_ffi.SELECT_MAX_KEEP, params.neg_pool))
+    if params.meta_paths and not params.kg:
+        p.error("-meta_paths needs -kg: the patterns select among the paths found in a graph")
     if not 0.0 <= params.holdout < 1.0:
         p.error("-holdout must be in 0 .. 1 (the share of the interactions held out)")
     if params.holdout > 0 and not params.kg:

@@ -12,6 +12,8 @@ model flag -K here, because -k is the number of items to return), plus
   -k K                 items to return;  -explain_paths M  strongest paths printed per item
   -min_hops / -max_hops / -max_paths   the finder's limits (1, 3, 28)
   -walks N [-sampleSeed 1]             -max_hops 4 or 5: the paths of more than 3 hops are sampled, N walks (1..256) per item and hop count
+  -meta_paths FILE                     only the paths whose relation sequence matches a pattern of FILE count: one pattern per line, positions separated
+                       by blanks, a position `*` or relation names joined by `|` (graph.parse_meta_paths; include/kprn.h "meta-paths")
 Output, tab separated: one line `rank, item, %.5f score, paths kept, paths found` per item, then one line `rank, place, %.5f weight, %.6g score, path`
 per explained path (the path as scoring.format_path prints it)."""
 import argparse
@@ -33,6 +35,7 @@ def main(argv=None, out=sys.stdout):
     p.add_argument("-walks", type=int, default=0)
     p.add_argument("-interaction_rel", default=""); p.add_argument("-seen", type=int, default=0, choices=(0, 1))
     p.add_argument("-max_candidates", type=int, default=0)
+    p.add_argument("-meta_paths", default="")
     args, rest = p.parse_known_args(argv)
     model.check_walks(args.max_hops, args.walks, p.error)
     if args.max_candidates and args.items:
@@ -51,6 +54,9 @@ def main(argv=None, out=sys.stdout):
     if (kg.Vt, kg.Ve, kg.Vr) != (params.entityTypeVocabSize, params.entityVocabSize, params.relationVocabSize):
         sys.exit("the vocabularies hold %d types, %d entities, %d relations; the model flags say %d, %d, %d"
                  % (kg.Vt, kg.Ve, kg.Vr, params.entityTypeVocabSize, params.entityVocabSize, params.relationVocabSize))
+    if args.meta_paths:
+        with open(args.meta_paths) as f:
+            kg.patterns = graph.parse_meta_paths(f, kg)
     items, catalogue = None, None
     if args.items:
         with open(args.items) as f:

@@ -14,6 +14,8 @@ and keeps the -negatives that score highest, their rows taken from the scored ba
 -holdout 0.2 [-holdout_seed 1 -eval_users 0 -max_candidates N] (with -kg) holds that share of the interactions out (KnowledgeGraph.holdout), trains on the
 rest -- positives, catalogue, weights and paths are the train graph's -- and every -evaluationFrequency epochs ranks the held pairs among everything
 their users reach (graph.evaluate_from_graph): the evaluation line of -rank_samples, plus the held pairs that never reached the ranking stage.
+-meta_paths FILE (with -kg) keeps only the paths whose relation sequence matches a pattern of FILE (graph.parse_meta_paths; include/kprn.h "meta-paths"), in
+training and in the -holdout evaluation.
 """
 import os
 import sys
@@ -73,6 +75,9 @@ def train_from_kg(params, eng, callbacks):
     from . import graph
     from .pathformat import Vocabs
     kg = graph.KnowledgeGraph.from_triples(graph.read_triples(params.kg), Vocabs(params.vocab_dir), params.numEntityTypes)
+    if params.meta_paths:   # (the split below hands the set to the train graph)
+        with open(params.meta_paths) as f:
+            kg.patterns = graph.parse_meta_paths(f, kg)
     held = None
     if params.holdout > 0:   # everything below -- positives, catalogue, weights, paths -- is the train graph's
         kg, held = kg.holdout(params.interaction_rel, 1.0 - params.holdout, params.holdout_seed)
