@@ -238,6 +238,9 @@ int kprn_forward_batch_async(kprn_handle* h, const kprn_batch* b, int32_t class_
  * collective has compute to hide under while most of the pass shared the chip with the training forward).  Whatever waits for the pass
  * (the optimiser step, kprn_read_probs) places a forgotten second part itself. */
 int kprn_forward_batch_async_rest(kprn_handle* h);
+/* the selected class's probabilities of the most recent scoring pass, probs [B] with B at most that pass's pairs.  A pass queued by
+ * kprn_forward_batch_async stays that pass across training steps made before it is read (beside it, or carrying it: "score_dual"), with its own
+ * pair count, whatever the training batch's; the next kprn_forward_batch_async replaces it. */
 int kprn_read_probs(kprn_handle* h, float* probs, int32_t B);
 /* embedding sub-net output x[N,T,D] (FeatureEmbedding.lua:112-121), for bit-exact checks */
 int kprn_embed(kprn_handle* h, const int32_t* idx, int64_t N, int32_t T, int32_t F, float* x);

@@ -244,7 +244,9 @@ void forward_impl(kprn_handle* h, const kprn_batch* b, int class_id, bool save_f
     generic::forward(h, b, save_for_backward);
   }
   if (do_pool) pool_stage(h, b, class_id - 1, every_class);
-  h->last_B = b->B;
+  // a training forward beside (or carrying) a queued scoring pass leaves that pass the one kprn_read_probs / kprn_board_put hand out: its pair count stays
+  // (a pass of MORE pairs than the training batch could not be read otherwise)
+  if (!(save_for_backward && h->last_forward_side)) h->last_B = b->B;
 }
 
 static void dp_release(kprn_handle* h);
