@@ -87,6 +87,7 @@ int kprn_host_rank_targets(const float*, int64_t, const int64_t*, const int64_t*
 int kprn_explain_batch(kprn_handle*, const kprn_batch*, int32_t, const int32_t*, int32_t, int32_t, int32_t*, float*, float*, float*, float*);
 int kprn_recommend_explain_ragged(kprn_handle*, const int32_t*, const int32_t*, int32_t, int64_t, int32_t, int32_t, int32_t, const int32_t*, int32_t, int32_t, int32_t, int32_t, int32_t*, float*, int32_t*, float*, float*, float*);
 int kprn_host_explain(const float*, const int32_t*, int32_t, int32_t, int32_t, int32_t, int32_t, const int32_t*, int32_t, int32_t, int32_t*, float*, float*, float*, float*);
+int kprn_host_explain_gamma(const float*, const int32_t*, int32_t, int32_t, int32_t, int32_t, int32_t, const int32_t*, int32_t, int32_t, int32_t*, float*, float*, float*, float*, float);
 int kprn_host_dropout_keep(uint64_t, unsigned int, int32_t, int32_t, int64_t, int32_t, float, unsigned char*);
 /* pairwise loss: a batch's group table and the rule on the host cores (include/kprn.h "pairwise loss"; kprn_set_option "loss" "bpr") */
 int kprn_batch_set_groups(kprn_handle*, kprn_batch*, const int32_t*, int32_t, int64_t*);

@@ -327,10 +327,11 @@ int kprn_host_rank_targets(const float* scores, int64_t n_scores, const int64_t*
 
 /* ---- explaining a recommendation (an extension: the paper's pooling layer read backwards) ----
  * Which paths put a pair where it is: the M strongest paths behind the pair's pooled score in the selected class, each with the share it takes of that
- * score, w_q = d pooled / d s_q (the factor the loss stage multiplies dy by).  For a pair whose cnt paths have the fp32 scores s_0 .. s_{cnt-1}:
+ * score (for LogSumExp at the default "pool_gamma" that is d pooled / d s_q, the factor the loss stage multiplies dy by; under a temperature see
+ * "pooling temperature" below, rule 4).  For a pair whose cnt paths have the fp32 scores s_0 .. s_{cnt-1}:
  *  - order: score descending, then path index ascending among equal scores (plain fp32 > / ==, so -0 and +0 tie; the reducers' own tie rule); a NaN
  *    score sorts after every number, lower index first.
- *  - weight: LogSumExp: expf(s_q - m) / sum_p expf(s_p - m), m = the maximum; Max: 1 for the first place, 0 elsewhere; TopK + Mean: 1 / kk for the
+ *  - weight: LogSumExp: expf((s_q - m) ig) / sum_p expf((s_p - m) ig), m = the maximum, ig = 1 unless "pool_gamma" is set; Max: 1 for the first place, 0 elsewhere; TopK + Mean: 1 / kk for the
  *    first kk = min(K, cnt) places, 0 elsewhere.
  *  - per explained pair, 1 <= M <= KPRN_EXPLAIN_MAX_M: path_idx [M] (index within the pair, 0-based; -1 where cnt < M), path_score [M] (the raw fp32
  *    score; 0.0f in empty places), path_weight [M] (0.0f in empty places), pooled (the reducer's output) and prob = sigmoid(pooled): the bits a scoring
@@ -354,6 +355,32 @@ int kprn_recommend_explain_ragged(kprn_handle* h, const int32_t* idx, const int3
 int kprn_host_explain(const float* path_scores, const int32_t* offsets /* [B+1] */, int32_t B, int32_t C, int32_t class_id, int32_t reducer,
                       int32_t K_reducer, const int32_t* pairs, int32_t n_pairs, int32_t M, int32_t* path_idx, float* path_score, float* path_weight,
                       float* pooled, float* probs);
+
+/* ---- pooling temperature (an extension of module/LogSumExp.lua: the gamma of the paper's weighted pooling layer, g = log sum_k exp(s_k / gamma)) ----
+ * kprn_set_option(h, "pool_gamma", "<decimal>") on a handle whose reducer is 2 (LogSumExp); default "1", the reference's layer.  A small gamma moves the
+ * layer towards max pooling, a large one towards mean pooling (plus log cnt), and it decides how peaked the shares are that an explanation reports.
+ * ig = (float)(1.0 / (double)gamma) is formed once on the host and handed to every kernel.  For a pair with the fp32 scores s_0 .. s_{cnt-1} in the
+ * selected class, m their maximum:
+ *  1. t_q = (s_q - m) * ig;  sum = sum_q expf(t_q), in the order the thread / wave form adds without the option;  pooled = logf(sum) + m * ig, with m * ig
+ *     rounded on its own (no fused multiply-add);  prob = sigmoid(pooled).  No factor gamma stands outside the logarithm: the paper's form.
+ *  2. At ig == 1.0f every product above is exact and expf / logf are the library's: the results are bit for bit those of a handle that never saw the
+ *     option.  At any other ig the exponential and the logarithm above (and the sigmoid's) are the engine's own plain-fp32 functions (csrc/reduce_dev.h
+ *     exp_shared / log_shared, about 1 and 2 units in the last place), the same code in the kernels and in kprn_host_explain_gamma -- which is why that
+ *     call returns the kernels' bits, where two libraries' expf would differ in the last places.
+ *  3. Backward: d loss / d s_q = expf(t_q) / sum * (dy * ig), dy = d loss / d pooled scaled once per pair -- under "loss" "bce" (both forms of the
+ *     criterion's gradient) and "bpr" alike.
+ *  4. Explanation: path_weight_q = expf(t_q) / sum, the path's NORMALISED SHARE; the shares of a pair add up to 1.  It is not d pooled / d s_q, which is
+ *     the share times ig and adds up to 1 / gamma.  Order, tie rule, path_score (the raw s_q), pooled and prob are as above.
+ *  5. Max and TopK + Mean are unchanged and never see ig.
+ * A scoring pass that rides in a training launch ("score_dual") pools under the value of that training call.  kprn_save writes gamma's float bits into
+ * header word 14 when gamma != 1 and 0 otherwise (the files of before, byte for byte); kprn_load on a reducer-2 handle adopts a non-zero word 14 as the
+ * handle's "pool_gamma", a zero word leaves the option alone.  The Torch7 container carries no gamma.
+ * kprn_host_explain_gamma: kprn_host_explain under a temperature -- the bit-exact host statement of 1 and 4 -- with that call's refusals and the option's:
+ * gamma not finite or outside [1e-3, 1e3] is KPRN_E_ARG, gamma != 1 with reducer 0 or 1 KPRN_E_UNSUPPORTED; a refused call writes nothing.
+ * kprn_host_explain is this call at gamma = 1.                                                                                               */
+int kprn_host_explain_gamma(const float* path_scores, const int32_t* offsets /* [B+1] */, int32_t B, int32_t C, int32_t class_id, int32_t reducer,
+                            int32_t K_reducer, const int32_t* pairs, int32_t n_pairs, int32_t M, int32_t* path_idx, float* path_score,
+                            float* path_weight, float* pooled, float* probs, float gamma);
 
 /* ---- finding a pair's paths (an extension: the reference mines paths offline, data_prepare/path_find_depth_3.py, by random walks) ----
  * From a knowledge graph to a ragged batch on the device: the graph lives in HBM as CSR, and kprn_find_paths enumerates -- exhaustively and
@@ -873,6 +900,10 @@ int kprn_profile_get(kprn_handle* h, kprn_prof_entry* out, int32_t cap, int32_t*
  *   "path_cap"        "first" (default) | "spread": which of a pair's paths a find call keeps when more exist than max_paths -- the first ones in the pair's
  *                     order | one drawn in each of max_paths strata of that order ("finding a pair's paths", cap mode).  Read by every find call that has a
  *                     seed and a draw; kprn_find_paths has none and always keeps the first.  With "first" nothing changes.  Any other value: KPRN_E_ARG
+ *   "pool_gamma"      "1" (default) | a decimal temperature in [1e-3, 1e3] (the syntax of "dropout"): the gamma of the paper's pooling layer
+ *                     log sum_k exp(s_k / gamma) on a LogSumExp handle (see "pooling temperature").  Read at every scoring, explaining and training call.
+ *                     Not such a number, not finite or outside the range: KPRN_E_ARG.  A value other than 1 on a handle whose reducer is not 2 (LogSumExp):
+ *                     KPRN_E_UNSUPPORTED -- Max and TopK + Mean have no temperature.  A refused call leaves the previous value.  With "1" nothing changes
  *   "dropout_seed"    decimal or 0x hex uint64 (default: kprn_config.seed + rank, so data-parallel replicas draw different masks): the generator's seed;
  *                     setting it restarts the draw count at 0
  *   (also: "small_tiles", "score_split", "loss_accumulate", "feed_build" / "feed_threads" / "feed_workers", "dp_comm_stream",

@@ -212,9 +212,10 @@ def _explain_out(shape, M, out, scalars=True):
     return res
 
 
-def host_explain(path_scores, offsets, class_id, reducer, K_reducer, M, pairs=None, out=None):
-    """kprn_host_explain (no handle, no GPU): the explanation rule of include/kprn.h over a host score matrix path_scores [N,C]; pair b owns the rows
-    offsets[b] .. offsets[b+1]-1; pairs None = every pair -> dict(path_idx / path_score / path_weight [n,M], pooled / probs [n])"""
+def host_explain(path_scores, offsets, class_id, reducer, K_reducer, M, pairs=None, out=None, gamma=1.0):
+    """kprn_host_explain_gamma (no handle, no GPU): the explanation rule of include/kprn.h over a host score matrix path_scores [N,C]; pair b owns the rows
+    offsets[b] .. offsets[b+1]-1; pairs None = every pair -> dict(path_idx / path_score / path_weight [n,M], pooled / probs [n]).  gamma: the pooling
+    temperature (include/kprn.h "pooling temperature"); 1.0 is kprn_host_explain"""
     sc = np.ascontiguousarray(path_scores, np.float32)
     off = np.ascontiguousarray(offsets, np.int32)
     if sc.ndim != 2 or off.ndim != 1 or off.shape[0] < 2 or int(off[-1]) > sc.shape[0]:
@@ -223,10 +224,11 @@ def host_explain(path_scores, offsets, class_id, reducer, K_reducer, M, pairs=No
     pr = None if pairs is None else np.ascontiguousarray(pairs, np.int32).reshape(-1)
     n = B if pr is None else int(pr.shape[0])
     res = _explain_out((n,), M, out)
-    rc = lib().kprn_host_explain(_fp(sc), _fp(off), B, int(sc.shape[1]), int(class_id), int(reducer), int(K_reducer), _fp(pr), n, int(M),
-                                 _fp(res["path_idx"]), _fp(res["path_score"]), _fp(res["path_weight"]), _fp(res["pooled"]), _fp(res["probs"]))
+    rc = lib().kprn_host_explain_gamma(_fp(sc), _fp(off), B, int(sc.shape[1]), int(class_id), int(reducer), int(K_reducer), _fp(pr), n, int(M),
+                                       _fp(res["path_idx"]), _fp(res["path_score"]), _fp(res["path_weight"]), _fp(res["pooled"]), _fp(res["probs"]),
+                                       C.c_float(float(gamma)))
     if rc != 0:
-        raise KprnError(rc, "kprn_host_explain: bad offsets / class_id / reducer / pairs / M")
+        raise KprnError(rc, "kprn_host_explain_gamma: bad offsets / class_id / reducer / pairs / M / gamma")
     return res
 
 

@@ -1,11 +1,12 @@
 // Explanation stage (include/kprn.h "explaining a recommendation"): the M strongest paths behind a pair's pooled score, each with the share it takes of that
-// score: w_q = d pooled / d s_q, the factor bce_pair (kernels_basic.hip) multiplies dy by.  Forward only; reads column cid of the mapper output S [N][C] in
+// score: the path's normalised share of the pooled value (for LogSumExp at pooling temperature 1 that is d pooled / d s_q, the factor the loss stage multiplies
+// dy by; under a temperature gamma the derivative is the share / gamma and the share is what is reported).  Forward only; reads column cid of the mapper output S [N][C] in
 // place (stride C), writes no float atomics, uses no LDS.
 //
 // One definition of the rule serves the kernels and the host twin (namespace ex, __host__ __device__):
 //   order   score descending, then path index ascending among equal scores (plain fp32 > / ==; -0 == +0); a NaN sorts after every number, lower index
 //           first.  Found by repeated selection with an exclusion bound (the last selected (score, index)), as reduce_col's TopK branch does.
-//   weight  LogSumExp: expf(s_q - m) / sum_p expf(s_p - m);  Max: 1 at place 0;  TopK + Mean: 1 / kk at the places < kk = min(K, cnt)
+//   weight  LogSumExp: expf((s_q - m) ig) / sum_p expf((s_p - m) ig), ig = 1 / gamma (option "pool_gamma"; reduce_dev.h lse_term);  Max: 1 at place 0;  TopK + Mean: 1 / kk at the places < kk = min(K, cnt)
 // Two forms, as for the ragged reducer (kernels_basic.hip):
 //   k_explain_thread  one thread per explained pair; every pair of the batch has at most RAGGED_THREAD_MAX paths.  m and the sum are formed in reduce_col's order.
 //   k_explain_wave    one 64-lane wave per explained pair, four to a workgroup.  A pair of at most RAGGED_THREAD_MAX paths is still done by one lane in the
@@ -41,23 +42,23 @@ __host__ __device__ static inline void next_best(const float* __restrict__ s, in
     if (after(v, p, lv, li) && before(v, p, best, bi)) { best = v; bi = p; }
   }
 }
-__host__ __device__ static inline float place_weight(int reducer, int kk, int place, float v, float m, float sum) {
-  if (reducer == 2) return expf(v - m) / sum;
+__host__ __device__ static inline float place_weight(int reducer, int kk, int place, float v, float m, float sum, float ig) {
+  if (reducer == 2) return lse_term(v, m, ig) / sum;
   if (reducer == 0) return place == 0 ? 1.f : 0.f;
   return place < kk ? 1.f / (float)kk : 0.f;
 }
 __host__ __device__ static inline void empty_place(int32_t* idx, float* score, float* weight, int r) { idx[r] = -1; score[r] = 0.f; weight[r] = 0.f; }
 
 // m and sum of the LogSumExp weights in reduce_col's order (cnt <= RAGGED_THREAD_MAX on the device)
-__host__ __device__ static inline void lse_serial(const float* __restrict__ s, int cnt, int C, float& m, float& sum) {
+__host__ __device__ static inline void lse_serial(const float* __restrict__ s, int cnt, int C, float ig, float& m, float& sum) {
   m = s[0];
   for (int p = 1; p < cnt; ++p) m = fmaxf(m, s[(int64_t)p * C]);
   sum = 0.f;
-  for (int p = 0; p < cnt; ++p) sum += expf(s[(int64_t)p * C] - m);
+  for (int p = 0; p < cnt; ++p) sum += lse_term(s[(int64_t)p * C], m, ig);
 }
 // the M places of one pair by one thread (m, sum: LogSumExp only)
-__host__ __device__ static inline void places_serial(const float* __restrict__ s, int cnt, int C, int reducer, int K, int M, float m, float sum, int32_t* idx,
-                                                     float* score, float* weight) {
+__host__ __device__ static inline void places_serial(const float* __restrict__ s, int cnt, int C, int reducer, int K, int M, float m, float sum, float ig,
+                                                     int32_t* idx, float* score, float* weight) {
   const int kk = K < cnt ? K : cnt;
   float lv = INFINITY;
   int li = -1;
@@ -65,7 +66,7 @@ __host__ __device__ static inline void places_serial(const float* __restrict__ s
     if (r >= cnt) { empty_place(idx, score, weight, r); continue; }
     float best; int bi;
     next_best(s, cnt, C, 0, 1, lv, li, best, bi);
-    idx[r] = bi; score[r] = best; weight[r] = place_weight(reducer, kk, r, best, m, sum);
+    idx[r] = bi; score[r] = best; weight[r] = place_weight(reducer, kk, r, best, m, sum, ig);
     lv = best; li = bi;
   }
 }
@@ -77,13 +78,13 @@ __device__ static inline int pair_of(const Args& a, int64_t i) {
 }
 __device__ static inline void emit_pooled(const Args& a, int64_t i, float y) {
   if (a.pooled) a.pooled[i] = y;
-  if (a.prob) a.prob[i] = sigmoidf_(y);
+  if (a.prob) a.prob[i] = pool_sigmoid_of(y, a.ig);
 }
 __device__ static inline void pair_serial(const Args& a, int64_t i, const float* __restrict__ s, int cnt) {
   float m = 0.f, sum = 1.f;
-  if (a.reducer == 2) lse_serial(s, cnt, a.C, m, sum);
-  places_serial(s, cnt, a.C, a.reducer, a.K, a.M, m, sum, a.idx + i * a.M, a.score + i * a.M, a.weight + i * a.M);
-  if (a.pooled || a.prob) emit_pooled(a, i, reduce_col(s, cnt, a.C, a.reducer, a.K));
+  if (a.reducer == 2) lse_serial(s, cnt, a.C, a.ig, m, sum);
+  places_serial(s, cnt, a.C, a.reducer, a.K, a.M, m, sum, a.ig, a.idx + i * a.M, a.score + i * a.M, a.weight + i * a.M);
+  if (a.pooled || a.prob) emit_pooled(a, i, reduce_col(s, cnt, a.C, a.reducer, a.K, a.ig));
 }
 
 __global__ __launch_bounds__(256) void k_explain_thread(Args a) {
@@ -134,7 +135,7 @@ __global__ __launch_bounds__(256) void k_explain_wave(Args a) {
     for (int p = lane; p < cnt; p += 64) m = fmaxf(m, s[(int64_t)p * C]);
     m = wave_all_max(m);
     sum = 0.f;
-    for (int p = lane; p < cnt; p += 64) sum += expf(s[(int64_t)p * C] - m);
+    for (int p = lane; p < cnt; p += 64) sum += lse_term(s[(int64_t)p * C], m, a.ig);
     sum = wave_all_sum(sum);
   }
   const int kk = a.K < cnt ? a.K : cnt;
@@ -148,11 +149,11 @@ __global__ __launch_bounds__(256) void k_explain_wave(Args a) {
     float best; int bi;
     next_best(s, cnt, C, lane, 64, lv, li, best, bi);
     wave_best(best, bi);
-    if (lane == 0) { idx[r] = bi; score[r] = best; weight[r] = place_weight(a.reducer, kk, r, best, m, sum); }
+    if (lane == 0) { idx[r] = bi; score[r] = best; weight[r] = place_weight(a.reducer, kk, r, best, m, sum, a.ig); }
     lv = best; li = bi;
   }
   if (a.pooled || a.prob) {   // (a rectangular batch pools every pair in reduce_col's order, whatever its P: k_pool<false, ..>)
-    const float y = a.seg_wave ? reduce_col_wave(s, cnt, C, a.reducer, a.K, lane) : reduce_col(s, cnt, C, a.reducer, a.K);
+    const float y = a.seg_wave ? reduce_col_wave(s, cnt, C, a.reducer, a.K, a.ig, lane) : reduce_col(s, cnt, C, a.reducer, a.K, a.ig);
     if (lane == 0) emit_pooled(a, i, y);
   }
 }
@@ -176,12 +177,17 @@ void launch(hipStream_t s, const Args& a, int max_cnt) {
 }  // namespace ex
 
 // The host twin.  A pair of more than RAGGED_THREAD_MAX paths sums its exponentials the way the wave does (64 strided partial sums, then the butterfly's
-// tree), so that the same error bound holds for both; the selection is the shared rule.
-extern "C" int kprn_host_explain(const float* path_scores, const int32_t* offsets, int32_t B, int32_t C, int32_t class_id, int32_t reducer, int32_t K_reducer,
-                                 const int32_t* pairs, int32_t n_pairs, int32_t M, int32_t* path_idx, float* path_score, float* path_weight, float* pooled,
-                                 float* probs) {
+// tree), so that the same error bound holds for both; the selection is the shared rule.  gamma: the pooling temperature with the refusals of option
+// "pool_gamma" (include/kprn.h "pooling temperature"); the exponents and the pooled value are formed by reduce_dev.h's lse_term / lse_finish / pool_sigmoid_of, as on the
+// device: under a temperature their exp and log are exp_shared / log_shared, plain fp32 arithmetic that gives the kernels' bits on the host.
+extern "C" int kprn_host_explain_gamma(const float* path_scores, const int32_t* offsets, int32_t B, int32_t C, int32_t class_id, int32_t reducer,
+                                       int32_t K_reducer, const int32_t* pairs, int32_t n_pairs, int32_t M, int32_t* path_idx, float* path_score,
+                                       float* path_weight, float* pooled, float* probs, float gamma) {
   if (!path_scores || !offsets || !path_idx || !path_score || !path_weight) return KPRN_E_ARG;
   if (C < 1 || class_id < 1 || class_id > C || reducer < 0 || reducer > 2 || (reducer == 1 && K_reducer < 1)) return KPRN_E_ARG;
+  if (!kk::pool_gamma_ok((double)gamma)) return KPRN_E_ARG;
+  if (gamma != 1.0f && reducer != 2) return KPRN_E_UNSUPPORTED;
+  const float ig = kk::pool_ig_of(gamma);
   const int rc = ex::validate(B, pairs, n_pairs, M, nullptr);
   if (rc != KPRN_OK) return rc;
   if (offsets[0] < 0) return KPRN_E_ARG;
@@ -195,14 +201,14 @@ extern "C" int kprn_host_explain(const float* path_scores, const int32_t* offset
     const float* s = path_scores + (int64_t)offsets[b] * C + (class_id - 1);
     float m = 0.f, sum = 1.f;
     if (reducer == 2) {
-      if (cnt <= kk::RAGGED_THREAD_MAX) ex::lse_serial(s, cnt, C, m, sum);
+      if (cnt <= kk::RAGGED_THREAD_MAX) ex::lse_serial(s, cnt, C, ig, m, sum);
       else {
         m = -INFINITY;
         for (int p = 0; p < cnt; ++p) m = fmaxf(m, s[(int64_t)p * C]);
         float lanes[64];
         for (int l = 0; l < 64; ++l) {
           float a = 0.f;
-          for (int p = l; p < cnt; p += 64) a += expf(s[(int64_t)p * C] - m);
+          for (int p = l; p < cnt; p += 64) a += lse_term(s[(int64_t)p * C], m, ig);
           lanes[l] = a;
         }
         for (int w = 32; w > 0; w >>= 1)
@@ -210,10 +216,10 @@ extern "C" int kprn_host_explain(const float* path_scores, const int32_t* offset
         sum = lanes[0];
       }
     }
-    ex::places_serial(s, cnt, C, reducer, K_reducer, M, m, sum, path_idx + (int64_t)i * M, path_score + (int64_t)i * M, path_weight + (int64_t)i * M);
+    ex::places_serial(s, cnt, C, reducer, K_reducer, M, m, sum, ig, path_idx + (int64_t)i * M, path_score + (int64_t)i * M, path_weight + (int64_t)i * M);
     if (pooled || probs) {
       float y;
-      if (reducer == 2) y = logf(sum) + m;
+      if (reducer == 2) y = lse_finish(sum, m, ig);
       else {
         const int kk = reducer == 0 ? 1 : (K_reducer < cnt ? K_reducer : cnt);
         float acc = 0.f, lv = INFINITY;
@@ -226,8 +232,14 @@ extern "C" int kprn_host_explain(const float* path_scores, const int32_t* offset
         y = reducer == 0 ? acc : acc / (float)kk;
       }
       if (pooled) pooled[i] = y;
-      if (probs) probs[i] = 1.0f / (1.0f + expf(-y));
+      if (probs) probs[i] = pool_sigmoid_of(y, ig);
     }
   }
   return KPRN_OK;
+}
+
+extern "C" int kprn_host_explain(const float* path_scores, const int32_t* offsets, int32_t B, int32_t C, int32_t class_id, int32_t reducer, int32_t K_reducer,
+                                 const int32_t* pairs, int32_t n_pairs, int32_t M, int32_t* path_idx, float* path_score, float* path_weight, float* pooled,
+                                 float* probs) {
+  return kprn_host_explain_gamma(path_scores, offsets, B, C, class_id, reducer, K_reducer, pairs, n_pairs, M, path_idx, path_score, path_weight, pooled, probs, 1.0f);
 }

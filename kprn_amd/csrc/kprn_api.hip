@@ -186,7 +186,7 @@ void pool_stage(kprn_handle* h, const kprn_batch* b, int cid, bool every_class) 
   Workspace& w = h->ws;
   ProfScope ps(h, "pool_sigmoid");
   const kk::Segs g{b->B, b->P, b->off, b->wg, b->n_wg, b->seg_wave};
-  kk::pool_sigmoid(h->stream, w.S, g, c.C, c.reducer, c.K, every_class ? w.pooled : nullptr, every_class ? w.probs : nullptr, cid, w.sel, h->sel_host_armed);
+  kk::pool_sigmoid(h->stream, w.S, g, c.C, c.reducer, c.K, h->pool_ig, every_class ? w.pooled : nullptr, every_class ? w.probs : nullptr, cid, w.sel, h->sel_host_armed);
 }
 
 void check_batch(kprn_handle* h, const kprn_batch* b, int class_id) {
@@ -372,12 +372,12 @@ static void backward_impl(kprn_handle* h, const kprn_batch* b, int class_id, int
     const kk::Segs g{b->B, b->P, b->off, b->wg, b->n_wg, b->seg_wave};   // (a ragged batch or a ragged passenger: the launcher takes the segmented form)
     if (h->loss_bpr) {
       const float scale = inv_batch > 0.f ? inv_batch : (b->n_terms > 0 ? 1.0f / (float)b->n_terms : 0.f);
-      h->loss_pending = kk::loss_stage_pairwise(h->stream, h->score_buf, b->labels, g, b->groups + 2, b->n_groups, c.C, cid, c.reducer, c.K, scale, w.sel, w.dS,
-                                                fusedp ? b->slot_of : nullptr, h->loss_partial, have_tj ? &tj : nullptr,
+      h->loss_pending = kk::loss_stage_pairwise(h->stream, h->score_buf, b->labels, g, b->groups + 2, b->n_groups, c.C, cid, c.reducer, c.K, h->pool_ig, scale, w.sel,
+                                                w.dS, fusedp ? b->slot_of : nullptr, h->loss_partial, have_tj ? &tj : nullptr,
                                                 h->loss_early_armed ? h->loss_mirror : nullptr, pj.B > 0 ? &pj : nullptr);
     } else
-    h->loss_pending = kk::loss_stage(h->stream, h->score_buf, b->labels, g, c.C, cid, c.reducer, c.K, literal, invB, w.sel, w.dS, fusedp ? b->slot_of : nullptr,
-                                     h->loss_partial, have_tj ? &tj : nullptr, h->loss_early_armed ? h->loss_mirror : nullptr, pj.B > 0 ? &pj : nullptr);
+    h->loss_pending = kk::loss_stage(h->stream, h->score_buf, b->labels, g, c.C, cid, c.reducer, c.K, h->pool_ig, literal, invB, w.sel, w.dS,
+                                     fusedp ? b->slot_of : nullptr, h->loss_partial, have_tj ? &tj : nullptr, h->loss_early_armed ? h->loss_mirror : nullptr, pj.B > 0 ? &pj : nullptr);
     if (h->loss_early_armed) {   // what kprn_train_step_batch waits for instead of the end of the step
       h->loss_early_n = h->loss_pending;
       HIP_TRY(hipEventRecord(h->ev_loss, h->stream));
@@ -1102,6 +1102,8 @@ int kprn_save(kprn_handle* h, const char* path) {
   KPRN_REQUIRE(f, KPRN_E_IO, std::string("cannot open for writing: ") + path);
   const kprn_config& c = h->cfg;
   int32_t hdr[16] = {c.Vt, c.Ve, c.Vr, c.dt, c.de, c.dr, c.F, c.num_types, c.H, c.L, c.C, c.rnn_type, c.reducer, c.K, 0, 0};
+  // word 14: the pooling temperature's float bits, 0 at gamma = 1 (the files written before option "pool_gamma" existed, byte for byte)
+  if (h->pool_gamma != 1.0f) memcpy(&hdr[14], &h->pool_gamma, sizeof(float));
   bool ok = fwrite(kMagic, 1, 8, f) == 8 && fwrite(hdr, sizeof(int32_t), 16, f) == 16 && fwrite(&h->n_params, sizeof(int64_t), 1, f) == 1 &&
             fwrite(flat.data(), sizeof(float), flat.size(), f) == flat.size();
   ok = (fclose(f) == 0) && ok;
@@ -1126,7 +1128,14 @@ int kprn_load(kprn_handle* h, const char* path) {
   if (ok) { flat.resize((size_t)n); ok = fread(flat.data(), sizeof(float), flat.size(), f) == flat.size(); }
   fclose(f);
   KPRN_REQUIRE(ok, KPRN_E_IO, "not a kprn checkpoint for this configuration");
-  return kprn_set_flat_params(h, flat.data(), n);
+  // a non-zero word 14 is the pooling temperature the file was saved under: a LogSumExp handle adopts it (a zero word leaves the option alone)
+  float gamma = 0.f;
+  memcpy(&gamma, &hdr[14], sizeof(float));
+  const bool adopt = hdr[14] != 0 && c.reducer == 2;
+  KPRN_REQUIRE(!adopt || kk::pool_gamma_ok((double)gamma), KPRN_E_IO, "checkpoint header word 14 is not a pooling temperature in [1e-3, 1e3]");
+  const int rc = kprn_set_flat_params(h, flat.data(), n);
+  if (rc == KPRN_OK && adopt) { h->pool_gamma = gamma; h->pool_ig = kk::pool_ig_of(gamma); }
+  return rc;
   API_END(h)
 }
 
@@ -1388,6 +1397,18 @@ int kprn_set_option(kprn_handle* h, const char* key, const char* value) {
       KPRN_REQUIRE(h->cfg.compute_dtype == 0, KPRN_E_UNSUPPORTED, "dropout > 0: built for compute_dtype 0 (fp32) only; the bf16-product pipeline has no dropped form");
     }
     h->dropout_p = (float)p;
+  } else if (strcmp(key, "pool_gamma") == 0) {
+    // temperature of the LogSumExp reducer, the paper's log sum exp(s / gamma) (include/kprn.h "pooling temperature"); "1" (default): the bits
+    // the kernels produced before this option existed.  Read at every scoring, explaining and training call.  The decimal syntax of "dropout".
+    char* end = nullptr;
+    const bool decimal = (isdigit((unsigned char)value[0]) || value[0] == '.') && value[strspn(value, "0123456789.eE+-")] == 0;
+    const double g = decimal ? strtod(value, &end) : 0.0;
+    KPRN_REQUIRE(decimal && end != value && *end == 0 && kk::pool_gamma_ok(g) && kk::pool_gamma_ok((double)(float)g), KPRN_E_ARG,
+                 "pool_gamma must be a decimal temperature in [1e-3, 1e3]");
+    KPRN_REQUIRE((float)g == 1.0f || h->cfg.reducer == 2, KPRN_E_UNSUPPORTED,
+                 "pool_gamma != 1: the handle's reducer is not 2 (LogSumExp) -- Max and TopK + Mean have no temperature");
+    h->pool_gamma = (float)g;
+    h->pool_ig = kk::pool_ig_of(h->pool_gamma);
   } else if (strcmp(key, "dropout_seed") == 0) {
     // seed of the mask generator (decimal or 0x hex uint64; default cfg.seed + cfg.rank); setting it restarts the draw count
     char* end = nullptr;

@@ -310,6 +310,9 @@ struct kprn_handle {
   // "2" (generic fp32 pipelines too): 1 and 2 launch the same kernels wherever 1 trains; 2 adds the slab forms of the generic backward's joins
   int deterministic = 0;
   int loss_bpr = 0;            // option "loss": 0 "bce" (nn.BCECriterion per pair) | 1 "bpr" (the pairwise loss over the batch's groups, include/kprn.h "pairwise loss")
+  // option "pool_gamma": the LogSumExp reducer's temperature (include/kprn.h "pooling temperature").  pool_ig = (float)(1.0 / (double)pool_gamma)
+  // is what every pooling, loss and explanation launch takes; both are 1 unless cfg.reducer == 2
+  float pool_gamma = 1.0f, pool_ig = 1.0f;
   DetScratch det_slab;         // "2": where the generic backward's producers plain-store their partials (one buffer: producer and join are stream-ordered)
   float* det_seg = nullptr; int64_t det_seg_cap = 0;   // "2": bidx::DetEntity::seg_part of the row-major entity gradient [segments][2][de]
   // option "dropout" (rnn cell, fp32): nn.Dropout on every layer's step input in TRAINING forwards.  Masks are regenerated, never stored:
@@ -455,22 +458,27 @@ struct PoolJob { const float* S; int B, P, cid; float* sel; float* sel_host; con
 // off[b] .. off[b+1]-1; wg / n_wg: the loss stage's workgroup table of a ragged batch; wave: a wave per pair instead of a thread per pair
 struct Segs { int B, P; const int32_t* off; const int32_t* wg; int n_wg; int wave; };
 // segment limits of a ragged batch (DESIGN.md 'ragged batches')
-constexpr int RAGGED_MAX_SEG = 4096;     // longest pair kprn_host_ragged_plan accepts
+// the pooling temperature's accepted range: option "pool_gamma", kprn_host_explain_gamma and a checkpoint's header word 14 (false for a NaN)
+inline bool pool_gamma_ok(double g) { return g >= 1e-3 && g <= 1e3; }
+inline float pool_ig_of(float gamma) { return (float)(1.0 / (double)gamma); }
+constexpr int RAGGED_MAX_SEG = 4096;    // longest pair kprn_host_ragged_plan accepts
 constexpr int RAGGED_THREAD_MAX = 28;    // longest pair a single thread reduces (the reference's largest path count: reduce_col's range)
 constexpr int RAGGED_WG_PAIRS = 16;      // pairs per loss-stage workgroup, rectangular or ragged
 constexpr int RAGGED_WG_PATHS = 448;     // paths per loss-stage workgroup (16 pairs of 28); a longer pair has a workgroup to itself
 // offsets [B+1], workgroup table wg [<= B+1], summary {n_wg, max_cnt, wave}; false: a count < 1 or > RAGGED_MAX_SEG, or sum != N
 bool ragged_plan(const int32_t* counts, int32_t B, int64_t N, int32_t* off, int32_t* wg, int32_t* summary);
-// loss_stage.hip.  Reducer + sigmoid + select of a scoring pass; pooled / probs null: the selected class only.  The ragged forms launch when g.off is set
-void pool_sigmoid(hipStream_t s, const float* S, const Segs& g, int C, int reducer, int K, float* pooled, float* probs, int cid, float* sel, float* sel_host = nullptr);
+// loss_stage.hip.  Reducer + sigmoid + select of a scoring pass; pooled / probs null: the selected class only.  The ragged forms launch when g.off is set.
+// ig (here and in the two loss stages): kprn_handle::pool_ig, the LogSumExp reducer's inverse temperature (option "pool_gamma"; 1.0f = the plain reducer's bits)
+void pool_sigmoid(hipStream_t s, const float* S, const Segs& g, int C, int reducer, int K, float ig, float* pooled, float* probs, int cid, float* sel,
+                  float* sel_host = nullptr);
 // the loss stage of a training step; the ragged form launches when the batch or the passenger pooling job is ragged.  Returns the number of partials
 // (slot_of nullable: dS[slot_of[n]]; partial_host: optional page-locked mirror of the per-workgroup loss partials)
-int loss_stage(hipStream_t s, const float* S, const float* labels, const Segs& g, int C, int cid, int reducer, int K, int literal, float invB, float* sel,
-               float* dS, const int32_t* slot_of, float* partial, const TransposeJob* tj = nullptr, float* partial_host = nullptr, const PoolJob* pj = nullptr);
+int loss_stage(hipStream_t s, const float* S, const float* labels, const Segs& g, int C, int cid, int reducer, int K, float ig, int literal, float invB,
+               float* sel, float* dS, const int32_t* slot_of, float* partial, const TransposeJob* tj = nullptr, float* partial_host = nullptr, const PoolJob* pj = nullptr);
 // the loss stage under option "loss" = "bpr": a workgroup per group of the table go [G+1] (device), the same passengers; returns G, the number of partials
 constexpr int PAIRWISE_MAX_GROUP = 1024;   // pairs per group (KPRN_PAIRWISE_MAX_GROUP)
-int loss_stage_pairwise(hipStream_t s, const float* S, const float* labels, const Segs& g, const int32_t* go, int G, int C, int cid, int reducer, int K, float scale,
-                        float* sel, float* dS, const int32_t* slot_of, float* partial, const TransposeJob* tj = nullptr, float* partial_host = nullptr,
+int loss_stage_pairwise(hipStream_t s, const float* S, const float* labels, const Segs& g, const int32_t* go, int G, int C, int cid, int reducer, int K, float ig,
+                        float scale, float* sel, float* dS, const int32_t* slot_of, float* partial, const TransposeJob* tj = nullptr, float* partial_host = nullptr,
                         const PoolJob* pj = nullptr);
 void count_pair_terms(hipStream_t s, const float* labels, const int32_t* go, int G, int64_t* out);   // *out (device) = sum over the groups of positives x negatives
 const char* pairwise_groups_why(const int32_t* go, int32_t G, int32_t B);   // what is wrong with a (host) group table over B pairs, or null
@@ -543,7 +551,8 @@ struct Args {   // device pointers
   const int32_t* off; int B, P;   // the batch's pairs: off [B+1], or null = P paths each
   int seg_wave;              // the batch pools a pair of more than RAGGED_THREAD_MAX paths by a wave (kprn_batch::seg_wave): pooled's order
   int C, cid, reducer, K, M;
-  const int32_t* pairs;      // [n] pair per item; null = item i is pair i
+  float ig;                  // LogSumExp's inverse pooling temperature (kprn_handle::pool_ig); Max and TopK never read it
+  const int32_t* pairs;     // [n] pair per item; null = item i is pair i
   const int64_t* goff; int per_group;   // non-null: pairs holds a ranking's top-K rows [G][per_group] (index within the group, -1 = empty place)
   int64_t n;
   int32_t* idx; float* score; float* weight;   // [n][M]

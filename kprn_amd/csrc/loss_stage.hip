@@ -13,6 +13,11 @@
 //      stage of a scoring pass that rode in the training forward's launch (kk::PoolJob, "score_dual")
 //   2' the pairwise (BPR) loss over groups of pairs instead of stage 2 (option "loss" = "bpr"; include/kprn.h "pairwise loss"): k_loss_stage_pairwise, a
 //      workgroup per group, with the same stages 1, 3, 4 and 5 around it
+//   ig the LogSumExp reducer's inverse pooling temperature (option "pool_gamma", include/kprn.h "pooling temperature"): a float argument of every kernel here,
+//      handed down to reduce_dev.h's lse_term / lse_finish / pool_sigmoid_of and to stage 3, where dy is scaled by it once per pair.  One set of instantiations: at
+//      ig == 1.0f every product is exact and the bits are those of the plain reducer.  Max and TopK + Mean never read it.  VGPRs now / before the option
+//      (no scratch anywhere, occupancy as before): k_pool 14 / 17 / 24 / 28 (13 / 16 / 24 / 28), k_loss_stage 34 and 49 (32 and 44), k_loss_stage_pairwise
+//      37 and 50 (37 and 48) -- the growth is exp_shared / log_shared, the temperature path's own exp and log (reduce_dev.h).
 // (The head's weight gradient is NOT formed here: the fused top-layer backward or the generic pipeline's head_bwd does that.)
 //
 //   6  Two forms.  A batch is kk::Segs: B pairs of P paths each, or (off != null, a ragged batch -- an extension, the reference has one path
@@ -37,16 +42,16 @@ inline unsigned nblocks(int64_t n, int per = TPB) { return (unsigned)((n + per -
 // Stage 1 for one (pair b, class c): reduce the pair's column, sigmoid, store.  pooled != null: every class is asked (pooled / probs [B][C], at = b C + c);
 // sel / sel_host (page-locked mirror: kprn_forward_batch hands the probabilities out without a copy operation) take class cid.
 // Wave form (SEG and wave): the whole wave calls, lane 0 stores.  (b is 64 bits wide and the rectangular form multiplies it out itself: the every-class
-// instantiations keep their former register counts that way, 16 and 28; through an int they take 17 and 30.)
+// instantiations took 16 and 28 registers that way and 17 and 30 through an int; with the temperature path's exp and log they take 17 and 28.)
 template <bool SEG>
 __device__ __forceinline__ void pool_pair(const float* __restrict__ S, const int32_t* __restrict__ off, int P, int wave, int lane, int64_t b, int c, int C,
-                                          int reducer, int K, float* __restrict__ pooled, float* __restrict__ probs, int64_t at, int cid, float* __restrict__ sel,
-                                          float* __restrict__ sel_host) {
+                                          int reducer, int K, float ig, float* __restrict__ pooled, float* __restrict__ probs, int64_t at, int cid,
+                                          float* __restrict__ sel, float* __restrict__ sel_host) {
   if constexpr (!SEG) off = nullptr;
   const float* s = S + (SEG ? seg_begin(off, P, (int)b) : b * P) * C + c;
   const int cnt = seg_count(off, P, (int)b);
-  const float y = SEG ? reduce_seg(s, cnt, C, reducer, K, wave, lane) : reduce_col(s, cnt, C, reducer, K);
-  const float pr = sigmoidf_(y);
+  const float y = SEG ? reduce_seg(s, cnt, C, reducer, K, ig, wave, lane) : reduce_col(s, cnt, C, reducer, K, ig);
+  const float pr = pool_sigmoid_of(y, ig);
   if (SEG && wave && lane != 0) return;
   if (pooled) { pooled[at] = y; probs[at] = pr; }
   if (c == cid) {
@@ -58,14 +63,14 @@ __device__ __forceinline__ void pool_pair(const float* __restrict__ S, const int
 // The pooling stage of a scoring pass.  EVERY_CLASS: an item is a (pair, class), else a pair (only the selected class is reduced: what
 // model:forward hands the caller, test_from_checkpoint.lua:82).  Thread form: one thread per item; wave form: one wave per item, four to a workgroup.
 template <bool SEG, bool EVERY_CLASS>
-__global__ __launch_bounds__(TPB) void k_pool(const float* __restrict__ S, kk::Segs g, int C, int reducer, int K, float* __restrict__ pooled,
+__global__ __launch_bounds__(TPB) void k_pool(const float* __restrict__ S, kk::Segs g, int C, int reducer, int K, float ig, float* __restrict__ pooled,
                                               float* __restrict__ probs, int cid, float* __restrict__ sel, float* __restrict__ sel_host) {
   const bool wave = SEG && g.wave;
   const int64_t item = wave ? (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6) : (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (item >= (EVERY_CLASS ? (int64_t)g.B * C : (int64_t)g.B)) return;   // (wave form: the whole wave leaves)
   const int64_t b = EVERY_CLASS ? item / C : item;
-  pool_pair<SEG>(S, g.off, g.P, g.wave, threadIdx.x & 63, b, EVERY_CLASS ? (int)(item % C) : cid, C, reducer, K, EVERY_CLASS ? pooled : nullptr, probs, item,
-                 cid, sel, sel_host);
+  pool_pair<SEG>(S, g.off, g.P, g.wave, threadIdx.x & 63, b, EVERY_CLASS ? (int)(item % C) : cid, C, reducer, K, ig, EVERY_CLASS ? pooled : nullptr, probs,
+                 item, cid, sel, sel_host);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -86,14 +91,16 @@ struct PairGrad {
   __device__ __forceinline__ float& operator()(int q) const { return slot ? dS[slot[q]] : dpair[q]; }
 };
 
-// Stage 3 for one pair by one thread: back through the reducer given dy = d loss / d (pooled value)
-__device__ void reducer_bwd(const float* __restrict__ s, int P, int C, int reducer, int K, float dy, PairGrad d) {
+// Stage 3 for one pair by one thread: back through the reducer given dy = d loss / d (pooled value).  LogSumExp under the pooling temperature:
+// d pooled / d s_q = ig x the path's share, so dy is scaled once per pair and the per-path expression keeps its shape (dy * 1.0f == dy).
+__device__ void reducer_bwd(const float* __restrict__ s, int P, int C, int reducer, int K, float ig, float dy, PairGrad d) {
   if (reducer == 2) {
+    dy *= ig;
     float m = s[0];
     for (int q = 1; q < P; ++q) m = fmaxf(m, s[(int64_t)q * C]);
     float sum = 0.f;
-    for (int q = 0; q < P; ++q) sum += expf(s[(int64_t)q * C] - m);
-    for (int q = 0; q < P; ++q) d(q) = expf(s[(int64_t)q * C] - m) / sum * dy;
+    for (int q = 0; q < P; ++q) sum += lse_term(s[(int64_t)q * C], m, ig);
+    for (int q = 0; q < P; ++q) d(q) = lse_term(s[(int64_t)q * C], m, ig) / sum * dy;
   } else if (reducer == 0) {
     int arg = 0;
     for (int q = 1; q < P; ++q) if (s[(int64_t)q * C] > s[(int64_t)arg * C]) arg = q;
@@ -115,23 +122,25 @@ __device__ void reducer_bwd(const float* __restrict__ s, int P, int C, int reduc
 }
 
 // Stages 1-3 for one pair by one thread; returns the probability
-__device__ float bce_pair(const float* __restrict__ s, int P, int C, int reducer, int K, int literal, float invB, float t, PairGrad d, float* lossterm) {
-  const float p = sigmoidf_(reduce_col(s, P, C, reducer, K));
-  reducer_bwd(s, P, C, reducer, K, bce(p, t, literal, invB, lossterm), d);
+__device__ float bce_pair(const float* __restrict__ s, int P, int C, int reducer, int K, float ig, int literal, float invB, float t, PairGrad d,
+                          float* lossterm) {
+  const float p = pool_sigmoid_of(reduce_col(s, P, C, reducer, K, ig), ig);
+  reducer_bwd(s, P, C, reducer, K, ig, bce(p, t, literal, invB, lossterm), d);
   return p;
 }
 
 // Stage 3 by one wave (cnt > RAGGED_THREAD_MAX; the whole wave calls, under wave-uniform control flow).  Path q's gradient is written by lane q % 64 only,
 // so the TopK form's zero-then-set is one thread's program order.
-__device__ void reducer_bwd_wave(const float* __restrict__ s, int cnt, int C, int reducer, int K, float dy, PairGrad d, int lane) {
+__device__ void reducer_bwd_wave(const float* __restrict__ s, int cnt, int C, int reducer, int K, float ig, float dy, PairGrad d, int lane) {
   if (reducer == 2) {
+    dy *= ig;
     float m = -INFINITY;
     for (int q = lane; q < cnt; q += 64) m = fmaxf(m, s[(int64_t)q * C]);
     m = wave_all_max(m);
     float sum = 0.f;
-    for (int q = lane; q < cnt; q += 64) sum += expf(s[(int64_t)q * C] - m);
+    for (int q = lane; q < cnt; q += 64) sum += lse_term(s[(int64_t)q * C], m, ig);
     sum = wave_all_sum(sum);
-    for (int q = lane; q < cnt; q += 64) d(q) = expf(s[(int64_t)q * C] - m) / sum * dy;
+    for (int q = lane; q < cnt; q += 64) d(q) = lse_term(s[(int64_t)q * C], m, ig) / sum * dy;
   } else if (reducer == 0) {
     float best; int arg;
     lane_best(s, cnt, C, lane, INFINITY, -1, best, arg);
@@ -152,20 +161,21 @@ __device__ void reducer_bwd_wave(const float* __restrict__ s, int cnt, int C, in
 }
 
 // Stages 1-3 for one pair by one wave
-__device__ float bce_pair_wave(const float* __restrict__ s, int cnt, int C, int reducer, int K, int literal, float invB, float t, PairGrad d, float* lossterm,
-                               int lane) {
-  const float p = sigmoidf_(reduce_col_wave(s, cnt, C, reducer, K, lane));
-  reducer_bwd_wave(s, cnt, C, reducer, K, bce(p, t, literal, invB, lossterm), d, lane);
+__device__ float bce_pair_wave(const float* __restrict__ s, int cnt, int C, int reducer, int K, float ig, int literal, float invB, float t, PairGrad d,
+                               float* lossterm, int lane) {
+  const float p = pool_sigmoid_of(reduce_col_wave(s, cnt, C, reducer, K, ig, lane), ig);
+  reducer_bwd_wave(s, cnt, C, reducer, K, ig, bce(p, t, literal, invB, lossterm), d, lane);
   return p;
 }
 
 // ---------------------------------------------------------------------------------------
-// Stage 5, the passengers: workgroup rb of the pooling job (k_pool<SEG, false>'s items of pj's batch) / of the transposes (64 workgroups per 256x64 matrix)
+// Stage 5, the passengers: workgroup rb of the pooling job (k_pool<SEG, false>'s items of pj's batch, under the launch's ig: a pass that rides in a training
+// launch pools under the same temperature) / of the transposes (64 workgroups per 256x64 matrix)
 template <bool SEG>
-__device__ __forceinline__ void pool_passenger(int rb, int tid, int C, int reducer, int K, const kk::PoolJob& pj) {
+__device__ __forceinline__ void pool_passenger(int rb, int tid, int C, int reducer, int K, float ig, const kk::PoolJob& pj) {
   const int b = (SEG && pj.wave) ? rb * 4 + (tid >> 6) : rb * 256 + tid;
   if (b >= pj.B) return;
-  pool_pair<SEG>(pj.S, pj.off, pj.P, pj.wave, tid & 63, b, pj.cid, C, reducer, K, nullptr, nullptr, 0, pj.cid, pj.sel, pj.sel_host);
+  pool_pair<SEG>(pj.S, pj.off, pj.P, pj.wave, tid & 63, b, pj.cid, C, reducer, K, ig, nullptr, nullptr, 0, pj.cid, pj.sel, pj.sel_host);
 }
 __device__ __forceinline__ void transpose_passenger(int rb, int tid, const kk::TransposeJob& tj) {
   const int m = rb >> 6, i = (rb & 63) * 256 + tid;  // over the 64*256 outputs of matrix m
@@ -178,12 +188,12 @@ __device__ __forceinline__ void transpose_passenger(int rb, int tid, const kk::T
 // workgroups behind them are the passengers.  SEG = true also serves a rectangular batch that carries a ragged passenger, and the reverse.
 template <bool SEG>
 __global__ __launch_bounds__(256) void k_loss_stage(const float* __restrict__ S, const float* __restrict__ labels, kk::Segs g, int C, int cid, int reducer, int K,
-                                                    int literal, float invB, float* __restrict__ sel, float* __restrict__ dS,
+                                                    float ig, int literal, float invB, float* __restrict__ sel, float* __restrict__ dS,
                                                     const int32_t* __restrict__ slot_of, float* __restrict__ partial, int n_loss_blocks, kk::TransposeJob tj,
                                                     float* __restrict__ partial_host, kk::PoolJob pj) {
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   if ((int)blockIdx.x >= n_loss_blocks + 64 * tj.n) {  // (workgroup-uniform) passenger: the pooling stage of a scoring pass
-    pool_passenger<SEG>((int)blockIdx.x - n_loss_blocks - 64 * tj.n, tid, C, reducer, K, pj);
+    pool_passenger<SEG>((int)blockIdx.x - n_loss_blocks - 64 * tj.n, tid, C, reducer, K, ig, pj);
     return;
   }
   if ((int)blockIdx.x >= n_loss_blocks) {  // (workgroup-uniform) passenger: 256x64 weight transposes
@@ -205,8 +215,8 @@ __global__ __launch_bounds__(256) void k_loss_stage(const float* __restrict__ S,
       const int cnt = seg_count(off, g.P, b);
       const PairGrad d{dS + n0, dS, slot_of ? slot_of + n0 : nullptr};
       float pr = 0.f;
-      if (wave && cnt > kk::RAGGED_THREAD_MAX) pr = bce_pair_wave(S + n0 * C + cid, cnt, C, reducer, K, literal, invB, labels[b], d, &lt, lane);
-      else if (!wave || lane == 0) pr = bce_pair(S + n0 * C + cid, cnt, C, reducer, K, literal, invB, labels[b], d, &lt);
+      if (wave && cnt > kk::RAGGED_THREAD_MAX) pr = bce_pair_wave(S + n0 * C + cid, cnt, C, reducer, K, ig, literal, invB, labels[b], d, &lt, lane);
+      else if (!wave || lane == 0) pr = bce_pair(S + n0 * C + cid, cnt, C, reducer, K, ig, literal, invB, labels[b], d, &lt);
       if (!wave || lane == 0) sel[b] = pr;
     }
     if (!wave || lane == 0) lossw[i] = lt;
@@ -258,12 +268,12 @@ static_assert(PW_MAX == KPRN_PAIRWISE_MAX_GROUP, "the header states the limit");
 // LDS: y, dy and the members' term sums, 3 x 4 KiB, and the label bits, 1 KiB.
 template <bool SEG>
 __global__ __launch_bounds__(256) void k_loss_stage_pairwise(const float* __restrict__ S, const float* __restrict__ labels, kk::Segs g, const int32_t* __restrict__ go,
-                                                             int G, int C, int cid, int reducer, int K, float s, float* __restrict__ sel, float* __restrict__ dS,
+                                                             int G, int C, int cid, int reducer, int K, float ig, float s, float* __restrict__ sel, float* __restrict__ dS,
                                                              const int32_t* __restrict__ slot_of, float* __restrict__ partial, kk::TransposeJob tj,
                                                              float* __restrict__ partial_host, kk::PoolJob pj) {
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   if ((int)blockIdx.x >= G + 64 * tj.n) {  // (workgroup-uniform)
-    pool_passenger<SEG>((int)blockIdx.x - G - 64 * tj.n, tid, C, reducer, K, pj);
+    pool_passenger<SEG>((int)blockIdx.x - G - 64 * tj.n, tid, C, reducer, K, ig, pj);
     return;
   }
   if ((int)blockIdx.x >= G) {  // (workgroup-uniform)
@@ -281,17 +291,17 @@ __global__ __launch_bounds__(256) void k_loss_stage_pairwise(const float* __rest
     const int cnt = seg_count(off, g.P, b);
     pos_s[i] = labels[b] > 0.5f ? 1 : 0;
     if (wave && cnt > kk::RAGGED_THREAD_MAX) continue;
-    const float y = reduce_col(S + seg_begin(off, g.P, b) * C + cid, cnt, C, reducer, K);
+    const float y = reduce_col(S + seg_begin(off, g.P, b) * C + cid, cnt, C, reducer, K, ig);
     y_s[i] = y;
-    sel[b] = sigmoidf_(y);
+    sel[b] = pool_sigmoid_of(y, ig);
   }
   if (wave) {
     for (int i = wv; i < n; i += 4) {
       const int b = b0 + i;
       const int cnt = seg_count(off, g.P, b);
       if (cnt <= kk::RAGGED_THREAD_MAX) continue;
-      const float y = reduce_col_wave(S + seg_begin(off, g.P, b) * C + cid, cnt, C, reducer, K, lane);
-      if (lane == 0) { y_s[i] = y; sel[b] = sigmoidf_(y); }
+      const float y = reduce_col_wave(S + seg_begin(off, g.P, b) * C + cid, cnt, C, reducer, K, ig, lane);
+      if (lane == 0) { y_s[i] = y; sel[b] = pool_sigmoid_of(y, ig); }
     }
   }
   __syncthreads();
@@ -316,7 +326,7 @@ __global__ __launch_bounds__(256) void k_loss_stage_pairwise(const float* __rest
     const int cnt = seg_count(off, g.P, b);
     if (wave && cnt > kk::RAGGED_THREAD_MAX) continue;
     const int64_t n0 = seg_begin(off, g.P, b);
-    reducer_bwd(S + n0 * C + cid, cnt, C, reducer, K, dy_s[i], PairGrad{dS + n0, dS, slot_of ? slot_of + n0 : nullptr});
+    reducer_bwd(S + n0 * C + cid, cnt, C, reducer, K, ig, dy_s[i], PairGrad{dS + n0, dS, slot_of ? slot_of + n0 : nullptr});
   }
   if (wave) {
     for (int i = wv; i < n; i += 4) {
@@ -324,7 +334,7 @@ __global__ __launch_bounds__(256) void k_loss_stage_pairwise(const float* __rest
       const int cnt = seg_count(off, g.P, b);
       if (cnt <= kk::RAGGED_THREAD_MAX) continue;
       const int64_t n0 = seg_begin(off, g.P, b);
-      reducer_bwd_wave(S + n0 * C + cid, cnt, C, reducer, K, dy_s[i], PairGrad{dS + n0, dS, slot_of ? slot_of + n0 : nullptr}, lane);
+      reducer_bwd_wave(S + n0 * C + cid, cnt, C, reducer, K, ig, dy_s[i], PairGrad{dS + n0, dS, slot_of ? slot_of + n0 : nullptr}, lane);
     }
   }
 }
@@ -373,18 +383,19 @@ __global__ void k_sum_partials(const float* __restrict__ partial, int n, float* 
 
 namespace kk {
 
-void pool_sigmoid(hipStream_t s, const float* S, const Segs& g, int C, int reducer, int K, float* pooled, float* probs, int cid, float* sel, float* sel_host) {
+void pool_sigmoid(hipStream_t s, const float* S, const Segs& g, int C, int reducer, int K, float ig, float* pooled, float* probs, int cid, float* sel,
+                  float* sel_host) {
   if (g.B <= 0) return;
   const int64_t items = pooled ? (int64_t)g.B * C : (int64_t)g.B;
   auto* const k = g.off ? (pooled ? k_pool<true, true> : k_pool<true, false>) : (pooled ? k_pool<false, true> : k_pool<false, false>);
-  hipLaunchKernelGGL(k, dim3(nblocks(items, g.off && g.wave ? 4 : TPB)), dim3(TPB), 0, s, S, g, C, reducer, K, pooled, probs, cid, sel, sel_host);
+  hipLaunchKernelGGL(k, dim3(nblocks(items, g.off && g.wave ? 4 : TPB)), dim3(TPB), 0, s, S, g, C, reducer, K, ig, pooled, probs, cid, sel, sel_host);
   CHECK_LAUNCH();
 }
 
 int loss_partials(int B) { return (B + PPW - 1) / PPW; }
 
-int loss_stage(hipStream_t s, const float* S, const float* labels, const Segs& g, int C, int cid, int reducer, int K, int literal, float invB, float* sel,
-               float* dS, const int32_t* slot_of, float* partial, const TransposeJob* tj, float* partial_host, const PoolJob* pj) {
+int loss_stage(hipStream_t s, const float* S, const float* labels, const Segs& g, int C, int cid, int reducer, int K, float ig, int literal, float invB,
+               float* sel, float* dS, const int32_t* slot_of, float* partial, const TransposeJob* tj, float* partial_host, const PoolJob* pj) {
   if (g.B <= 0) return 0;
   TransposeJob t;
   memset(&t, 0, sizeof(t));
@@ -396,13 +407,13 @@ int loss_stage(hipStream_t s, const float* S, const float* labels, const Segs& g
   const int nlb = g.wg ? g.n_wg : loss_partials(g.B);
   const int npb = (int)nblocks(pjob.B, seg && pjob.wave ? 4 : 256);
   hipLaunchKernelGGL(seg ? k_loss_stage<true> : k_loss_stage<false>, dim3((unsigned)(nlb + 64 * t.n + npb)), dim3(256), 0, s, S, labels, g, C, cid, reducer, K,
-                     literal, invB, sel, dS, slot_of, partial, nlb, t, partial_host, pjob);
+                     ig, literal, invB, sel, dS, slot_of, partial, nlb, t, partial_host, pjob);
   CHECK_LAUNCH();
   return nlb;
 }
 
-int loss_stage_pairwise(hipStream_t s, const float* S, const float* labels, const Segs& g, const int32_t* go, int G, int C, int cid, int reducer, int K, float scale,
-                        float* sel, float* dS, const int32_t* slot_of, float* partial, const TransposeJob* tj, float* partial_host, const PoolJob* pj) {
+int loss_stage_pairwise(hipStream_t s, const float* S, const float* labels, const Segs& g, const int32_t* go, int G, int C, int cid, int reducer, int K, float ig,
+                        float scale, float* sel, float* dS, const int32_t* slot_of, float* partial, const TransposeJob* tj, float* partial_host, const PoolJob* pj) {
   if (g.B <= 0 || G <= 0) return 0;
   TransposeJob t;
   memset(&t, 0, sizeof(t));
@@ -413,7 +424,7 @@ int loss_stage_pairwise(hipStream_t s, const float* S, const float* labels, cons
   const bool seg = g.off || pjob.off;
   const int npb = (int)nblocks(pjob.B, seg && pjob.wave ? 4 : 256);
   hipLaunchKernelGGL(seg ? k_loss_stage_pairwise<true> : k_loss_stage_pairwise<false>, dim3((unsigned)(G + 64 * t.n + npb)), dim3(256), 0, s, S, labels, g, go, G, C,
-                     cid, reducer, K, scale, sel, dS, slot_of, partial, t, partial_host, pjob);
+                     cid, reducer, K, ig, scale, sel, dS, slot_of, partial, t, partial_host, pjob);
   CHECK_LAUNCH();
   return G;
 }

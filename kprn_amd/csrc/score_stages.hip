@@ -486,7 +486,7 @@ static ex::Args explain_args(kprn_handle* h, const kprn_batch* b, int class_id, 
   const kprn_config& c = h->cfg;
   ex::Args a;
   a.S = h->score_buf; a.off = b->off; a.B = b->B; a.P = b->P; a.seg_wave = b->off ? b->seg_wave : 0;
-  a.C = c.C; a.cid = class_id - 1; a.reducer = c.reducer; a.K = c.K; a.M = M;
+  a.C = c.C; a.cid = class_id - 1; a.reducer = c.reducer; a.K = c.K; a.M = M; a.ig = h->pool_ig;
   a.pairs = nullptr; a.goff = nullptr; a.per_group = 1; a.n = 0;
   a.idx = nullptr; a.score = nullptr; a.weight = nullptr; a.pooled = nullptr; a.prob = nullptr;
   return a;

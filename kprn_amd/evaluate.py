@@ -25,7 +25,8 @@ def main(argv=None, out=sys.stdout):
     p.add_argument("-model_path", default=""); p.add_argument("-gpu_id", type=int, default=-1); p.add_argument("-top_k", type=int, default=2)
     p.add_argument("-min_hops", type=int, default=1)
     args, rest = p.parse_known_args(argv)
-    params = model.parse_flags(rest)
+    params = model.parse_flags(rest, gamma_beside=None)
+    model.check_gamma(params.gamma, model.reducer_of_score_flag(args.top_k), "-top_k", p.error)
     if not params.kg or params.holdout <= 0:
         p.error("needs -kg triples.tsv -vocab_dir DIR -interaction_rel NAME and -holdout SHARE (above 0)")
     params.reducer, params.initModel, params.gpuid = model.reducer_of_score_flag(args.top_k), args.model_path, args.gpu_id

@@ -70,6 +70,8 @@ def flag_parser():
     a("-max_candidates", type=int, default=0, help="evaluation ranks among each user's N strongest candidates by path count only (0 = all of them)")
     a("-meta_paths", default="", help="with -kg: a file of relation-sequence patterns, one per line (graph.parse_meta_paths: positions separated by blanks, "
       "a position `*` or relation names joined by `|`); only the paths that match one are found, as candidates, for training and for evaluation")
+    a("-gamma", type=float, default=None, help="temperature of the LogSumExp reducer, the paper's log sum exp(s / gamma), in 0.001 .. 1000 (the engine's option "
+      "\"pool_gamma\"); unset = what the checkpoint carried (1 if nothing); given, it is applied after the checkpoint is loaded; needs the LogSumExp reducer")
     return p
 
 
@@ -84,9 +86,26 @@ def check_walks(max_hops, walks, error):
         error("-walks must be in 0..%d" % _ffi.FIND_MAX_WALKS)
 
 
-def parse_flags(argv=None):
+POOL_GAMMA_MIN, POOL_GAMMA_MAX = 1e-3, 1e3   # the range of the engine's option "pool_gamma"
+
+
+def check_gamma(gamma, reducer, reducer_flag, error):
+    """-gamma, decided on the host before an engine exists: error(message) for a value outside the option's range, or for one other than 1 beside a reducer
+    flag (named reducer_flag: -topK when training, -top_k when scoring) that does not select LogSumExp -- Max and TopK + Mean have no temperature"""
+    if gamma is None:
+        return
+    if not POOL_GAMMA_MIN <= gamma <= POOL_GAMMA_MAX:   # (false for a NaN)
+        error("-gamma must be in %g .. %g, got %r" % (POOL_GAMMA_MIN, POOL_GAMMA_MAX, gamma))
+    if gamma != 1 and reducer != 2:
+        error("-gamma %r needs %s 2 (LogSumExp): %s has no temperature" % (gamma, reducer_flag, "TopK + Mean" if reducer == 1 else "max pooling"))
+
+
+def parse_flags(argv=None, gamma_beside="-topK"):
+    """gamma_beside: the reducer flag -gamma is checked against here (-topK, the training flag); None = the caller checks it against its own (check_gamma)"""
     p = flag_parser()
     params = p.parse_args(argv)
+    if gamma_beside is not None:
+        check_gamma(params.gamma, reducer_of_train_flag(params.topK), gamma_beside, p.error)
     if params.kg and not (params.vocab_dir and params.interaction_rel):
         p.error("-kg needs -vocab_dir DIR (the vocabulary files) and -interaction_rel NAME (the relation of the user-item edges to train on)")
     if params.loss == "bpr" and not params.kg:
@@ -194,6 +213,8 @@ def build_engine(params, rank=0, world=1, device_id=None, stream=None):
             eng.set_option("deterministic", str(int(params.deterministic)))   # (a training call on a pipeline without fixed-order sums then raises KprnError(E_UNSUPPORTED))
         if params.initModel:
             load_checkpoint(eng, params.initModel)  # OneModel.lua:277-282
+        if getattr(params, "gamma", None) is not None:
+            eng.set_option("pool_gamma", repr(float(params.gamma)))   # (after the checkpoint: a given -gamma overrides the one a native checkpoint carries)
     except Exception:
         eng.close()   # (a refused option or an unreadable checkpoint: the handle and its device memory go now, not when the object is collected)
         raise

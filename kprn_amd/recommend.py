@@ -48,7 +48,8 @@ def main(argv=None, out=sys.stdout):
         sys.exit("-explain_paths must be in 1..32")
     if not 1 <= args.k <= 64:
         sys.exit("-k must be in 1..64")
-    params = model.parse_flags(rest)
+    params = model.parse_flags(rest, gamma_beside=None)
+    model.check_gamma(params.gamma, model.reducer_of_score_flag(args.top_k), "-top_k", p.error)
     params.reducer, params.initModel, params.gpuid = model.reducer_of_score_flag(args.top_k), args.model_path, args.gpu_id
     kg = graph.KnowledgeGraph.from_triples(graph.read_triples(args.kg), Vocabs(args.vocab_dir), params.numEntityTypes)
     if (kg.Vt, kg.Ve, kg.Vr) != (params.entityTypeVocabSize, params.entityVocabSize, params.relationVocabSize):

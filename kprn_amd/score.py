@@ -21,7 +21,8 @@ def main(argv=None):
     p.add_argument("-explain_out", default=""); p.add_argument("-explain_paths", type=int, default=3)
     args, rest = p.parse_known_args(argv)
     assert args.input_dir != "", "input_dir isnt set. Point to the dir where train/dev/test.list files reside"
-    params = model.parse_flags(rest)
+    params = model.parse_flags(rest, gamma_beside=None)
+    model.check_gamma(params.gamma, model.reducer_of_score_flag(args.top_k), "-top_k", p.error)
     import os as _os
     params.reducer, params.K, params.initModel = model.reducer_of_score_flag(args.top_k), args.k, args.model_path
     params.gpuid = int(_os.environ.get("LOCAL_RANK", args.gpu_id)) if "LOCAL_RANK" in _os.environ else args.gpu_id
