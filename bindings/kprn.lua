@@ -125,6 +125,9 @@ int kprn_host_find_candidates(const int32_t*, const int32_t*, const int32_t*, in
 int kprn_find_candidates_top(kprn_handle*, const kprn_graph*, const kprn_sampler*, const int32_t*, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t*, int64_t*);
 int kprn_read_candidate_paths(kprn_handle*, int64_t*, int64_t);
 int kprn_host_find_candidates_top(const int32_t*, const int32_t*, const int32_t*, int64_t, int32_t, const int32_t*, int64_t, const int32_t*, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t*, int32_t*, int64_t*);
+/* sampled evaluation groups: each held pair's negatives drawn from the user's rows of the candidate list, the list cut down to the rows some sample needs */
+int kprn_sample_eval_groups(kprn_handle*, const int32_t*, int32_t, const int64_t*, const int32_t*, int32_t, uint64_t, unsigned int, int32_t*, int64_t*, int32_t*, int32_t*, int32_t*);
+int kprn_host_sample_eval_groups(const int32_t*, int64_t, int32_t, const int32_t*, int32_t, const int64_t*, const int32_t*, int32_t, uint64_t, unsigned int, int32_t*, int64_t*, int32_t*, int32_t*, int32_t*, int32_t*);
 /* meta-paths: a graph's pattern set -- only the paths whose relation sequence matches a pattern are found (include/kprn.h "meta-paths") */
 int kprn_graph_set_patterns(kprn_handle*, kprn_graph*, const int32_t*, const int64_t*, const int32_t*, int32_t);
 int kprn_graph_num_patterns(kprn_handle*, const kprn_graph*, int32_t*);

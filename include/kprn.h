@@ -296,7 +296,8 @@ int kprn_recommend_ragged(kprn_handle* h, const int32_t* idx, const int32_t* cou
 int kprn_host_rank_groups(const float* scores, int64_t n_scores, const int64_t* members, const int64_t* group_offsets, const int32_t* pos, int32_t G,
                           int32_t mode, int32_t K, int32_t* ranks, int32_t* topk_idx, float* topk_score, int64_t* hist, int32_t hist_len);
 
-/* ---- ranking targets in groups of any size (an extension: held-out evaluation against everything a user reaches, not against 100 sampled negatives) ----
+/* ---- ranking targets in groups of any size (an extension: held-out evaluation against everything a user reaches; the reference's own protocol, each held
+ * pair against 100 sampled negatives, is "sampled evaluation groups" below and ranks with kprn_rank_groups) ----
  * kprn_rank_groups stops at 4096 members and one positive; in three hops a user reaches most of a catalogue and has several held-out items.  Here a
  * group has any size and any number of TARGETS, and only the targets' places and their histogram come back.
  *  - groups: scores live on the board; group g = members[group_offsets[g] .. group_offsets[g + 1]) as in kprn_rank_groups, members NULL = the
@@ -566,8 +567,8 @@ int kprn_find_training_paths_sampled(kprn_handle* h, const kprn_graph* g, const 
                                      int32_t n_neg, int32_t max_attempts, uint64_t seed, unsigned int draw /* uint32 */, int32_t min_hops, int32_t max_hops,
                                      int32_t max_paths, int32_t T, int32_t walks, int32_t* pairs_out, int32_t* counts, int64_t* found, kprn_batch** out);
 
-/* ---- candidates of a user (an extension: the reference takes its candidates from files of 100 sampled negatives per user, data_prepare/sample.py, which
- * are not restated; here the candidates are the catalogue items the graph reaches from the user) ----
+/* ---- candidates of a user (an extension: the reference takes its candidates from files of 100 sampled negatives per user, data_prepare/sample.py; here
+ * the candidates are the catalogue items the graph reaches from the user, and "sampled evaluation groups" below draws such negatives from them) ----
  * "What should this user get" without a candidate list from the caller: the walk runs from the user outward on the device, deg(u) * deg(a) * deg(b) steps,
  * and leaves the (user, item) rows in HBM, where the finder reads them.
  *  - catalogue: the item list of a kprn_sampler, items [M], ascending entity ids.  Its weights are not looked at: an item of weight 0 is still a member.
@@ -634,6 +635,46 @@ int kprn_read_candidate_paths(kprn_handle* h, int64_t* n_paths_out /* [total] */
 int kprn_host_find_candidates_top(const int32_t* src, const int32_t* dst, const int32_t* rel, int64_t E, int32_t Ve, const int32_t* items, int64_t M,
                                   const int32_t* users, int32_t B, int32_t min_hops, int32_t max_hops, int32_t exclude_adjacent, int32_t cap, int32_t threads,
                                   int32_t* group_counts, int32_t* cand /* [sum] entity ids, or NULL = counts only */, int64_t* n_paths /* [sum] or NULL */);
+
+/* ---- sampled evaluation groups (the reference's evaluation protocol: data_prepare/sample.py draws 100 negatives for every held positive from the user's
+ * non-interacted items that have paths, eval/eval_score.py ranks each positive among its 101) ----
+ * For every held pair of B users: its negatives drawn from the user's rows of the handle's candidate list, the list cut down to the rows some sample needs,
+ * and the rows of every group in the new list -- on the device, the list never visits the host.
+ *  - input: the handle's candidate list as kprn_find_candidates / _top left it: B users' groups of group_counts[b] consecutive rows (u, c), within a user by
+ *    entity id ascending.  Targets: target_items[target_offsets[b] .. target_offsets[b + 1]) are user slot b's held items, entity ids, strictly ascending
+ *    within a user; a user may have none; target_offsets[0] = 0 and NT = target_offsets[B] >= 1.
+ *  - for user slot b with user id u: H = its target items; D = its rows whose item is not in H, d = |D|; a target i is REACHABLE iff i is the item of one
+ *    of the user's rows.  An unreachable target draws nothing.
+ *  - key(u, i, c) = ((uint64)w0 << 32) | (uint32)c, w0 = word 0 of Philox4x32-10 with key (seed & 0xffffffff, seed >> 32) and counter (c, i, u, draw).
+ *    Keys of one sample are distinct because c is.  For a reachable target i: S(u, i) = D if d <= n_neg, else the n_neg rows of D with the smallest keys --
+ *    an exactly uniform draw without replacement, with no attempt limit and no floating point.  The key is a function of ids only: a pair's sample does not
+ *    depend on the user's slot, on how the users are cut into calls, or on the list's layout.  Targets of a user are never each other's negatives.
+ *  - kept rows of a user: the rows of its reachable targets and the union of their S.  The new candidate list is the kept rows in the old order; it
+ *    REPLACES the handle's list.  The companion n_paths array is dropped: kprn_read_candidate_paths is KPRN_E_ARG afterwards; kprn_read_candidates and
+ *    kprn_find_paths_of_candidates work on the new list as on any other.
+ *  - outputs, on the host: new_group_counts [B]; *new_total; target_rows [NT] = the target's row in the new list, -1 = unreachable; neg_rows [NT][n_neg] =
+ *    the rows of S in the new list, ascending, padded with -1; n_drawn [NT] = |S|, 0 for an unreachable target.  [target_rows[k], neg_rows[k][0 .. n_drawn[k])]
+ *    mapped to board lines is a group of kprn_rank_groups' `members` with pos 0.
+ *  - nothing depends on timing: randomness enters only through the keys; membership is a bitmap (a set: set-only atomicOr), the cut is found by counting (a
+ *    radix select over histograms), ranks come from prefix sums, and no atomic hands out a slot.
+ *  - refusals, all decided on the host before anything is allocated or written: KPRN_E_ARG for no list, sum(group_counts) != the list's total, a negative
+ *    count, B < 1, NT < 1, target_offsets[0] != 0 or decreasing, targets not strictly ascending within a user, n_neg outside 1 .. KPRN_RANK_MAX_GROUP - 1
+ *    (4095), NT * (n_neg + 1) >= 2^31, a NULL argument; KPRN_E_INDEX for a target id outside 1..Ve-1 (the Ve of the graph the list was made on).  A refused
+ *    call writes nothing and leaves the list and its path counts as they were.  The new list is written to a block of its own and swapped in only after the
+ *    fill pass's row count agrees with the counting pass's: on a disagreement the call returns KPRN_E_DEVICE and the old list stays.
+ *  - weighted draws (sample.py's alpha != 0, a multinomial whose stream cannot be reproduced) are not restated: the draw is uniform.
+ * Synchronous: the call waits once for the counts (the new list's size) and once for the fill pass's verdict and the results.                          */
+int kprn_sample_eval_groups(kprn_handle* h, const int32_t* group_counts /* [B] */, int32_t B, const int64_t* target_offsets /* [B+1] */,
+                            const int32_t* target_items /* [NT] */, int32_t n_neg, uint64_t seed, unsigned int draw /* uint32 */,
+                            int32_t* new_group_counts /* [B] */, int64_t* new_total, int32_t* target_rows /* [NT] */, int32_t* neg_rows /* [NT][n_neg] */,
+                            int32_t* n_drawn /* [NT] */);
+/* the same rule on the host cores (no handle, no GPU) over a host list [total][2] made on a graph of Ve entities: the same arguments and refusals (a NULL
+ * list with total > 0 is KPRN_E_ARG), and the list's own shape is checked too -- an id outside 1..Ve-1 is KPRN_E_INDEX, a group of more than one user or
+ * items not strictly ascending KPRN_E_ARG.  new_list [*new_total][2] (room for `total` rows always suffices), or NULL = everything but the rows.           */
+int kprn_host_sample_eval_groups(const int32_t* list /* [total][2] */, int64_t total, int32_t Ve, const int32_t* group_counts, int32_t B,
+                                 const int64_t* target_offsets, const int32_t* target_items, int32_t n_neg, uint64_t seed, unsigned int draw,
+                                 int32_t* new_group_counts, int64_t* new_total, int32_t* target_rows, int32_t* neg_rows, int32_t* n_drawn,
+                                 int32_t* new_list /* [new_total][2] or NULL */);
 
 /* ---- training ---------------------------------------------------------------------- */
 /* fEval of MyOptimizer.lua:184-195: zeroGradParameters; forward; BCE; backward.

@@ -474,6 +474,41 @@ def host_find_candidates_top(src, dst, rel, Ve, items, users, min_hops, max_hops
     return cand, gc, n_paths
 
 
+EVAL_MAX_NEG = RANK_MAX_GROUP - 1   # kprn_sample_eval_groups: negatives per held pair (a group of kprn_rank_groups with its positive)
+
+
+def _eval_sample_args(group_counts, target_offsets, target_items, n_neg):
+    """the arrays of kprn_sample_eval_groups / kprn_host_sample_eval_groups; what the C call reads through an array's length is checked here, the rest there"""
+    gc = np.ascontiguousarray(group_counts, np.int32).reshape(-1)
+    toff = np.ascontiguousarray(target_offsets, np.int64).reshape(-1)
+    ti = np.ascontiguousarray(target_items, np.int32).reshape(-1)
+    B, n_neg = int(gc.shape[0]), int(n_neg)
+    if toff.shape[0] != B + 1 or toff[-1] != ti.shape[0]:
+        raise KprnError(E_ARG, "group_counts must be [B] and target_offsets [B+1] end at len(target_items)")
+    NT = int(ti.shape[0])
+    out = dict(group_counts=np.full(B, -3, np.int32), target_rows=np.full(NT, -3, np.int32),
+               neg_rows=np.full((NT, min(max(n_neg, 1), EVAL_MAX_NEG)), -3, np.int32), n_drawn=np.full(NT, -3, np.int32))
+    return gc, toff, ti, B, n_neg, out
+
+
+def host_sample_eval_groups(pairs, Ve, group_counts, target_offsets, target_items, n_neg, seed, draw=0):
+    """kprn_host_sample_eval_groups (no handle, no GPU): the rule of include/kprn.h "sampled evaluation groups" over a host candidate list `pairs`
+    [total, 2] made on a graph of Ve entities -> dict(pairs [new_total, 2] the cut list, group_counts [B], target_rows [NT] (-1: unreachable), neg_rows
+    [NT, n_neg] (rows of the cut list, ascending, -1-padded), n_drawn [NT])"""
+    pr = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+    gc, toff, ti, B, n_neg, out = _eval_sample_args(group_counts, target_offsets, target_items, n_neg)
+    new_list = np.zeros((max(int(pr.shape[0]), 1), 2), np.int32)
+    total = C.c_int64(-3)
+    sd, dr = _seed_draw(seed, draw)
+    rc = lib().kprn_host_sample_eval_groups(_fp(pr) if pr.size else None, C.c_int64(int(pr.shape[0])), int(Ve), _fp(gc), B, _fp(toff), _fp(ti), n_neg, sd, dr,
+                                            _fp(out["group_counts"]), C.byref(total), _fp(out["target_rows"]), _fp(out["neg_rows"]), _fp(out["n_drawn"]),
+                                            _fp(new_list))
+    if rc != 0:
+        raise KprnError(rc, "kprn_host_sample_eval_groups: bad list / group_counts / targets / n_neg")
+    out["pairs"] = new_list[:int(total.value)].copy()
+    return out
+
+
 def host_find_candidates_patterns(src, dst, rel, Ve, items, users, min_hops, max_hops, cap=2**31 - 1, exclude_adjacent=True, patterns=None, threads=1):
     """kprn_host_find_candidates_patterns (no handle, no GPU): host_find_candidates_top where only the paths that match one of `patterns` count (include/kprn.h
     "meta-paths"); cap = 2^31 - 1: the plain candidates; no patterns: exactly host_find_candidates_top -> (cand, group_counts, n_paths)"""
@@ -1197,6 +1232,21 @@ class Engine:
         n_paths = np.zeros(total, np.int64)
         self._ck(self.L.kprn_read_candidate_paths(self.h, _fp(n_paths), C.c_int64(total)))
         return n_paths
+
+    def sample_eval_groups(self, group_counts, target_offsets, target_items, n_neg, seed, draw=0):
+        """kprn_sample_eval_groups + kprn_read_candidates: for every held pair (user slot b, target_items[target_offsets[b] : target_offsets[b + 1]], ascending)
+        up to n_neg negatives drawn from the user's rows of the engine's candidate list (group_counts as find_candidates returned them), on the device; the
+        list is cut down to the rows some sample needs and replaces the engine's (include/kprn.h "sampled evaluation groups") -> dict(pairs [new_total, 2]
+        the cut list, group_counts [B], target_rows [NT] (-1: unreachable), neg_rows [NT, n_neg] (rows of the cut list, ascending, -1-padded), n_drawn [NT])"""
+        gc, toff, ti, B, n_neg, out = _eval_sample_args(group_counts, target_offsets, target_items, n_neg)
+        total = C.c_int64(-3)
+        sd, dr = _seed_draw(seed, draw)
+        self._ck(self.L.kprn_sample_eval_groups(self.h, _fp(gc), B, _fp(toff), _fp(ti), n_neg, sd, dr, _fp(out["group_counts"]), C.byref(total),
+                                                _fp(out["target_rows"]), _fp(out["neg_rows"]), _fp(out["n_drawn"])))
+        self._cand_total = int(total.value)
+        out["pairs"] = np.zeros((self._cand_total, 2), np.int32)
+        self._ck(self.L.kprn_read_candidates(self.h, _fp(out["pairs"]), C.c_int64(self._cand_total)))
+        return out
 
     def find_paths_of_candidates(self, graph, total, min_hops, max_hops, max_paths, T, walks=0, seed=0, draw=0):
         """kprn_find_paths_of_candidates: find_paths over the engine's candidate list (`total` rows, as find_candidates returned them), which never visits

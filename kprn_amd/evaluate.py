@@ -7,10 +7,13 @@ Flags: those of `python -m kprn_amd.score` that shape and load the model (-model
   -kg triples.tsv  -vocab_dir DIR  -interaction_rel R   the graph, its vocabularies, the relation of the user-item edges (as for train -kg)
   -holdout 0.2 [-holdout_seed 1]                        the share held out and the shuffle's seed: give what training was given
   -eval_users N  -max_candidates N                      the first N held-out users only; only each user's N strongest candidates by path count
+  -eval_negatives N                                     the reference's protocol: every held pair against at most N negatives drawn on the device from its
+                                                        user's candidates that it did not interact with (include/kprn.h "sampled evaluation groups"); 0 = all
   -min_hops / -max_hops / -max_paths / -walks / -sampleSeed   the finder's limits (1, 3, 28), as for python -m kprn_amd.recommend
   -meta_paths FILE                                      only the paths whose relation sequence matches a pattern of FILE (graph.parse_meta_paths)
 Output: the two lines of eval_score.py (`hit scores`, `ndcg scores`, k = 1..15), then `samples \\t unreachable \\t zero`: the held pairs evaluated, those
-that never reached the ranking stage (misses), and the zero samples (misses)."""
+that never reached the ranking stage (misses), and the zero samples (misses); with -eval_negatives N > 0 a fourth field `short`: the ranked samples with
+fewer than N negatives."""
 import argparse
 import sys
 
@@ -44,12 +47,13 @@ def main(argv=None, out=sys.stdout):
     eng = model.build_engine(params)
     try:
         res = graph.evaluate_from_graph(eng, train_kg, held, eng.sampler(catalogue), min_hops=args.min_hops, max_hops=params.max_hops, max_paths=params.max_paths,
-                                        walks=params.walks, seed=params.sampleSeed, max_candidates=params.max_candidates, max_users=params.eval_users)
+                                        walks=params.walks, seed=params.sampleSeed, max_candidates=params.max_candidates, max_users=params.eval_users,
+                                        eval_negatives=params.eval_negatives)
     finally:
         eng.close()
     for line in evalrank.format_metric_lines(res["hits"], res["ndcgs"]):
         out.write(line)
-    out.write("%d\t%d\t%d\n" % (res["n"], res["n_unreachable"], res["n_zero"]))
+    out.write("%d\t%d\t%d" % (res["n"], res["n_unreachable"], res["n_zero"]) + ("\t%d" % res["n_short"] if params.eval_negatives > 0 else "") + "\n")
     return 0
 
 

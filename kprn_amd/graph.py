@@ -258,15 +258,20 @@ def _rank_key(scores, mode):
     return np.where(np.isnan(s), -np.inf, s.astype(np.float64))
 
 
-def _score_candidates(eng, graph, sampler, users, min_hops, max_hops, max_paths, T, class_id, walks, seed, draw, exclude_adjacent, max_candidates):
+def _score_candidates(eng, graph, sampler, users, min_hops, max_hops, max_paths, T, class_id, walks, seed, draw, exclude_adjacent, max_candidates, cut=None):
     """The front half of recommend_users and evaluate_from_graph, up to the board put: the users' candidates found on the device (capped at max_candidates by
     path count when that is > 0), the finder reading that list where it lies, the batch scored, its probabilities put on a board of exactly batch.B lines.
+    cut(pairs, group_counts) -> (pairs, group_counts): a stage that replaces the engine's candidate list before the finder reads it (sampled evaluation).
     -> None when no user has a candidate with a path, else (batch, pairs, cand, uoff, found): pair b of the batch is row cand[b] of the candidate list
     `pairs` [n, 2] = (user, item), user g's surviving pairs are the batch's pairs uoff[g] .. uoff[g + 1] = those board lines.  The caller frees the batch."""
     T = max_hops + 1 if T is None else int(T)
     pairs, gc = eng.find_candidates(graph, sampler, users, min_hops, min(int(max_hops), _ffi.FIND_MAX_HOPS), exclude_adjacent, cap=max_candidates)
     if len(pairs) == 0:
         return None
+    if cut is not None:
+        pairs, gc = cut(pairs, gc)
+        if len(pairs) == 0:
+            return None
     batch, counts, found = eng.find_paths_of_candidates(graph, len(pairs), min_hops, max_hops, max_paths, T, walks=walks, seed=seed, draw=draw)
     if batch is None:
         return None
@@ -353,17 +358,66 @@ def recommend_users(eng, kg, sampler, users, K, M=0, min_hops=1, max_hops=3, max
 PLACE_UNREACHABLE = -3   # evaluate_from_graph's place of a held pair that never reached the ranking stage
 
 
+def _rank_sampled(eng, graph, sampler, users, items, ends, n_neg, chain, mode, hist_len, places, hist):
+    """One chunk of evaluate_from_graph under eval_negatives = n_neg: user g's held items are items[ends[g - 1] : ends[g]] (ascending), `chain` the arguments
+    of _score_candidates behind the users.  The candidates, one sample_eval_groups call (seed = chain[6], draw 0) that cuts the list down to the rows some
+    sample needs, the finder on that list, the pass, the board put, one rank_groups call with a members table: every reachable held pair is the group
+    [target, its negatives ascending], pos 0.  Writes the ranks into places (a view: one entry per held item) and adds the histogram to hist
+    -> the ranked samples with fewer than n_neg negatives"""
+    hoff = np.concatenate([[0], ends]).astype(np.int64)
+    drawn = {}
+
+    def cut(pairs, gc):
+        drawn.update(eng.sample_eval_groups(gc, hoff, items, n_neg, chain[6], 0))
+        return drawn["pairs"], drawn["group_counts"]
+    scored = _score_candidates(eng, graph, sampler, users, *chain, cut=cut)
+    if scored is None:
+        return 0
+    batch, pairs, cand, _uoff, _found = scored
+    try:
+        line = np.full(len(pairs), -1, np.int64)            # the board line of every list row; -1: the finder dropped the pair
+        line[cand] = np.arange(len(cand))
+        trow, nd = drawn["target_rows"], drawn["n_drawn"]
+        members, goff, rows, n_short = [], [0], [], 0
+        for k in np.nonzero(trow >= 0)[0]:
+            if line[trow[k]] < 0:
+                continue                                    # a dropped target is unreachable
+            neg = line[drawn["neg_rows"][k, :nd[k]]]
+            neg = neg[neg >= 0]                             # a negative whose pair the finder dropped leaves its group
+            members += [line[trow[k]:trow[k] + 1], neg]
+            goff.append(goff[-1] + 1 + len(neg)); rows.append(k)
+            n_short += len(neg) < n_neg
+        if not rows:
+            return 0
+        res = eng.rank_groups(np.array(goff, np.int64), members=np.concatenate(members), pos=np.zeros(len(rows), np.int32), mode=mode, hist_len=hist_len)
+        places[np.array(rows)] = res["ranks"]
+        hist += res["hist"]
+        return int(n_short)
+    finally:
+        batch.free()
+
+
 def evaluate_from_graph(eng, train_kg, held, sampler, users_per_call=64, min_hops=1, max_hops=3, max_paths=28, T=None, class_id=1, mode=_ffi.RANK_PRINTED, walks=0,
-                        seed=1, max_candidates=0, ks=range(1, 16), max_users=0):
+                        seed=1, max_candidates=0, ks=range(1, 16), max_users=0, eval_negatives=0):
     """Held-out evaluation against everything a user reaches (KnowledgeGraph.holdout made train_kg and held): for the held pairs' distinct users,
     users_per_call at a time (max_users > 0: the first that many users only), the chain of recommend_users up to the board put on the TRAIN graph with
     exclude_adjacent -- so a user's train items are no candidates and its held items are -- and then ONE rank_targets call: the groups are the users'
     surviving pairs, the targets the held items among them, each placed among the user's non-held candidates (include/kprn.h "ranking targets in groups
     of any size").  A held pair that is not there -- its item outside the sampler's catalogue, not reached, cut by max_candidates, or left without a
     kept path -- is a miss for every k: it is counted in hist[hist_len] and reported as n_unreachable.
+    eval_negatives = N > 0: the reference's protocol instead (data_prepare/sample.py, eval/eval_score.py): every held pair is ranked against at most N
+    negatives drawn from its user's candidates that are no held items of that user (include/kprn.h "sampled evaluation groups").  After the candidates
+    (cap included) ONE sample_eval_groups call per chunk with the users' held items, `seed` and draw 0 -- every epoch ranks the same samples -- cuts the
+    list down to the rows some sample needs; only those are given paths and scored; ONE rank_groups call with a members table then ranks every reachable
+    held pair as the group [target, its negatives ascending] with pos 0.  A negative whose pair the finder dropped leaves its group; a dropped target is
+    unreachable.  The held pairs must be distinct.
     -> dict(hits, ndcgs, n (evalrank.metrics_from_hist over the summed histogram), n_unreachable, n_zero, places [m] int32 in the order of `held` (the
-    evaluated rows: place, _ffi.RANK_ZERO_GROUP or PLACE_UNREACHABLE), held [m, 2], hist)."""
+    evaluated rows: place, _ffi.RANK_ZERO_GROUP or PLACE_UNREACHABLE), held [m, 2], hist); with eval_negatives > 0 also n_short = the ranked samples
+    with fewer than N negatives."""
     from . import evalrank
+    eval_negatives = int(eval_negatives)
+    if eval_negatives < 0 or eval_negatives > _ffi.EVAL_MAX_NEG:
+        raise ValueError("eval_negatives must be in 0..%d" % _ffi.EVAL_MAX_NEG)
     graph = train_kg.on(eng) if isinstance(train_kg, KnowledgeGraph) else train_kg
     held = np.ascontiguousarray(held, np.int32).reshape(-1, 2)
     held = held[np.lexsort((held[:, 1], held[:, 0]))]
@@ -380,8 +434,14 @@ def evaluate_from_graph(eng, train_kg, held, sampler, users_per_call=64, min_hop
     last = np.searchsorted(held[:, 0], users, side="right")
     places = np.full(len(held), PLACE_UNREACHABLE, np.int32)
     hist = np.zeros(hist_len + 4, np.int64)
+    n_short = 0
     for lo in range(0, len(users), per):
         us = users[lo:lo + per]
+        if eval_negatives > 0:                              # (the chunk's held rows are consecutive: held[first[lo] : last[lo + len(us) - 1]], user by user)
+            n_short += _rank_sampled(eng, graph, sampler, us, held[first[lo]:last[lo + len(us) - 1], 1], last[lo:lo + len(us)] - first[lo], eval_negatives,
+                                     (min_hops, max_hops, max_paths, T, class_id, walks, seed, 0, True, int(max_candidates)), mode, hist_len,
+                                     places[first[lo]:last[lo + len(us) - 1]], hist)
+            continue
         scored = _score_candidates(eng, graph, sampler, us, min_hops, max_hops, max_paths, T, class_id, walks, seed, 0, True, int(max_candidates))
         if scored is None:
             continue
@@ -408,7 +468,10 @@ def evaluate_from_graph(eng, train_kg, held, sampler, users_per_call=64, min_hop
     n_unreachable = int((places == PLACE_UNREACHABLE).sum())
     hist[hist_len] += n_unreachable
     hits, ndcgs, n = evalrank.metrics_from_hist(hist, hist_len, ks)
-    return dict(hits=hits, ndcgs=ndcgs, n=n, n_unreachable=n_unreachable, n_zero=int(hist[hist_len + 1]), places=places, held=held, hist=hist)
+    out = dict(hits=hits, ndcgs=ndcgs, n=n, n_unreachable=n_unreachable, n_zero=int(hist[hist_len + 1]), places=places, held=held, hist=hist)
+    if eval_negatives > 0:
+        out["n_short"] = int(n_short)
+    return out
 
 
 def groups_from_counts(counts, n_neg):

@@ -68,6 +68,9 @@ def flag_parser():
     a("-holdout_seed", type=int, default=1, help="seed of the split's shuffle")
     a("-eval_users", type=int, default=0, help="evaluate the first N held-out users only (0 = all)")
     a("-max_candidates", type=int, default=0, help="evaluation ranks among each user's N strongest candidates by path count only (0 = all of them)")
+    a("-eval_negatives", type=int, default=0, help="with -holdout: every held pair is ranked against at most N negatives drawn on the device from its user's "
+      "candidates (the reference's sample.py / eval_score.py protocol with N = 100; the engine's \"sampled evaluation groups\"), at most 4095; 0 = against "
+      "everything the user reaches")
     a("-meta_paths", default="", help="with -kg: a file of relation-sequence patterns, one per line (graph.parse_meta_paths: positions separated by blanks, "
       "a position `*` or relation names joined by `|`); only the paths that match one are found, as candidates, for training and for evaluation")
     a("-gamma", type=float, default=None, help="temperature of the LogSumExp reducer, the paper's log sum exp(s / gamma), in 0.001 .. 1000 (the engine's option "
@@ -125,6 +128,10 @@ def parse_flags(argv=None, gamma_beside="-topK"):
         p.error("-holdout needs -kg: it splits the graph's -interaction_rel edges")
     if not 0 <= params.max_candidates <= 2**31 - 1 or params.eval_users < 0:
         p.error("-max_candidates must be in 0 .. 2^31 - 1 and -eval_users >= 0")
+    if not 0 <= params.eval_negatives <= _ffi.EVAL_MAX_NEG:
+        p.error("-eval_negatives must be in 0 .. %d" % _ffi.EVAL_MAX_NEG)
+    if params.eval_negatives > 0 and params.holdout <= 0:
+        p.error("-eval_negatives needs -holdout: it draws the negatives of the held pairs")
     return params
 
 

@@ -14,6 +14,8 @@ and keeps the -negatives that score highest, their rows taken from the scored ba
 -holdout 0.2 [-holdout_seed 1 -eval_users 0 -max_candidates N] (with -kg) holds that share of the interactions out (KnowledgeGraph.holdout), trains on the
 rest -- positives, catalogue, weights and paths are the train graph's -- and every -evaluationFrequency epochs ranks the held pairs among everything
 their users reach (graph.evaluate_from_graph): the evaluation line of -rank_samples, plus the held pairs that never reached the ranking stage.
+-eval_negatives N (with -holdout) ranks every held pair against at most N negatives drawn on the device from its user's candidates instead (the reference's
+sample.py / eval_score.py protocol; include/kprn.h "sampled evaluation groups"); the line then ends with the samples that got fewer than N.
 -meta_paths FILE (with -kg) keeps only the paths whose relation sequence matches a pattern of FILE (graph.parse_meta_paths; include/kprn.h "meta-paths"), in
 training and in the -holdout evaluation.
 """
@@ -62,11 +64,12 @@ def make_graph_evaluator(eng, params, train_kg, held, sampler, log=None):
 
     def evaluator(i):
         res = graph.evaluate_from_graph(eng, train_kg, held, sampler, min_hops=params.min_hops, max_hops=params.max_hops, max_paths=params.max_paths,
-                                        walks=params.walks, seed=params.sampleSeed, max_candidates=params.max_candidates, max_users=params.eval_users)
+                                        walks=params.walks, seed=params.sampleSeed, max_candidates=params.max_candidates, max_users=params.eval_users,
+                                        eval_negatives=params.eval_negatives)
         hits, ndcgs = res["hits"], res["ndcgs"]
         print("evaluation at epoch %d over %d samples: " % (i, res["n"]) +
-              "  ".join("hit@%d %.5f ndcg@%d %.5f" % (k, hits[k], k, ndcgs[k]) for k in (1, 5, 10, 15)) + "  unreachable %d" % res["n_unreachable"],
-              file=log or sys.stdout)
+              "  ".join("hit@%d %.5f ndcg@%d %.5f" % (k, hits[k], k, ndcgs[k]) for k in (1, 5, 10, 15)) + "  unreachable %d" % res["n_unreachable"] +
+              ("  short %d" % res["n_short"] if params.eval_negatives > 0 else ""), file=log or sys.stdout)
         return res
     return evaluator
 
