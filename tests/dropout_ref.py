@@ -47,10 +47,12 @@ def keep_mask(seed, draw, layer, T, N, Din, p):
 
 
 def forward_backward(lay, cfg, theta, idx, labels, masks, s, class_id=1):
-    """lay: Oracle.layout(); cfg: the oracle's Cfg (rnn_type 1, F = 3, one type slot, reducer LogSumExp); theta float64 flat; idx [B, P, T, 3] 1-based;
+    """lay: Oracle.layout(); cfg: the oracle's Cfg (rnn_type 1, reducer LogSumExp; numTypes type slots whose rows are summed -- CAddTable, FeatureEmbedding.lua:55 --
+    in the columns before entity and relation, the mask on the summed row); theta float64 flat; idx [B, P, T, F] 1-based;
     masks: per layer a bool / 0-1 array [T, N, Din] (N = B P, path n = b P + p); s: the kept elements' factor -> loss, flat gradient (float64), probs [B]"""
     import torch
-    assert cfg.rnn_type == 1 and cfg.F == 3 and cfg.numTypes == 1 and cfg.reducer == 2
+    F, nT = cfg.F, cfg.numTypes
+    assert cfg.rnn_type == 1 and nT >= 1 and F >= nT + 2 and cfg.reducer == 2
     th = torch.tensor(np.asarray(theta, np.float64), dtype=torch.float64, requires_grad=True)
 
     def par(name):
@@ -60,8 +62,10 @@ def forward_backward(lay, cfg, theta, idx, labels, masks, s, class_id=1):
     idx = np.asarray(idx)
     B, P, T, _ = idx.shape
     N = B * P
-    ids = torch.tensor(idx.reshape(N, T, 3).astype(np.int64)) - 1
-    x = torch.cat([par("type_emb")[ids[:, :, 0]], par("entity_emb")[ids[:, :, 1]], par("relation_emb")[ids[:, :, 2]]], dim=2)   # [N, T, D]
+    assert idx.shape[3] == F
+    ids = torch.tensor(idx.reshape(N, T, F).astype(np.int64)) - 1
+    types = sum(par("type_emb")[ids[:, :, F - nT - 2 + k]] for k in range(nT))
+    x = torch.cat([types, par("entity_emb")[ids[:, :, F - 2]], par("relation_emb")[ids[:, :, F - 1]]], dim=2)   # [N, T, D]
     inp = x.permute(1, 0, 2)   # [T, N, D]
     for l in range(cfg.L):
         Wi, bi = par(f"rnn{l + 1}.i2h.weight"), par(f"rnn{l + 1}.i2h.bias")
