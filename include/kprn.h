@@ -439,6 +439,47 @@ int kprn_host_find_paths(const int32_t* src, const int32_t* dst, const int32_t* 
                          int32_t num_types, int32_t end_relation, const int32_t* pairs, int32_t B, int32_t min_hops, int32_t max_hops, int32_t max_paths,
                          int32_t T, int32_t F, int32_t threads, int32_t* counts, int64_t* found, int32_t* idx);
 
+/* ---- updating a graph in place (an extension: the reference rebuilds its pickled dictionaries from the rating file for every change) ----
+ * A recommender's graph never stands still: an interaction is a new rate / _rate edge, a withdrawn item a set of removed ones.  kprn_graph_update edits a
+ * stored graph by merging a sorted delta into the sorted CSR -- one streaming pass over the E stored edges instead of the build's sorts over them.
+ *  - result: with S = the edges g stores, D = the stored edges the removals name and A = the additions less self-loops, duplicates collapsed, g stores
+ *    afterwards exactly what kprn_graph_create stores for the edge set (S \ D) u A: rowptr, col, rel (kprn_graph_read) and kprn_graph_num_edges are the same
+ *    bits as a fresh build's, and so is the answer of every find, candidates and sampler call on g.
+ *  - order inside one call: removals first, then additions.  An edge named in both is stored afterwards.
+ *  - removals (del_src[k], del_dst[k], del_rel[k]), k < n_del: del_rel in 1 .. Vr names that one edge; del_rel == 0 names every stored edge
+ *    del_src -> del_dst, whatever its relation.  Removing an edge that is not stored is a no-op; a removal may be listed twice.
+ *  - additions (add_src[k], add_dst[k], add_rel[k]), k < n_add, in any order: adding a stored edge is a no-op, self-loops are dropped as the build drops them.
+ *  - counts (either may be NULL): *n_added = the edges of A that are not in S \ D, *n_removed = the edges of S in D.  E_new = E + n_added - n_removed always
+ *    holds: an edge that is removed and added again counts in both.
+ *  - limits: n_add = n_del = 0 is KPRN_OK and changes nothing; an empty graph may be added to; every edge may be removed (E = 0).
+ *  - refusals, made on the host before anything is queued; a refused call leaves the graph untouched, bit for bit: g not a graph of h, n_add or n_del
+ *    outside 0 .. 2^31 - 1, a NULL array with a positive count: KPRN_E_ARG; a node outside 1 .. Ve-1, an added relation outside 1 .. Vr, a removed relation
+ *    outside 0 .. Vr: KPRN_E_INDEX.  E_new > 2^31 - 1 is KPRN_E_ARG: it is known after the counting pass, before any array of g is written or replaced.  If
+ *    the merge places another number of edges than the counting pass found, or any of them outside [0, E_new), the call is KPRN_E_DEVICE and the old
+ *    arrays stay in place.  Nothing depends on timing: every edge's place is a rank from two prefix sums, never an atomic counter.
+ *  - what survives: the pattern set of kprn_graph_set_patterns (its table depends on Vr only), the node types, end_relation.  Batches and candidate lists
+ *    found earlier are copies and stay valid.
+ *  - synchronisation: synchronous.  The call waits for everything queued on the handle's streams before it swaps the arrays, and frees the old ones
+ *    afterwards.  It needs device memory for the new col / rel beside the old ones, 5 E bytes of temporaries and the delta's sort.                          */
+int kprn_graph_update(kprn_handle* h, kprn_graph* g, const int32_t* add_src, const int32_t* add_dst, const int32_t* add_rel, int64_t n_add,
+                      const int32_t* del_src, const int32_t* del_dst, const int32_t* del_rel, int64_t n_del, int64_t* n_added, int64_t* n_removed);
+/* the CSR as stored, back on the host: rowptr [Ve + 1] by 1-based node id (the edges of node n are rowptr[n] .. rowptr[n + 1] - 1; node 0 has none), col [E]
+ * the destinations and rel [E] the relations, E = kprn_graph_num_edges (col and rel may be NULL when E == 0).  It is what makes the equality above testable,
+ * and how a caller checkpoints an updated graph: (the source of each row, col, rel) given to kprn_graph_create builds the same graph.  Synchronous.       */
+int kprn_graph_read(kprn_handle* h, const kprn_graph* g, int32_t* rowptr /* [Ve + 1] */, int32_t* col /* [E] */, int32_t* rel /* [E] */);
+/* replaces the type rows of n entities -- a node that first appears in a delta still has the row the graph was created with: rows [k] = the num_types slot
+ * ids of entities [k], as kprn_graph_create's node_types holds them.  A plain row copy on the handle's stream, behind the calls queued before it;
+ * synchronous.  An entity outside 1 .. Ve-1 or a type id outside 1 .. Vt is KPRN_E_INDEX, an entity listed twice or n outside 0 .. Ve-1 KPRN_E_ARG; a
+ * refused call writes nothing.                                                                                                                          */
+int kprn_graph_set_node_types(kprn_handle* h, kprn_graph* g, const int32_t* entities /* [n] */, const int32_t* rows /* [n][num_types] */, int64_t n);
+/* the same rule on the host over raw arrays (no handle, no GPU): (src, dst, rel) [E] is an edge list in any order, as kprn_graph_create takes it; the result
+ * is the CSR of the updated graph: rowptr [Ve + 1], col and rel_out with room for E + n_add entries of which *E_out are written, and the two counts (either
+ * may be NULL), which are taken against the stored set S -- the list less duplicates and self-loops.  The refusals are kprn_graph_update's, plus
+ * kprn_graph_create's for E, Ve, Vr and the edges' ids and KPRN_E_ARG for a NULL rowptr, col, rel_out or E_out; a refused call writes no output.          */
+int kprn_host_graph_update(const int32_t* src, const int32_t* dst, const int32_t* rel, int64_t E, int32_t Ve, int32_t Vr, const int32_t* add_src,
+                           const int32_t* add_dst, const int32_t* add_rel, int64_t n_add, const int32_t* del_src, const int32_t* del_dst, const int32_t* del_rel,
+                           int64_t n_del, int32_t* rowptr, int32_t* col, int32_t* rel_out, int64_t* E_out, int64_t* n_added, int64_t* n_removed);
+
 /* ---- sampled paths of four and five hops (an extension: the reference extends a three-hop path twice, data_prepare/path_find_depth_5.py, by sampling a few
  * neighbours of the last item and one random item behind each; its draws, Python's random, cannot be reproduced and are not restated) ----
  * The *_sampled calls accept 1 <= min_hops <= max_hops <= 5.  Hops 1..3 stay exhaustive, exactly as above.  Hops h in {4, 5} are sampled: a random prefix of

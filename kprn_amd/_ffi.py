@@ -354,6 +354,43 @@ def host_find_paths_cap(src, dst, rel, node_types, Vr, Vt, end_relation, pairs, 
 PATTERN_MAX, PATTERN_MAX_HOPS = 32, 5   # KPRN_PATTERN_MAX; a pattern's positions (include/kprn.h "meta-paths")
 
 
+def _delta_array(d):
+    """a delta's additions or removals: [n, 3] int32 rows of (src, dst, rel); None or empty: no rows"""
+    if d is None:
+        return np.zeros((0, 3), np.int32)
+    d = np.ascontiguousarray(d, np.int32)
+    if d.size == 0:
+        return np.zeros((0, 3), np.int32)
+    if d.ndim != 2 or d.shape[1] != 3:
+        raise KprnError(E_ARG, "a delta is [n, 3] = (src, dst, rel)")
+    return d
+
+
+def _delta_args(adds, removes):
+    """the six delta arguments of kprn_graph_update / kprn_host_graph_update (the columns as arrays of their own, kept alive by the returned list)"""
+    cols = [np.ascontiguousarray(d[:, k]) for d in (_delta_array(adds), _delta_array(removes)) for k in range(3)]
+    a, r = cols[:3], cols[3:]
+    return cols, ([_fp(c) if len(c) else None for c in a] + [C.c_int64(len(a[0]))] + [_fp(c) if len(c) else None for c in r] + [C.c_int64(len(r[0]))])
+
+
+def host_graph_update(src, dst, rel, Ve, Vr, adds=None, removes=None):
+    """kprn_host_graph_update (no handle, no GPU): the update rule of include/kprn.h "updating a graph in place" over an edge list in any order ->
+    (rowptr [Ve + 1], col [E_new], rel [E_new], n_added, n_removed): the CSR kprn_graph_create stores for the updated edge set"""
+    src, dst, rel = (np.ascontiguousarray(a, np.int32).reshape(-1) for a in (src, dst, rel))
+    if not (src.shape == dst.shape == rel.shape):
+        raise KprnError(E_ARG, "a graph is src / dst / rel [E]")
+    keep, args = _delta_args(adds, removes)
+    room = int(src.shape[0]) + len(keep[0])
+    rowptr, col, rel_out = np.zeros(int(Ve) + 1 if int(Ve) >= 0 else 1, np.int32), np.zeros(room + 1, np.int32), np.zeros(room + 1, np.int32)
+    E_out, n_added, n_removed = C.c_int64(-1), C.c_int64(-1), C.c_int64(-1)
+    rc = lib().kprn_host_graph_update(_fp(src), _fp(dst), _fp(rel), C.c_int64(int(src.shape[0])), int(Ve), int(Vr), *args, _fp(rowptr), _fp(col), _fp(rel_out),
+                                      C.byref(E_out), C.byref(n_added), C.byref(n_removed))
+    if rc != 0:
+        raise KprnError(rc, "kprn_host_graph_update: bad graph ids / delta ids / sizes")
+    n = int(E_out.value)
+    return rowptr, col[:n].copy(), rel_out[:n].copy(), int(n_added.value), int(n_removed.value)
+
+
 def _pattern_arrays(patterns):
     """patterns: a list of patterns, each a list of positions, each an iterable of relation ids or None / empty for any -> the four pattern arguments of
     kprn_graph_set_patterns: (hops [n] int32, set_offsets [S + 1] int64, set_rels int32, n); None or an empty list: (None, None, None, 0)"""
@@ -801,6 +838,32 @@ class Graph:
         n = C.c_int64()
         self.engine._ck(self.engine.L.kprn_graph_num_edges(self.engine.h, self.ptr, C.byref(n)))
         return int(n.value)
+
+    def update(self, adds=None, removes=None):
+        """kprn_graph_update (include/kprn.h "updating a graph in place"): adds / removes are [n, 3] int32 rows of (src, dst, rel); the removals apply first;
+        a removal's rel 0 names every stored edge src -> dst.  Afterwards the graph stores what a fresh build of the edited edge set stores, bit for bit.
+        A refused call leaves the graph untouched -> (n_added, n_removed)"""
+        keep, args = _delta_args(adds, removes)
+        n_added, n_removed = C.c_int64(), C.c_int64()
+        self.engine._ck(self.engine.L.kprn_graph_update(self.engine.h, self.ptr, *args, C.byref(n_added), C.byref(n_removed)))
+        return int(n_added.value), int(n_removed.value)
+
+    def read_csr(self):
+        """kprn_graph_read: the CSR as stored -> (rowptr [Ve + 1], col [E], rel [E]) int32"""
+        E = self.n_edges
+        rowptr, col, rel = np.zeros(self.engine.cfg.Ve + 1, np.int32), np.zeros(E, np.int32), np.zeros(E, np.int32)
+        self.engine._ck(self.engine.L.kprn_graph_read(self.engine.h, self.ptr, _fp(rowptr), _fp(col) if E else None, _fp(rel) if E else None))
+        return rowptr, col, rel
+
+    def set_node_types(self, entities, rows):
+        """kprn_graph_set_node_types: the type rows of `entities` [n] become rows [n, num_types] (a node that first appears in a delta has the row the
+        graph was created with)"""
+        ent = np.ascontiguousarray(entities, np.int32).reshape(-1)
+        rows = np.ascontiguousarray(rows, np.int32)
+        if rows.shape != (ent.shape[0], self.engine.cfg.num_types):
+            raise KprnError(E_ARG, "rows must be [n, num_types] for entities [n]")
+        self.engine._ck(self.engine.L.kprn_graph_set_node_types(self.engine.h, self.ptr, _fp(ent) if len(ent) else None, _fp(rows) if len(ent) else None,
+                                                                C.c_int64(len(ent))))
 
     def set_patterns(self, patterns):
         """kprn_graph_set_patterns (include/kprn.h "meta-paths"): from the next call on, every device call that takes this graph sees only the paths whose

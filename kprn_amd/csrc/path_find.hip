@@ -259,19 +259,41 @@ __global__ void k_rowptr(const unsigned long long* __restrict__ key, int64_t E, 
 }
 
 static int bits_for(int64_t v) { int b = 1; while (b < 63 && ((int64_t)1 << b) <= v) ++b; return b; }
-static unsigned blocks_for(int64_t n) { return (unsigned)((n + TPB - 1) / TPB); }
 
-// temporaries of one build, freed whatever happens
-struct Tmp {
-  std::vector<void*> v;
-  ~Tmp() { for (void* p : v) hipFree(p); }
-  template <typename T> T* get(int64_t n) {
-    void* p = nullptr;
-    if (kprn_dev_malloc(&p, (size_t)std::max<int64_t>(n, 1) * sizeof(T)) != hipSuccess) throw KprnError{KPRN_E_NOMEM, "hipMalloc failed (graph build)"};
-    v.push_back(p);
-    return (T*)p;
-  }
-};
+// The build's order and its dedupe over E edges already in HBM (shared with graph_update.hip, which runs it over a delta's additions): on return, once the
+// stream has drained, *n_out [0] = the edges kept = the input's less self-loops and exact duplicates, in (src, dst, rel) order: *key_out [k] = src << 32 | dst,
+// d_src [k] = the destination, d_dst [k] = the relation (the inputs are consumed).  Every block comes from tmp
+void sort_dedupe(Tmp& tmp, hipStream_t s, int32_t* d_src, int32_t* d_dst, int32_t* d_rel, int64_t E, int32_t Ve, int32_t Vr, unsigned long long** key_out,
+                 int32_t** n_out) {
+  unsigned long long* key0 = tmp.get<unsigned long long>(E); unsigned long long* key1 = tmp.get<unsigned long long>(E);
+  unsigned long long* key2 = tmp.get<unsigned long long>(E);
+  int32_t* rel1 = tmp.get<int32_t>(E); int32_t* rel2 = tmp.get<int32_t>(E);
+  int32_t* keep = tmp.get<int32_t>(E); int32_t* col2 = tmp.get<int32_t>(E);
+  int32_t* d_n = tmp.get<int32_t>(4);
+  hipLaunchKernelGGL(k_edge_keys, dim3(blocks_for(E)), dim3(TPB), 0, s, d_src, d_dst, E, key0);
+  HIP_TRY(hipGetLastError());
+  // (src, dst, rel) order from two stable passes: by relation, then by (src, dst)
+  const int rbits = bits_for(Vr), kbits = 32 + bits_for(Ve);
+  size_t need1 = 0, need2 = 0, need3 = 0;
+  HIP_TRY(rocprim::radix_sort_pairs(nullptr, need1, (uint32_t*)d_rel, (uint32_t*)rel1, key0, key1, (size_t)E, 0, rbits, s));
+  HIP_TRY(rocprim::radix_sort_pairs(nullptr, need2, key1, key2, rel1, rel2, (size_t)E, 0, kbits, s));
+  HIP_TRY(rocprim::select(nullptr, need3, key2, keep, key0, d_n, (size_t)E, s));
+  size_t need4 = 0;
+  HIP_TRY(rocprim::select(nullptr, need4, col2, keep, d_src, d_n, (size_t)E, s));
+  const size_t need = std::max(std::max(need1, need2), std::max(need3, need4));
+  char* work = tmp.get<char>((int64_t)need);
+  size_t nb = need;
+  HIP_TRY(rocprim::radix_sort_pairs(work, nb, (uint32_t*)d_rel, (uint32_t*)rel1, key0, key1, (size_t)E, 0, rbits, s));
+  nb = need;
+  HIP_TRY(rocprim::radix_sort_pairs(work, nb, key1, key2, rel1, rel2, (size_t)E, 0, kbits, s));
+  hipLaunchKernelGGL(k_keep, dim3(blocks_for(E)), dim3(TPB), 0, s, key2, rel2, E, keep, col2);
+  HIP_TRY(hipGetLastError());
+  // compaction: the stored key (for rowptr), destination and relation of every kept edge (d_src / d_dst are free again)
+  nb = need; HIP_TRY(rocprim::select(work, nb, key2, keep, key0, d_n, (size_t)E, s));
+  nb = need; HIP_TRY(rocprim::select(work, nb, col2, keep, d_src, d_n, (size_t)E, s));
+  nb = need; HIP_TRY(rocprim::select(work, nb, rel2, keep, d_dst, d_n, (size_t)E, s));
+  *key_out = key0; *n_out = d_n;
+}
 
 // the refusals shared by kprn_graph_create and the host twin
 static int validate_graph(const int32_t* src, const int32_t* dst, const int32_t* rel, int64_t E, const int32_t* node_types, int32_t Ve, int32_t Vr, int32_t Vt,
@@ -326,36 +348,12 @@ static kprn_graph* build_graph(kprn_handle* h, const int32_t* src, const int32_t
     }
     Tmp tmp;
     int32_t* d_src = tmp.get<int32_t>(E); int32_t* d_dst = tmp.get<int32_t>(E); int32_t* d_rel = tmp.get<int32_t>(E);
-    unsigned long long* key0 = tmp.get<unsigned long long>(E); unsigned long long* key1 = tmp.get<unsigned long long>(E);
-    unsigned long long* key2 = tmp.get<unsigned long long>(E);
-    int32_t* rel1 = tmp.get<int32_t>(E); int32_t* rel2 = tmp.get<int32_t>(E);
-    int32_t* keep = tmp.get<int32_t>(E); int32_t* col2 = tmp.get<int32_t>(E);
-    int32_t* d_n = tmp.get<int32_t>(4);
     HIP_TRY(hipMemcpyAsync(d_src, src, (size_t)E * sizeof(int32_t), hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(d_dst, dst, (size_t)E * sizeof(int32_t), hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(d_rel, rel, (size_t)E * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_edge_keys, dim3(blocks_for(E)), dim3(TPB), 0, s, d_src, d_dst, E, key0);
-    HIP_TRY(hipGetLastError());
-    // (src, dst, rel) order from two stable passes: by relation, then by (src, dst)
-    const int rbits = bits_for(c.Vr), kbits = 32 + bits_for(c.Ve);
-    size_t need1 = 0, need2 = 0, need3 = 0;
-    HIP_TRY(rocprim::radix_sort_pairs(nullptr, need1, (uint32_t*)d_rel, (uint32_t*)rel1, key0, key1, (size_t)E, 0, rbits, s));
-    HIP_TRY(rocprim::radix_sort_pairs(nullptr, need2, key1, key2, rel1, rel2, (size_t)E, 0, kbits, s));
-    HIP_TRY(rocprim::select(nullptr, need3, key2, keep, key0, d_n, (size_t)E, s));
-    size_t need4 = 0;
-    HIP_TRY(rocprim::select(nullptr, need4, col2, keep, d_src, d_n, (size_t)E, s));
-    const size_t need = std::max(std::max(need1, need2), std::max(need3, need4));
-    char* work = tmp.get<char>((int64_t)need);
-    size_t nb = need;
-    HIP_TRY(rocprim::radix_sort_pairs(work, nb, (uint32_t*)d_rel, (uint32_t*)rel1, key0, key1, (size_t)E, 0, rbits, s));
-    nb = need;
-    HIP_TRY(rocprim::radix_sort_pairs(work, nb, key1, key2, rel1, rel2, (size_t)E, 0, kbits, s));
-    hipLaunchKernelGGL(k_keep, dim3(blocks_for(E)), dim3(TPB), 0, s, key2, rel2, E, keep, col2);
-    HIP_TRY(hipGetLastError());
-    // compaction: the stored key (for rowptr), destination and relation of every kept edge (d_src / d_dst are free again)
-    nb = need; HIP_TRY(rocprim::select(work, nb, key2, keep, key0, d_n, (size_t)E, s));
-    nb = need; HIP_TRY(rocprim::select(work, nb, col2, keep, d_src, d_n, (size_t)E, s));
-    nb = need; HIP_TRY(rocprim::select(work, nb, rel2, keep, d_dst, d_n, (size_t)E, s));
+    unsigned long long* key0 = nullptr;
+    int32_t* d_n = nullptr;
+    sort_dedupe(tmp, s, d_src, d_dst, d_rel, E, c.Ve, c.Vr, &key0, &d_n);
     int32_t n_kept = 0;
     HIP_TRY(hipMemcpyAsync(&n_kept, d_n, sizeof(int32_t), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));

@@ -173,14 +173,37 @@ KPRN_HD int64_t keep_lower(const Keep& k, int64_t r, int64_t from = 0) {
   return l;
 }
 
+// ---- the build's pieces that an update of the graph runs again over its delta (path_find.hip; graph_update.hip) ----
+static inline unsigned blocks_for(int64_t n) { return (unsigned)((n + TPB - 1) / TPB); }
+// temporaries of one build or update, freed whatever happens
+struct Tmp {
+  std::vector<void*> v;
+  ~Tmp() { for (void* p : v) hipFree(p); }
+  template <typename T> T* get(int64_t n) {
+    void* p = nullptr;
+    if (kprn_dev_malloc(&p, (size_t)std::max<int64_t>(n, 1) * sizeof(T)) != hipSuccess) throw KprnError{KPRN_E_NOMEM, "hipMalloc failed (graph build)"};
+    v.push_back(p);
+    return (T*)p;
+  }
+};
+// the build's order and dedupe over E >= 1 edges already in HBM: see path_find.hip
+void sort_dedupe(Tmp& tmp, hipStream_t s, int32_t* d_src, int32_t* d_dst, int32_t* d_rel, int64_t E, int32_t Ve, int32_t Vr, unsigned long long** key_out,
+                 int32_t** n_out);
+
 // ---- host twins: the same rule over a CSR built by std::sort --------------------------------------------------------------------------------
-struct HostCsr { std::vector<int32_t> rowptr, col, rel; };
-static inline HostCsr host_csr(const int32_t* src, const int32_t* dst, const int32_t* rel, int64_t E, int32_t Ve) {
-  std::vector<std::tuple<int32_t, int32_t, int32_t>> ed;
+// the build rule: the edges less self-loops and exact duplicates, ascending by (src, dst, rel)
+typedef std::tuple<int32_t, int32_t, int32_t> HostEdge;
+static inline std::vector<HostEdge> host_edges(const int32_t* src, const int32_t* dst, const int32_t* rel, int64_t E) {
+  std::vector<HostEdge> ed;
   ed.reserve((size_t)E);
   for (int64_t e = 0; e < E; ++e) if (src[e] != dst[e]) ed.emplace_back(src[e], dst[e], rel[e]);
   std::sort(ed.begin(), ed.end());
   ed.erase(std::unique(ed.begin(), ed.end()), ed.end());
+  return ed;
+}
+struct HostCsr { std::vector<int32_t> rowptr, col, rel; };
+static inline HostCsr host_csr(const int32_t* src, const int32_t* dst, const int32_t* rel, int64_t E, int32_t Ve) {
+  const std::vector<HostEdge> ed = host_edges(src, dst, rel, E);
   HostCsr g;
   g.rowptr.assign((size_t)Ve + 2, 0);
   g.col.resize(ed.size() + 1); g.rel.resize(ed.size() + 1);

@@ -122,6 +122,31 @@ class KnowledgeGraph:
                                self.patterns)
         return train, held
 
+    def apply(self, adds=None, removes=None, node_types=None):
+        """A delta applied to this graph and to every device copy of it (include/kprn.h "updating a graph in place"): adds / removes are [n, 3] int32 rows of
+        (src, dst, rel) entity and relation ids; the removals apply first, a removal's rel 0 names every stored edge src -> dst.  node_types (optional):
+        (entities [n], rows [n, num_types]) -- the type rows of nodes that first appear in the delta (read_delta returns them).
+        The host arrays src / dst / rel become the updated edge set in stored order (the host twin, kprn_host_graph_update: duplicates and self-loops are
+        gone), so interactions(), item_weights() and holdout() see the new graph; every device copy made by .on(eng) is edited with one Graph.update.  A
+        delta the rule refuses raises before anything changes.  `patterns` is untouched.  -> (n_added, n_removed)"""
+        rowptr, col, rel, n_added, n_removed = _ffi.host_graph_update(self.src, self.dst, self.rel, self.Ve, self.Vr, adds, removes)
+        if node_types is not None:
+            ent = np.ascontiguousarray(node_types[0], np.int32).reshape(-1)
+            rows = np.ascontiguousarray(node_types[1], np.int32).reshape(len(ent), self.num_types)
+            if len(ent) and (ent.min() < 1 or ent.max() >= self.Ve or rows.min() < 1 or rows.max() > self.Vt or len(np.unique(ent)) != len(ent)):
+                raise ValueError("node_types: distinct entities in 1..Ve-1 and type ids in 1..Vt")
+        live = [g for g in self._device.values() if g.ptr and g.engine.h]
+        for g in live:
+            if node_types is not None and len(ent):
+                g.set_node_types(ent, rows)
+            if g.update(adds, removes) != (n_added, n_removed):
+                raise RuntimeError("a device copy of the graph was out of step with the host arrays")
+        if node_types is not None and len(ent):
+            self.node_types[ent - 1] = rows
+        self.src = np.repeat(np.arange(self.Ve, dtype=np.int32), np.diff(rowptr))
+        self.dst, self.rel = col, rel
+        return n_added, n_removed
+
     def host_find_paths(self, pairs, min_hops, max_hops, max_paths, T, F=None, threads=1, want_idx=True, walks=0, seed=0, draw=0, cap="first"):
         """walks > 0: the hops past 3 sampled (_ffi.host_find_paths_sampled); cap = "spread": the cap keeps a spread of a pair's paths under (seed, draw)
         (_ffi.host_find_paths_cap); with `patterns` set, only the matching paths (_ffi.host_find_paths_patterns)"""
@@ -177,6 +202,45 @@ def read_triples(path):
             parts = line.rstrip("\n").split("\t")
             if len(parts) >= 3:
                 yield parts[0], parts[1], parts[2]
+
+
+def read_delta(path, kg):
+    """A delta file for KnowledgeGraph.apply: one change per line, `+\thead\trelation\ttail` adds an edge and `-\thead\trelation\ttail` removes one;
+    relation `*` on a `-` line stands for every relation between the two; blank lines and lines that start with `#` are skipped.  Names are resolved as
+    from_triples resolves them (unknown ones fall back to #UNK_ENTITY / #UNK_RELATION); a head or tail of a `+` line that kg has not seen -- its type row
+    is still the pad row -- gets the row PathFormatter prints for it.  A malformed line, or `*` on a `+` line, raises ValueError naming the line number.
+    -> (adds [n, 3], removes [m, 3], (entities [k], rows [k, num_types])): the arguments of KnowledgeGraph.apply"""
+    vocabs = kg.vocabs
+    fmt = PathFormatter(vocabs, 0, kg.num_types)
+    unk_rel = int(vocabs.relation["#UNK_RELATION"]) + 1
+    adds, removes, new = [], [], {}
+
+    def node(name, added):
+        feat = fmt._feature(name, "#END_RELATION").split(",")
+        e = int(feat[kg.num_types]) + 1
+        if added and e not in new and 1 <= e < kg.Ve and (kg.node_types[e - 1] == kg.Vt).all():
+            new[e] = [int(t) + 1 for t in feat[:kg.num_types]]
+        return e
+
+    with open(path) as f:
+        for no, line in enumerate(f, 1):
+            line = line.rstrip("\r\n")
+            if not line.strip() or line.startswith("#"):
+                continue
+            parts = line.split("\t")
+            if len(parts) != 4 or parts[0] not in ("+", "-") or not all(parts[1:]):
+                raise ValueError("delta line %d: expected `+|-<TAB>head<TAB>relation<TAB>tail`" % no)
+            sign, head, r, tail = parts
+            if r == "*":
+                if sign == "+":
+                    raise ValueError("delta line %d: `*` stands for every relation on a `-` line only" % no)
+                rid = 0
+            else:
+                rid = int(vocabs.relation[r]) + 1 if r in vocabs.relation else unk_rel
+            (adds if sign == "+" else removes).append((node(head, sign == "+"), node(tail, sign == "+"), rid))
+    ent = np.array(sorted(new), np.int32)
+    rows = np.array([new[e] for e in sorted(new)], np.int32).reshape(len(ent), kg.num_types)
+    return np.array(adds, np.int32).reshape(-1, 3), np.array(removes, np.int32).reshape(-1, 3), (ent, rows)
 
 
 class path_cap:

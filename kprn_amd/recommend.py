@@ -14,6 +14,10 @@ model flag -K here, because -k is the number of items to return), plus
   -walks N [-sampleSeed 1]             -max_hops 4 or 5: the paths of more than 3 hops are sampled, N walks (1..256) per item and hop count
   -meta_paths FILE                     only the paths whose relation sequence matches a pattern of FILE count: one pattern per line, positions separated
                        by blanks, a position `*` or relation names joined by `|` (graph.parse_meta_paths; include/kprn.h "meta-paths")
+  -kg_delta FILE                       changes to the graph since -kg was written, one per line: `+ \\t head \\t relation \\t tail` adds an edge,
+                       `- \\t head \\t relation \\t tail` removes one (relation `*`: every relation between the two); graph.read_delta.  The graph goes to
+                       the device as -kg holds it and is updated there in place (include/kprn.h "updating a graph in place") before anything is found:
+                       the output is that of a -kg file with the delta folded in
 Output, tab separated: one line `rank, item, %.5f score, paths kept, paths found` per item, then one line `rank, place, %.5f weight, %.6g score, path`
 per explained path (the path as scoring.format_path prints it)."""
 import argparse
@@ -35,7 +39,7 @@ def main(argv=None, out=sys.stdout):
     p.add_argument("-walks", type=int, default=0)
     p.add_argument("-interaction_rel", default=""); p.add_argument("-seen", type=int, default=0, choices=(0, 1))
     p.add_argument("-max_candidates", type=int, default=0)
-    p.add_argument("-meta_paths", default="")
+    p.add_argument("-meta_paths", default=""); p.add_argument("-kg_delta", default="")
     args, rest = p.parse_known_args(argv)
     model.check_walks(args.max_hops, args.walks, p.error)
     if args.max_candidates and args.items:
@@ -58,17 +62,25 @@ def main(argv=None, out=sys.stdout):
     if args.meta_paths:
         with open(args.meta_paths) as f:
             kg.patterns = graph.parse_meta_paths(f, kg)
-    items, catalogue = None, None
-    if args.items:
-        with open(args.items) as f:
-            items = [kg.entity_id(l.strip()) for l in f if l.strip()]
-    else:
+
+    def candidates():
+        """-> (the -items list or None, the catalogue or None) of the graph as it stands"""
+        if args.items:
+            with open(args.items) as f:
+                return [kg.entity_id(l.strip()) for l in f if l.strip()], None
         positives = kg.interactions(args.interaction_rel)
         if len(positives) == 0:
             sys.exit("the graph has no edge of relation %s" % args.interaction_rel)
-        catalogue = np.unique(positives[:, 1])
+        return None, np.unique(positives[:, 1])
+
+    if not args.kg_delta:
+        items, catalogue = candidates()
     eng = model.build_engine(params)
     try:
+        if args.kg_delta:   # the graph on the device as -kg holds it, then edited in place; the catalogue is the updated graph's
+            kg.on(eng)
+            kg.apply(*graph.read_delta(args.kg_delta, kg))
+            items, catalogue = candidates()
         sampler = None if catalogue is None else eng.sampler(catalogue)
         res = graph.recommend(eng, kg, kg.entity_id(args.user), items, args.k, args.explain_paths, args.min_hops, args.max_hops,
                               args.max_paths, walks=args.walks, seed=params.sampleSeed, sampler=sampler, exclude_adjacent=not args.seen,
