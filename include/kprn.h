@@ -922,7 +922,8 @@ int kprn_profile_get(kprn_handle* h, kprn_prof_entry* out, int32_t cap, int32_t*
  *   "bf16_gemm_pingpong" "0" (default) | "1", "bf16_gemm_regstage" "0" | "1", "bf16_gemm_touch" "0" | chunks ahead, "bf16_t_pad" "64" | 0..512
  *                     (elements, a multiple of 8): measured alternatives of the bf16 split-K dW product (two wave groups one barrier apart; operands
  *                     staged through registers; L2 prefetch by touch; row pitch of its transposed operands) -- none faster than the default,
- *                     kept as the record of DESIGN.md section 7-3 and run against the default by tests/test_gpu_persist.py
+ *                     kept as the record of DESIGN.md section 7-3 and run against the default by tests/test_gpu_persist.py.  All four per handle,
+ *                     read at every backward (and by kprn_debug_gemm what 5 / 6 on that handle)
  *   "score_rest_before_bptt" "0" (default) | "1": with "score_split" f > 0, the deferred part is queued right behind the loss stage on a stream of the lowest
  *                     priority: its single-tile workgroups take the CUs the first BPTT launch leaves idle in its tail
  *   "score_rest_in_backward" "0" (default) | "1": with "score_split" f > 0, the fused backward places the deferred part of the scoring pass itself, right behind its

@@ -1177,8 +1177,8 @@ int kprn_debug_gemm(kprn_handle* h, int32_t what, int64_t M, int32_t N, int64_t 
   API_BEGIN(h)
   KPRN_REQUIRE(ms && M > 0 && N > 0 && K > 0 && iters > 0, KPRN_E_ARG, "bad argument");
   hipStream_t s = h->stream;
-  if (what == 5 || what == 6) {   // the bf16 pipeline's product (lstm_bf16.hip): 5 = C = A B^T, 6 = split-K accumulate
-    *ms = bf16p::debug_gemm16(s, M, N, K, what == 6 ? 1024 : 1, iters);
+  if (what == 5 || what == 6) {   // the bf16 pipeline's product (gemm_bf16.hip) under h's "bf16_gemm_*" options: 5 = C = A B^T, 6 = split-K accumulate
+    *ms = bf16p::debug_gemm16(h, M, N, K, what == 6 ? 1024 : 1, iters);
     return KPRN_OK;
   }
   float *A = nullptr, *B = nullptr, *C = nullptr, *X = nullptr, *Z = nullptr;
@@ -1290,17 +1290,20 @@ int kprn_set_option(kprn_handle* h, const char* key, const char* value) {
     join_score(h);   // (a pass already queued keeps the head it was queued under)
     h->head_select = atoi(value) != 0;
   } else if (strcmp(key, "bf16_t_pad") == 0) {
-    bf16p::set_t_pad(atoi(value));   // small-table route: pad (elements) of the row pitch of dA^T / Z^T ("0": rows 2^18-aligned at the bench's size)
+    // small-table route: pad (elements, a multiple of 8, 0 .. 512) of the row pitch of dA^T / Z^T ("0": rows 2^18-aligned at the bench's size)
+    const int n = atoi(value);
+    h->bf16_t_pad = n < 0 ? 0 : (n > 512 ? 512 : (n & ~7));
   } else if (strcmp(key, "bf16_gemm_regstage") == 0) {
     // bf16 split-K products on gx::k_gemm16r ("1": opt-in, operands global -> registers -> LDS, four chunks in flight per thread) or gx::k_gemm16x ("0", default: LDS-DMA, two)
-    bf16p::set_gemm_regstage(atoi(value) != 0);
+    h->bf16_gemm.regstage = atoi(value) != 0;
   } else if (strcmp(key, "bf16_gemm_touch") == 0) {
-    // bf16 products on gx::k_gemm16x: every wave touches (one dword per tile row = one cache line) the chunk this many chunks ahead of its DMA: an L2 prefetch
-    // for a launch that is bound by its operand staging ("0": off).  Process-wide.
-    bf16p::set_gemm_touch(atoi(value));
+    // bf16 products on gx::k_gemm16x: every wave touches (one dword per tile row = one cache line) the chunk this many chunks (0 .. 32) ahead of its DMA: an L2
+    // prefetch for a launch that is bound by its operand staging ("0": off)
+    const int n = atoi(value);
+    h->bf16_gemm.touch = n < 0 ? 0 : (n > 32 ? 32 : n);
   } else if (strcmp(key, "bf16_gemm_pingpong") == 0) {
-    // bf16 pipeline: split-K products with >= 256 x 256 outputs on the two-group kernel gx::k_gemm16p ("1": opt-in, measured slower) or on gx::k_gemm16x ("0", default).  Process-wide.
-    bf16p::set_gemm_pingpong(atoi(value) != 0);
+    // bf16 pipeline: split-K products with >= 256 x 256 outputs on the two-group kernel gx::k_gemm16p ("1": opt-in, measured slower) or on gx::k_gemm16x ("0", default)
+    h->bf16_gemm.pingpong = atoi(value) != 0;
   } else if (strcmp(key, "bf16_bptt_dxe") == 0) {
     // bf16 pipeline with "bf16_small_tables": the entity slice of dx is formed INSIDE the persistent BPTT launch (a fourth result tile per wave; value =
     // depth of its weight ring, 8 (default) or 16) or by its own product launch reading dA^T once more ("0")

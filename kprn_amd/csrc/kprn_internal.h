@@ -139,6 +139,20 @@ struct kprn_batch {
   struct HostResult { bool bad = false; int kmax = 0; int32_t ref[16] = {0}; int32_t n_uniq = 0; int64_t exec_steps = 0; } hres;
 };
 
+// A/B switches of the bf16 products (gemm_bf16.hip), per handle; all off by default, each one the record of a measurement:
+struct Bf16GemmOpts {
+  // option "bf16_gemm_touch": chunks ahead of its DMA k_gemm16x touches a chunk's cache lines.  MEASURED SLOWER (merged dW 1.06 -> 1.64 ms at 3 / 6 / 12 chunks: loads
+  // retire in issue order, so a touch that misses to HBM holds back the retirement of every DMA piece issued behind it -- the prefetch sits on the critical path it
+  // was meant to shorten).  The test holds it equal to the untouched launch.
+  int touch = 0;
+  bool regstage = false;   // option "bf16_gemm_regstage": the split-K products on k_gemm16r (operands through registers, four chunks in flight); measured no faster
+  // option "bf16_gemm_pingpong": the split-K products of the bf16 backward on k_gemm16p where the shape suits it.  MEASURED SLOWER than the lockstep kernel
+  // (profiles/r05/bench_c4_m_*, bench_c4_n_*: merged dW 1.50 against 1.10 ms at 64 K ranges, 1.62 / 2.05 / 1.97 at 32 / 16 / 8; k_gemm16x 1.08-1.12 at every count):
+  // neither the SIMD-level phase collision nor the number of atomic passes is what holds these products at 0.28 of the bf16 peak.  tests/test_gpu_persist.py holds
+  // it equal to k_gemm16x to fp32 reordering.
+  bool pingpong = false;
+};
+
 struct kprn_handle {
   kprn_config cfg;
   int D = 0;
@@ -256,6 +270,8 @@ struct kprn_handle {
   float* lp_wot = nullptr; int64_t lp_wot_cap = 0;     // layer_f32_persist.hip: W_o2g^T of the layer whose BPTT launch is queued
   float* st_ctmp = nullptr; int64_t st_ctmp_cap = 0;   //   ... its [GH][ns + de] product result
   bool bf16_small_tables = true;  // option "bf16_small_tables": configs[3] backward forms the type / relation gradients from G = dA^T [S_r | S_t] (lstm_bf16.hip)
+  int bf16_t_pad = 64;            // option "bf16_t_pad": pad (elements, a multiple of 8, <= 512) of the row pitch of dA^T / Z^T on the small-table route
+  Bf16GemmOpts bf16_gemm;         // options "bf16_gemm_touch" / "bf16_gemm_regstage" / "bf16_gemm_pingpong"
   bool small_tiles_on = true;     // option "small_tiles": batches of <= 8 192 paths run on tiles of one 16-row m-tile (no identical-prefix plan)
   // option "tile_handover": the fused D = H = 64 BACKWARD launches let a tile change workgroups once between two of its steps, so that the workgroups'
   // step sums differ by less than a step (lstm_fused_common.h ho_plan).  "2" (default): workgroup b is paired with b + G / 2; "1": with G - 1 - b; "0": whole
@@ -714,7 +730,7 @@ void merge_rows(hipStream_t s, const void* all, int world, int cap, int de, int 
                 int32_t* mark /*persistent [Ve], zero on entry and exit*/, void* scratch, size_t scratch_sz, int64_t tail_words = 0);
 }  // namespace bidx
 
-// ---- bf16 pipeline (lstm_bf16.hip): compute_dtype 1 with bf16 storage, FastLSTM, 8-element rows, >= 256 paths ----------------
+// ---- bf16 pipeline (lstm_bf16.hip; its products: gemm_bf16.hip / gemm_bf16.h): compute_dtype 1 with bf16 storage, FastLSTM, 8-element rows, >= 256 paths ----------------
 namespace bf16p {
 bool supported(const kprn_handle* h, const kprn_batch* b);
 void forward(kprn_handle* h, const kprn_batch* b, bool save);
@@ -722,11 +738,7 @@ void backward(kprn_handle* h, const kprn_batch* b, int cid);
 void params_changed(kprn_handle* h, bool entity_rows_only);   // parameters rewritten: shadows are stale (rows only: the dense arena + listed rows)
 void rows_updated(kprn_handle* h, const int32_t* rows, const int32_t* count, int64_t max_rows);
 void release(kprn_handle* h);
-float debug_gemm16(hipStream_t s, int64_t M, int N, int64_t K, int split_k, int iters);
-void set_gemm_touch(int chunks);   // (process-wide) L2 prefetch distance of k_gemm16x (0: off)
-void set_gemm_regstage(bool on);   // (process-wide) the split-K bf16 products on gx::k_gemm16r (register-staged operands, four chunks in flight)
-void set_t_pad(int elements);      // (process-wide) pad of the transposed images' row pitch on the small-table route (HBM channel spread)
-void set_gemm_pingpong(bool on);   // (process-wide) the split-K bf16 products on the two-group 256 x 256 kernel (opt-in) or on k_gemm16x (default)   // ms per launch (kprn_debug_gemm what 5 / 6)
+float debug_gemm16(kprn_handle* h, int64_t M, int N, int64_t K, int split_k, int iters);   // gemm_bf16.hip: ms per launch (kprn_debug_gemm what 5 / 6)
 }  // namespace bf16p
 
 // ---- fused D = H = 64 path (lstm_fused_*.hip): the host entry points ------------------------------------------------------------------

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Knock-out builds of the split-K bf16 product gx::k_gemm16x on configs[3]'s merged dW shape (1 536 x 640, K = 393 216) through kprn_debug_gemm (what 6):
 what does the launch cost without its MFMAs / its fragment reads / its DMA / its epilogue?  Needs the measurement build:
-  KPRN_VARIANT_FILES=lstm_bf16.hip python scripts/build_variants.py && KPRN_LIB=kprn_amd/libkprn_variants.so python scripts/gpu_gemm16_knockouts.py
+  KPRN_VARIANT_FILES=gemm_bf16.hip python scripts/build_variants.py && KPRN_LIB=kprn_amd/libkprn_variants.so python scripts/gpu_gemm16_knockouts.py
 (each mask runs in its own process: the switch is read once)."""
 import ctypes as C, json, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
