@@ -995,6 +995,34 @@ int kprn_set_option(kprn_handle* h, const char* key, const char* value);
 /* measurement hook: mean milliseconds per launch of one GEMM shape of the generic pipeline on random data (scripts/gpu_gemm_bench.py).
  * what: 0 C = A B^T, 1 C = A B, 2 C += A^T B (split-K), 3 FastLSTM step kernel (M paths, N = H, K = Din), 4 Recurrence step kernel */
 int kprn_debug_gemm(kprn_handle* h, int32_t what, int64_t M, int32_t N, int64_t K, int32_t iters, float* ms);
+/* test hook (tests/test_gpu_gemm16_products.py): ONE launch of a bf16 product of the bf16 pipeline (gemm_bf16.hip) on the caller's data, on h's stream,
+ * under h's "bf16_gemm_*" options and with a zero block of its own:  C[M][N] (fp32) = or += bf16(A)[M][K] bf16(B)[N][K]^T (+ bias[N]).
+ * A, B, C are host fp32 arrays of a_count / b_count / c_count elements; the operands are windows inside them: origin a_off / b_off / c_off (elements),
+ * row pitch lda / ldb / ldc.  A and B are converted on the device with the pipeline's own conversion (round to nearest even) -- whole arrays, so what
+ * surrounds a window may hold anything, NaN included; the whole C array goes up and comes back, so the caller sees every element a launch wrote.
+ * route: 0 = gemm16 as the pipeline calls it (the LDS-DMA kernels where they cover the shape, else k_gemm16), 1 = the LDS-DMA kernels alone,
+ *        2 = the k-major-A product: A is AT[K][lda] (lda >= M = T Np columns (step, path), Np - Nv pad columns per step), C has T Nv rows,
+ *        3 = k_gemm16 alone.
+ * accumulate, split_k (routes 0, 1, 3), n_lo, k_lo, sx_min (route 1), Np, Nv (route 2), bias (routes 0, 3; NULL = none) are handed to the product as they are.
+ * KPRN_E_ARG, before anything is allocated or launched, for what the products' contracts exclude: K, lda, ldb, k_lo or Np not a multiple of 8; a_off or b_off
+ * not a multiple of 8 or c_off not a multiple of 4 (16-byte aligned operands); a pitch below the extent or a window that does not fit its array; Nv > Np or
+ * Nv < 1; M not a multiple of Np; a bias with accumulate or on routes 1, 2; M, N, K < 1; a NULL pointer.
+ * ran: what the launchers report -- kernel (KPRN_GEMM16_*; DECLINED: the route does not cover the shape, nothing was launched, C comes back as it went up),
+ * the number of K ranges and their width; dx_t_ok = dx_from_transposed_ok(M, N, K, Np), what the BPTT launch is promised (route 2 only, else 0). */
+enum { KPRN_GEMM16_DECLINED = 0, KPRN_GEMM16_SMALL = 1, KPRN_GEMM16_BIG = 2, KPRN_GEMM16_X = 3, KPRN_GEMM16_R = 4, KPRN_GEMM16_P = 5, KPRN_GEMM16_XT = 6 };
+typedef struct kprn_gemm16_call {
+  int32_t route, accumulate, split_k, n_lo, sx_min, N;
+  int64_t M, K, k_lo, Np, Nv;
+  int64_t a_count, a_off, lda;
+  int64_t b_count, b_off, ldb;
+  int64_t c_count, c_off, ldc;
+} kprn_gemm16_call;
+typedef struct kprn_gemm16_ran {
+  int32_t kernel, nsplit;
+  int64_t kchunk;
+  int32_t dx_t_ok, reserved;
+} kprn_gemm16_ran;
+int kprn_debug_gemm16_run(kprn_handle* h, const kprn_gemm16_call* call, const float* A, const float* B, const float* bias, float* C, kprn_gemm16_ran* ran);
 
 #ifdef __cplusplus
 }

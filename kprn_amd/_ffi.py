@@ -41,6 +41,19 @@ class ProfEntry(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("total_ms", C.c_double), ("launches", C.c_int64)]
 
 
+class Gemm16Call(C.Structure):   # kprn_gemm16_call
+    _fields_ = [(n, C.c_int32) for n in ("route", "accumulate", "split_k", "n_lo", "sx_min", "N")] + \
+               [(n, C.c_int64) for n in ("M", "K", "k_lo", "Np", "Nv", "a_count", "a_off", "lda", "b_count", "b_off", "ldb", "c_count", "c_off", "ldc")]
+
+
+class Gemm16Ran(C.Structure):    # kprn_gemm16_ran
+    _fields_ = [("kernel", C.c_int32), ("nsplit", C.c_int32), ("kchunk", C.c_int64), ("dx_t_ok", C.c_int32), ("reserved", C.c_int32)]
+
+
+GEMM16_ROUTES = {"gemm16": 0, "x": 1, "xt": 2, "k_gemm16": 3}                          # kprn_gemm16_call.route
+GEMM16_KERNELS = ("declined", "k_gemm16_small", "k_gemm16_big", "x", "r", "p", "xt")   # KPRN_GEMM16_*
+
+
 def declared_symbols():
     """every function include/kprn.h declares (used by the CPU test that the library exports them all)."""
     txt = open(HEADER).read()
@@ -1469,3 +1482,21 @@ class Engine:
     def set_option(self, key, value):
         self._ck(self.L.kprn_set_option(self.h, key.encode(), value.encode()))
         self.options[key] = value
+
+    def gemm16_run(self, route, A, B, C_, M, N, K, lda, ldb, ldc, a_off=0, b_off=0, c_off=0, accumulate=False, split_k=1, n_lo=0, k_lo=0, sx_min=1,
+                   Np=0, Nv=0, bias=None):
+        """kprn_debug_gemm16_run: ONE launch of a bf16 product (route: a key of GEMM16_ROUTES) on windows of the flat float32 arrays A, B, C_ under this
+        handle's "bf16_gemm_*" options; C_ is overwritten with the whole array as the device left it.  -> {"kernel": a name of GEMM16_KERNELS, "nsplit",
+        "kchunk", "dx_t_ok"}.  KprnError(E_ARG) for what the products' contracts exclude, C_ untouched"""
+        for name, a in (("A", A), ("B", B), ("C", C_)):
+            if not (isinstance(a, np.ndarray) and a.dtype == np.float32 and a.ndim == 1 and a.flags.c_contiguous and a.size >= 1):
+                raise KprnError(E_ARG, "%s must be a flat C-contiguous float32 array" % name)
+        if bias is not None:
+            bias = np.ascontiguousarray(bias, np.float32)
+            if bias.shape != (N,):
+                raise KprnError(E_ARG, "bias must be [N]")
+        call = Gemm16Call(GEMM16_ROUTES[route], int(bool(accumulate)), split_k, n_lo, sx_min, N, M, K, k_lo, Np, Nv,
+                          A.size, a_off, lda, B.size, b_off, ldb, C_.size, c_off, ldc)
+        ran = Gemm16Ran()
+        self._ck(self.L.kprn_debug_gemm16_run(self.h, C.byref(call), _fp(A), _fp(B), _fp(bias), _fp(C_), C.byref(ran)))
+        return {"kernel": GEMM16_KERNELS[ran.kernel], "nsplit": int(ran.nsplit), "kchunk": int(ran.kchunk), "dx_t_ok": bool(ran.dx_t_ok)}

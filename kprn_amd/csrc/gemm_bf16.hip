@@ -284,8 +284,13 @@ void lstm_step16(hipStream_t s, GArgs a) {
 
 // C[M][N] (fp32) = or += A[M][K] B[N][K]^T; K, lda, ldb multiples of 8 elements, 16-byte aligned pointers
 void gemm16(hipStream_t s, Bf16GemmOpts o, const bf16* zero, const bf16* A, int64_t lda, const bf16* B, int64_t ldb, float* C, int64_t ldc, int64_t M, int N, int64_t K,
-            bool accumulate, const float* bias, int split_k) {
-  if (!bias && gemm16x(s, o, zero, A, lda, B, ldb, C, ldc, M, N, K, accumulate, split_k)) return;   // the LDS-DMA kernel (large products without a bias)
+            bool accumulate, const float* bias, int split_k, Ran* ran) {
+  if (!bias && gemm16x(s, o, zero, A, lda, B, ldb, C, ldc, M, N, K, accumulate, split_k, 0, 0, 1, ran)) return;   // the LDS-DMA kernel (large products without a bias)
+  gemm16_plain(s, A, lda, B, ldb, C, ldc, M, N, K, accumulate, bias, split_k, ran);
+}
+// k_gemm16 alone: what gemm16 runs after gemm16x declines
+void gemm16_plain(hipStream_t s, const bf16* A, int64_t lda, const bf16* B, int64_t ldb, float* C, int64_t ldc, int64_t M, int N, int64_t K,
+                  bool accumulate, const float* bias, int split_k, Ran* ran) {
   GArgs a;
   memset(&a, 0, sizeof(a));
   a.A = A; a.lda = lda; a.B = B; a.ldb = ldb; a.K = K; a.C = C; a.ldc = ldc; a.M = M; a.N = N; a.bias = bias;
@@ -301,6 +306,7 @@ void gemm16(hipStream_t s, Bf16GemmOpts o, const bf16* zero, const bf16* A, int6
   kchunk = ((kchunk + TK - 1) / TK) * TK;
   split_k = (int)((K + kchunk - 1) / kchunk);
   a.kchunk = kchunk; a.use_atomic = split_k > 1 ? 1 : 0;
+  if (ran) *ran = Ran{big ? KPRN_GEMM16_BIG : KPRN_GEMM16_SMALL, split_k, kchunk};
   if (big) { if (accumulate) launch16<EPI_ACCUM, 1>(s, a, 1); else launch16<EPI_STORE, 1>(s, a, 1); }
   else if (accumulate) launch16<EPI_ACCUM, 0>(s, a, split_k); else launch16<EPI_STORE, 0>(s, a, split_k);
 }
@@ -880,7 +886,8 @@ __global__ __launch_bounds__(NTHR, 2) void k_gemm16p(XArgs a) {
 struct XKernel { void (*fn)(gx::XArgs); int bm, bn, bk; size_t lds_bytes; };
 
 bool gemm16x(hipStream_t s, Bf16GemmOpts o, const bf16* zero, const bf16* A, int64_t lda, const bf16* B, int64_t ldb, float* C, int64_t ldc, int64_t M, int N, int64_t K,
-             bool accumulate, int split_k, int n_lo, int64_t k_lo, int sx_min) {
+             bool accumulate, int split_k, int n_lo, int64_t k_lo, int sx_min, Ran* ran) {
+  if (ran) *ran = Ran{};
   static const bool off = KPRN_DEV_ENV("KPRN_BF16_GEMM") && KPRN_DEV_ENV("KPRN_BF16_GEMM")[0] == 'o';   // "old": k_gemm16 everywhere (A/B measurements, tests)
   if (off || M < gx::BM || N < gx::BN || (K & 7) || (lda & 7) || (ldb & 7)) return false;
   gx::XArgs a;
@@ -921,6 +928,7 @@ bool gemm16x(hipStream_t s, Bf16GemmOpts o, const bf16* zero, const bf16* A, int
   kchunk = ((kchunk + bk - 1) / bk) * bk;
   split_k = (int)((K + kchunk - 1) / kchunk);
   a.kchunk = kchunk; a.nsplit = split_k;
+  if (ran) *ran = Ran{k.fn == p.fn ? KPRN_GEMM16_P : k.fn == r.fn ? KPRN_GEMM16_R : KPRN_GEMM16_X, split_k, kchunk};
   static PerDeviceOnce attr_done;
   if (attr_done.need()) {
     for (const XKernel& v : {xs, xa, r, p}) HIP_TRY(hipFuncSetAttribute((const void*)v.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)v.lds_bytes));
@@ -950,8 +958,11 @@ static bool dx_t_off() {   // KPRN_BF16_DX_T=0: dx from a row-major dA (tests/te
 static bool xt_shape_ok(int64_t Mp, int N, int64_t K, int64_t Np, int64_t ldat, int64_t ldb) {
   return !dx_t_off() && Mp >= gx::BM && Mp < ((int64_t)1 << 32) && N >= gx::BN && !(K & 7) && !(ldat & 7) && !(ldb & 7) && !(Np & 7);
 }
-bool gemm16xt(hipStream_t s, const bf16* zero, const bf16* AT, int64_t ldat, const bf16* B, int64_t ldb, float* C, int64_t ldc, int64_t Mp, int N, int64_t K, int64_t Np, int64_t Nv) {
+bool gemm16xt(hipStream_t s, const bf16* zero, const bf16* AT, int64_t ldat, const bf16* B, int64_t ldb, float* C, int64_t ldc, int64_t Mp, int N, int64_t K, int64_t Np, int64_t Nv,
+              Ran* ran) {
+  if (ran) *ran = Ran{};
   if (!xt_shape_ok(Mp, N, K, Np, ldat, ldb)) return false;
+  if (ran) *ran = Ran{KPRN_GEMM16_XT, 1, ((K + gx::BK - 1) / gx::BK) * gx::BK};
   gx::XTArgs a;
   memset(&a, 0, sizeof(a));
   a.AT = AT; a.ldat = ldat; a.B = B; a.ldb = ldb; a.C = C; a.ldc = ldc; a.Mp = Mp; a.N = N; a.K = K; a.Np = Np; a.Nv = Nv; a.zero = zero;
@@ -994,6 +1005,66 @@ float debug_gemm16(kprn_handle* h, int64_t M, int N, int64_t K, int split_k, int
   hipEventDestroy(e0); hipEventDestroy(e1);
   hipFree(f); hipFree(A); hipFree(B); hipFree(C); hipFree(Z);
   return t / (float)iters;
+}
+
+// test hook (kprn_debug_gemm16_run, include/kprn.h): one launch of one route on the caller's data.  Everything the products' contracts exclude is refused
+// here, before anything is allocated; which kernel ran and on what K ranges is what the launcher itself reports (Ran).
+void debug_gemm16_run(kprn_handle* h, const kprn_gemm16_call& c, const float* A, const float* B, const float* bias, float* C, kprn_gemm16_ran* ran) {
+  KPRN_REQUIRE(A && B && C && ran, KPRN_E_ARG, "gemm16_run: NULL argument");
+  const bool xt = c.route == 2;
+  const int64_t lim = (int64_t)1 << 31, big = (int64_t)1 << 40;
+  KPRN_REQUIRE(c.route >= 0 && c.route <= 3, KPRN_E_ARG, "gemm16_run: route must be 0..3");
+  KPRN_REQUIRE(c.M >= 1 && c.N >= 1 && c.K >= 1 && c.M < lim && c.K < lim, KPRN_E_ARG, "gemm16_run: M, N, K must be in 1 .. 2^31 - 1");
+  KPRN_REQUIRE(c.lda >= 1 && c.ldb >= 1 && c.ldc >= 1 && c.lda < lim && c.ldb < lim && c.ldc < lim, KPRN_E_ARG, "gemm16_run: a pitch must be in 1 .. 2^31 - 1");
+  KPRN_REQUIRE(c.a_off >= 0 && c.b_off >= 0 && c.c_off >= 0 && c.a_count >= 1 && c.b_count >= 1 && c.c_count >= 1 && c.a_count < big && c.b_count < big && c.c_count < big,
+               KPRN_E_ARG, "gemm16_run: an array's element count or a window's origin is out of range");
+  KPRN_REQUIRE(!(c.K & 7) && !(c.lda & 7) && !(c.ldb & 7), KPRN_E_ARG, "gemm16_run: K, lda and ldb must be multiples of 8");
+  KPRN_REQUIRE(!(c.a_off & 7) && !(c.b_off & 7) && !(c.c_off & 3), KPRN_E_ARG, "gemm16_run: a_off, b_off must be multiples of 8 and c_off of 4 (16-byte aligned operands)");
+  KPRN_REQUIRE(c.k_lo >= 0 && !(c.k_lo & 7) && c.n_lo >= 0 && c.split_k >= 0 && c.sx_min >= 0, KPRN_E_ARG, "gemm16_run: k_lo must be a multiple of 8; n_lo, split_k, sx_min >= 0");
+  KPRN_REQUIRE(!(bias && (c.accumulate || c.route == 1 || xt)), KPRN_E_ARG, "gemm16_run: a bias goes with the storing form of routes 0 and 3 only");
+  int64_t c_rows = c.M;
+  if (xt) {
+    KPRN_REQUIRE(!c.accumulate, KPRN_E_ARG, "gemm16_run: the k-major-A product has no accumulating form");
+    KPRN_REQUIRE(c.Np >= 8 && !(c.Np & 7) && c.Nv >= 1 && c.Nv <= c.Np && c.M % c.Np == 0, KPRN_E_ARG, "gemm16_run: Np must be a multiple of 8, 1 <= Nv <= Np, M a multiple of Np");
+    KPRN_REQUIRE(c.lda >= c.M && c.a_off + (c.K - 1) * c.lda + c.M <= c.a_count, KPRN_E_ARG, "gemm16_run: the AT window does not fit its array");
+    c_rows = (c.M / c.Np) * c.Nv;
+  } else {
+    KPRN_REQUIRE(c.lda >= c.K && c.a_off + (c.M - 1) * c.lda + c.K <= c.a_count, KPRN_E_ARG, "gemm16_run: the A window does not fit its array");
+  }
+  KPRN_REQUIRE(c.ldb >= c.K && c.b_off + (int64_t)(c.N - 1) * c.ldb + c.K <= c.b_count, KPRN_E_ARG, "gemm16_run: the B window does not fit its array");
+  KPRN_REQUIRE(c.ldc >= c.N && c.c_off + (c_rows - 1) * c.ldc + c.N <= c.c_count, KPRN_E_ARG, "gemm16_run: the C window does not fit its array");
+  struct Dev {   // (freed on every way out)
+    float *f = nullptr, *C = nullptr, *bias = nullptr; bf16 *A = nullptr, *B = nullptr, *Z = nullptr;
+    ~Dev() { hipFree(f); hipFree(C); hipFree(bias); hipFree(A); hipFree(B); hipFree(Z); }
+  } d;
+  hipStream_t strm = h->stream;
+  d.f = dalloc<float>(std::max(c.a_count, c.b_count));
+  d.A = dalloc<bf16>(c.a_count); d.B = dalloc<bf16>(c.b_count); d.Z = dalloc<bf16>(128);   // Z: the zero block of this launch
+  d.C = dalloc<float>(c.c_count);
+  HIP_TRY(hipMemcpyAsync(d.f, A, (size_t)c.a_count * sizeof(float), hipMemcpyHostToDevice, strm));
+  cvt16(strm, d.f, d.A, c.a_count);
+  HIP_TRY(hipStreamSynchronize(strm));   // (pageable host memory: the staging block is free again)
+  HIP_TRY(hipMemcpyAsync(d.f, B, (size_t)c.b_count * sizeof(float), hipMemcpyHostToDevice, strm));
+  cvt16(strm, d.f, d.B, c.b_count);
+  HIP_TRY(hipMemsetAsync(d.Z, 0, 256, strm));
+  HIP_TRY(hipMemcpyAsync(d.C, C, (size_t)c.c_count * sizeof(float), hipMemcpyHostToDevice, strm));
+  if (bias) {
+    d.bias = dalloc<float>(c.N);
+    HIP_TRY(hipMemcpyAsync(d.bias, bias, (size_t)c.N * sizeof(float), hipMemcpyHostToDevice, strm));
+  }
+  const bf16 *a = d.A + c.a_off, *b = d.B + c.b_off;
+  float* cw = d.C + c.c_off;
+  Ran r;
+  memset(ran, 0, sizeof(*ran));
+  if (c.route == 0) gemm16(strm, h->bf16_gemm, d.Z, a, c.lda, b, c.ldb, cw, c.ldc, c.M, c.N, c.K, c.accumulate != 0, d.bias, c.split_k, &r);
+  else if (c.route == 1) gemm16x(strm, h->bf16_gemm, d.Z, a, c.lda, b, c.ldb, cw, c.ldc, c.M, c.N, c.K, c.accumulate != 0, c.split_k, c.n_lo, c.k_lo, c.sx_min, &r);
+  else if (xt) {
+    gemm16xt(strm, d.Z, a, c.lda, b, c.ldb, cw, c.ldc, c.M, c.N, c.K, c.Np, c.Nv, &r);
+    ran->dx_t_ok = dx_from_transposed_ok(c.M, c.N, c.K, c.Np) ? 1 : 0;
+  } else gemm16_plain(strm, a, c.lda, b, c.ldb, cw, c.ldc, c.M, c.N, c.K, c.accumulate != 0, d.bias, c.split_k, &r);
+  ran->kernel = r.kernel; ran->nsplit = r.nsplit; ran->kchunk = r.kchunk;
+  HIP_TRY(hipMemcpyAsync(C, d.C, (size_t)c.c_count * sizeof(float), hipMemcpyDeviceToHost, strm));
+  HIP_TRY(hipStreamSynchronize(strm));
 }
 
 }  // namespace bf16p

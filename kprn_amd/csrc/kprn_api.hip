@@ -1213,6 +1213,14 @@ int kprn_debug_gemm(kprn_handle* h, int32_t what, int64_t M, int32_t N, int64_t 
   API_END(h)
 }
 
+/* test hook (tests/test_gpu_gemm16_products.py): one launch of one bf16 product on the caller's data (gemm_bf16.hip debug_gemm16_run) */
+int kprn_debug_gemm16_run(kprn_handle* h, const kprn_gemm16_call* call, const float* A, const float* B, const float* bias, float* C, kprn_gemm16_ran* ran) {
+  API_BEGIN(h)
+  KPRN_REQUIRE(call, KPRN_E_ARG, "gemm16_run: NULL argument");
+  bf16p::debug_gemm16_run(h, *call, A, B, bias, C, ran);
+  API_END(h)
+}
+
 int kprn_set_option(kprn_handle* h, const char* key, const char* value) {
   API_BEGIN(h)
   KPRN_REQUIRE(key && value, KPRN_E_ARG, "NULL argument");

@@ -739,6 +739,7 @@ void params_changed(kprn_handle* h, bool entity_rows_only);   // parameters rewr
 void rows_updated(kprn_handle* h, const int32_t* rows, const int32_t* count, int64_t max_rows);
 void release(kprn_handle* h);
 float debug_gemm16(kprn_handle* h, int64_t M, int N, int64_t K, int split_k, int iters);   // gemm_bf16.hip: ms per launch (kprn_debug_gemm what 5 / 6)
+void debug_gemm16_run(kprn_handle* h, const kprn_gemm16_call& c, const float* A, const float* B, const float* bias, float* C, kprn_gemm16_ran* ran);   // gemm_bf16.hip: kprn_debug_gemm16_run
 }  // namespace bf16p
 
 // ---- fused D = H = 64 path (lstm_fused_*.hip): the host entry points ------------------------------------------------------------------
